@@ -10,16 +10,25 @@ per-tile (M, maxC, status) after the timed region (and the tiny all-reduces of -
     python bench.py                                  # N=1, prints ONE JSON line
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W [--slide-pooled]
-    python bench.py --gpus N                         # no launcher: re-executes ITSELF under torch.distributed.run with N ranks,
-                                                     # or exits with status 2 when the box has fewer than N GPUs -- it never
-                                                     # measures fewer GPUs than it was asked for
+    python bench.py --gpus N                         # no launcher: runs ITSELF under torch.distributed.run with N ranks (a child
+                                                     # process), or exits with status 2 when the box has fewer than N GPUs -- it
+                                                     # never measures fewer GPUs than it was asked for
+    python bench.py --full                           # the headline and every extra object listed below
+    python bench.py --dump-outputs DIR               # also writes what the last timed step returned (rank 0) as DIR/*.npy
+
+A plain run does only what the headline needs: set-up, the clock spin-up and W warm-up steps, the K timed steps, and the line
+(metric, value, unit, higher_is_better, dtype, ms_per_step, config, distributed).  The timed steps run with default SlParams: no
+event or counter is attached to them.  --dump-outputs writes M.npy (N, 2, 3) and maxC.npy (N, 2) float64, status.npy (N,) float64,
+and out_sample.npy: float32 (n, 3), the output pixels at 2^21 fixed, seeded positions of the batch, sorted (all pixels when the batch
+has fewer).  The inputs depend on the arguments only, so two builds can be compared file by file.
 
 Environment (tests and dry runs only): SL_BENCH_BACKEND=gloo (process group on the CPU), SL_BENCH_SHARE_GPU=1 (ranks may share a
 device: N-rank logic on a 1-GPU box), SL_BENCH_DRY=1 (NO kernels at all: launcher, rendezvous, placement and the collectives of
 the line with a sleeping stand-in step -- the line says "dry_run": true and its value means nothing), SL_BENCH_FORCE_DIST=1
 (the N > 1 path with one rank).
 
-Extra objects in the JSON line:
+Extra objects in the JSON line, all but `distributed` with --full only (its timed region brackets the dominant kernel with HIP
+events and attaches the counters that fallbacks / prefilter / two_sweep report):
   roofline        the dominant kernel (the fused persistent transform), timed with HIP events on its own stream INSIDE
                   the timed region; algorithmic bytes = SURVEY 8(d)'s COMPULSORY 6 B/px (one read + one write of the tile) x the
                   pixels of one launch: `frac` is that fraction of 8 TB/s.  The kernel's own schedule moves more (three read sweeps
@@ -58,7 +67,7 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+HBM_PEAK_GBS = 8000.0          # MI355X HBM3E: 8.0 TB/s spec
 
 
 # ----------------------------------------------------------------------------------------------
@@ -270,6 +279,23 @@ def _timed(fn, reps=10, warm=2, spin_up_ms=60.0):
     e1.record()
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) / reps
+
+
+DUMP_PIXELS = 1 << 21          # out_sample.npy: 2^21 pixels x 3 x float32 = 25 MB (M, maxC, status add 64 B per tile)
+
+
+def dump_outputs(path, out, M, maxC, status):
+    """What one step returns to its caller, as float32 / float64 .npy files: (M, maxC, status) whole, the (N, H, W, 3) uint8 output at
+    DUMP_PIXELS pixel positions drawn with a fixed seed (sorted; every pixel when the batch has fewer)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    px = out.reshape(-1, 3)
+    if px.shape[0] > DUMP_PIXELS:
+        pick = np.sort(np.random.default_rng(0).choice(px.shape[0], DUMP_PIXELS, replace=False))
+        px = px[torch.from_numpy(pick).to(px.device)]
+    for name, t in (("out_sample", px.float()), ("M", M), ("maxC", maxC), ("status", status.double())):
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
 
 
 def _flips(got, want):
@@ -495,7 +521,7 @@ def _free_port():
 def self_launch(n_gpus, argv, dry, share):
     """`python bench.py --gpus N` (N > 1) without RANK / WORLD_SIZE in the environment: become the launcher the driver would have
     used -- one rank per GPU under torch.distributed.run on 127.0.0.1 -- or refuse (exit status 2) when the box has fewer than N
-    devices.  Never returns."""
+    devices.  Never returns: exits with the launcher's status."""
     if not dry and not share:
         import torch
         have = torch.cuda.device_count()
@@ -510,7 +536,9 @@ def self_launch(n_gpus, argv, dry, share):
            "--master-port", str(_free_port()), os.path.abspath(__file__)] + list(argv)
     sys.stderr.write("bench.py: no launcher in the environment, starting " + " ".join(cmd[1:9]) + " ...\n")
     sys.stderr.flush()
-    os.execve(sys.executable, cmd, env)
+    # a child process, not exec(): device_count() above may already have opened the GPU runtime in this process
+    rc = subprocess.run(cmd, env=env).returncode
+    sys.exit(rc if rc >= 0 else 128 - rc)
 
 
 def _cpus_of_list(text):
@@ -599,7 +627,13 @@ def main():
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary configs (N=1 only)")
     ap.add_argument("--slide-pooled", action="store_true",
                     help="also run configs[4]: pooled slide statistics over ALL ranks' tiles (RCCL all-reduces)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: CPU baseline, roofline and per-kernel passes, "
+                         "sustained rate, parity against the oracle, two-sweep A/B, secondary configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned (rank 0) as DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     launched = "RANK" in os.environ and "WORLD_SIZE" in os.environ
     dry = os.environ.get("SL_BENCH_DRY") == "1"                  # launcher / placement / collective logic only: NO kernels
@@ -621,7 +655,7 @@ def main():
     dist_on = world > 1 or os.environ.get("SL_BENCH_FORCE_DIST") == "1"
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not dry:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and not dry:
         cpu = cpu_baseline(a.size)
 
     import numpy as np
@@ -765,16 +799,18 @@ def main():
     assert int(st[0]) == 0
     Mt, mct = Mt[0].contiguous(), mct[0].contiguous()
     ws = engine.Workspace()
-    n_groups_max = 4 * B + 64
-    ev = HipEvents(2 * n_groups_max * max(a.steps, 1))
     params = _ffi.default_params()
-    fallbacks = engine.attach_fallbacks(params, B, device=dev)
-    resweeps = torch.zeros((B,), dtype=torch.int32, device=dev)     # tiles whose concentration percentiles needed the separate sweep 3
-    params.resweeps_out = resweeps.data_ptr()
-    prefilter = torch.zeros((B,), dtype=torch.int32, device=dev)    # bit 0: the selection sweep ran behind the colour-cube mask; bits 8..: share (%)
-    params.prefilter_out = prefilter.data_ptr()
-    twosweep = torch.zeros((B,), dtype=torch.int32, device=dev)     # SL_TWOSWEEP_* per tile: what became of the two-sweep attempt
-    params.twosweep_out = twosweep.data_ptr()
+    if a.full:
+        n_groups_max = 4 * B + 64
+        # (room for 20 steps of the per-phase schedule's launches; the fused schedule launches once per step: all of them for any K)
+        ev = HipEvents(2 * n_groups_max * min(a.steps, 20))
+        fallbacks = engine.attach_fallbacks(params, B, device=dev)
+        resweeps = torch.zeros((B,), dtype=torch.int32, device=dev)     # tiles whose concentration percentiles needed the separate sweep 3
+        params.resweeps_out = resweeps.data_ptr()
+        prefilter = torch.zeros((B,), dtype=torch.int32, device=dev)    # bit 0: the selection sweep ran behind the colour-cube mask; bits 8..: share (%)
+        params.prefilter_out = prefilter.data_ptr()
+        twosweep = torch.zeros((B,), dtype=torch.int32, device=dev)     # SL_TWOSWEEP_* per tile: what became of the two-sweep attempt
+        params.twosweep_out = twosweep.data_ptr()
 
     def step(p):
         return engine.macenko_transform(rgb, Mt, mct, params=p, out=out, ws=ws)
@@ -793,10 +829,11 @@ def main():
         step(params)
     torch.cuda.synchronize()
 
-    # ---- timed region: exactly K steps; the dominant kernel (the fused persistent transform, or k_apply in
+    # ---- timed region: exactly K steps; with --full the dominant kernel (the fused persistent transform, or k_apply in
     # the one-launch-per-phase schedule) is bracketed by HIP events on the stream it is launched on
-    prof = ev.profile(_ffi.PROF_APPLY | _ffi.PROF_FUSED_TRANSFORM)
-    params.profile = C.pointer(prof)
+    if a.full:
+        prof = ev.profile(_ffi.PROF_APPLY | _ffi.PROF_FUSED_TRANSFORM)
+        params.profile = C.pointer(prof)
     barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -807,11 +844,14 @@ def main():
     barrier()
     t1 = time.perf_counter()
     elapsed = t1 - t0
-    timed_pairs = ev.pairs(prof)
     status = res[3]
     n_bad = int((status != 0).sum())
-    n_fallbacks = int(fallbacks.sum())
-    n_resweeps = int((resweeps != 0).sum())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, *res)
+    if a.full:
+        timed_pairs = ev.pairs(prof)
+        n_fallbacks = int(fallbacks.sum())
+        n_resweeps = int((resweeps != 0).sum())
 
     ranks = placement(B * a.steps / t_mine)
     per_rank = [r["tiles_per_s"] for r in ranks]
@@ -819,9 +859,10 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax[0])
-        fb_all = torch.tensor([float(n_fallbacks)], dtype=torch.float64, device=coll_dev)
-        dist.all_reduce(fb_all, op=dist.ReduceOp.SUM)
-        n_fallbacks = int(fb_all[0])
+        if a.full:
+            fb_all = torch.tensor([float(n_fallbacks)], dtype=torch.float64, device=coll_dev)
+            dist.all_reduce(fb_all, op=dist.ReduceOp.SUM)
+            n_fallbacks = int(fb_all[0])
         # QC gather of per-tile stats (36 B/tile) -- the only collective of the per-tile mode, outside the timed region
         stats = torch.cat([res[1].reshape(B, 6).float(), res[2].float(), status.float().reshape(B, 1)], dim=1).to(coll_dev)
         gathered = [torch.empty_like(stats) for _ in range(world)]
@@ -832,7 +873,7 @@ def main():
     # at the package power limit the clocks settle lower).  Every rank loops; rank 0 reads sclk / package power mid-loop.
     params.profile = None
     sustained = None
-    if a.sustain_s > 0:
+    if a.full and a.sustain_s > 0:
         smi_box = {}
         th = None
         if rank == 0:
@@ -890,7 +931,9 @@ def main():
                   "ranks_agree_bitwise": same, "M_slide": [round(float(x), 6) for x in M_s.reshape(-1).tolist()]}
 
     line = None
-    if rank == 0:
+    tiles_per_s = world * B * a.steps / elapsed
+    full = {}
+    if rank == 0 and a.full:
         # ---- untimed instrumented passes: every kernel class of the schedule the timed region used, then of the
         # one-launch-per-phase schedule (sweeps and finish steps separately)
         prof_all = ev.profile(255)
@@ -937,7 +980,6 @@ def main():
         ap_ms = _timed(lambda: engine.normalize_apply(rgb, res[1], res[2], Mt, mct, out=out), reps=10, warm=1)
         ap_bytes = 6.0 * P * B
         ap_gbs = ap_bytes / (ap_ms * 1e-3) / 1e9
-        tiles_per_s = world * B * a.steps / elapsed
         per_gpu = tiles_per_s / world
 
         # HBM traffic from PMC counters: collected in separate rocprofv3 --pmc passes (profiles/*_pmc_traffic.json
@@ -1030,25 +1072,7 @@ def main():
                                 "(the back-off); on real tissue the attempt mostly declines after the sample's eigen-solve (+2-3 % against "
                                 "two_sweep=1 there); results are identical in every mode (tests)"}
 
-        line = {
-            "metric": "1024x1024 H&E tiles/sec normalized (Macenko)",
-            "value": round(tiles_per_s, 1),
-            "unit": "tiles/s",
-            "n_gpus": world,
-            "steps": a.steps,
-            "warmup": a.warmup,
-            "ms_per_step": round(1e3 * elapsed / a.steps, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {"workload": f"configs[1]: batch of {B} tiles {h}x{w}x3 uint8 per GPU, Macenko transform "
-                                   "(fit once outside the timed region), tiles resident in HBM",
-                       "tiles_per_gpu": B, "tile": [h, w, 3], "sharding": f"independent tiles x{world}, no data-path collective",
-                       "clock_spin_up": f"{n_prewarm} untimed launches ({PREWARM_MS:.0f} ms) before the {a.warmup} warm-up steps: after the idle "
-                                        "seconds of the host-side setup the first ~12 launches run at ramping clocks (2.6 -> 1.94 ms)",
-                       "failed_tiles": n_bad},
+        full = {
             "arithmetic": "per-pixel arithmetic binary32 (optical-density table, lasso, exp2, truncating pack); moment sums, eigen-solve, "
                           "percentile interpolation, trigonometry and per-tile constants binary64; order statistics exact on binary32 keys. "
                           "The reference is float64 throughout: see parity.prequant_max_rel_err against the north star's 1e-4.  What binary64 "
@@ -1092,6 +1116,28 @@ def main():
                                   "re-tests only the pixels of the other cells exactly (SlParams.prefilter; results do not depend on it)"},
             "two_sweep": two_sweep_ab,
             "parity": parity,
+        }
+    if rank == 0:
+        line = {
+            "metric": "1024x1024 H&E tiles/sec normalized (Macenko)",
+            "value": round(tiles_per_s, 1),
+            "unit": "tiles/s",
+            "n_gpus": world,
+            "steps": a.steps,
+            "warmup": a.warmup,
+            "ms_per_step": round(1e3 * elapsed / a.steps, 4),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic",
+            "config": {"workload": f"configs[1]: batch of {B} tiles {h}x{w}x3 uint8 per GPU, Macenko transform "
+                                   "(fit once outside the timed region), tiles resident in HBM",
+                       "tiles_per_gpu": B, "tile": [h, w, 3], "sharding": f"independent tiles x{world}, no data-path collective",
+                       "clock_spin_up": f"{n_prewarm} untimed launches ({PREWARM_MS:.0f} ms) before the {a.warmup} warm-up steps: after the idle "
+                                        "seconds of the host-side setup the first ~12 launches run at ramping clocks (2.6 -> 1.94 ms)",
+                       "failed_tiles": n_bad},
+            **full,
             "distributed": {"backend": (dist.get_backend() if dist_on else None), "world_size": (dist.get_world_size() if dist_on else 1),
                             "per_rank_tiles_per_s": [round(x, 1) for x in per_rank], "ranks": ranks, "device_of_rank0": dev_index,
                             "cpu_affinity_of_rank0": affinity, "slide_pooled": pooled},
@@ -1099,11 +1145,12 @@ def main():
         if cpu is not None:
             line["cpu_baseline"] = cpu
             line["gpu_over_cpu"] = round(tiles_per_s / cpu["value"], 1)
-        if world == 1 and not a.no_secondary:
+        if a.full and world == 1 and not a.no_secondary:
             del rgb, out
             torch.cuda.empty_cache()
             line["secondary"] = secondary_configs(dev, Mt, mct)
-    ev.close()
+    if a.full:
+        ev.close()
     if dist_on:
         barrier()
         dist.destroy_process_group()

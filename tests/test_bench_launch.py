@@ -110,7 +110,7 @@ def test_core_slices_follow_the_gpus_numa_nodes(monkeypatch, tmp_path):
 @pytest.mark.gpu
 def test_gpus_2_on_one_gpu_with_gloo_runs_the_real_step_on_two_ranks():
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--tiles", "48", "--size", "256", "--sustain-s", "0.2",
-                        "--no-cpu-baseline", "--no-secondary"], cwd=ROOT,
+                        "--full", "--no-cpu-baseline", "--no-secondary"], cwd=ROOT,
                        env=_clean_env(SL_BENCH_BACKEND="gloo", SL_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0"),
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
@@ -119,6 +119,38 @@ def test_gpus_2_on_one_gpu_with_gloo_runs_the_real_step_on_two_ranks():
     d = line["distributed"]
     assert d["backend"] == "gloo" and d["world_size"] == 2 and len(d["per_rank_tiles_per_s"]) == 2
     assert line["sustained"]["steps"] >= 16 and line["roofline"]["bytes_per_pixel"] == 6.0
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_only_and_dumps_what_the_last_step_returned(tmp_path):
+    """A run without --full prints the headline and no extra object; --dump-outputs writes the step's (M, maxC, status) and the
+    seeded pixel sample of its output, which the same call in this process reproduces from bench.py's seeds."""
+    import numpy as np
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--tiles", "48", "--size", "256",
+                        "--dump-outputs", str(tmp_path)], cwd=ROOT, env=_clean_env(), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
+    line = _line(r.stdout)
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0 and line["config"]["failed_tiles"] == 0
+    assert (line["metric"], line["unit"], line["higher_is_better"], line["dtype"]) == ("1024x1024 H&E tiles/sec normalized (Macenko)", "tiles/s", True, "f32")
+    assert not {"roofline", "sustained", "parity", "cpu_baseline", "secondary"} & set(line), sorted(line)
+    got = {n: np.load(tmp_path / f"{n}.npy") for n in ("out_sample", "M", "maxC", "status")}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values()) and sum(v.nbytes for v in got.values()) <= 64 << 20
+    import torch
+    sys.path.insert(0, ROOT)
+    from oracle import stain_oracle as so
+    from stainlib_amd import engine
+    from tools.synth import synth_tiles
+    dev = torch.device("cuda", 0)
+    tgt = synth_tiles(1, 256, 256, seed=1, device=dev, M_true=so.M_TRUE_TGT.tolist())
+    Mt, mct, _ = engine.macenko_fit(tgt)
+    out, M, mc, st = engine.macenko_transform(synth_tiles(48, 256, 256, seed=7, device=dev), Mt[0].contiguous(), mct[0].contiguous())
+    px = out.reshape(-1, 3).cpu().numpy()
+    pick = np.sort(np.random.default_rng(0).choice(px.shape[0], 1 << 21, replace=False))
+    assert got["out_sample"].shape == (1 << 21, 3) and np.abs(got["out_sample"] - px[pick]).max() <= 1
+    assert (got["out_sample"] != px[pick]).mean() < 1e-4
+    np.testing.assert_allclose(got["M"], M.cpu().numpy(), rtol=0, atol=1e-12)
+    np.testing.assert_allclose(got["maxC"], mc.cpu().numpy(), rtol=1e-12)
+    np.testing.assert_array_equal(got["status"], st.cpu().numpy())
 
 
 @pytest.mark.gpu

@@ -18,7 +18,7 @@ def test_bench_under_the_launcher_with_a_one_rank_rccl_group():
     env = dict(os.environ, SL_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29611", "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--tiles", "48", "--size", "256",
-           "--no-cpu-baseline", "--no-secondary", "--slide-pooled"]
+           "--full", "--no-cpu-baseline", "--no-secondary", "--slide-pooled"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     line = json.loads([ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1])
