@@ -123,9 +123,15 @@ _SIGNATURES = {
     "sl_pool2_exact": (C.c_int, [_P, _P, _P]),
     "sl_pool2_step": (C.c_int, [_P, C.c_int, _P, _P]),
     "sl_pool2_local": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(SlParams), C.c_int, _P, C.c_size_t, _P, _P]),
+    # the pooled slide-level Vahadane dictionary (state: SDICT_STATE_DOUBLES doubles; workspace: sl_sdict_workspace_bytes)
+    "sl_sdict_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "sl_sdict_begin": (C.c_int, [C.POINTER(SlParams), C.c_int, _P, _P]),
+    "sl_sdict_sweep": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(SlParams), C.c_int, _P, _P, C.c_size_t, _P, _P]),
+    "sl_sdict_step": (C.c_int, [_P, _P, C.POINTER(SlParams), _P]),
 }
 POOL_STATE_DOUBLES, POOL_M, POOL_MAXC, POOL_STATUS, POOL_MISS = 64, 0, 6, 8, 9
 POOL2_STATE_DOUBLES, POOL2_HIST_WORDS, POOL2_WHY = 256, 2 * 8192 + 8 * 32, 33
+SDICT_STATE_DOUBLES, SDICT_SUMS, SDICT_M, SDICT_STATUS, SDICT_SWEEPS, SDICT_ROUNDS, SDICT_MODE, SDICT_D, SDICT_NPX = 64, 32, 0, 6, 7, 8, 9, 10, 16
 EXPECTED_VERSION = 600     # the SL_VERSION this binding (SlParams, signatures) was written for
 EXPORTS = tuple(_SIGNATURES)
 

@@ -22,6 +22,10 @@ This is an extension (the reference has no notion of a slide); its check is the 
     key is pinned by a 4-round radix select whose 256-bin histograms are all-reduced (two order statistics per
     sweep, 4 KiB per round).  All
     collectives are tiny and latency-bound.  Oracle: the reference restatement on the concatenated image.
+    With a Vahadane normalizer (``PooledVahadaneStatistics``) the stain matrix is the dictionary learnt on every tissue pixel of the
+    slide: under one shared dictionary a sweep reduces each rank's tiles to 31 class-moment sums, those are all-reduced (32 doubles
+    with the pixel count), and one workgroup takes the update on every rank alike; a few such rounds reach the fixed point.  The 99th
+    percentile of each concentration under that matrix is pinned by the same order-statistic machinery as Macenko's.
 """
 from __future__ import annotations
 
@@ -205,6 +209,45 @@ def window_rank_pairs(sample_hist_fn, window_fn, ks, totals, group=None):
     return out
 
 
+def key_rank_pairs(tiles_local: torch.Tensor, keyset: int, basis, ks, totals, sample_log2: int, params, group=None, path=None):
+    """Per target of the key set under ``basis``: the binary32 keys of ranks ks[t] and ks[t] + 1 of the whole slide as floats.  One sweep
+    with the window centred on an estimate from a pixel sample (one row in 2**sample_log2), the radix rounds if it missed; appends
+    "window" or "radix" to ``path``.  A rank without tiles takes part in every collective with empty histograms."""
+    from . import engine
+    dev = tiles_local.device
+    empty = tiles_local.shape[0] == 0
+    if empty:                    # (the library refuses n == 0: the counts of no pixel are zeros)
+        hist_s = lambda pre, bits: torch.zeros((2, 256), dtype=torch.int64, device=dev)
+        win = lambda lo: torch.zeros((2 * 65536 + 2,), dtype=torch.int64, device=dev)
+        hist = lambda pre, bits: torch.zeros((2, 256), dtype=torch.int64, device=dev)
+        hist16 = lambda pre: torch.zeros((2, 65536), dtype=torch.int64, device=dev)
+        above = lambda o: [0xffffffff, 0xffffffff]
+    else:
+        hist_s = lambda pre, bits: engine.slide_key_histogram_sampled(tiles_local, keyset, basis, pre, bits, sample_log2, params=params)
+        win = lambda lo: engine.slide_key_window(tiles_local, keyset, basis, lo, params=params)
+        hist = lambda pre, bits: engine.slide_key_histogram(tiles_local, keyset, basis, pre, bits, params=params)
+        hist16 = lambda pre: engine.slide_key_histogram16(tiles_local, keyset, basis, pre, params=params)
+        above = lambda o: engine.slide_key_next_above(tiles_local, keyset, basis, o, params=params)
+    res = window_rank_pairs(hist_s, win, ks, totals, group)
+    if path is not None:
+        path.append("window" if res is not None else "radix")
+    if res is None:
+        res = exact_rank_pairs(hist, above, ks, group, hist16_fn=hist16)
+    return [(ord_to_float(a), ord_to_float(b)) for a, b, _ in res]
+
+
+def _agreed_pixels(tiles_local, n_tiles_total, world, group):
+    """The slide's pixel count as every rank computes it alike (see ``PooledSlideStatistics.enqueue``)."""
+    n_local, h, w, _ = tiles_local.shape
+    if n_tiles_total is not None:
+        return int(n_tiles_total) * h * w
+    if _coll(world, group) and world > 1:
+        nl = torch.tensor([n_local], dtype=torch.int64, device=tiles_local.device if dist.get_backend(group) == "nccl" else "cpu")
+        dist.all_reduce(nl, op=dist.ReduceOp.MAX, group=group)
+        return world * int(nl.item()) * h * w
+    return world * n_local * h * w
+
+
 class PooledSlideStatistics:
     """Stain matrix and 99th-percentile concentrations of the tall image made of every tile on every rank."""
 
@@ -282,14 +325,7 @@ class PooledSlideStatistics:
 
     def _agreed_pixels(self, tiles_local, n_tiles_total, world):
         """The slide's pixel count as every rank computes it alike (see ``enqueue``)."""
-        n_local, h, w, _ = tiles_local.shape
-        if n_tiles_total is not None:
-            return int(n_tiles_total) * h * w
-        if _coll(world, self.group) and world > 1:
-            nl = torch.tensor([n_local], dtype=torch.int64, device=tiles_local.device if dist.get_backend(self.group) == "nccl" else "cpu")
-            dist.all_reduce(nl, op=dist.ReduceOp.MAX, group=self.group)
-            return world * int(nl.item()) * h * w
-        return world * n_local * h * w
+        return _agreed_pixels(tiles_local, n_tiles_total, world, self.group)
 
     def enqueue_merged(self, tiles_local: torch.Tensor, ws=None, n_tiles_total: Optional[int] = None) -> torch.Tensor:
         """DEVICE-DRIVEN, ONE full sweep (round 6; csrc/slide_merged.hip): a stratified pixel sample of the whole slide gives an estimate
@@ -402,15 +438,7 @@ class PooledSlideStatistics:
         # ---- exact angular percentiles over those pixels (:29-34): both in the same four sweeps
         def pairs(keyset, basis, ks, totals):
             # one sweep, with the window centred on an estimate from a 1/64 pixel sample; the radix rounds if it missed
-            res = window_rank_pairs(lambda pre, bits: engine.slide_key_histogram_sampled(tiles_local, keyset, basis, pre, bits, slog, params=params),
-                                    lambda lo: engine.slide_key_window(tiles_local, keyset, basis, lo, params=params), ks, totals, self.group)
-            self.last_path.append("window" if res is not None else "radix")
-            if res is not None:
-                return [(ord_to_float(a), ord_to_float(b)) for a, b, _ in res]
-            res = exact_rank_pairs(lambda pre, bits: engine.slide_key_histogram(tiles_local, keyset, basis, pre, bits, params=params),
-                                   lambda o: engine.slide_key_next_above(tiles_local, keyset, basis, o, params=params), ks, self.group,
-                                   hist16_fn=lambda pre: engine.slide_key_histogram16(tiles_local, keyset, basis, pre, params=params))
-            return [(ord_to_float(a), ord_to_float(b)) for a, b, _ in res]
+            return key_rank_pairs(tiles_local, keyset, basis, ks, totals, slog, params, self.group, self.last_path)
 
         def angle_of_pseudo(p):
             if abs(p) <= 1.0:
@@ -431,21 +459,122 @@ class PooledSlideStatistics:
         return M, np.asarray(maxC, dtype=np.float64)
 
 
+class PooledVahadaneStatistics:
+    """Vahadane stain matrix and 99th-percentile concentrations of the tall image made of every tile on every rank
+    (vahadane_stain_extractor.py:28-43 and normalizer.py:36,47 on the concatenation; csrc/slide_dict.hip).
+
+    The dictionary stage is DEVICE-DRIVEN: blocks of ROUNDS_PER_BLOCK rounds (sweep -> all-reduce of 32 doubles -> step) are enqueued
+    without a read-back; one read-back of the state per block says whether another block is needed.  Every rank reads the same state
+    (each step consumes all-reduced sums only), so the ranks agree on it without a collective.  The concentrations are then pinned
+    exactly by ``key_rank_pairs`` under the learnt matrix.  A rank may hold no tile; it still takes part in every collective."""
+
+    ROUNDS_PER_BLOCK = 4         # rounds enqueued between two read-backs (like kDictFixedSweeps of the per-tile schedule)
+
+    def __init__(self, group=None, luminosity_threshold=0.8, angular_percentile=99.0, lasso_lambda=0.01, dl_lambda=0.1, dl_tol=1e-7,
+                 dl_max_sweeps=200):
+        self.group = group
+        self.thr, self.pct, self.lam = luminosity_threshold, angular_percentile, lasso_lambda
+        self.dl_lambda, self.dl_tol, self.dl_max_sweeps = dl_lambda, dl_tol, int(dl_max_sweeps)
+        self.sample_log2 = None      # None: follows the slide's pixel count (sample_log2_for); 0...12: one 64-pixel sub-row in 2**s (the same on every rank)
+        self.last_path = []          # how the concentration stage settled: ["window"] or ["radix"]
+        self.last_status = 0         # SL_TILE_* of the last call
+        self.last_rounds = 0         # dictionary updates taken (sampled and full)
+        self.last_sweeps = 0         # full sweeps among them
+        self.last_blocks = 0         # read-backs of the dictionary stage
+        self._ws = None
+
+    @staticmethod
+    def sample_log2_for(n_pixels: int) -> int:
+        """Density of the sampled rounds: 1/64 of the sub-rows up to 4 Mpx (the per-tile fit samples 1/64 of the pixels), sparser beyond
+        like the one-sweep Macenko chain's sample (PooledSlideStatistics.sample_log2_for), at most one sub-row in 4096."""
+        return int(min(12, PooledSlideStatistics.sample_log2_for(n_pixels) + 6))
+
+    def params(self):
+        from . import engine
+        return engine.make_params(luminosity_threshold=self.thr, angular_percentile=self.pct, lasso_lambda=self.lam,
+                                  dl_lambda=self.dl_lambda, dl_tol=self.dl_tol, dl_max_sweeps=self.dl_max_sweeps)
+
+    def dictionary(self, tiles_local: torch.Tensor, n_tiles_total: Optional[int] = None):
+        """The dictionary stage; returns the final state as a float64 numpy array (_ffi.SDICT_STATE_DOUBLES).
+        n_tiles_total: the slide's tile count over ALL ranks (the same on every rank, or on none -- part of the collective contract, as for
+        ``PooledSlideStatistics.enqueue``); without it one MAX all-reduce agrees on the sample density."""
+        from . import engine, _ffi
+        params = self.params()
+        _, world = _world(self.group)
+        coll = _coll(world, self.group)
+        n_local, h, w, _ = tiles_local.shape
+        dev = tiles_local.device
+        slog = self.sample_log2_for(_agreed_pixels(tiles_local, n_tiles_total, world, self.group)) if self.sample_log2 is None else int(self.sample_log2)
+        if self._ws is None or self._ws[0] != (n_local, h, w, dev):
+            self._ws = ((n_local, h, w, dev), engine.sdict_workspace(n_local, h, w, dev))
+        ws = self._ws[1]
+        state = engine.sdict_begin(slog, dev, params=params)
+        sums = torch.empty((self.ROUNDS_PER_BLOCK, _ffi.SDICT_SUMS), dtype=torch.float64, device=dev)
+        # the sample stage takes at most 40 updates and the full sweeps dl_max_sweeps: the iteration settles within this many blocks
+        max_blocks = (40 + self.dl_max_sweeps + 1) // self.ROUNDS_PER_BLOCK + 2
+        for blk in range(max_blocks):
+            for r in range(self.ROUNDS_PER_BLOCK):
+                part = engine.sdict_sweep(tiles_local, slog, state, ws, sums=sums[r], params=params)
+                if coll:
+                    dist.all_reduce(part, group=self.group)
+                engine.sdict_step(state, part, params=params)
+            s = state.cpu().numpy()
+            if int(s[_ffi.SDICT_MODE]) == 0:
+                break
+        else:
+            raise RuntimeError("the slide dictionary did not settle within its sweep budget")
+        self.last_blocks = blk + 1
+        self.last_rounds, self.last_sweeps = int(s[_ffi.SDICT_ROUNDS]), int(s[_ffi.SDICT_SWEEPS])
+        return s
+
+    def __call__(self, tiles_local: torch.Tensor, n_tiles_total: Optional[int] = None):
+        """(M (2, 3), maxC (2,)) of the slide as numpy float64.  Raises TissueMaskException on an empty tissue mask (stain_utils.py:46-47).
+        A degenerate dictionary (a dead atom, parallel atoms) or a zero concentration percentile gives NaN and self.last_status != 0."""
+        import math
+        import numpy as np
+        from . import _ffi
+        from .utils.excepts import TissueMaskException
+        self.last_path = []
+        s = self.dictionary(tiles_local, n_tiles_total)
+        status = int(s[_ffi.SDICT_STATUS])
+        self.last_status = status
+        if status == _ffi.TILE_EMPTY_MASK:
+            raise TissueMaskException("Empty tissue mask computed")
+        nan = np.full(2, np.nan)
+        if status != 0:
+            return np.full((2, 3), np.nan), nan
+        M = s[_ffi.SDICT_M:_ffi.SDICT_M + 6].reshape(2, 3).copy()
+        # ---- 99th percentile of each concentration over every pixel (normalizer.py:36,47): both columns per sweep
+        n_pixels = int(round(float(s[_ffi.SDICT_NPX])))
+        slog = min(6, max(0, int(math.floor(math.log2(max(n_pixels, 1) / 4.0e6))))) if n_pixels > 4.0e6 else 0
+        k, g = percentile_position(n_pixels, 99.0)
+        (ca0, cb0), (ca1, cb1) = key_rank_pairs(tiles_local, _ffi.KEYSET_CONC, M.reshape(6), (k, k), (n_pixels, n_pixels), slog,
+                                                self.params(), self.group, self.last_path)
+        maxC = np.array([np_lerp(float(ca0), float(cb0), g), np_lerp(float(ca1), float(cb1), g)], dtype=np.float64)
+        if not (maxC > 0).all():             # normalizer.py:48 would divide by it
+            self.last_status = _ffi.TILE_ZERO_MAXC
+        return M, maxC
+
+
 class SlideNormalizer:
     """Slide-level Macenko/Vahadane normalisation over a sharded set of tiles (see module docstring).
 
     mode="median" (default): per-tile fits, all-gather, element-wise median.  mode="pooled": the exact statistics
-    of the concatenated slide (Macenko only).
+    of the concatenated slide -- ``PooledSlideStatistics`` for a Macenko normalizer, ``PooledVahadaneStatistics`` for a Vahadane one
+    (dispatched on ``normalizer.method``).
 
     graph=True (pooled mode on ONE process: no collective sits between the steps): the one-sweep chain and the apply pass behind it --
     some fifty launches -- are captured into a HIP graph the first time a (tiles buffer, out buffer) pair is seen and REPLAYED on every
     later call with the same buffers (a pipeline that refills fixed staging buffers): 512 tiles 1.92 -> 1.84 ms, 128 tiles 0.79 -> 0.77.
     The read-back after the replay is the same one; a replay that ends in a miss falls back exactly like the eager chain.  `out` is
-    allocated once and reused when the caller passes none."""
+    allocated once and reused when the caller passes none.  Macenko only: graph=True with a Vahadane normalizer raises ValueError
+    (its dictionary stage reads the state back between blocks of rounds)."""
 
     def __init__(self, normalizer, group=None, mode="median", merged=True, graph=False):
         if mode not in ("median", "pooled"):
             raise ValueError("mode must be 'median' or 'pooled'")
+        if graph and getattr(normalizer, "method", "macenko") == "vahadane":
+            raise ValueError("graph=True is not supported with a Vahadane normalizer")
         self.normalizer = normalizer          # a fitted stainlib_amd ExtractiveStainNormalizer
         self.group = group
         self.mode = mode
@@ -467,6 +596,8 @@ class SlideNormalizer:
         n_tiles_total (pooled mode, optional): the slide's tile count over all ranks; saves the one tiny all-reduce that otherwise
         agrees on the sample density.  On failure (TissueMaskException) `out` holds a copy of the input tiles."""
         from . import engine
+        if self.mode == "pooled" and getattr(self.normalizer, "method", "macenko") == "vahadane":
+            return self._transform_vahadane(tiles_local, out, n_tiles_total)
         if self.mode == "pooled":
             from . import _ffi
             stats = PooledSlideStatistics(self.group)
@@ -535,3 +666,32 @@ class SlideNormalizer:
         Mt, mct = self._targets(tiles_local.device)
         out = engine.normalize_apply(tiles_local, M_s.expand(n, 2, 3).contiguous(), maxC_s.expand(n, 2).contiguous(), Mt, mct, out=out)
         return out, M_s, maxC_s, status
+
+    def _transform_vahadane(self, tiles_local: torch.Tensor, out: Optional[torch.Tensor], n_tiles_total: Optional[int]):
+        """Pooled mode with a Vahadane normalizer: the slide's dictionary and concentrations, then the apply pass of the Macenko mode."""
+        from . import engine
+        from .utils.excepts import TissueMaskException
+        if self.graph:
+            raise ValueError("graph=True is not supported with a Vahadane normalizer")
+        stats = PooledVahadaneStatistics(self.group)
+        dev = tiles_local.device
+        n = tiles_local.shape[0]
+        if out is None:
+            out = torch.empty_like(tiles_local)
+        try:
+            M_np, maxC_np = stats(tiles_local, n_tiles_total=n_tiles_total)
+        except TissueMaskException:
+            out.copy_(tiles_local)
+            raise
+        finally:
+            self.last_path = stats.last_path
+            self.last_rounds, self.last_sweeps = stats.last_rounds, stats.last_sweeps
+        M_s = torch.as_tensor(M_np, dtype=torch.float64, device=dev)
+        maxC_s = torch.as_tensor(maxC_np, dtype=torch.float64, device=dev)
+        if stats.last_status != 0:             # unusable statistics: the tiles go through unchanged, as k_apply does for a failed tile
+            out.copy_(tiles_local)
+            return out, M_s, maxC_s, torch.full((n,), stats.last_status, dtype=torch.int32, device=dev)
+        if n:
+            Mt, mct = self._targets(dev)
+            out = engine.normalize_apply(tiles_local, M_s.expand(n, 2, 3).contiguous(), maxC_s.expand(n, 2).contiguous(), Mt, mct, out=out)
+        return out, M_s, maxC_s, torch.zeros((n,), dtype=torch.int32, device=dev)

@@ -554,6 +554,42 @@ def pool2_step(state, keyset, hist_reduced):
     _ffi.check(_ffi.lib().sl_pool2_step(_ptr(state), int(keyset), _ptr(hist_reduced), _stream()), "sl_pool2_step")
 
 
+# ---- the pooled slide-level Vahadane dictionary (sl_sdict_*): rounds of sweep -> all-reduce -> step, nothing read back ----------------
+def sdict_workspace(n, h, w, device) -> torch.Tensor:
+    need = int(_ffi.lib().sl_sdict_workspace_bytes(int(n), int(h), int(w)))
+    if need == 0:
+        raise ValueError("sl_sdict_workspace_bytes: bad arguments")
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def sdict_begin(sample_log2, device, state=None, params=None):
+    """The dictionary iteration at the Ruifrok start.  Returns the state tensor ((SDICT_STATE_DOUBLES,) float64)."""
+    p = params if params is not None else _ffi.default_params()
+    if state is None:
+        state = torch.empty((_ffi.SDICT_STATE_DOUBLES,), dtype=torch.float64, device=device)
+    _ffi.check(_ffi.lib().sl_sdict_begin(C.byref(p), int(sample_log2), _ptr(state), _stream()), "sl_sdict_begin")
+    return state
+
+
+def sdict_sweep(rgb, sample_log2, state, ws, sums=None, params=None):
+    """One round over this process's tiles (n may be 0) under the state's dictionary -> (SDICT_SUMS,) float64 to be all-reduced."""
+    if not (isinstance(rgb, torch.Tensor) and rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.dim() == 4 and rgb.shape[-1] == 3
+            and rgb.is_contiguous()):
+        raise ValueError("expected a contiguous CUDA uint8 tensor of shape (N, H, W, 3)")
+    n, h, w, _ = rgb.shape
+    p = params if params is not None else _ffi.default_params()
+    if sums is None:
+        sums = torch.empty((_ffi.SDICT_SUMS,), dtype=torch.float64, device=rgb.device)
+    _ffi.check(_ffi.lib().sl_sdict_sweep(_ptr(rgb) if n else C.c_void_p(0), n, h, w, C.byref(p), int(sample_log2), _ptr(state), _ptr(ws),
+                                         ws.numel(), _ptr(sums), _stream()), "sl_sdict_sweep")
+    return sums
+
+
+def sdict_step(state, sums_reduced, params=None):
+    p = params if params is not None else _ffi.default_params()
+    _ffi.check(_ffi.lib().sl_sdict_step(_ptr(state), _ptr(sums_reduced), C.byref(p), _stream()), "sl_sdict_step")
+
+
 def slide_key_next_above(rgb, keyset, basis, key_ords, params=None):
     """Per target: smallest key (ordered uint32, Python ints) above key_ords[t] among this process's pixels; 0xffffffff if none."""
     n, h, w = _check_tiles(rgb)
