@@ -63,11 +63,7 @@ size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 Layout make_layout(int n, long P, int method = kMethodMacenko, int schedule = 0, int fused_min_tiles = 0) {
     Layout L;
     L.max_grid = max_resident_grid();
-    L.parts = parts_for(P);
-    {   // the persistent sweep kernels walk tiles x parts items: no more parts than it takes to give every workgroup ~4 items
-        const long want = (4L * L.max_grid + n - 1) / (n > 0 ? n : 1);
-        if (L.parts > want) L.parts = (int)(want < 1 ? 1 : want);
-    }
+    L.parts = sweep_parts(P, n, L.max_grid);
     // The pixel sample steers the brackets (never the results): its SIZE sets how many pixels a bracket holds (the rank uncertainty
     // of a sample quantile goes with 1/sqrt(sample)), so Macenko tiles below 1 Mpixel are sampled more densely -- one pixel in 16 from
     // 256 Ki pixels down, up to the 16 Ki entries of a 1024^2 tile -- or their member lists overflow on real tissue (a soak over
@@ -139,7 +135,7 @@ StatsArgs stats_args(const uint8_t* rgb, int g0, int m, long P, const SlParams& 
     a.n_items = m * L.parts;
     a.stride_log2 = L.stride_log2;
     a.n_sample = L.n_sample;
-    a.ylimf = (float)y_limit_for_threshold(p.luminosity_threshold) - 2048.0f;   // exact: y_lim < 2^24
+    a.ylimf = tissue_ylimf(p);
     a.lam = p.lasso_lambda;
     a.pct = p.angular_percentile;
     a.partials = (double*)(ws + L.off_partials);
@@ -247,7 +243,7 @@ int run_fused(int method, const uint8_t* rgb, uint8_t* out, int n, long P, const
     a.P = (int)P;
     a.stride_log2 = L.stride_log2;
     a.n_sample = L.n_sample;
-    a.ylimf = (float)y_limit_for_threshold(p.luminosity_threshold) - 2048.0f;   // exact: y_lim < 2^24
+    a.ylimf = tissue_ylimf(p);
     a.lam = p.lasso_lambda;
     a.pct = p.angular_percentile;
     a.M_tgt = M_tgt;
@@ -428,9 +424,7 @@ extern "C" int sl_macenko_fit(const uint8_t* rgb, int n, int h, int w, const SlP
     // this plan's own need: sl_workspace_bytes_for(op, n, h, w, params) (sl_workspace_bytes(), the maximum over every SlParams, always suffices)
     int rc = check_common(rgb, n, h, w, workspace, workspace_bytes, pl.total);
     if (rc) return rc;
-    SlParams p;
-    sl_default_params(&p);
-    if (params) p = *params;
+    const SlParams p = params_or_defaults(params);
     char* ws = (char*)workspace;
     double* M_all = M_out ? M_out : (double*)(ws + pl.L.off_M);
     double* maxC_all = maxC_out ? maxC_out : (double*)(ws + pl.L.off_maxC);
@@ -449,9 +443,7 @@ extern "C" int sl_macenko_transform(const uint8_t* rgb, uint8_t* out, int n, int
     int rc = check_common(rgb, n, h, w, workspace, workspace_bytes, pl.total);
     if (rc) return rc;
     if (!out || !M_tgt || !maxC_tgt) return SL_ERR_BADARG;
-    SlParams p;
-    sl_default_params(&p);
-    if (params) p = *params;
+    const SlParams p = params_or_defaults(params);
     char* ws = (char*)workspace;
     double* M_all = M_src_out ? M_src_out : (double*)(ws + pl.L.off_M);
     double* maxC_all = maxC_src_out ? maxC_src_out : (double*)(ws + pl.L.off_maxC);
@@ -468,9 +460,7 @@ extern "C" int sl_vahadane_fit(const uint8_t* rgb, int n, int h, int w, const Sl
     const Layout L = (n > 0 && h > 0 && w > 0) ? make_layout(n, P, kMethodVahadane, params ? params->schedule : 0, params ? params->fused_min_tiles : 0) : Layout{};
     int rc = check_common(rgb, n, h, w, workspace, workspace_bytes, L.total);
     if (rc) return rc;
-    SlParams p;
-    sl_default_params(&p);
-    if (params) p = *params;
+    const SlParams p = params_or_defaults(params);
     char* ws = (char*)workspace;
     double* M_all = M_out ? M_out : (double*)(ws + L.off_M);
     double* maxC_all = maxC_out ? maxC_out : (double*)(ws + L.off_maxC);
@@ -496,9 +486,7 @@ extern "C" int sl_vahadane_transform(const uint8_t* rgb, uint8_t* out, int n, in
     int rc = check_common(rgb, n, h, w, workspace, workspace_bytes, L.total);
     if (rc) return rc;
     if (!out || !M_tgt || !maxC_tgt) return SL_ERR_BADARG;
-    SlParams p;
-    sl_default_params(&p);
-    if (params) p = *params;
+    const SlParams p = params_or_defaults(params);
     char* ws = (char*)workspace;
     double* M_all = M_src_out ? M_src_out : (double*)(ws + L.off_M);
     double* maxC_all = maxC_src_out ? maxC_src_out : (double*)(ws + L.off_maxC);

@@ -21,10 +21,21 @@ inline int launch_status() { return hip_err(hipGetLastError()); }
 // (and with its enumerated fields inside their ranges: an unknown two_sweep used to run as "automatic" without a word)
 inline bool params_ok(const SlParams* p) { return !p || (p->struct_size == (uint32_t)sizeof(SlParams) && p->two_sweep >= 0 && p->two_sweep <= 4); }
 
+// The SlParams a call runs with, once params_ok has accepted them: the caller's, or the defaults for NULL.
+inline SlParams params_or_defaults(const SlParams* params) {
+    SlParams p;
+    sl_default_params(&p);
+    if (params) p = *params;
+    return p;
+}
+
 // Largest index into OpenCV's LabCbrtTab_b whose 8-bit L satisfies L/255.0 < threshold, +1,
 // shifted to the fixed-point scale the kernels compare against (see is_tissue()).
 // 0 means "no pixel is tissue".
 uint32_t y_limit_for_threshold(double luminosity_threshold);
+
+// The tissue limit as the sweep kernels take it: y_limit_for_threshold - 2048 as a float (exact: y_lim < 2^24).
+inline float tissue_ylimf(const SlParams& p) { return (float)y_limit_for_threshold(p.luminosity_threshold) - 2048.0f; }
 
 // resident persistent-sweep workgroups of the current device (2 per CU; see common.hip)
 int max_resident_grid();
@@ -44,6 +55,14 @@ inline bool aligned4(const void* p, long pixels_per_tile) {
 inline int parts_for(long P) {
     long p = (P + 32767) / 32768;
     return (int)(p < 1 ? 1 : p);
+}
+
+// parts_for(P) for n tiles walked by max_grid persistent workgroups: no more parts than it takes to give every workgroup ~4 items.
+// (n <= 0 is taken as one tile: workspace sizing asks before the tile count is checked.)
+inline int sweep_parts(long P, int n, int max_grid) {
+    const int parts = parts_for(P);
+    const long want = (4L * max_grid + n - 1) / (n > 0 ? n : 1);
+    return parts > want ? (int)(want < 1 ? 1 : want) : parts;
 }
 
 // Brackets one launch with two caller-provided events when the class is selected (see SlProfile).

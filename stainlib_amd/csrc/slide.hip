@@ -461,17 +461,13 @@ int fill_args(SlideArgs& a, const uint8_t* rgb, int n, int h, int w, const SlPar
     if (!rgb || n <= 0 || h <= 0 || w <= 0 || !basis_host) return SL_ERR_BADARG;
     if ((long)h * w > (1L << 30)) return SL_ERR_BADARG;
     if (keyset != SL_KEYSET_ANGLE && keyset != SL_KEYSET_CONC) return SL_ERR_BADARG;
-    SlParams p;
-    sl_default_params(&p);
     if (!params_ok(params)) return SL_ERR_BADARG;
-    if (params) p = *params;
+    const SlParams p = params_or_defaults(params);
     a.rgb = rgb;
     a.P = h * w;
-    a.parts = parts_for((long)h * w);
-    const long want = (4L * max_resident_grid() + n - 1) / n;   // ~4 items per persistent workgroup
-    if (a.parts > want) a.parts = (int)(want < 1 ? 1 : want);
+    a.parts = sweep_parts((long)h * w, n, max_resident_grid());
     a.n_items = n * a.parts;
-    a.ylimf = (float)y_limit_for_threshold(p.luminosity_threshold) - 2048.0f;
+    a.ylimf = tissue_ylimf(p);
     a.keyset = keyset;
     a.lam = p.lasso_lambda;
     for (int i = 0; i < 6; ++i) { a.V[i] = (float)basis_host[i]; a.M[i] = basis_host[i]; }
@@ -647,6 +643,9 @@ void launch_keys(const SlideArgs& a, bool al, unsigned long long* hist, uint32_t
     }
 }
 
+// the basis fill_args is given by the sl_pool_* sweeps, whose keys come from the pool state (SlideArgs::dyn) instead
+const double kIdentityBasis[6] = {1, 0, 0, 0, 1, 0};
+
 }  // namespace
 
 extern "C" int sl_tile_moments(const uint8_t* rgb, int n, int h, int w, const SlParams* params, double* moments_out,
@@ -654,18 +653,13 @@ extern "C" int sl_tile_moments(const uint8_t* rgb, int n, int h, int w, const Sl
     if (!rgb || !moments_out || n <= 0 || h <= 0 || w <= 0) return SL_ERR_BADARG;
     const long P = (long)h * w;
     if (P > (1L << 30)) return SL_ERR_BADARG;
-    int parts = parts_for(P);
-    const size_t need = sizeof(double) * 10 * (size_t)parts * (size_t)n;
+    const size_t need = sizeof(double) * 10 * (size_t)parts_for(P) * (size_t)n;
     if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7u)) return SL_ERR_WORKSPACE;
     const int mg = max_resident_grid();
-    const long want = (4L * mg + n - 1) / n;                      // ~4 items per persistent workgroup
-    if (parts > want) parts = (int)(want < 1 ? 1 : want);
+    const int parts = sweep_parts(P, n, mg);
     const long items = (long)n * parts;
-    SlParams p;
-    sl_default_params(&p);
     if (!params_ok(params)) return SL_ERR_BADARG;
-    if (params) p = *params;
-    const float ylimf = (float)y_limit_for_threshold(p.luminosity_threshold) - 2048.0f;
+    const float ylimf = tissue_ylimf(params_or_defaults(params));
     hipStream_t s = (hipStream_t)stream;
     const dim3 g((unsigned)(items < mg ? items : mg)), b(kSweepThreads);
     if (aligned4(rgb, P))
@@ -716,6 +710,23 @@ extern "C" int sl_slide_key_histogram_sampled(const uint8_t* rgb, int n, int h, 
     return launch_status();
 }
 
+namespace {
+
+// the window sweep of sl_slide_key_window and sl_pool_window
+void launch_window(const SlideArgs& a, bool al, unsigned long long* hist_below, hipStream_t s) {
+    const int mg = max_resident_grid();
+    const dim3 g((unsigned)(a.n_items < mg ? a.n_items : mg)), b(kSweepThreads);
+    if (a.keyset == SL_KEYSET_ANGLE) {
+        if (al) hipLaunchKernelGGL((k_slide_window<SL_KEYSET_ANGLE, true>), g, b, 0, s, a, hist_below);
+        else    hipLaunchKernelGGL((k_slide_window<SL_KEYSET_ANGLE, false>), g, b, 0, s, a, hist_below);
+    } else {
+        if (al) hipLaunchKernelGGL((k_slide_window<SL_KEYSET_CONC, true>), g, b, 0, s, a, hist_below);
+        else    hipLaunchKernelGGL((k_slide_window<SL_KEYSET_CONC, false>), g, b, 0, s, a, hist_below);
+    }
+}
+
+}  // namespace
+
 extern "C" int sl_slide_key_window(const uint8_t* rgb, int n, int h, int w, const SlParams* params, int keyset,
                                    const double* basis, const uint32_t* window_lo, unsigned long long* hist_below, void* stream) {
     SlideArgs a;
@@ -736,19 +747,7 @@ extern "C" int sl_slide_key_window(const uint8_t* rgb, int n, int h, int w, cons
     // concentrations: the binary32 comparison stands in for the ordered-integer one only for c >= +0 (g12 < 0 included: exact keys either way)
     if (!usable)
         for (int t = 0; t < 2; ++t) { a.win_flo[t] = -INFINITY; a.win_fhi[t] = INFINITY; }
-    {
-        const bool al = aligned4(rgb, (long)h * w);
-        const int mg = max_resident_grid();
-        const dim3 g((unsigned)(a.n_items < mg ? a.n_items : mg)), b(kSweepThreads);
-        hipStream_t s = (hipStream_t)stream;
-        if (keyset == SL_KEYSET_ANGLE) {
-            if (al) hipLaunchKernelGGL((k_slide_window<SL_KEYSET_ANGLE, true>), g, b, 0, s, a, hist_below);
-            else    hipLaunchKernelGGL((k_slide_window<SL_KEYSET_ANGLE, false>), g, b, 0, s, a, hist_below);
-        } else {
-            if (al) hipLaunchKernelGGL((k_slide_window<SL_KEYSET_CONC, true>), g, b, 0, s, a, hist_below);
-            else    hipLaunchKernelGGL((k_slide_window<SL_KEYSET_CONC, false>), g, b, 0, s, a, hist_below);
-        }
-    }
+    launch_window(a, aligned4(rgb, (long)h * w), hist_below, (hipStream_t)stream);
     return launch_status();
 }
 
@@ -767,19 +766,15 @@ extern "C" int sl_slide_key_next_above(const uint8_t* rgb, int n, int h, int w, 
 // ---- device-driven pooled statistics: see k_pool_* above and include/stainlib_hip.h ----
 extern "C" int sl_pool_begin(const double* moments11, const SlParams* params, double* state, void* stream) {
     if (!moments11 || !state) return SL_ERR_BADARG;
-    SlParams p;
-    sl_default_params(&p);
     if (!params_ok(params)) return SL_ERR_BADARG;
-    if (params) p = *params;
-    hipLaunchKernelGGL(k_pool_begin, dim3(1), dim3(64), 0, (hipStream_t)stream, moments11, state, p.angular_percentile);
+    hipLaunchKernelGGL(k_pool_begin, dim3(1), dim3(64), 0, (hipStream_t)stream, moments11, state, params_or_defaults(params).angular_percentile);
     return launch_status();
 }
 
 extern "C" int sl_pool_histogram(const uint8_t* rgb, int n, int h, int w, const SlParams* params, int keyset, const double* state,
                                  int round, int sample_log2, unsigned long long* hist, void* stream) {
-    static const double dummy_basis[6] = {1, 0, 0, 0, 1, 0};
     SlideArgs a;
-    const int rc = fill_args(a, rgb, n, h, w, params, keyset, dummy_basis);
+    const int rc = fill_args(a, rgb, n, h, w, params, keyset, kIdentityBasis);
     if (rc) return rc;
     if (!hist || !state || round < 0 || round > 3 || sample_log2 < 0 || sample_log2 > 12) return SL_ERR_BADARG;
     a.dyn = state;
@@ -797,32 +792,18 @@ extern "C" int sl_pool_pick(double* state, int keyset, int round, const unsigned
 
 extern "C" int sl_pool_window(const uint8_t* rgb, int n, int h, int w, const SlParams* params, int keyset, const double* state,
                               unsigned long long* hist_below, void* stream) {
-    static const double dummy_basis[6] = {1, 0, 0, 0, 1, 0};
     SlideArgs a;
-    const int rc = fill_args(a, rgb, n, h, w, params, keyset, dummy_basis);
+    const int rc = fill_args(a, rgb, n, h, w, params, keyset, kIdentityBasis);
     if (rc) return rc;
     if (!hist_below || !state) return SL_ERR_BADARG;
     a.dyn = state;
-    const bool al = aligned4(rgb, (long)h * w);
-    const int mg = max_resident_grid();
-    const dim3 g((unsigned)(a.n_items < mg ? a.n_items : mg)), b(kSweepThreads);
-    hipStream_t s = (hipStream_t)stream;
-    if (keyset == SL_KEYSET_ANGLE) {
-        if (al) hipLaunchKernelGGL((k_slide_window<SL_KEYSET_ANGLE, true>), g, b, 0, s, a, hist_below);
-        else    hipLaunchKernelGGL((k_slide_window<SL_KEYSET_ANGLE, false>), g, b, 0, s, a, hist_below);
-    } else {
-        if (al) hipLaunchKernelGGL((k_slide_window<SL_KEYSET_CONC, true>), g, b, 0, s, a, hist_below);
-        else    hipLaunchKernelGGL((k_slide_window<SL_KEYSET_CONC, false>), g, b, 0, s, a, hist_below);
-    }
+    launch_window(a, aligned4(rgb, (long)h * w), hist_below, (hipStream_t)stream);
     return launch_status();
 }
 
 extern "C" int sl_pool_resolve(double* state, int keyset, const unsigned long long* window_reduced, const SlParams* params, void* stream) {
     if (!state || !window_reduced || (keyset != SL_KEYSET_ANGLE && keyset != SL_KEYSET_CONC)) return SL_ERR_BADARG;
-    SlParams p;
-    sl_default_params(&p);
     if (!params_ok(params)) return SL_ERR_BADARG;
-    if (params) p = *params;
-    hipLaunchKernelGGL(k_pool_resolve, dim3(1), dim3(1024), 0, (hipStream_t)stream, state, window_reduced, keyset, p.lasso_lambda);
+    hipLaunchKernelGGL(k_pool_resolve, dim3(1), dim3(1024), 0, (hipStream_t)stream, state, window_reduced, keyset, params_or_defaults(params).lasso_lambda);
     return launch_status();
 }

@@ -183,13 +183,6 @@ __global__ __launch_bounds__(kSdStepThreads) void k_sd_step(double* st, const do
     }
 }
 
-bool sd_params(const SlParams* params, SlParams& p) {
-    if (!params_ok(params)) return false;
-    sl_default_params(&p);
-    if (params) p = *params;
-    return true;
-}
-
 }  // namespace
 
 extern "C" size_t sl_sdict_workspace_bytes(int n, int h, int w) {
@@ -200,17 +193,16 @@ extern "C" size_t sl_sdict_workspace_bytes(int n, int h, int w) {
 }
 
 extern "C" int sl_sdict_begin(const SlParams* params, int sample_log2, double* state, void* stream) {
-    SlParams p;
-    if (!state || sample_log2 < 0 || sample_log2 > 12 || !sd_params(params, p)) return SL_ERR_BADARG;
+    if (!state || sample_log2 < 0 || sample_log2 > 12 || !params_ok(params)) return SL_ERR_BADARG;
     hipLaunchKernelGGL(k_sd_begin, dim3(1), dim3(64), 0, (hipStream_t)stream, state, sample_log2);
     return launch_status();
 }
 
 extern "C" int sl_sdict_sweep(const uint8_t* rgb, int n, int h, int w, const SlParams* params, int sample_log2, const double* state,
                               void* workspace, size_t workspace_bytes, double* sums_out, void* stream) {
-    SlParams p;
     if (!state || !sums_out || n < 0 || h <= 0 || w <= 0 || (n > 0 && !rgb)) return SL_ERR_BADARG;
-    if (sample_log2 < 0 || sample_log2 > 12 || !sd_params(params, p)) return SL_ERR_BADARG;
+    if (sample_log2 < 0 || sample_log2 > 12 || !params_ok(params)) return SL_ERR_BADARG;
+    const SlParams p = params_or_defaults(params);
     const long P = (long)h * w;
     if (P > (1L << 30) || (long)n * P > (1L << 40)) return SL_ERR_BADARG;
     const size_t need = sl_sdict_workspace_bytes(n, h, w);
@@ -221,7 +213,7 @@ extern "C" int sl_sdict_sweep(const uint8_t* rgb, int n, int h, int w, const SlP
         const int parts = sd_parts(P);
         const int items = n * parts;
         rows = sd_grid(n, P);
-        const float ylimf = (float)y_limit_for_threshold(p.luminosity_threshold) - 2048.0f;
+        const float ylimf = tissue_ylimf(p);
         const dim3 g((unsigned)rows), b(kSweepThreads);
         if (aligned4(rgb, P))
             hipLaunchKernelGGL((k_sd_sweep<true>), g, b, 0, s, rgb, (int)P, parts, items, sample_log2, ylimf, p.dl_lambda, state, (double*)workspace);
@@ -233,8 +225,8 @@ extern "C" int sl_sdict_sweep(const uint8_t* rgb, int n, int h, int w, const SlP
 }
 
 extern "C" int sl_sdict_step(double* state, const double* sums_reduced, const SlParams* params, void* stream) {
-    SlParams p;
-    if (!state || !sums_reduced || !sd_params(params, p)) return SL_ERR_BADARG;
+    if (!state || !sums_reduced || !params_ok(params)) return SL_ERR_BADARG;
+    const SlParams p = params_or_defaults(params);
     if (!(p.dl_lambda >= 0.0) || !(p.dl_tol > 0.0) || p.dl_max_sweeps < 1) return SL_ERR_BADARG;
     hipLaunchKernelGGL(k_sd_step, dim3(1), dim3(kSdStepThreads), 0, (hipStream_t)stream, state, sums_reduced, p.dl_lambda, p.dl_tol,
                        p.dl_max_sweeps);

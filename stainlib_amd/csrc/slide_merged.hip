@@ -98,9 +98,7 @@ P2Layout p2_layout(int n, int h, int w, int slog) {
     P2Layout L;
     const long P = (long)h * w;
     const int mg = max_resident_grid();
-    L.parts = parts_for(P);
-    const long want = (4L * mg + n - 1) / n;
-    if (L.parts > want) L.parts = (int)(want < 1 ? 1 : want);
+    L.parts = sweep_parts(P, n, mg);
     L.n_items = n * L.parts;
     L.grid = L.n_items < mg ? L.n_items : mg;
     const long nch = (P + 3) >> 2;
@@ -1125,9 +1123,8 @@ __global__ __launch_bounds__(1024) void k_p2_step(double* st, const unsigned lon
 int p2_check(const uint8_t* rgb, int n, int h, int w, const SlParams* params, int slog, const void* ws, size_t ws_bytes, SlParams& p, P2Layout& L) {
     if (!rgb || n <= 0 || h <= 0 || w <= 0 || slog < 0 || slog > 12) return SL_ERR_BADARG;
     if ((long)h * w > (1L << 30) || (long)n * h * w > (1L << 40)) return SL_ERR_BADARG;
-    sl_default_params(&p);
     if (!params_ok(params)) return SL_ERR_BADARG;
-    if (params) p = *params;
+    p = params_or_defaults(params);
     L = p2_layout(n, h, w, slog);
     if (!ws || ws_bytes < L.total || ((uintptr_t)ws & 255u)) return SL_ERR_WORKSPACE;
     return SL_OK;
@@ -1152,7 +1149,7 @@ extern "C" int sl_pool2_sample(const uint8_t* rgb, int n, int h, int w, const Sl
     zero_async(ws, 256, s);                                     // (a kernel: see common.hip)
     P2SampleArgs a;
     a.rgb = rgb; a.P = h * w; a.parts = L.parts; a.n_items = L.n_items; a.slog = sample_log2; a.bpi = L.bpi;
-    a.ylimf = (float)y_limit_for_threshold(p.luminosity_threshold) - 2048.0f;
+    a.ylimf = tissue_ylimf(p);
     a.list = P2List{(uint32_t*)(ws + L.s_entries), (uint32_t*)(ws + L.s_counts), (unsigned int*)(ws + L.hdr), L.s_cap, kP2SampleBlkLog2, 0u, 0u};
     a.partials = (double*)(ws + L.partials);
     const dim3 g((unsigned)L.grid), b(kSweepThreads);
@@ -1165,10 +1162,8 @@ extern "C" int sl_pool2_sample(const uint8_t* rgb, int n, int h, int w, const Sl
 
 extern "C" int sl_pool2_begin(const double* moments16_reduced, const SlParams* params, int sample_log2, double* state, void* stream) {
     if (!moments16_reduced || !state || sample_log2 < 0 || sample_log2 > 12) return SL_ERR_BADARG;
-    SlParams p;
-    sl_default_params(&p);
     if (!params_ok(params)) return SL_ERR_BADARG;
-    if (params) p = *params;
+    const SlParams p = params_or_defaults(params);
     hipLaunchKernelGGL(k_p2_begin, dim3(1), dim3(64), 0, (hipStream_t)stream, moments16_reduced, state, p.angular_percentile, p.lasso_lambda,
                        sample_log2);
     return launch_status();
@@ -1241,7 +1236,7 @@ extern "C" int sl_pool2_sweep(const uint8_t* rgb, int n, int h, int w, const SlP
     zero_async(ws + L.c_counts, 4 * (size_t)L.c_cap, s);
     P2SweepArgs a;
     a.rgb = rgb; a.P = h * w; a.parts = L.parts; a.n_items = L.n_items;
-    a.ylimf = (float)y_limit_for_threshold(p.luminosity_threshold) - 2048.0f;
+    a.ylimf = tissue_ylimf(p);
     a.state = state;
     const uint32_t pool0 = (uint32_t)L.grid * (kSweepThreads / 64) * L.c_priv;
     a.list = P2List{(uint32_t*)(ws + L.c_entries), (uint32_t*)(ws + L.c_counts), (unsigned int*)(ws + L.hdr + 64), L.c_cap, kP2CandBlkLog2, L.c_priv, pool0};

@@ -29,8 +29,10 @@ This is an extension (the reference has no notion of a slide); its check is the 
 """
 from __future__ import annotations
 
+import math
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -52,6 +54,13 @@ def _coll(world: int, group=None) -> bool:
     if world > 1:
         return True
     return bool(COLLECTIVES_AT_WORLD_1 and group is not False and dist.is_available() and dist.is_initialized())
+
+
+def _reduced(t: torch.Tensor, world: int, group=None) -> torch.Tensor:
+    """t, summed over the ranks in place when the collectives run (``_coll``)."""
+    if _coll(world, group):
+        dist.all_reduce(t, group=group)
+    return t
 
 
 def _world(group=None):
@@ -106,7 +115,6 @@ def ord_to_float(o: int) -> float:
 
 def percentile_position(n: int, pct: float):
     """numpy.percentile(method='linear'): 0-based rank k and interpolation weight g between ranks k and k+1."""
-    import math
     vi = min(max((pct / 100.0) * (n - 1), 0.0), float(n - 1))
     k = math.floor(vi)
     return int(k), vi - k
@@ -128,7 +136,6 @@ def exact_rank_pairs(hist_fn, next_above_fn, ks, group=None, hist16_fn=None, fra
     int64 (2, 65536) (the low 16 bits of the keys under a 16-bit prefix) the last two rounds are one sweep: 8 + 8 + 16
     bits.  The k+1-th key is read off the last round's histogram (its bins are keys); the extra next_above sweep only
     runs when the k-th key is the largest of its window and unique."""
-    import numpy as np
     _, world = _world(group)
     prefix, below, in_bin, total, k = [0, 0], [0, 0], [0, 0], [None, None], [int(ks[0]), int(ks[1])]
     succ = [None, None]          # the next larger key inside the last round's window, if there is one
@@ -182,7 +189,6 @@ def window_rank_pairs(sample_hist_fn, window_fn, ks, totals, group=None):
     lo[t].  The window is centred on the estimate; if the wanted ranks k and k + 1 (totals[t] keys in all) do not both
     fall inside it -- the estimate was off by more than 32768 consecutive binary32 values -- the answer is None and the
     caller takes the radix rounds.  Everything is all-reduced, so all ranks decide alike."""
-    import numpy as np
     _, world = _world(group)
     fr = [(int(ks[t]) / (totals[t] - 1)) if totals[t] > 1 else 0.0 for t in range(2)]
     try:
@@ -237,7 +243,11 @@ def key_rank_pairs(tiles_local: torch.Tensor, keyset: int, basis, ks, totals, sa
 
 
 def _agreed_pixels(tiles_local, n_tiles_total, world, group):
-    """The slide's pixel count as every rank computes it alike (see ``PooledSlideStatistics.enqueue``)."""
+    """The slide's pixel count as every rank computes it alike.  A sample density must be the SAME on every rank (the sampled histograms
+    are all-reduced), so it is derived from a rank-independent tile count: the caller's n_tiles_total, else the largest shard (shard_range
+    gives ceil(n / world) to some rank) agreed on with one tiny MAX all-reduce whose result is read back -- NOT from this rank's own n_local,
+    which differs by one tile across ranks on uneven shards and can sit on the other side of a power of two (3 vs 4 tiles of 1024^2 on two
+    ranks; round-3 advisor finding).  Results never depend on it, only which route settles them."""
     n_local, h, w, _ = tiles_local.shape
     if n_tiles_total is not None:
         return int(n_tiles_total) * h * w
@@ -248,17 +258,41 @@ def _agreed_pixels(tiles_local, n_tiles_total, world, group):
     return world * n_local * h * w
 
 
-class PooledSlideStatistics:
-    """Stain matrix and 99th-percentile concentrations of the tall image made of every tile on every rank."""
+def window_sample_log2(n_pixels: int) -> int:
+    """Density of the window path's pixel sample (one row in 2**result): ~4 M pixels of the slide or more, everything for small slides."""
+    return min(6, max(0, int(math.floor(math.log2(max(n_pixels, 1) / 4.0e6))))) if n_pixels > 4.0e6 else 0
+
+
+def pooled_max_concentrations(tiles_local: torch.Tensor, M, n_pixels: int, params, group=None, path=None):
+    """99th percentile of each concentration under the stain matrix M (numpy 2x3) over the slide's n_pixels pixels (normalizer.py:36,47),
+    both columns per sweep, as numpy float64 (2,).  Appends the route of ``key_rank_pairs`` to ``path``."""
+    from . import _ffi
+    k, g = percentile_position(n_pixels, 99.0)
+    (ca0, cb0), (ca1, cb1) = key_rank_pairs(tiles_local, _ffi.KEYSET_CONC, M.reshape(6), (k, k), (n_pixels, n_pixels),
+                                            window_sample_log2(n_pixels), params, group, path)
+    return np.array([np_lerp(float(ca0), float(cb0), g), np_lerp(float(ca1), float(cb1), g)], dtype=np.float64)
+
+
+class _PooledStatistics:
+    """What the pooled statistics of both methods share: the process group and the normalizer's parameters."""
 
     def __init__(self, group=None, luminosity_threshold=0.8, angular_percentile=99.0, lasso_lambda=0.01):
         self.group = group
         self.thr, self.pct, self.lam = luminosity_threshold, angular_percentile, lasso_lambda
-        self.last_path = []          # per stage of the last call: "merged" (the one-sweep chain), "window" (a sweep per stage) or "radix" (the fallback rounds)
-        self.last_miss = 0           # state[POOL_MISS] of the last device-driven chain read back
-        self.last_why = 0            # state[POOL2_WHY] of the last one-sweep chain (why the sample gave no estimate)
+        self.last_path = []          # how each stage of the last call settled ("merged", "window" or "radix")
         self.sample_log2 = None      # None: the sample density follows the slide's pixel count (sample_log2_for); 0...12: one 64-pixel sub-row in 2^s
                                      # (tests and experiments; the same on every rank -- the RESULT does not depend on it, only which route settles it)
+
+    def params(self):
+        from . import engine
+        return engine.make_params(luminosity_threshold=self.thr, angular_percentile=self.pct, lasso_lambda=self.lam)
+
+
+class PooledSlideStatistics(_PooledStatistics):
+    """Stain matrix and 99th-percentile concentrations of the tall image made of every tile on every rank."""
+
+    last_miss = 0                # state[POOL_MISS] of the last device-driven chain read back
+    last_why = 0                 # state[POOL2_WHY] of the last one-sweep chain (why the sample gave no estimate)
 
     def enqueue(self, tiles_local: torch.Tensor, ws=None, n_tiles_total: Optional[int] = None) -> torch.Tensor:
         """DEVICE-DRIVEN: enqueue the whole computation (4 full sweeps, 6 sampled passes, the all-reduces between them and the
@@ -271,44 +305,24 @@ class PooledSlideStatistics:
         the sample density is agreed on with one small MAX all-reduce of the shard sizes whose result IS read back (a host
         synchronisation per call): pass the total where the call sits on a latency-critical path.  Ranks that disagree on whether they
         pass it issue different collective sequences and hang -- it is part of the call's collective contract."""
-        import math
         from . import engine, _ffi
-        params = engine.make_params(luminosity_threshold=self.thr, angular_percentile=self.pct, lasso_lambda=self.lam)
+        params = self.params()
         _, world = _world(self.group)
         n_local, h, w, _ = tiles_local.shape
         dev = tiles_local.device
         # 10 moment sums + this rank's pixel count (torch.full: a fill kernel -- a scalar copied from the host could not be captured)
-        mom = torch.cat([engine.tile_moments(tiles_local, params=params, ws=ws).sum(dim=0),
-                         torch.full((1,), float(n_local * h * w), dtype=torch.float64, device=dev)])
-        if _coll(world, self.group):
-            dist.all_reduce(mom, group=self.group)
+        mom = _reduced(torch.cat([engine.tile_moments(tiles_local, params=params, ws=ws).sum(dim=0),
+                                  torch.full((1,), float(n_local * h * w), dtype=torch.float64, device=dev)]), world, self.group)
         state = engine.pool_begin(mom, params=params)
-        # the sample: ~4 M pixels of the slide or more.  The density must be the SAME on every rank (the sampled histograms are
-        # all-reduced), so it is derived from a rank-independent tile count: the caller's n_tiles_total, else the largest shard
-        # (shard_range gives ceil(n / world) to some rank) agreed on with one tiny MAX all-reduce -- NOT from this rank's own
-        # n_local, which differs by one tile across ranks on uneven shards and can sit on the other side of a power of two
-        # (3 vs 4 tiles of 1024^2 on two ranks; round-3 advisor finding).  Results never depended on it, the window hit rate did.
-        if n_tiles_total is not None:
-            n_pixels = int(n_tiles_total) * h * w
-        elif _coll(world, self.group) and world > 1:
-            nl = torch.tensor([n_local], dtype=torch.int64, device=dev if dist.get_backend(self.group) == "nccl" else "cpu")
-            dist.all_reduce(nl, op=dist.ReduceOp.MAX, group=self.group)
-            n_pixels = world * int(nl.item()) * h * w
-        else:
-            n_pixels = world * n_local * h * w
-        slog = min(6, max(0, int(math.floor(math.log2(max(n_pixels, 1) / 4.0e6))))) if n_pixels > 4.0e6 else 0
+        slog = window_sample_log2(_agreed_pixels(tiles_local, n_tiles_total, world, self.group))
         hists = torch.zeros((2, 3, 2, 256), dtype=torch.int64, device=dev)
         wins = torch.zeros((2, 2 * 65536 + 2), dtype=torch.int64, device=dev)
         for si, keyset in enumerate((_ffi.KEYSET_ANGLE, _ffi.KEYSET_CONC)):
             for rnd in range(3):
                 hb = engine.pool_histogram(tiles_local, keyset, state, rnd, slog, hists[si, rnd], params=params)
-                if _coll(world, self.group):
-                    dist.all_reduce(hb, group=self.group)
-                engine.pool_pick(state, keyset, rnd, hb)
+                engine.pool_pick(state, keyset, rnd, _reduced(hb, world, self.group))
             wb = engine.pool_window(tiles_local, keyset, state, wins[si], params=params)
-            if _coll(world, self.group):
-                dist.all_reduce(wb, group=self.group)
-            engine.pool_resolve(state, keyset, wb, params=params)
+            engine.pool_resolve(state, keyset, _reduced(wb, world, self.group), params=params)
         return state
 
     MERGED_LEVELS = 3            # window levels enqueued per key set by the one-sweep chain (11 key bits each; SL_POOL2_LEVELS)
@@ -318,31 +332,26 @@ class PooledSlideStatistics:
     def sample_log2_for(n_pixels: int) -> int:
         """Density of the merged chain's pixel sample (one 64-pixel sub-row in 2**result): everything up to 4 Mpx, then the sample grows
         like the slide's size to the power 2/3 -- the candidate lists shrink like 1/sqrt(sample) while the sample passes grow with it."""
-        import math
         if n_pixels <= (1 << 22):
             return 0
         return int(min(12, max(0, math.floor((math.log2(n_pixels) - 11.0) / 3.0))))
-
-    def _agreed_pixels(self, tiles_local, n_tiles_total, world):
-        """The slide's pixel count as every rank computes it alike (see ``enqueue``)."""
-        return _agreed_pixels(tiles_local, n_tiles_total, world, self.group)
 
     def enqueue_merged(self, tiles_local: torch.Tensor, ws=None, n_tiles_total: Optional[int] = None) -> torch.Tensor:
         """DEVICE-DRIVEN, ONE full sweep (round 6; csrc/slide_merged.hip): a stratified pixel sample of the whole slide gives an estimate
         of the eigenvectors, the angular brackets and the stain matrix; the one sweep over the tiles computes the exact moment sums AND
         appends every pixel that is not proven plain under that estimate to a candidate list; the exact order statistics are then those
-        of the candidates (four passes over the list).  Eight small all-reduces; returns the pool state (device float64,
-        _ffi.POOL2_STATE_DOUBLES) with the layout of ``enqueue``'s in its first ten entries.  state[POOL_MISS] != 0 at the end: a check
-        of the estimate failed (or a list overflowed) -- results never depend on the sample, the caller takes ``enqueue`` then.
+        of the candidates (four passes over the list).  Ten small all-reduces: the sample moments, the two sample histograms, the sweep
+        totals and six candidate levels -- and one MAX more when n_tiles_total is None on more than one rank.  Returns the pool state
+        (device float64, _ffi.POOL2_STATE_DOUBLES) with the layout of ``enqueue``'s in its first ten entries.  state[POOL_MISS] != 0 at the
+        end: a check of the estimate failed (or a list overflowed) -- results never depend on the sample, the caller takes ``enqueue`` then.
         n_tiles_total: as for ``enqueue`` (the same on every rank, or on none).  ws: None, or a dict the caller keeps between calls (the
         chain's workspace -- sample list, candidate list of up to 1/8 of the pixels -- is then allocated once per shape)."""
         from . import engine, _ffi
-        params = engine.make_params(luminosity_threshold=self.thr, angular_percentile=self.pct, lasso_lambda=self.lam)
+        params = self.params()
         _, world = _world(self.group)
         n_local, h, w, _ = tiles_local.shape
         dev = tiles_local.device
-        coll = _coll(world, self.group)
-        slog = self.sample_log2_for(self._agreed_pixels(tiles_local, n_tiles_total, world)) if self.sample_log2 is None else int(self.sample_log2)
+        slog = self.sample_log2_for(_agreed_pixels(tiles_local, n_tiles_total, world, self.group)) if self.sample_log2 is None else int(self.sample_log2)
         if ws is None or ws.get("key") != (n_local, h, w, slog, dev):
             buf = engine.pool2_workspace(n_local, h, w, slog, dev)
             if ws is not None:               # a caller's cache (a dict): the buffer is reused by its next call with this shape
@@ -350,32 +359,27 @@ class PooledSlideStatistics:
                 ws.update(key=(n_local, h, w, slog, dev), buf=buf)
             ws = {"buf": buf}
         ws = ws["buf"]
-        if not coll and self.one_call:       # one process: the chain enqueued by ONE call into the library (the same kernels in the same order)
+        if not _coll(world, self.group) and self.one_call:   # one process: the chain enqueued by ONE call into the library (the same kernels in the same order)
             self._merged_ws = ws
             return engine.pool2_local(tiles_local, slog, ws, params=params)
         shape = (n_local, h, w)
         hists = torch.empty((2 + 2 * self.MERGED_LEVELS, _ffi.POOL2_HIST_WORDS), dtype=torch.int64, device=dev)   # every pass writes its buffer whole
-
-        def reduced(t):
-            if coll:
-                dist.all_reduce(t, group=self.group)
-            return t
-        mom = reduced(engine.pool2_sample(tiles_local, slog, ws, params=params))
+        mom = _reduced(engine.pool2_sample(tiles_local, slog, ws, params=params), world, self.group)
         state = engine.pool2_begin(mom, slog, params=params)
         for i, keyset in enumerate((_ffi.KEYSET_ANGLE, _ffi.KEYSET_CONC)):
-            engine.pool2_bands(state, keyset, reduced(engine.pool2_hist(0, keyset, 0, shape, slog, state, ws, hists[i], params=params)))
-        engine.pool2_exact(reduced(engine.pool2_sweep(tiles_local, slog, state, ws, params=params)), state)
+            hist = engine.pool2_hist(0, keyset, 0, shape, slog, state, ws, hists[i], params=params)
+            engine.pool2_bands(state, keyset, _reduced(hist, world, self.group))
+        engine.pool2_exact(_reduced(engine.pool2_sweep(tiles_local, slog, state, ws, params=params), world, self.group), state)
         for i, keyset in enumerate((_ffi.KEYSET_ANGLE, _ffi.KEYSET_CONC)):
             for level in range(self.MERGED_LEVELS):      # (a settled key set turns its remaining passes and steps into no-ops)
-                h = hists[2 + self.MERGED_LEVELS * i + level]
-                engine.pool2_step(state, keyset, reduced(engine.pool2_hist(1, keyset, 1, shape, slog, state, ws, h, params=params)))
+                hist = engine.pool2_hist(1, keyset, 1, shape, slog, state, ws, hists[2 + self.MERGED_LEVELS * i + level], params=params)
+                engine.pool2_step(state, keyset, _reduced(hist, world, self.group))
         self._merged_ws = ws             # (kept until the next call: the chain's kernels are still queued when this returns)
         return state
 
     def finish(self, state: torch.Tensor):
         """The one read-back of the device-driven path: (M, maxC) as numpy, or None when a window missed (the caller then runs the
         host-driven rounds).  Raises like the reference on an empty tissue mask."""
-        import numpy as np
         from . import _ffi
         from .utils.excepts import TissueMaskException
         s = state.cpu().numpy()
@@ -390,27 +394,36 @@ class PooledSlideStatistics:
         self.last_path = ["merged", "merged"] if len(s) == _ffi.POOL2_STATE_DOUBLES else ["window", "window"]
         return s[_ffi.POOL_M:_ffi.POOL_M + 6].reshape(2, 3).copy(), s[_ffi.POOL_MAXC:_ffi.POOL_MAXC + 2].copy()
 
-    def __call__(self, tiles_local: torch.Tensor, device_driven: bool = True, n_tiles_total: Optional[int] = None, merged: bool = True):
-        """(M, maxC) of the slide.  n_tiles_total: see ``enqueue`` (the same on every rank, or on none).  The one-sweep chain first
-        (``merged``), the three-sweep chain if one of its checks fails, the host-driven radix rounds if a window misses: the same
-        numbers whichever route settles them (up to the order of the moment sums)."""
-        if device_driven:
-            if merged:
-                got = self.finish(self.enqueue_merged(tiles_local, n_tiles_total=n_tiles_total))
-                if got is not None:
-                    return got
-            got = self.finish(self.enqueue(tiles_local, n_tiles_total=n_tiles_total))
+    def settle(self, tiles_local: torch.Tensor, n_tiles_total: Optional[int] = None, merged: bool = True, ws=None, behind=None, first=None):
+        """(M, maxC, state) of the slide: the one-sweep chain (``merged``; or first(), a replay of it that returns its state), the three-sweep
+        chain if one of its checks fails, the host-driven radix rounds if a window misses -- the same numbers whichever route settles them.
+        behind(state) enqueues work behind each eager chain, before its one read-back.  state: the pool state of the chain that settled
+        them, None after the host-driven rounds.  n_tiles_total: see ``enqueue``; ws: the one-sweep chain's cache (``enqueue_merged``)."""
+        def eager(enqueue, **kw):
+            state = enqueue(tiles_local, n_tiles_total=n_tiles_total, **kw)
+            if behind is not None:
+                behind(state)
+            return state
+        rungs = ([first or (lambda: eager(self.enqueue_merged, ws=ws))] if merged else []) + [lambda: eager(self.enqueue)]
+        for rung in rungs:
+            state = rung()
+            got = self.finish(state)
             if got is not None:
-                return got
-        return self.host_driven(tiles_local)
+                return got + (state,)
+        return self.host_driven(tiles_local) + (None,)
+
+    def __call__(self, tiles_local: torch.Tensor, device_driven: bool = True, n_tiles_total: Optional[int] = None, merged: bool = True):
+        """(M, maxC) of the slide, settled as ``settle`` does; device_driven=False: the host-driven rounds only.  n_tiles_total: see
+        ``enqueue`` (the same on every rank, or on none)."""
+        if not device_driven:
+            return self.host_driven(tiles_local)
+        return self.settle(tiles_local, n_tiles_total, merged)[:2]
 
     def host_driven(self, tiles_local: torch.Tensor):
         """The same statistics with the decisions on the host (a read-back per step): the radix fallback lives here."""
-        import math
-        import numpy as np
         from . import engine, _ffi
         from .utils.excepts import TissueMaskException
-        params = engine.make_params(luminosity_threshold=self.thr, angular_percentile=self.pct, lasso_lambda=self.lam)
+        params = self.params()
         self.last_path = []
         _, world = _world(self.group)
         n_local, h, w, _ = tiles_local.shape
@@ -422,8 +435,6 @@ class PooledSlideStatistics:
             dist.all_reduce(npx, group=self.group)
         m = mom.cpu().numpy()
         T, n_pixels = int(round(m[0])), int(round(float(npx.item())))
-        # the sample: ~4 M pixels of the slide or more (one row in 2**slog), everything for small slides
-        slog = min(6, max(0, int(math.floor(math.log2(max(n_pixels, 1) / 4.0e6))))) if n_pixels > 4.0e6 else 0
         if T < 1:
             raise TissueMaskException("Empty tissue mask computed")
         mean = m[1:4] / T
@@ -436,30 +447,23 @@ class PooledSlideStatistics:
                 V[:, i] *= -1.0
         Vf = V.astype(np.float32).astype(np.float64)                # the keys are evaluated in binary32
         # ---- exact angular percentiles over those pixels (:29-34): both in the same four sweeps
-        def pairs(keyset, basis, ks, totals):
-            # one sweep, with the window centred on an estimate from a 1/64 pixel sample; the radix rounds if it missed
-            return key_rank_pairs(tiles_local, keyset, basis, ks, totals, slog, params, self.group, self.last_path)
-
         def angle_of_pseudo(p):
             if abs(p) <= 1.0:
                 return math.atan2(p, 1.0 - abs(p))
             pp = 2.0 - p if p > 0 else -2.0 - p
             return math.atan2(pp, -(1.0 - abs(pp)))
         (k_lo, g_lo), (k_hi, g_hi) = percentile_position(T, 100.0 - self.pct), percentile_position(T, self.pct)
-        (xa0, xb0), (xa1, xb1) = pairs(_ffi.KEYSET_ANGLE, Vf.reshape(6), (k_lo, k_hi), (T, T))
+        (xa0, xb0), (xa1, xb1) = key_rank_pairs(tiles_local, _ffi.KEYSET_ANGLE, Vf.reshape(6), (k_lo, k_hi), (T, T),
+                                                window_sample_log2(n_pixels), params, self.group, self.last_path)
         phis = [np_lerp(angle_of_pseudo(xa0), angle_of_pseudo(xb0), g_lo), np_lerp(angle_of_pseudo(xa1), angle_of_pseudo(xb1), g_hi)]
         v1 = V @ np.array([math.cos(phis[0]), math.sin(phis[0])])          # :36-37
         v2 = V @ np.array([math.cos(phis[1]), math.sin(phis[1])])
         M = np.array([v1, v2]) if v1[0] > v2[0] else np.array([v2, v1])     # :40-43
         M = M / np.linalg.norm(M, axis=1, keepdims=True)                    # :44
-        # ---- 99th percentile of each concentration over every pixel (normalizer.py:36,47): both columns per sweep
-        k, g = percentile_position(n_pixels, 99.0)
-        (ca0, cb0), (ca1, cb1) = pairs(_ffi.KEYSET_CONC, M.reshape(6), (k, k), (n_pixels, n_pixels))
-        maxC = [np_lerp(float(ca0), float(cb0), g), np_lerp(float(ca1), float(cb1), g)]
-        return M, np.asarray(maxC, dtype=np.float64)
+        return M, pooled_max_concentrations(tiles_local, M, n_pixels, params, self.group, self.last_path)
 
 
-class PooledVahadaneStatistics:
+class PooledVahadaneStatistics(_PooledStatistics):
     """Vahadane stain matrix and 99th-percentile concentrations of the tall image made of every tile on every rank
     (vahadane_stain_extractor.py:28-43 and normalizer.py:36,47 on the concatenation; csrc/slide_dict.hip).
 
@@ -472,11 +476,8 @@ class PooledVahadaneStatistics:
 
     def __init__(self, group=None, luminosity_threshold=0.8, angular_percentile=99.0, lasso_lambda=0.01, dl_lambda=0.1, dl_tol=1e-7,
                  dl_max_sweeps=200):
-        self.group = group
-        self.thr, self.pct, self.lam = luminosity_threshold, angular_percentile, lasso_lambda
+        super().__init__(group, luminosity_threshold, angular_percentile, lasso_lambda)
         self.dl_lambda, self.dl_tol, self.dl_max_sweeps = dl_lambda, dl_tol, int(dl_max_sweeps)
-        self.sample_log2 = None      # None: follows the slide's pixel count (sample_log2_for); 0...12: one 64-pixel sub-row in 2**s (the same on every rank)
-        self.last_path = []          # how the concentration stage settled: ["window"] or ["radix"]
         self.last_status = 0         # SL_TILE_* of the last call
         self.last_rounds = 0         # dictionary updates taken (sampled and full)
         self.last_sweeps = 0         # full sweeps among them
@@ -501,7 +502,6 @@ class PooledVahadaneStatistics:
         from . import engine, _ffi
         params = self.params()
         _, world = _world(self.group)
-        coll = _coll(world, self.group)
         n_local, h, w, _ = tiles_local.shape
         dev = tiles_local.device
         slog = self.sample_log2_for(_agreed_pixels(tiles_local, n_tiles_total, world, self.group)) if self.sample_log2 is None else int(self.sample_log2)
@@ -515,9 +515,7 @@ class PooledVahadaneStatistics:
         for blk in range(max_blocks):
             for r in range(self.ROUNDS_PER_BLOCK):
                 part = engine.sdict_sweep(tiles_local, slog, state, ws, sums=sums[r], params=params)
-                if coll:
-                    dist.all_reduce(part, group=self.group)
-                engine.sdict_step(state, part, params=params)
+                engine.sdict_step(state, _reduced(part, world, self.group), params=params)
             s = state.cpu().numpy()
             if int(s[_ffi.SDICT_MODE]) == 0:
                 break
@@ -530,8 +528,6 @@ class PooledVahadaneStatistics:
     def __call__(self, tiles_local: torch.Tensor, n_tiles_total: Optional[int] = None):
         """(M (2, 3), maxC (2,)) of the slide as numpy float64.  Raises TissueMaskException on an empty tissue mask (stain_utils.py:46-47).
         A degenerate dictionary (a dead atom, parallel atoms) or a zero concentration percentile gives NaN and self.last_status != 0."""
-        import math
-        import numpy as np
         from . import _ffi
         from .utils.excepts import TissueMaskException
         self.last_path = []
@@ -540,17 +536,10 @@ class PooledVahadaneStatistics:
         self.last_status = status
         if status == _ffi.TILE_EMPTY_MASK:
             raise TissueMaskException("Empty tissue mask computed")
-        nan = np.full(2, np.nan)
         if status != 0:
-            return np.full((2, 3), np.nan), nan
+            return np.full((2, 3), np.nan), np.full(2, np.nan)
         M = s[_ffi.SDICT_M:_ffi.SDICT_M + 6].reshape(2, 3).copy()
-        # ---- 99th percentile of each concentration over every pixel (normalizer.py:36,47): both columns per sweep
-        n_pixels = int(round(float(s[_ffi.SDICT_NPX])))
-        slog = min(6, max(0, int(math.floor(math.log2(max(n_pixels, 1) / 4.0e6))))) if n_pixels > 4.0e6 else 0
-        k, g = percentile_position(n_pixels, 99.0)
-        (ca0, cb0), (ca1, cb1) = key_rank_pairs(tiles_local, _ffi.KEYSET_CONC, M.reshape(6), (k, k), (n_pixels, n_pixels), slog,
-                                                self.params(), self.group, self.last_path)
-        maxC = np.array([np_lerp(float(ca0), float(cb0), g), np_lerp(float(ca1), float(cb1), g)], dtype=np.float64)
+        maxC = pooled_max_concentrations(tiles_local, M, int(round(float(s[_ffi.SDICT_NPX]))), self.params(), self.group, self.last_path)
         if not (maxC > 0).all():             # normalizer.py:48 would divide by it
             self.last_status = _ffi.TILE_ZERO_MAXC
         return M, maxC
@@ -591,85 +580,92 @@ class SlideNormalizer:
             return cached(device)
         return self.normalizer.stain_matrix_target, self.normalizer.maxC_target.reshape(2)
 
+    @staticmethod
+    def _apply(tiles_local, M_s, maxC_s, Mt, mct, out):
+        """The apply pass of every tile under the one slide matrix M_s (2, 3) and maxC_s (2,) (device float64)."""
+        from . import engine
+        n = tiles_local.shape[0]
+        return engine.normalize_apply(tiles_local, M_s.expand(n, 2, 3).contiguous(), maxC_s.expand(n, 2).contiguous(), Mt, mct, out=out)
+
+    @staticmethod
+    def _slide_stats(state):         # views of the slide's (M, maxC) in a pool state
+        from . import _ffi
+        return state[_ffi.POOL_M:_ffi.POOL_M + 6].reshape(2, 3), state[_ffi.POOL_MAXC:_ffi.POOL_MAXC + 2]
+
     def transform_shard(self, tiles_local: torch.Tensor, out: Optional[torch.Tensor] = None, n_tiles_total: Optional[int] = None):
         """tiles_local: this rank's (n_local,H,W,3) uint8 device tensor.  Returns (out, M_slide, maxC_slide, status_local).
         n_tiles_total (pooled mode, optional): the slide's tile count over all ranks; saves the one tiny all-reduce that otherwise
         agrees on the sample density.  On failure (TissueMaskException) `out` holds a copy of the input tiles."""
-        from . import engine
-        if self.mode == "pooled" and getattr(self.normalizer, "method", "macenko") == "vahadane":
+        if self.mode == "median":
+            return self._transform_median(tiles_local, out)
+        if getattr(self.normalizer, "method", "macenko") == "vahadane":
             return self._transform_vahadane(tiles_local, out, n_tiles_total)
-        if self.mode == "pooled":
-            from . import _ffi
-            stats = PooledSlideStatistics(self.group)
-            dev = tiles_local.device
-            n = tiles_local.shape[0]
-            # device-driven: the statistics AND the apply pass are enqueued before anything is read back; the one read-back
-            # afterwards only confirms that both windows caught their ranks (else: the host-driven rounds, and the pass again).
-            # When the chain ends in an unusable state (a window miss, an empty tissue mask, a degenerate covariance) its last step
-            # leaves NaN in (M, maxC) and the enqueued apply pass COPIES the tiles through (k_apply's rule for unusable statistics):
-            # `out` then holds the input, never exp(NaN) bytes, until the host-driven rounds below rewrite it -- or, on an empty
-            # mask, when TissueMaskException leaves this function.
-            Mt, mct = self._targets(dev)
-            got = None
-            chains = (stats.enqueue_merged, stats.enqueue) if self.merged else (stats.enqueue,)
-            _, world = _world(self.group)
-            if self.graph and self.merged and stats.one_call and not _coll(world, self.group):
-                # the captured chain: same buffers as last time -> replay; else capture (one warm-up run, one run under capture)
-                import numpy as np
-                tgt_key = (np.asarray(self.normalizer.stain_matrix_target, dtype=np.float64).tobytes(),
-                           np.asarray(self.normalizer.maxC_target, dtype=np.float64).tobytes())          # (host values: no device read-back for the key)
-                if out is None:
-                    out = self._graphed[2]["out"] if (self._graphed and self._graphed[2]["out"].shape == tiles_local.shape
-                                                      and self._graphed[2]["out"].device == dev) else torch.empty_like(tiles_local)
-                key = (tiles_local.data_ptr(), out.data_ptr(), tuple(tiles_local.shape), n_tiles_total, str(dev), stats.thr, stats.pct, stats.lam, tgt_key)
-                if self._graphed is None or self._graphed[0] != key:
-                    keep = {"out": out, "tiles": tiles_local,
-                            "Mt": torch.as_tensor(Mt, dtype=torch.float64, device=dev).reshape(2, 3).clone(),
-                            "mct": torch.as_tensor(mct, dtype=torch.float64, device=dev).reshape(2).clone()}
+        return self._transform_macenko(tiles_local, out, n_tiles_total)
 
-                    def captured():
-                        st_ = stats.enqueue_merged(tiles_local, n_tiles_total=n_tiles_total, ws=self._pool2_ws)
-                        M_ = st_[_ffi.POOL_M:_ffi.POOL_M + 6].reshape(2, 3)
-                        mc_ = st_[_ffi.POOL_MAXC:_ffi.POOL_MAXC + 2]
-                        engine.normalize_apply(tiles_local, M_.expand(n, 2, 3).contiguous(), mc_.expand(n, 2).contiguous(), keep["Mt"], keep["mct"], out=out)
-                        return st_, M_, mc_
-                    self._graphed = None                       # (the old graph goes before its buffers do)
-                    self._graphed = (key, engine.Graphed(captured), keep)
-                state, M_s, maxC_s = self._graphed[1].replay()
-                got = stats.finish(state)
-                chains = chains[1:]                            # a miss: the three-sweep chain, eagerly
-            for chain in (chains if got is None else ()):
-                def run(chain=chain):
-                    st_ = chain(tiles_local, n_tiles_total=n_tiles_total, ws=self._pool2_ws if chain == stats.enqueue_merged else None)
-                    M_ = st_[_ffi.POOL_M:_ffi.POOL_M + 6].reshape(2, 3)
-                    mc_ = st_[_ffi.POOL_MAXC:_ffi.POOL_MAXC + 2]
-                    o_ = engine.normalize_apply(tiles_local, M_.expand(n, 2, 3).contiguous(), mc_.expand(n, 2).contiguous(), Mt, mct, out=out)
-                    return st_, M_, mc_, o_
-                state, M_s, maxC_s, out = run()
-                got = stats.finish(state)
-                if got is not None:
-                    break
-            if got is None:
-                M_np, maxC_np = stats.host_driven(tiles_local)
-                M_s = torch.as_tensor(M_np, dtype=torch.float64, device=dev)
-                maxC_s = torch.as_tensor(maxC_np, dtype=torch.float64, device=dev)
-                out = engine.normalize_apply(tiles_local, M_s.expand(n, 2, 3).contiguous(), maxC_s.expand(n, 2).contiguous(), Mt, mct, out=out)
-            else:
-                M_s, maxC_s = M_s.clone(), maxC_s.clone()
-            self.last_path = stats.last_path             # per stage: "merged" (one sweep for both), "window" (one each) or "radix"
-            self.last_miss, self.last_why = stats.last_miss, stats.last_why
-            return out, M_s, maxC_s, torch.zeros((n,), dtype=torch.int32, device=dev)
+    def _transform_median(self, tiles_local: torch.Tensor, out: Optional[torch.Tensor]):
+        """Per-tile fits, all-gathered; every tile normalised with their element-wise median."""
         M, maxC, status = self.normalizer.fit_batch_targets(tiles_local)
-        M_all, maxC_all, st_all = gather_tile_stats(M, maxC, status, self.group)
-        M_s, maxC_s = slide_statistics(M_all, maxC_all, st_all)
-        n = tiles_local.shape[0]
-        Mt, mct = self._targets(tiles_local.device)
-        out = engine.normalize_apply(tiles_local, M_s.expand(n, 2, 3).contiguous(), maxC_s.expand(n, 2).contiguous(), Mt, mct, out=out)
+        M_s, maxC_s = slide_statistics(*gather_tile_stats(M, maxC, status, self.group))
+        out = self._apply(tiles_local, M_s, maxC_s, *self._targets(tiles_local.device), out)
         return out, M_s, maxC_s, status
+
+    def _transform_macenko(self, tiles_local: torch.Tensor, out: Optional[torch.Tensor], n_tiles_total: Optional[int]):
+        """Pooled mode with a Macenko normalizer.  Device-driven: the statistics AND the apply pass are enqueued before anything is read
+        back; the one read-back afterwards only confirms that both windows caught their ranks (else the next chain, or the host-driven
+        rounds, and the pass again).  When a chain ends in an unusable state (a window miss, an empty tissue mask, a degenerate
+        covariance) its last step leaves NaN in (M, maxC) and the enqueued apply pass COPIES the tiles through (k_apply's rule for
+        unusable statistics): `out` then holds the input, never exp(NaN) bytes, until a later route rewrites it -- or, on an empty mask,
+        when TissueMaskException leaves this function."""
+        stats = PooledSlideStatistics(self.group)
+        dev = tiles_local.device
+        n = tiles_local.shape[0]
+        Mt, mct = self._targets(dev)
+        _, world = _world(self.group)
+        first = None
+        if self.graph and self.merged and stats.one_call and not _coll(world, self.group):
+            graphed, out = self._captured_chain(stats, tiles_local, out, n_tiles_total, Mt, mct)
+            first = graphed.replay
+
+        def behind(st):                     # the apply pass behind each eager chain; the next route writes the same `out`
+            nonlocal out
+            out = self._apply(tiles_local, *self._slide_stats(st), Mt, mct, out)
+        M_np, maxC_np, state = stats.settle(tiles_local, n_tiles_total, self.merged, ws=self._pool2_ws, first=first, behind=behind)
+        if state is None:                   # the host-driven rounds settled it: the pass again, under their numbers
+            M_s = torch.as_tensor(M_np, dtype=torch.float64, device=dev)
+            maxC_s = torch.as_tensor(maxC_np, dtype=torch.float64, device=dev)
+            out = self._apply(tiles_local, M_s, maxC_s, Mt, mct, out)
+        else:
+            M_s, maxC_s = (t.clone() for t in self._slide_stats(state))
+        self.last_path = stats.last_path             # per stage: "merged" (one sweep for both), "window" (one each) or "radix"
+        self.last_miss, self.last_why = stats.last_miss, stats.last_why
+        return out, M_s, maxC_s, torch.zeros((n,), dtype=torch.int32, device=dev)
+
+    def _captured_chain(self, stats, tiles_local: torch.Tensor, out: Optional[torch.Tensor], n_tiles_total: Optional[int], Mt, mct):
+        """graph=True: (engine.Graphed of the one-sweep chain with the apply pass behind it, the `out` it writes).  The same buffers as
+        last time are replayed; else the chain is captured (one warm-up run, one run under capture)."""
+        from . import engine
+        dev = tiles_local.device
+        tgt_key = (np.asarray(self.normalizer.stain_matrix_target, dtype=np.float64).tobytes(),
+                   np.asarray(self.normalizer.maxC_target, dtype=np.float64).tobytes())          # (host values: no device read-back for the key)
+        if out is None:
+            out = self._graphed[2]["out"] if (self._graphed and self._graphed[2]["out"].shape == tiles_local.shape
+                                              and self._graphed[2]["out"].device == dev) else torch.empty_like(tiles_local)
+        key = (tiles_local.data_ptr(), out.data_ptr(), tuple(tiles_local.shape), n_tiles_total, str(dev), stats.thr, stats.pct, stats.lam, tgt_key)
+        if self._graphed is None or self._graphed[0] != key:
+            keep = {"out": out, "tiles": tiles_local,
+                    "Mt": torch.as_tensor(Mt, dtype=torch.float64, device=dev).reshape(2, 3).clone(),
+                    "mct": torch.as_tensor(mct, dtype=torch.float64, device=dev).reshape(2).clone()}
+
+            def captured():
+                state = stats.enqueue_merged(tiles_local, n_tiles_total=n_tiles_total, ws=self._pool2_ws)
+                self._apply(tiles_local, *self._slide_stats(state), keep["Mt"], keep["mct"], out)
+                return state
+            self._graphed = None                       # (the old graph goes before its buffers do)
+            self._graphed = (key, engine.Graphed(captured), keep)
+        return self._graphed[1], out
 
     def _transform_vahadane(self, tiles_local: torch.Tensor, out: Optional[torch.Tensor], n_tiles_total: Optional[int]):
         """Pooled mode with a Vahadane normalizer: the slide's dictionary and concentrations, then the apply pass of the Macenko mode."""
-        from . import engine
         from .utils.excepts import TissueMaskException
         if self.graph:
             raise ValueError("graph=True is not supported with a Vahadane normalizer")
@@ -692,6 +688,5 @@ class SlideNormalizer:
             out.copy_(tiles_local)
             return out, M_s, maxC_s, torch.full((n,), stats.last_status, dtype=torch.int32, device=dev)
         if n:
-            Mt, mct = self._targets(dev)
-            out = engine.normalize_apply(tiles_local, M_s.expand(n, 2, 3).contiguous(), maxC_s.expand(n, 2).contiguous(), Mt, mct, out=out)
+            out = self._apply(tiles_local, M_s, maxC_s, *self._targets(dev), out)
         return out, M_s, maxC_s, torch.zeros((n,), dtype=torch.int32, device=dev)

@@ -89,7 +89,8 @@ def _scratch(ws, op, n, h, w, device, params=None) -> torch.Tensor:
 class Graphed:
     """A sequence of engine calls captured ONCE into a HIP graph and replayed.  Every fit / transform / apply / augment
     entry point of the C ABI is capture-safe -- kernel launches on the caller's stream, no allocation, no synchronisation,
-    no host read-back (the pooled slide mode, which reads histograms back between stages, is not).  What it buys is the
+    no host read-back; so is the one-sweep chain of the pooled slide mode on one process, which SlideNormalizer(graph=True)
+    captures with the apply pass behind it.  What it buys is the
     LATENCY of an isolated small call on the one-launch-per-phase schedule (7 launches for Macenko, 11 for Vahadane), whose
     first kernels otherwise wait for the host to issue the next launch: 1024^2 Macenko transform, call-to-completion, 16
     tiles 274 -> 239 us, 128 tiles 671 -> 623 us.  Calls queued back to back gain nothing (the host already runs ahead
