@@ -14,12 +14,8 @@ extern "C" int sl_normalize_apply(const uint8_t* rgb, uint8_t* out, int n, int h
     const dim3 grid((unsigned)((long)n * parts)), block(kWG);
     hipStream_t s = (hipStream_t)stream;
     const bool al = aligned4(rgb, P) && aligned4(out, P);
-#define SL_GO(A, Q)                                                                                         \
-    hipLaunchKernelGGL((k_apply<A, Q>), grid, block, 0, s, rgb, out, (int)P, parts, M_src, maxC_src, M_tgt, \
-                       maxC_tgt, lasso_lambda, prequant)
-    if (al) { if (prequant) SL_GO(true, true); else SL_GO(true, false); }
-    else    { if (prequant) SL_GO(false, true); else SL_GO(false, false); }
-#undef SL_GO
+    launch_aligned(al, prequant ? k_apply<true, true> : k_apply<true, false>, prequant ? k_apply<false, true> : k_apply<false, false>, grid, block,
+                   0, s, rgb, out, (int)P, parts, M_src, maxC_src, M_tgt, maxC_tgt, lasso_lambda, prequant);
     return launch_status();
 }
 
@@ -37,12 +33,8 @@ extern "C" int sl_stain_augment(const uint8_t* rgb, uint8_t* out, int n, int h, 
     const dim3 grid((unsigned)(items < max_grid ? items : max_grid)), block(kAugThreads);
     const uint32_t y_lim = y_limit_for_threshold(p.luminosity_threshold);
     hipStream_t s = (hipStream_t)stream;
-    if (aligned4(rgb, P) && aligned4(out, P))
-        hipLaunchKernelGGL((k_stain_augment<true>), grid, block, 0, s, rgb, out, (int)P, parts, (int)items, M, alpha_beta,
-                           augment_background, y_lim, p.lasso_lambda);
-    else
-        hipLaunchKernelGGL((k_stain_augment<false>), grid, block, 0, s, rgb, out, (int)P, parts, (int)items, M, alpha_beta,
-                           augment_background, y_lim, p.lasso_lambda);
+    launch_aligned(aligned4(rgb, P) && aligned4(out, P), k_stain_augment<true>, k_stain_augment<false>, grid, block, 0, s, rgb, out, (int)P,
+                   parts, (int)items, M, alpha_beta, augment_background, y_lim, p.lasso_lambda);
     return launch_status();
 }
 
@@ -54,8 +46,7 @@ extern "C" int sl_grayscale_augment(const uint8_t* rgb, uint8_t* out, int n, int
     const int parts = parts_for(P);
     const dim3 grid((unsigned)((long)n * parts)), block(kWG);
     hipStream_t s = (hipStream_t)stream;
-    if (aligned4(rgb, P) && aligned4(out, P)) hipLaunchKernelGGL((k_grayscale<true>), grid, block, 0, s, rgb, out, (int)P, parts, alpha_beta);
-    else hipLaunchKernelGGL((k_grayscale<false>), grid, block, 0, s, rgb, out, (int)P, parts, alpha_beta);
+    launch_aligned(aligned4(rgb, P) && aligned4(out, P), k_grayscale<true>, k_grayscale<false>, grid, block, 0, s, rgb, out, (int)P, parts, alpha_beta);
     return launch_status();
 }
 
@@ -77,7 +68,10 @@ extern "C" int sl_tissue_mask(const uint8_t* rgb, int n, int h, int w, double lu
     if (P > (1L << 30)) return SL_ERR_BADARG;
     const int parts = parts_for(P);
     hipStream_t s = (hipStream_t)stream;
-    if (counts) zero_async(counts, sizeof(int64_t) * (size_t)n, s);
+    static_assert(sizeof(int64_t) % 4 == 0, "zero_async clears whole words");
+    if (counts) {
+        if (const int rc = zero_async(counts, sizeof(int64_t) * (size_t)n, s)) return rc;
+    }
     hipLaunchKernelGGL(k_tissue_mask, dim3((unsigned)((long)n * parts)), dim3(kWG), 0, s, rgb, (int)P, parts,
                        y_limit_for_threshold(luminosity_threshold), mask_out, (unsigned long long*)counts);
     return launch_status();

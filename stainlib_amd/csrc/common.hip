@@ -44,12 +44,13 @@ int max_resident_grid() {
 static __global__ __launch_bounds__(256) void k_zero_words(uint32_t* p, size_t n) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[i] = 0u;
 }
-void zero_async(void* p, size_t bytes, hipStream_t s) {                   // p 4-byte aligned, bytes a multiple of 4
+int zero_async(void* p, size_t bytes, hipStream_t s) {                    // p 4-byte aligned, bytes a multiple of 4
     const size_t words = bytes / 4;
-    if (!words) return;
+    if (!words) return SL_OK;
     size_t blocks = (words + 255) / 256;
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(k_zero_words, dim3((unsigned)blocks), dim3(256), 0, s, (uint32_t*)p, words);
+    return launch_status();
 }
 
 }  // namespace sl

@@ -6,11 +6,10 @@
 namespace sl {
 
 void launch_fused_vahadane(const FusedArgs& a, bool transform, bool aligned, unsigned grid, hipStream_t s) {
-    const dim3 g(grid), b(kFusedThreads);
-#define SL_GO(T, A) hipLaunchKernelGGL((k_fused<kMethodVahadane, T, A, kFusedThreads>), g, b, 0, s, a)
-    if (transform) { if (aligned) SL_GO(true, true); else SL_GO(true, false); }
-    else           { if (aligned) SL_GO(false, true); else SL_GO(false, false); }
-#undef SL_GO
+    constexpr int METHOD = kMethodVahadane, NT = kFusedThreads;
+    const dim3 g(grid), b(NT);
+    if (transform) launch_aligned(aligned, k_fused<METHOD, true, true, NT>, k_fused<METHOD, true, false, NT>, g, b, 0, s, a);
+    else launch_aligned(aligned, k_fused<METHOD, false, true, NT>, k_fused<METHOD, false, false, NT>, g, b, 0, s, a);
 }
 
 }  // namespace sl

@@ -249,17 +249,18 @@ extern "C" int sl_hed_augment(const uint8_t* rgb, uint8_t* out, int n, int h, in
     hc.log2_base = skimage_mode == SL_HED_EXPERIMENTAL_LOG10 ? 3.321928094887362 : 1.4426950408889634;
     hipStream_t s = (hipStream_t)stream;
     unsigned long long* sums = (unsigned long long*)workspace;
-    zero_async(sums, sizeof(unsigned long long) * (size_t)n, s);
+    static_assert(sizeof(unsigned long long) % 4 == 0, "zero_async clears whole words");
+    if (const int rc = zero_async(sums, sizeof(unsigned long long) * (size_t)n, s)) return rc;
     const int parts = parts_for(P);
     const dim3 grid((unsigned)((long)n * parts)), block(kWG);
     const bool al = aligned4(rgb, P) && aligned4(out, P);
-#define SL_GO(M, A) hipLaunchKernelGGL((k_hed<M, A>), grid, block, 0, s, rgb, out, (int)P, parts, sigma, bias, hc, sums)
-    if (skimage_mode == SL_HED_SKIMAGE_018)      { if (al) SL_GO(0, true); else SL_GO(0, false); }
-    else if (skimage_mode == SL_HED_SKIMAGE_019) { if (al) SL_GO(1, true); else SL_GO(1, false); }
-    else                                         { if (al) SL_GO(2, true); else SL_GO(2, false); }
-#undef SL_GO
-    if (al) hipLaunchKernelGGL((k_hed_fixup<true>), grid, block, 0, s, rgb, out, (int)P, parts, sums, cutoff_lo, cutoff_hi, applied);
-    else    hipLaunchKernelGGL((k_hed_fixup<false>), grid, block, 0, s, rgb, out, (int)P, parts, sums, cutoff_lo, cutoff_hi, applied);
+    const auto hed = [&](auto k_aligned, auto k_unaligned) {
+        launch_aligned(al, k_aligned, k_unaligned, grid, block, 0, s, rgb, out, (int)P, parts, sigma, bias, hc, sums);
+    };
+    if (skimage_mode == SL_HED_SKIMAGE_018) hed(k_hed<0, true>, k_hed<0, false>);
+    else if (skimage_mode == SL_HED_SKIMAGE_019) hed(k_hed<1, true>, k_hed<1, false>);
+    else hed(k_hed<2, true>, k_hed<2, false>);
+    launch_aligned(al, k_hed_fixup<true>, k_hed_fixup<false>, grid, block, 0, s, rgb, out, (int)P, parts, sums, cutoff_lo, cutoff_hi, applied);
     return launch_status();
 }
 
@@ -278,7 +279,8 @@ extern "C" int sl_hed_augment_f64(const double* rgb, double* out, int n, int h, 
     hc.log2_base = 0.0;
     hipStream_t s = (hipStream_t)stream;
     double* sums = (double*)workspace;
-    zero_async(sums, sizeof(double) * (size_t)n, s);
+    static_assert(sizeof(double) % 4 == 0, "zero_async clears whole words");
+    if (const int rc = zero_async(sums, sizeof(double) * (size_t)n, s)) return rc;
     const int parts = parts_for(P);
     const dim3 grid((unsigned)((long)n * parts)), block(kWG);
     if (skimage_mode == SL_HED_SKIMAGE_018) hipLaunchKernelGGL((k_hed_f64<0>), grid, block, 0, s, rgb, out, (int)P, parts, sigma, bias, hc, sums);

@@ -532,20 +532,15 @@ int lab_check(const void* rgb, const void* out, int n, int h, int w, const void*
 
 // the two statistics sweeps shared by the entry points below (and k_lab_pre between them: the tile's brightness table)
 int lab_statistics(const uint8_t* rgb, int n, long P, int standardize, int want_ab, double thr, LabScratch* sc, hipStream_t s) {
-    zero_async(sc, sizeof(LabScratch) * (size_t)n, s);
+    static_assert(sizeof(LabScratch) % 4 == 0, "zero_async clears whole words");
+    if (const int rc = zero_async(sc, sizeof(LabScratch) * (size_t)n, s)) return rc;
     LabTileTabs* tt = lab_tabs_of(sc, n);
     const int parts = lab_parts(n, P);
     const dim3 grid((unsigned)((long)n * parts)), block(kLabWG);
     const bool al = aligned4(rgb, P);
-    if (standardize) {
-        if (al) hipLaunchKernelGGL((k_byte_hist<true>), grid, block, 0, s, rgb, (int)P, parts, sc);
-        else    hipLaunchKernelGGL((k_byte_hist<false>), grid, block, 0, s, rgb, (int)P, parts, sc);
-    }
+    if (standardize) launch_aligned(al, k_byte_hist<true>, k_byte_hist<false>, grid, block, 0, s, rgb, (int)P, parts, sc);
     hipLaunchKernelGGL(k_lab_pre, dim3((unsigned)n), dim3(256), 0, s, sc, standardize, tt);
-    if (want_ab >= 0) {
-        if (al) hipLaunchKernelGGL((k_lab_hist<true>), grid, block, 0, s, rgb, (int)P, parts, want_ab, thr, sc, tt);
-        else    hipLaunchKernelGGL((k_lab_hist<false>), grid, block, 0, s, rgb, (int)P, parts, want_ab, thr, sc, tt);
-    }
+    if (want_ab >= 0) launch_aligned(al, k_lab_hist<true>, k_lab_hist<false>, grid, block, 0, s, rgb, (int)P, parts, want_ab, thr, sc, tt);
     return launch_status();
 }
 
@@ -553,8 +548,7 @@ template <int MODE>
 int lab_map(const LabMapArgs& a, int n, hipStream_t s) {
     if (MODE != 2) hipLaunchKernelGGL((k_lab_tables<MODE>), dim3((unsigned)n), dim3(256), 0, s, a);
     const dim3 grid((unsigned)((long)n * a.parts)), block(kLabWG);
-    if (aligned4(a.rgb, a.P) && aligned4(a.out, a.P)) hipLaunchKernelGGL((k_lab_map<MODE, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((k_lab_map<MODE, false>), grid, block, 0, s, a);
+    launch_aligned(aligned4(a.rgb, a.P) && aligned4(a.out, a.P), k_lab_map<MODE, true>, k_lab_map<MODE, false>, grid, block, 0, s, a);
     return launch_status();
 }
 
@@ -567,8 +561,8 @@ extern "C" int sl_rgb_to_lab8(const uint8_t* rgb, uint8_t* lab_out, int n, int h
     const long P = (long)h * w;
     const int parts = parts_for(P);
     const dim3 grid((unsigned)((long)n * parts)), block(kLabWG);
-    if (aligned4(rgb, P) && aligned4(lab_out, P)) hipLaunchKernelGGL((k_lab_convert<0, true>), grid, block, 0, (hipStream_t)stream, rgb, lab_out, (int)P, parts);
-    else hipLaunchKernelGGL((k_lab_convert<0, false>), grid, block, 0, (hipStream_t)stream, rgb, lab_out, (int)P, parts);
+    launch_aligned(aligned4(rgb, P) && aligned4(lab_out, P), k_lab_convert<0, true>, k_lab_convert<0, false>, grid, block, 0, (hipStream_t)stream,
+                   rgb, lab_out, (int)P, parts);
     return launch_status();
 }
 
@@ -577,8 +571,8 @@ extern "C" int sl_lab8_to_rgb(const uint8_t* lab, uint8_t* rgb_out, int n, int h
     const long P = (long)h * w;
     const int parts = parts_for(P);
     const dim3 grid((unsigned)((long)n * parts)), block(kLabWG);
-    if (aligned4(lab, P) && aligned4(rgb_out, P)) hipLaunchKernelGGL((k_lab_convert<1, true>), grid, block, 0, (hipStream_t)stream, lab, rgb_out, (int)P, parts);
-    else hipLaunchKernelGGL((k_lab_convert<1, false>), grid, block, 0, (hipStream_t)stream, lab, rgb_out, (int)P, parts);
+    launch_aligned(aligned4(lab, P) && aligned4(rgb_out, P), k_lab_convert<1, true>, k_lab_convert<1, false>, grid, block, 0, (hipStream_t)stream,
+                   lab, rgb_out, (int)P, parts);
     return launch_status();
 }
 
@@ -603,7 +597,10 @@ extern "C" int sl_lab_merge(const void* I1, const void* I2, const void* I3, int 
 extern "C" int sl_od_to_rgb(const double* od, size_t n_values, uint8_t* rgb_out, int32_t* negative_flag, void* stream) {
     if (!od || !rgb_out || n_values == 0) return SL_ERR_BADARG;
     hipStream_t s = (hipStream_t)stream;
-    if (negative_flag) zero_async(negative_flag, sizeof(int32_t), s);
+    static_assert(sizeof(int32_t) % 4 == 0, "zero_async clears whole words");
+    if (negative_flag) {
+        if (const int rc = zero_async(negative_flag, sizeof(int32_t), s)) return rc;
+    }
     const size_t blocks = (n_values + kLabWG - 1) / kLabWG;
     hipLaunchKernelGGL(k_od_to_rgb, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(kLabWG), 0, s, od, n_values, rgb_out, negative_flag);
     return launch_status();

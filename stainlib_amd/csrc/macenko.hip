@@ -25,7 +25,7 @@ constexpr size_t kGroupBytes = (size_t)2 << 30;   // uint8 bytes of one tile gro
 constexpr int kFusedMinTiles = 352;         // tiles of 512 Ki pixels and more (round 3: 416)
 constexpr int kFusedMinTilesMid = 320;      // 256 Ki < pixels < 512 Ki (round 3: 352)
 constexpr int kFusedMinTilesSmall = 288;    // up to 256 Ki pixels
-// The automatic split of a batch beyond the resident grid (plan_macenko): the remainder goes per phase when it is below these.  For small
+// The automatic split of a batch beyond the resident grid (make_plan): the remainder goes per phase when it is below these.  For small
 // tiles a second, partly empty fused round overlaps the first one's tail and the split pays only for short remainders (512^2, 640 tiles:
 // 0.91 split vs 0.97 fused, 768 tiles: 1.03 vs 0.98; 256^2: never).
 constexpr int kSplitMaxRest = 208 /* round 4: 1024^2, 768 tiles 2.58 split vs 2.49 fused (remainder 256), 640 tiles 2.20 vs 2.37 (remainder 128); was 416 */, kSplitMaxRestMid = 224, kSplitMaxRestSmall = 192, kSplitMaxRestTiny = 0;   // tiny: up to 64 Ki pixels
@@ -167,14 +167,12 @@ int run_stats_group(const uint8_t* rgb, int g0, int m, long P, const SlParams& p
     const dim3 bm(kMFinishThreads);
     {
         ProfScope ps(prof, SL_PROF_MOMENTS, m, s);
-        if (al) hipLaunchKernelGGL((k_moments<true>), gs, bs, SL_DYN_LDS, s, a);
-        else    hipLaunchKernelGGL((k_moments<false>), gs, bs, SL_DYN_LDS, s, a);
+        launch_aligned(al, k_moments<true>, k_moments<false>, gs, bs, SL_DYN_LDS, s, a);
     }
     { ProfScope ps(prof, SL_PROF_FINISH, m, s); hipLaunchKernelGGL(k_finish1m, gf, bm, 0, s, a); }
     {   // ONE selection sweep for the angular and the concentration candidates (as sweep 2 of the fused kernel)
         ProfScope ps(prof, SL_PROF_SELECT_ANGLE, m, s);
-        if (al) hipLaunchKernelGGL((k_select<kStageMerged, true>), gs, bs, SL_DYN_LDS, s, a);
-        else    hipLaunchKernelGGL((k_select<kStageMerged, false>), gs, bs, SL_DYN_LDS, s, a);
+        launch_aligned(al, k_select<kStageMerged, true>, k_select<kStageMerged, false>, gs, bs, SL_DYN_LDS, s, a);
     }
     {
         ProfScope ps(prof, SL_PROF_FINISH, m, s);
@@ -182,8 +180,7 @@ int run_stats_group(const uint8_t* rgb, int g0, int m, long P, const SlParams& p
     }
     {   // only the tiles whose exact stain matrix left the box the merged sweep assumed still have work here (none, normally)
         ProfScope ps(prof, SL_PROF_SELECT_CONC, m, s);
-        if (al) hipLaunchKernelGGL((k_select<kStageConc, true>), gs, bs, SL_DYN_LDS, s, a);
-        else    hipLaunchKernelGGL((k_select<kStageConc, false>), gs, bs, SL_DYN_LDS, s, a);
+        launch_aligned(al, k_select<kStageConc, true>, k_select<kStageConc, false>, gs, bs, SL_DYN_LDS, s, a);
     }
     {
         ProfScope ps(prof, SL_PROF_FINISH, m, s);
@@ -203,27 +200,23 @@ int run_dict_group(const uint8_t* rgb, int g0, int m, long P, const SlParams& p,
     SlProfile* prof = p.profile;
     {   // the sample, gathered without a sweep, and the dictionary iterated on it
         ProfScope ps(prof, SL_PROF_FINISH, m, s);
-        if (al) hipLaunchKernelGGL((k_dict_start<true>), gf, bd, 0, s, a);
-        else    hipLaunchKernelGGL((k_dict_start<false>), gf, bd, 0, s, a);
+        launch_aligned(al, k_dict_start<true>, k_dict_start<false>, gf, bd, 0, s, a);
     }
     const int fixed = a.dl_max_sweeps < kDictFixedSweeps ? a.dl_max_sweeps : kDictFixedSweeps;
     for (int i = 0; i < fixed; ++i) {
         {
             ProfScope ps(prof, SL_PROF_DICT, m, s);
-            if (al) hipLaunchKernelGGL((k_dict<true>), gs, bs, 0, s, a);
-            else    hipLaunchKernelGGL((k_dict<false>), gs, bs, 0, s, a);
+            launch_aligned(al, k_dict<true>, k_dict<false>, gs, bs, 0, s, a);
         }
         { ProfScope ps(prof, SL_PROF_FINISH, m, s); hipLaunchKernelGGL(k_dict_finish, gf, bd, 0, s, a); }
     }
     {
         ProfScope ps(prof, SL_PROF_FINISH, m, s);
-        if (al) hipLaunchKernelGGL((k_dict_tail<true>), gf, bd, 0, s, a);
-        else    hipLaunchKernelGGL((k_dict_tail<false>), gf, bd, 0, s, a);
+        launch_aligned(al, k_dict_tail<true>, k_dict_tail<false>, gf, bd, 0, s, a);
     }
     {
         ProfScope ps(prof, SL_PROF_SELECT_CONC, m, s);
-        if (al) hipLaunchKernelGGL((k_select<kStageConc, true>), gs, bs, 0, s, a);
-        else    hipLaunchKernelGGL((k_select<kStageConc, false>), gs, bs, 0, s, a);
+        launch_aligned(al, k_select<kStageConc, true>, k_select<kStageConc, false>, gs, bs, 0, s, a);
     }
     {
         ProfScope ps(prof, SL_PROF_FINISH, m, s);
@@ -279,7 +272,10 @@ int run_fused(int method, const uint8_t* rgb, uint8_t* out, int n, long P, const
     while (((long)a.cl_lines * kClusterPx << a.cl_scale_log2) < P && a.cl_scale_log2 < 30) ++a.cl_scale_log2;
     a.ts_out = p.twosweep_out;
     a.next_tile = (unsigned long long*)(ws + L.off_next);
-    if (n > L.grid) zero_async(a.next_tile, sizeof(unsigned long long), s);
+    static_assert(sizeof(unsigned long long) % 4 == 0, "zero_async clears whole words");
+    if (n > L.grid) {
+        if (const int rc = zero_async(a.next_tile, sizeof(unsigned long long), s)) return rc;
+    }
     const bool al = aligned4(rgb, P) && (!out || aligned4(out, P));
     ProfScope ps(p.profile, out ? SL_PROF_FUSED_TRANSFORM : SL_PROF_FUSED_FIT, n, s);
     // (the twelve instantiations of k_fused live in three translation units of their own -- fused_macenko.hip, fused_macenko_wide.hip,
@@ -298,25 +294,25 @@ int check_common(const void* rgb, int n, int h, int w, const void* ws, size_t ws
     return SL_OK;
 }
 
-// What a Macenko call does with its n tiles.  Automatic schedule only: a batch larger than the resident grid of the fused kernel
+// What a call does with its n tiles.  Macenko, automatic schedule only: a batch larger than the resident grid of the fused kernel
 // whose last round would be mostly empty (n mod grid below the crossover) gives that remainder to the one-launch-per-phase
 // schedule instead -- 640 tiles: one full fused round + 128 tiles per phase, 2.3 ms, where two fused rounds take 2.75 ms.  Results
-// do not depend on the split (both schedules select the same values).
-struct MacenkoPlan {
+// do not depend on the split (both schedules select the same values).  Vahadane never splits.
+struct Plan {
     Layout L;            // the whole batch (result arrays) and the fused part
     bool mixed;
     int n_fused;         // tiles [0, n_fused) fused, [n_fused, n) per phase (mixed only)
     Layout Lp;           // the per-phase remainder, placed behind L in the workspace
     size_t total;
 };
-MacenkoPlan plan_macenko(int n, long P, int schedule, int fused_min_tiles) {
-    MacenkoPlan pl;
-    pl.L = make_layout(n, P, kMethodMacenko, schedule, fused_min_tiles);
+Plan make_plan(int method, int n, long P, int schedule, int fused_min_tiles) {
+    Plan pl;
+    pl.L = make_layout(n, P, method, schedule, fused_min_tiles);
     pl.mixed = false;
     pl.n_fused = 0;
     pl.Lp = Layout{};
     pl.total = pl.L.total;
-    if (schedule == 0 && pl.L.fused && n > pl.L.max_grid) {
+    if (method == kMethodMacenko && schedule == 0 && pl.L.fused && n > pl.L.max_grid) {
         const int rest = n % pl.L.max_grid;
         const int max_rest = fused_min_tiles > 0 ? fused_min_tiles : split_max_rest(P);
         if (rest > 0 && rest < max_rest) {
@@ -329,19 +325,35 @@ MacenkoPlan plan_macenko(int n, long P, int schedule, int fused_min_tiles) {
     return pl;
 }
 
-// fit (out == nullptr) or transform of a batch according to its plan
-int run_macenko(const MacenkoPlan& pl, const uint8_t* rgb, uint8_t* out, int n, int h, int w, const SlParams& p, const double* M_tgt,
-                const double* maxC_tgt, double* M_all, double* maxC_all, int32_t* st_all, char* ws, void* stream) {
+// the caller's result array, or its slot in the workspace when the caller passed none
+template <class T>
+T* caller_or_slot(T* caller, char* ws, size_t off) { return caller ? caller : (T*)(ws + off); }
+
+// Fit (out == nullptr) or transform of a batch by either method.  The checks keep the order tests/abi_argcheck.c pins: SlParams, then
+// the shapes and the workspace against this plan's own need (sl_workspace_bytes_for(op, n, h, w, params); sl_workspace_bytes(), the
+// maximum over every SlParams, always suffices), then a transform's output and target.
+int fit_or_transform(int method, bool transform, const uint8_t* rgb, uint8_t* out, int n, int h, int w, const SlParams* params,
+                     const double* M_tgt, const double* maxC_tgt, double* M_out, double* maxC_out, int32_t* status, int32_t* sweeps_out,
+                     void* workspace, size_t workspace_bytes, void* stream) {
+    if (!params_ok(params)) return SL_ERR_BADARG;
+    const SlParams p = params_or_defaults(params);
     const long P = (long)h * w;
+    const Plan pl = (n > 0 && h > 0 && w > 0) ? make_plan(method, n, P, p.schedule, p.fused_min_tiles) : Plan{};
+    int rc = check_common(rgb, n, h, w, workspace, workspace_bytes, pl.total);
+    if (rc) return rc;
+    if (transform && (!out || !M_tgt || !maxC_tgt)) return SL_ERR_BADARG;
     const Layout& L = pl.L;
-    int rc;
-    if (L.fused && !pl.mixed)
-        return run_fused(kMethodMacenko, rgb, out, n, P, p, L, ws, M_tgt, maxC_tgt, M_all, maxC_all, st_all, nullptr, (hipStream_t)stream);
+    char* ws = (char*)workspace;
+    double* M_all = caller_or_slot(M_out, ws, L.off_M);
+    double* maxC_all = caller_or_slot(maxC_out, ws, L.off_maxC);
+    int32_t* st_all = caller_or_slot(status, ws, L.off_status);
+    const hipStream_t s = (hipStream_t)stream;
+    if (L.fused && !pl.mixed) return run_fused(method, rgb, out, n, P, p, L, ws, M_tgt, maxC_tgt, M_all, maxC_all, st_all, sweeps_out, s);
     int first = 0;
     const Layout* Lg = &L;
     char* wsg = ws;
     if (pl.mixed) {
-        rc = run_fused(kMethodMacenko, rgb, out, pl.n_fused, P, p, L, ws, M_tgt, maxC_tgt, M_all, maxC_all, st_all, nullptr, (hipStream_t)stream);
+        rc = run_fused(method, rgb, out, pl.n_fused, P, p, L, ws, M_tgt, maxC_tgt, M_all, maxC_all, st_all, sweeps_out, s);
         if (rc) return rc;
         first = pl.n_fused;
         Lg = &pl.Lp;
@@ -349,10 +361,11 @@ int run_macenko(const MacenkoPlan& pl, const uint8_t* rgb, uint8_t* out, int n, 
     }
     for (int g0 = first; g0 < n; g0 += Lg->G) {
         const int m = (n - g0) < Lg->G ? (n - g0) : Lg->G;
-        rc = run_stats_group(rgb, g0, m, P, p, *Lg, wsg, M_all, maxC_all, st_all, (hipStream_t)stream);
+        rc = method == kMethodMacenko ? run_stats_group(rgb, g0, m, P, p, *Lg, wsg, M_all, maxC_all, st_all, s)
+                                      : run_dict_group(rgb, g0, m, P, p, *Lg, wsg, M_all, maxC_all, st_all, sweeps_out, s);
         if (rc) return rc;
         if (out) {
-            ProfScope ps(p.profile, SL_PROF_APPLY, m, (hipStream_t)stream);
+            ProfScope ps(p.profile, SL_PROF_APPLY, m, s);
             rc = sl_normalize_apply(rgb + (size_t)g0 * 3 * P, out + (size_t)g0 * 3 * P, m, h, w, M_all + 6 * (size_t)g0, maxC_all + 2 * (size_t)g0,
                                     M_tgt, maxC_tgt, p.lasso_lambda, nullptr, stream);
             if (rc) return rc;
@@ -373,7 +386,7 @@ extern "C" size_t sl_workspace_bytes(int op, int n_tiles, int h, int w) {
             //  sized as a per-phase batch of at most one resident grid)
             const long P = (long)h * w;
             const size_t a = make_layout(n_tiles, P, kMethodMacenko, 1).total, b = make_layout(n_tiles, P, kMethodMacenko, 2).total;
-            size_t c = plan_macenko(n_tiles, P, 0, 0).total;
+            size_t c = make_plan(kMethodMacenko, n_tiles, P, 0, 0).total;
             const int mg = max_resident_grid();
             if (n_tiles > mg && n_tiles % mg) {                   // the largest remainder plan any fused_min_tiles could choose
                 const size_t d = b + make_layout(n_tiles % mg, P, kMethodMacenko, 1).total;
@@ -401,15 +414,14 @@ extern "C" size_t sl_workspace_bytes(int op, int n_tiles, int h, int w) {
 // What the call these SlParams select needs: one plan, not the maximum over all of them.
 extern "C" size_t sl_workspace_bytes_for(int op, int n_tiles, int h, int w, const SlParams* params) {
     if (n_tiles <= 0 || h <= 0 || w <= 0 || !params_ok(params)) return 0;
-    const long P = (long)h * w;
-    const int schedule = params ? params->schedule : 0, fmin = params ? params->fused_min_tiles : 0;
+    const SlParams p = params_or_defaults(params);
     switch (op) {
         case SL_OP_MACENKO_FIT:
         case SL_OP_MACENKO_TRANSFORM:
-            return plan_macenko(n_tiles, P, schedule, fmin).total;
+            return make_plan(kMethodMacenko, n_tiles, (long)h * w, p.schedule, p.fused_min_tiles).total;
         case SL_OP_VAHADANE_FIT:
         case SL_OP_VAHADANE_TRANSFORM:
-            return make_layout(n_tiles, P, kMethodVahadane, schedule, fmin).total;
+            return make_plan(kMethodVahadane, n_tiles, (long)h * w, p.schedule, p.fused_min_tiles).total;
         default:
             return sl_workspace_bytes(op, n_tiles, h, w);
     }
@@ -418,95 +430,32 @@ extern "C" size_t sl_workspace_bytes_for(int op, int n_tiles, int h, int w, cons
 extern "C" int sl_macenko_fit(const uint8_t* rgb, int n, int h, int w, const SlParams* params, double* M_out,
                               double* maxC_out, int32_t* status, void* workspace, size_t workspace_bytes,
                               void* stream) {
-    if (!params_ok(params)) return SL_ERR_BADARG;
-    const long P = (long)h * w;
-    const MacenkoPlan pl = (n > 0 && h > 0 && w > 0) ? plan_macenko(n, P, params ? params->schedule : 0, params ? params->fused_min_tiles : 0) : MacenkoPlan{};
-    // this plan's own need: sl_workspace_bytes_for(op, n, h, w, params) (sl_workspace_bytes(), the maximum over every SlParams, always suffices)
-    int rc = check_common(rgb, n, h, w, workspace, workspace_bytes, pl.total);
-    if (rc) return rc;
-    const SlParams p = params_or_defaults(params);
-    char* ws = (char*)workspace;
-    double* M_all = M_out ? M_out : (double*)(ws + pl.L.off_M);
-    double* maxC_all = maxC_out ? maxC_out : (double*)(ws + pl.L.off_maxC);
-    int32_t* st_all = status ? status : (int32_t*)(ws + pl.L.off_status);
-    return run_macenko(pl, rgb, nullptr, n, h, w, p, nullptr, nullptr, M_all, maxC_all, st_all, ws, stream);
+    return fit_or_transform(kMethodMacenko, false, rgb, nullptr, n, h, w, params, nullptr, nullptr, M_out, maxC_out, status, nullptr,
+                            workspace, workspace_bytes, stream);
 }
 
 extern "C" int sl_macenko_transform(const uint8_t* rgb, uint8_t* out, int n, int h, int w, const SlParams* params,
                                     const double* M_tgt, const double* maxC_tgt, double* M_src_out,
                                     double* maxC_src_out, int32_t* status, void* workspace, size_t workspace_bytes,
                                     void* stream) {
-    if (!params_ok(params)) return SL_ERR_BADARG;
-    const long P = (long)h * w;
-    const MacenkoPlan pl = (n > 0 && h > 0 && w > 0) ? plan_macenko(n, P, params ? params->schedule : 0, params ? params->fused_min_tiles : 0) : MacenkoPlan{};
-    // this plan's own need: sl_workspace_bytes_for(op, n, h, w, params) (sl_workspace_bytes(), the maximum over every SlParams, always suffices)
-    int rc = check_common(rgb, n, h, w, workspace, workspace_bytes, pl.total);
-    if (rc) return rc;
-    if (!out || !M_tgt || !maxC_tgt) return SL_ERR_BADARG;
-    const SlParams p = params_or_defaults(params);
-    char* ws = (char*)workspace;
-    double* M_all = M_src_out ? M_src_out : (double*)(ws + pl.L.off_M);
-    double* maxC_all = maxC_src_out ? maxC_src_out : (double*)(ws + pl.L.off_maxC);
-    int32_t* st_all = status ? status : (int32_t*)(ws + pl.L.off_status);
-    return run_macenko(pl, rgb, out, n, h, w, p, M_tgt, maxC_tgt, M_all, maxC_all, st_all, ws, stream);
+    return fit_or_transform(kMethodMacenko, true, rgb, out, n, h, w, params, M_tgt, maxC_tgt, M_src_out, maxC_src_out, status, nullptr,
+                            workspace, workspace_bytes, stream);
 }
 
 // Vahadane: the persistent kernel for large batches, one launch per phase below kDictFusedMinTiles tiles.
 extern "C" int sl_vahadane_fit(const uint8_t* rgb, int n, int h, int w, const SlParams* params, double* M_out,
                                double* maxC_out, int32_t* status, int32_t* sweeps_out, void* workspace,
                                size_t workspace_bytes, void* stream) {
-    if (!params_ok(params)) return SL_ERR_BADARG;
-    const long P = (long)h * w;
-    const Layout L = (n > 0 && h > 0 && w > 0) ? make_layout(n, P, kMethodVahadane, params ? params->schedule : 0, params ? params->fused_min_tiles : 0) : Layout{};
-    int rc = check_common(rgb, n, h, w, workspace, workspace_bytes, L.total);
-    if (rc) return rc;
-    const SlParams p = params_or_defaults(params);
-    char* ws = (char*)workspace;
-    double* M_all = M_out ? M_out : (double*)(ws + L.off_M);
-    double* maxC_all = maxC_out ? maxC_out : (double*)(ws + L.off_maxC);
-    int32_t* st_all = status ? status : (int32_t*)(ws + L.off_status);
-    if (L.fused)
-        return run_fused(kMethodVahadane, rgb, nullptr, n, P, p, L, ws, nullptr, nullptr, M_all, maxC_all, st_all, sweeps_out,
-                         (hipStream_t)stream);
-    for (int g0 = 0; g0 < n; g0 += L.G) {
-        const int m = (n - g0) < L.G ? (n - g0) : L.G;
-        rc = run_dict_group(rgb, g0, m, P, p, L, ws, M_all, maxC_all, st_all, sweeps_out, (hipStream_t)stream);
-        if (rc) return rc;
-    }
-    return SL_OK;
+    return fit_or_transform(kMethodVahadane, false, rgb, nullptr, n, h, w, params, nullptr, nullptr, M_out, maxC_out, status, sweeps_out,
+                            workspace, workspace_bytes, stream);
 }
 
 extern "C" int sl_vahadane_transform(const uint8_t* rgb, uint8_t* out, int n, int h, int w, const SlParams* params,
                                      const double* M_tgt, const double* maxC_tgt, double* M_src_out,
                                      double* maxC_src_out, int32_t* status, void* workspace, size_t workspace_bytes,
                                      void* stream) {
-    if (!params_ok(params)) return SL_ERR_BADARG;
-    const long P = (long)h * w;
-    const Layout L = (n > 0 && h > 0 && w > 0) ? make_layout(n, P, kMethodVahadane, params ? params->schedule : 0, params ? params->fused_min_tiles : 0) : Layout{};
-    int rc = check_common(rgb, n, h, w, workspace, workspace_bytes, L.total);
-    if (rc) return rc;
-    if (!out || !M_tgt || !maxC_tgt) return SL_ERR_BADARG;
-    const SlParams p = params_or_defaults(params);
-    char* ws = (char*)workspace;
-    double* M_all = M_src_out ? M_src_out : (double*)(ws + L.off_M);
-    double* maxC_all = maxC_src_out ? maxC_src_out : (double*)(ws + L.off_maxC);
-    int32_t* st_all = status ? status : (int32_t*)(ws + L.off_status);
-    if (L.fused)
-        return run_fused(kMethodVahadane, rgb, out, n, P, p, L, ws, M_tgt, maxC_tgt, M_all, maxC_all, st_all, nullptr,
-                         (hipStream_t)stream);
-    for (int g0 = 0; g0 < n; g0 += L.G) {
-        const int m = (n - g0) < L.G ? (n - g0) : L.G;
-        rc = run_dict_group(rgb, g0, m, P, p, L, ws, M_all, maxC_all, st_all, nullptr, (hipStream_t)stream);
-        if (rc) return rc;
-        {
-            ProfScope ps(p.profile, SL_PROF_APPLY, m, (hipStream_t)stream);
-            rc = sl_normalize_apply(rgb + (size_t)g0 * 3 * P, out + (size_t)g0 * 3 * P, m, h, w,
-                                    M_all + 6 * (size_t)g0, maxC_all + 2 * (size_t)g0, M_tgt, maxC_tgt,
-                                    p.lasso_lambda, nullptr, stream);
-        }
-        if (rc) return rc;
-    }
-    return SL_OK;
+    return fit_or_transform(kMethodVahadane, true, rgb, out, n, h, w, params, M_tgt, maxC_tgt, M_src_out, maxC_src_out, status, nullptr,
+                            workspace, workspace_bytes, stream);
 }
 
 #ifdef SL_DEVTOOLS

@@ -40,14 +40,23 @@ inline float tissue_ylimf(const SlParams& p) { return (float)y_limit_for_thresho
 // resident persistent-sweep workgroups of the current device (2 per CU; see common.hip)
 int max_resident_grid();
 
-// zeroes `bytes` (a multiple of 4) at the 4-byte aligned p with a kernel on s: see common.hip (hipMemsetAsync is not capture-safe here)
-void zero_async(void* p, size_t bytes, hipStream_t s);
+// zeroes `bytes` at p with a kernel on s and returns the launch status: see common.hip (hipMemsetAsync is not capture-safe here).
+// p must be 4-byte aligned and bytes a multiple of 4 (callers static_assert it where the size is a sizeof); nothing checks it here.
+int zero_async(void* p, size_t bytes, hipStream_t s);
 
 // workspace of the Lab family (lab.hip)
 size_t lab_workspace_bytes(int n_tiles);
 
 inline bool aligned4(const void* p, long pixels_per_tile) {
     return ((uintptr_t)p & 3u) == 0 && (pixels_per_tile & 3) == 0;
+}
+
+// Launches k_aligned when `aligned` (aligned4 of every tile pointer the kernel reads or writes), else k_unaligned: the two
+// instantiations of one sweep kernel, with the same geometry and arguments.
+template <class K, class... Args>
+inline void launch_aligned(bool aligned, K k_aligned, K k_unaligned, dim3 grid, dim3 block, unsigned lds, hipStream_t s, Args... args) {
+    if (aligned) hipLaunchKernelGGL(k_aligned, grid, block, lds, s, args...);
+    else hipLaunchKernelGGL(k_unaligned, grid, block, lds, s, args...);
 }
 
 // Workgroups a tile of P pixels is split into for the streaming sweeps: ~32 Ki pixels each,

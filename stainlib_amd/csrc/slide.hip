@@ -634,13 +634,10 @@ template <int NEXT>
 void launch_keys(const SlideArgs& a, bool al, unsigned long long* hist, uint32_t* min_out, hipStream_t s) {
     const int mg = max_resident_grid();
     const dim3 g((unsigned)(a.n_items < mg ? a.n_items : mg)), b(kSweepThreads);
-    if (a.keyset == SL_KEYSET_ANGLE) {
-        if (al) hipLaunchKernelGGL((k_slide_keys<SL_KEYSET_ANGLE, NEXT, true>), g, b, 0, s, a, hist, min_out);
-        else    hipLaunchKernelGGL((k_slide_keys<SL_KEYSET_ANGLE, NEXT, false>), g, b, 0, s, a, hist, min_out);
-    } else {
-        if (al) hipLaunchKernelGGL((k_slide_keys<SL_KEYSET_CONC, NEXT, true>), g, b, 0, s, a, hist, min_out);
-        else    hipLaunchKernelGGL((k_slide_keys<SL_KEYSET_CONC, NEXT, false>), g, b, 0, s, a, hist, min_out);
-    }
+    if (a.keyset == SL_KEYSET_ANGLE)
+        launch_aligned(al, k_slide_keys<SL_KEYSET_ANGLE, NEXT, true>, k_slide_keys<SL_KEYSET_ANGLE, NEXT, false>, g, b, 0, s, a, hist, min_out);
+    else
+        launch_aligned(al, k_slide_keys<SL_KEYSET_CONC, NEXT, true>, k_slide_keys<SL_KEYSET_CONC, NEXT, false>, g, b, 0, s, a, hist, min_out);
 }
 
 // the basis fill_args is given by the sl_pool_* sweeps, whose keys come from the pool state (SlideArgs::dyn) instead
@@ -662,10 +659,8 @@ extern "C" int sl_tile_moments(const uint8_t* rgb, int n, int h, int w, const Sl
     const float ylimf = tissue_ylimf(params_or_defaults(params));
     hipStream_t s = (hipStream_t)stream;
     const dim3 g((unsigned)(items < mg ? items : mg)), b(kSweepThreads);
-    if (aligned4(rgb, P))
-        hipLaunchKernelGGL((k_tile_moment_partials<true>), g, b, 0, s, rgb, (int)P, parts, (int)items, ylimf, (double*)workspace);
-    else
-        hipLaunchKernelGGL((k_tile_moment_partials<false>), g, b, 0, s, rgb, (int)P, parts, (int)items, ylimf, (double*)workspace);
+    launch_aligned(aligned4(rgb, P), k_tile_moment_partials<true>, k_tile_moment_partials<false>, g, b, 0, s, rgb, (int)P, parts, (int)items, ylimf,
+                   (double*)workspace);
     hipLaunchKernelGGL(k_sum_partials, dim3((unsigned)((n * 10 + 255) / 256)), dim3(256), 0, s, (const double*)workspace, n, parts,
                        moments_out);
     return launch_status();
@@ -716,13 +711,8 @@ namespace {
 void launch_window(const SlideArgs& a, bool al, unsigned long long* hist_below, hipStream_t s) {
     const int mg = max_resident_grid();
     const dim3 g((unsigned)(a.n_items < mg ? a.n_items : mg)), b(kSweepThreads);
-    if (a.keyset == SL_KEYSET_ANGLE) {
-        if (al) hipLaunchKernelGGL((k_slide_window<SL_KEYSET_ANGLE, true>), g, b, 0, s, a, hist_below);
-        else    hipLaunchKernelGGL((k_slide_window<SL_KEYSET_ANGLE, false>), g, b, 0, s, a, hist_below);
-    } else {
-        if (al) hipLaunchKernelGGL((k_slide_window<SL_KEYSET_CONC, true>), g, b, 0, s, a, hist_below);
-        else    hipLaunchKernelGGL((k_slide_window<SL_KEYSET_CONC, false>), g, b, 0, s, a, hist_below);
-    }
+    if (a.keyset == SL_KEYSET_ANGLE) launch_aligned(al, k_slide_window<SL_KEYSET_ANGLE, true>, k_slide_window<SL_KEYSET_ANGLE, false>, g, b, 0, s, a, hist_below);
+    else launch_aligned(al, k_slide_window<SL_KEYSET_CONC, true>, k_slide_window<SL_KEYSET_CONC, false>, g, b, 0, s, a, hist_below);
 }
 
 }  // namespace

@@ -215,10 +215,8 @@ extern "C" int sl_sdict_sweep(const uint8_t* rgb, int n, int h, int w, const SlP
         rows = sd_grid(n, P);
         const float ylimf = tissue_ylimf(p);
         const dim3 g((unsigned)rows), b(kSweepThreads);
-        if (aligned4(rgb, P))
-            hipLaunchKernelGGL((k_sd_sweep<true>), g, b, 0, s, rgb, (int)P, parts, items, sample_log2, ylimf, p.dl_lambda, state, (double*)workspace);
-        else
-            hipLaunchKernelGGL((k_sd_sweep<false>), g, b, 0, s, rgb, (int)P, parts, items, sample_log2, ylimf, p.dl_lambda, state, (double*)workspace);
+        launch_aligned(aligned4(rgb, P), k_sd_sweep<true>, k_sd_sweep<false>, g, b, 0, s, rgb, (int)P, parts, items, sample_log2, ylimf, p.dl_lambda,
+                       state, (double*)workspace);
     }
     hipLaunchKernelGGL(k_sd_reduce, dim3(1), dim3(kSdReduceThreads), 0, s, (const double*)workspace, rows, (double)n * (double)P, sums_out);
     return launch_status();

@@ -1146,15 +1146,14 @@ extern "C" int sl_pool2_sample(const uint8_t* rgb, int n, int h, int w, const Sl
     if (!moments16_out) return SL_ERR_BADARG;
     hipStream_t s = (hipStream_t)stream;
     uint8_t* ws = (uint8_t*)workspace;
-    zero_async(ws, 256, s);                                     // (a kernel: see common.hip)
+    if (const int rc = zero_async(ws, 256, s)) return rc;       // (a kernel: see common.hip)
     P2SampleArgs a;
     a.rgb = rgb; a.P = h * w; a.parts = L.parts; a.n_items = L.n_items; a.slog = sample_log2; a.bpi = L.bpi;
     a.ylimf = tissue_ylimf(p);
     a.list = P2List{(uint32_t*)(ws + L.s_entries), (uint32_t*)(ws + L.s_counts), (unsigned int*)(ws + L.hdr), L.s_cap, kP2SampleBlkLog2, 0u, 0u};
     a.partials = (double*)(ws + L.partials);
     const dim3 g((unsigned)L.grid), b(kSweepThreads);
-    if (aligned4(rgb, (long)h * w)) hipLaunchKernelGGL((k_p2_sample<true>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((k_p2_sample<false>), g, b, 0, s, a);
+    launch_aligned(aligned4(rgb, (long)h * w), k_p2_sample<true>, k_p2_sample<false>, g, b, 0, s, a);
     hipLaunchKernelGGL(k_p2_sum, dim3(1), dim3(1024), 0, s, (const double*)a.partials, L.grid, 11, moments16_out, 0.0, -1,
                        (const unsigned int*)(ws + L.hdr), L.s_cap, 11);
     return launch_status();
@@ -1232,8 +1231,8 @@ extern "C" int sl_pool2_sweep(const uint8_t* rgb, int n, int h, int w, const SlP
     if (!state || !totals16_out) return SL_ERR_BADARG;
     hipStream_t s = (hipStream_t)stream;
     uint8_t* ws = (uint8_t*)workspace;
-    zero_async(ws + 64, 64, s);
-    zero_async(ws + L.c_counts, 4 * (size_t)L.c_cap, s);
+    if (const int rc = zero_async(ws + 64, 64, s)) return rc;
+    if (const int rc = zero_async(ws + L.c_counts, 4 * (size_t)L.c_cap, s)) return rc;
     P2SweepArgs a;
     a.rgb = rgb; a.P = h * w; a.parts = L.parts; a.n_items = L.n_items;
     a.ylimf = tissue_ylimf(p);
@@ -1242,8 +1241,7 @@ extern "C" int sl_pool2_sweep(const uint8_t* rgb, int n, int h, int w, const SlP
     a.list = P2List{(uint32_t*)(ws + L.c_entries), (uint32_t*)(ws + L.c_counts), (unsigned int*)(ws + L.hdr + 64), L.c_cap, kP2CandBlkLog2, L.c_priv, pool0};
     a.partials = (double*)(ws + L.partials);
     const dim3 g((unsigned)L.grid), b(kSweepThreads);
-    if (aligned4(rgb, (long)h * w)) hipLaunchKernelGGL((k_p2_sweep<true>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((k_p2_sweep<false>), g, b, 0, s, a);
+    launch_aligned(aligned4(rgb, (long)h * w), k_p2_sweep<true>, k_p2_sweep<false>, g, b, 0, s, a);
     hipLaunchKernelGGL(k_p2_sum, dim3(1), dim3(1024), 0, s, (const double*)a.partials, L.grid, 12, totals16_out, (double)n * h * w, 12,
                        (const unsigned int*)(ws + L.hdr + 64), L.c_cap - pool0, 13);
     return launch_status();

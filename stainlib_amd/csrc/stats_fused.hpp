@@ -106,6 +106,14 @@ __device__ __forceinline__ void fused_lds_origin(const FusedShared<NT>& sh) {
 
 // (the finish steps inlined into the kernel again: measured +3.7 %)
 #define SL_FINISH_ATTR __noinline__
+// The development build's sub-step clocks (make dev: -DSL_DEBUG_SUBCLK): a barrier, then wall_clock64() into clk[j] when clk is set.
+// SL_SUB writes the slots of the phase functions' `subclk` argument (k_fused passes SL_TILE_SUBCLK); nothing in the product build.
+#ifdef SL_DEBUG_SUBCLK
+#define SL_SUB_AT(clk, j) { __syncthreads(); if ((clk) && tid == 0) (clk)[(j)] = wall_clock64(); }
+#else
+#define SL_SUB_AT(clk, j)
+#endif
+#define SL_SUB(j) SL_SUB_AT(subclk, j)
 // wave-uniform values arrive in VGPRs at an out-of-line function: back to SGPRs
 template <class T>
 __device__ __forceinline__ T* uni_ptr(T* p) {
@@ -162,11 +170,6 @@ __device__ SL_FINISH_ATTR void fused_finish1(FusedShared<NT>* shp, uint32_t* sam
     const double pct = uni_d(pct_), lam = uni_d(lam_);
     long long* subclk = uni_ptr(subclk_);
     const int tid = threadIdx.x;
-#ifdef SL_DEBUG_SUBCLK
-#define SL_SUB(j) { __syncthreads(); if (subclk && tid == 0) subclk[(j)] = wall_clock64(); }
-#else
-#define SL_SUB(j)
-#endif
     (void)subclk;
     {
         SampleAngleKey key;                                           // (scoped: kept alive across the function it cost the bracket code registers)
@@ -237,7 +240,6 @@ __device__ SL_FINISH_ATTR void fused_finish1(FusedShared<NT>* shp, uint32_t* sam
         if (tid == 0 && ((unsigned long long)sh.S.misc[32] << stride_log2) > (unsigned long long)P / 40ull) sh.xmin = -INFINITY;
         __syncthreads();
     }
-#undef SL_SUB
 }
 
 // ---- The sweeps of the fused kernel, each OUT OF LINE (round 4) like the finish steps since round 3: every one of them gets
@@ -420,11 +422,6 @@ __device__ SL_FINISH_ATTR int fused_finish2(FusedShared<NT>* shp, const uint8_t*
     const int ts = __builtin_amdgcn_readfirstlane(ts_);
     const int tid = threadIdx.x, wave = tid >> 6;
     int fallbacks = 0;
-#ifdef SL_DEBUG_SUBCLK
-#define SL_SUB(j) { __syncthreads(); if (subclk && tid == 0) subclk[(j)] = wall_clock64(); }
-#else
-#define SL_SUB(j)
-#endif
     (void)subclk;
     // ---------------- finish 2: exact angular percentiles -> M  (see "Finish 2 of the fused kernel" above wg_refine_s)
     const uint32_t T = (uint32_t)sh.sum[0];
@@ -534,7 +531,6 @@ __device__ SL_FINISH_ATTR int fused_finish2(FusedShared<NT>* shp, const uint8_t*
     }
     fin_tab_expand<NT>(sh.tab);                                   // the row table back for the sweeps to come
     return fallbacks;
-#undef SL_SUB
 }
 
 // ------------------------------------------------------------------------------------------
@@ -633,11 +629,6 @@ __device__ SL_FINISH_ATTR void fused_phase0(FusedShared<NT>* shp, const uint8_t*
     const int n_sample = n_lines * kClusterPx;
     constexpr int KPT = kMaxSample / NT;
     static_assert(KPT % 8 == 0, "");
-#ifdef SL_DEBUG_SUBCLK
-#define SL_SUB(j) { __syncthreads(); if (subclk && tid == 0) subclk[(j)] = wall_clock64(); }
-#else
-#define SL_SUB(j)
-#endif
     (void)subclk;
     SL_SUB(0);
     if (tid == 0) { sh.ts.ok = 0; sh.ts.why = kTsNoEstimate; sh.mk.ok = 0; sh.use_cube = 0; }
@@ -903,7 +894,6 @@ __device__ SL_FINISH_ATTR void fused_phase0(FusedShared<NT>* shp, const uint8_t*
         __syncthreads();
     }
     SL_SUB(6);
-#undef SL_SUB
 }
 
 // Sweep 1 of the two-sweep schedule: moments into sh.red (as fused_sweep1) and the candidates of all four order statistics into the
@@ -1082,12 +1072,7 @@ __device__ __noinline__ int fused_conc_resweep(FusedShared<NT>* shp, const uint8
     long long* subclk = uni_ptr(subclk_);
     const int tid = threadIdx.x;
     int fallbacks = 0;
-#ifdef SL_DEBUG_SUBCLK
-#define SL_SUB(j) { __syncthreads(); if (subclk && tid == 0) subclk[(j)] = wall_clock64(); }
-#else
-#define SL_SUB(j)
     (void)subclk;
-#endif
     if (tid == 0) {
         LassoK L;
         lasso_consts(sh.M, lam, L);
@@ -1143,7 +1128,6 @@ __device__ __noinline__ int fused_conc_resweep(FusedShared<NT>* shp, const uint8
         }
         __syncthreads();
     }
-#undef SL_SUB
     return fallbacks;
 }
 
@@ -1197,10 +1181,17 @@ static __global__ __launch_bounds__(NT, 4) void k_fused(FusedArgs a) {
 #else
 #define SL_PHASE(i)
 #endif
+// The clock slots of this tile (development build; nullptr in the product build): its 16 sub-step slots behind the [n_tiles][8] phase
+// clocks, which the kernel's own sub-steps and the phase functions write, and for phase 0 a third region, only for the tool that
+// allocates it (sl_debug_set_stop(-7)).  (Macros, not variables: a pointer computed once per tile moved the development build's code.)
 #ifdef SL_DEBUG_SUBCLK
-#define SL_SUB(j) { __syncthreads(); if (a.phase_clock && tid == 0) a.phase_clock[(size_t)a.n_tiles * 8 + (size_t)tile * 16 + (j)] = wall_clock64(); }
+#define SL_TILE_SUBCLK (a.phase_clock ? a.phase_clock + (size_t)a.n_tiles * 8 + (size_t)tile * 16 : nullptr)
+#define SL_TILE_SUBCLK0 ((a.phase_clock && a.debug_stop == -7) ? a.phase_clock + (size_t)a.n_tiles * 24 + (size_t)tile * 16 : nullptr)
+#define SL_TILE_SUB(j) SL_SUB_AT(a.phase_clock, (size_t)a.n_tiles * 8 + (size_t)tile * 16 + (j))
 #else
-#define SL_SUB(j)
+#define SL_TILE_SUBCLK nullptr
+#define SL_TILE_SUBCLK0 nullptr
+#define SL_TILE_SUB(j)
 #endif
         SL_PHASE(0);
         if (tile == (int)blockIdx.x) sh.tab.fill_b();       // the row table: written once, before the workgroup's first tile
@@ -1225,14 +1216,7 @@ static __global__ __launch_bounds__(NT, 4) void k_fused(FusedArgs a) {
             // declined attempt costs 50-160 us (real tissue, 2 048 tiles of 512^2: +9 % against three sweeps without the back-off).
             const bool ts_try = a.two_sweep >= 2 || (a.two_sweep == 1 && ts_backoff == 0);   // block-uniform (both workgroup sizes: the 1024-thread kernel gains 5-8 % at 192-256 tiles)
             if (ts_try) {
-                fused_phase0<NT>(&sh, src, samp, a.P, a.cl_lines, a.ylimf, a.pct, a.lam, a.two_sweep, a.cap_raw, a.cap_ang, a.cap_list,
-#ifdef SL_DEBUG_SUBCLK
-                                 // (development: a third region of the clock buffer, only for the tool that allocates it: sl_debug_set_stop(-7))
-                                 (a.phase_clock && a.debug_stop == -7) ? a.phase_clock + (size_t)a.n_tiles * 24 + (size_t)tile * 16 : nullptr
-#else
-                                 nullptr
-#endif
-                                 );
+                fused_phase0<NT>(&sh, src, samp, a.P, a.cl_lines, a.ylimf, a.pct, a.lam, a.two_sweep, a.cap_raw, a.cap_ang, a.cap_list, SL_TILE_SUBCLK0);
                 __syncthreads();
             }
             const bool ts_on = sh.ts.ok != 0;                                 // block-uniform
@@ -1252,7 +1236,7 @@ static __global__ __launch_bounds__(NT, 4) void k_fused(FusedArgs a) {
             __syncthreads();
             SL_PHASE(1);
             // ---------------- finish 1: eigenvectors, angle brackets
-            SL_SUB(0);
+            SL_TILE_SUB(0);
             if (lane_id() == 0) {
                 double Vd[6];
                 float Vf[6];
@@ -1261,7 +1245,7 @@ static __global__ __launch_bounds__(NT, 4) void k_fused(FusedArgs a) {
                 sh.conc_done = 0;
             }
             __syncthreads();
-            SL_SUB(1);
+            SL_TILE_SUB(1);
             bool direct = false;                                              // block-uniform: the two-sweep route settled the tile's M
             if (sh.status == SL_TILE_OK && ts_on) {                           // block-uniform
                 // ---------------- two-sweep finish: do the half-spaces the sweep tested against hold for the exact eigenvectors?
@@ -1276,12 +1260,7 @@ static __global__ __launch_bounds__(NT, 4) void k_fused(FusedArgs a) {
                 __syncthreads();
                 if (sh.ts.ok) {                                               // block-uniform
                     const int fb = fused_finish2<NT>(&sh, src, rawl, rawa, cand0, cand1, a.P, a.cap_raw, a.cap_ang, a.cap_list, a.ylimf, a.pct, a.lam,
-#ifdef SL_DEBUG_SUBCLK
-                                                     a.phase_clock ? a.phase_clock + (size_t)a.n_tiles * 8 + (size_t)tile * 16 : nullptr
-#else
-                                                     nullptr
-#endif
-                                                     , 1);
+                                                     SL_TILE_SUBCLK, 1);
                     if (fb >= 0) { fallbacks += fb; direct = true; }
                     else if (lane_id() == 0) { sh.ts.ok = 0; sh.ts.why = kTsBracket; }
                 }
@@ -1300,12 +1279,7 @@ static __global__ __launch_bounds__(NT, 4) void k_fused(FusedArgs a) {
                 // ---------------- finish 1, the rest of it (out of line like finish 2): angle brackets, the box of stain matrices the
                 // sample leaves possible, concentration brackets under its centre
                 fused_finish1<NT>(&sh, samp, ts_on ? a.cl_lines * kClusterPx : a.n_sample, ts_on ? -a.cl_scale_log2 : a.stride_log2, a.P, a.ylimf, a.pct, a.lam,
-#ifdef SL_DEBUG_SUBCLK
-                                  a.phase_clock ? a.phase_clock + (size_t)a.n_tiles * 8 + (size_t)tile * 16 : nullptr
-#else
-                                  nullptr
-#endif
-                                  , a.use_cube);
+                                  SL_TILE_SUBCLK, a.use_cube);
                 SL_PHASE(2);
                 // ---------------- sweep 2: angle select + concentration select under the box
                 run_select(true, src);
@@ -1313,13 +1287,7 @@ static __global__ __launch_bounds__(NT, 4) void k_fused(FusedArgs a) {
                 // ---------------- finish 2 (out of line: its registers are allocated apart from the sweeps'): exact angular percentiles
                 // -> M, then the concentration percentiles -> maxC from the same raw list
                 fallbacks += fused_finish2<NT>(&sh, src, rawl, (sh.use_cube & 1) ? rawa : nullptr, cand0, cand1, a.P, a.cap_raw, a.cap_ang, a.cap_list, a.ylimf,
-                                               a.pct, a.lam,
-#ifdef SL_DEBUG_SUBCLK
-                                               a.phase_clock ? a.phase_clock + (size_t)a.n_tiles * 8 + (size_t)tile * 16 : nullptr
-#else
-                                               nullptr
-#endif
-                                               );
+                                               a.pct, a.lam, SL_TILE_SUBCLK);
             }
         } else {
             // ---------------- Vahadane: class-moment dictionary learning
@@ -1357,12 +1325,7 @@ static __global__ __launch_bounds__(NT, 4) void k_fused(FusedArgs a) {
 #else
                                                          nullptr,
 #endif
-#ifdef SL_DEBUG_SUBCLK
-                                                         a.phase_clock ? a.phase_clock + (size_t)a.n_tiles * 8 + (size_t)tile * 16 : nullptr
-#else
-                                                         nullptr
-#endif
-                                                         );
+                                                         SL_TILE_SUBCLK);
         } else if (bad && sh.status != SL_TILE_ZERO_MAXC && lane_id() == 0) {     // (a zero maxC keeps its M and maxC, as after finish 3)
             for (int i = 0; i < 6; ++i) sh.M[i] = nan_d();
             sh.maxC[0] = sh.maxC[1] = nan_d();
@@ -1397,9 +1360,13 @@ static __global__ __launch_bounds__(NT, 4) void k_fused(FusedArgs a) {
         __syncthreads();     // sh.* is reused by the next tile
         SL_PHASE(7);
 #undef SL_PHASE
-#undef SL_SUB
+#undef SL_TILE_SUBCLK
+#undef SL_TILE_SUBCLK0
+#undef SL_TILE_SUB
     }
 }
+#undef SL_SUB
+#undef SL_SUB_AT
 
 // host-side launchers of the twelve instantiations, one translation unit per family (transform: with the apply sweep; aligned: 4-byte
 // aligned tiles of a multiple of four pixels)

@@ -21,6 +21,16 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def _params(params):
+    """ctypes reference to the caller's SlParams, or to the defaults when params is None."""
+    return C.byref(params if params is not None else _ffi.default_params())
+
+
+def _call(name, *args):
+    """lib().<name>(*args, current stream); an error code raises StainlibHipError("<name> failed: ...")."""
+    _ffi.check(getattr(_ffi.lib(), name)(*args, _stream()), name)
+
+
 def _check_tiles(rgb: torch.Tensor):
     if not (isinstance(rgb, torch.Tensor) and rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.dim() == 4
             and rgb.shape[-1] == 3 and rgb.is_contiguous()):
@@ -130,30 +140,21 @@ def normalize_apply(rgb, M_src, maxC_src, M_tgt, maxC_tgt, lasso_lambda=0.01, ou
     if out is None:
         out = torch.empty_like(rgb)
     pre = torch.empty((n, h, w, 3), dtype=torch.float32, device=dev) if want_prequant else None
-    _ffi.check(_ffi.lib().sl_normalize_apply(_ptr(rgb), _ptr(out), n, h, w, _ptr(M_src), _ptr(maxC_src),
-                                             _ptr(M_tgt), _ptr(maxC_tgt), float(lasso_lambda), _ptr(pre),
-                                             _stream()), "sl_normalize_apply")
+    _call("sl_normalize_apply", _ptr(rgb), _ptr(out), n, h, w, _ptr(M_src), _ptr(maxC_src), _ptr(M_tgt), _ptr(maxC_tgt),
+          float(lasso_lambda), _ptr(pre))
     return (out, pre) if want_prequant else out
 
 
 def _fit(fn_name, op, rgb, params, ws, with_sweeps=False):
     n, h, w = _check_tiles(rgb)
     dev = rgb.device
-    p = params if params is not None else _ffi.default_params()
     M = torch.empty((n, 2, 3), dtype=torch.float64, device=dev)
     maxC = torch.empty((n, 2), dtype=torch.float64, device=dev)
     status = torch.empty((n,), dtype=torch.int32, device=dev)
-    wsb = _scratch(ws, op, n, h, w, dev, p)
-    fn = getattr(_ffi.lib(), fn_name)
-    if with_sweeps:
-        sweeps = torch.empty((n,), dtype=torch.int32, device=dev)
-        code = fn(_ptr(rgb), n, h, w, C.byref(p), _ptr(M), _ptr(maxC), _ptr(status), _ptr(sweeps), _ptr(wsb),
-                  wsb.numel(), _stream())
-        _ffi.check(code, fn_name)
-        return M, maxC, status, sweeps
-    code = fn(_ptr(rgb), n, h, w, C.byref(p), _ptr(M), _ptr(maxC), _ptr(status), _ptr(wsb), wsb.numel(), _stream())
-    _ffi.check(code, fn_name)
-    return M, maxC, status
+    wsb = _scratch(ws, op, n, h, w, dev, params)
+    sweeps = (torch.empty((n,), dtype=torch.int32, device=dev),) if with_sweeps else ()
+    _call(fn_name, _ptr(rgb), n, h, w, _params(params), _ptr(M), _ptr(maxC), _ptr(status), *map(_ptr, sweeps), _ptr(wsb), wsb.numel())
+    return (M, maxC, status) + sweeps
 
 
 def macenko_fit(rgb, params=None, ws=None):
@@ -169,7 +170,6 @@ def vahadane_fit(rgb, params=None, ws=None):
 def _transform(fn_name, op, rgb, M_tgt, maxC_tgt, params, out, ws):
     n, h, w = _check_tiles(rgb)
     dev = rgb.device
-    p = params if params is not None else _ffi.default_params()
     M_tgt = _f64(M_tgt, (2, 3), dev)
     maxC_tgt = _f64(maxC_tgt, (2,), dev)
     if out is None:
@@ -177,10 +177,9 @@ def _transform(fn_name, op, rgb, M_tgt, maxC_tgt, params, out, ws):
     M = torch.empty((n, 2, 3), dtype=torch.float64, device=dev)
     maxC = torch.empty((n, 2), dtype=torch.float64, device=dev)
     status = torch.empty((n,), dtype=torch.int32, device=dev)
-    wsb = _scratch(ws, op, n, h, w, dev, p)
-    code = getattr(_ffi.lib(), fn_name)(_ptr(rgb), _ptr(out), n, h, w, C.byref(p), _ptr(M_tgt), _ptr(maxC_tgt),
-                                        _ptr(M), _ptr(maxC), _ptr(status), _ptr(wsb), wsb.numel(), _stream())
-    _ffi.check(code, fn_name)
+    wsb = _scratch(ws, op, n, h, w, dev, params)
+    _call(fn_name, _ptr(rgb), _ptr(out), n, h, w, _params(params), _ptr(M_tgt), _ptr(maxC_tgt), _ptr(M), _ptr(maxC), _ptr(status),
+          _ptr(wsb), wsb.numel())
     return out, M, maxC, status
 
 
@@ -203,9 +202,8 @@ def hed_augment(rgb, sigma, bias, cutoff=(0.05, 0.95), skimage_mode=0, out=None,
         out = torch.empty_like(rgb)
     applied = torch.empty((n,), dtype=torch.int32, device=dev)
     wsb = _scratch(ws, _ffi.OP_HED_AUGMENT, n, h, w, dev)
-    _ffi.check(_ffi.lib().sl_hed_augment(_ptr(rgb), _ptr(out), n, h, w, _ptr(sigma), _ptr(bias), float(cutoff[0]),
-                                         float(cutoff[1]), int(skimage_mode), _ptr(applied), _ptr(wsb), wsb.numel(),
-                                         _stream()), "sl_hed_augment")
+    _call("sl_hed_augment", _ptr(rgb), _ptr(out), n, h, w, _ptr(sigma), _ptr(bias), float(cutoff[0]), float(cutoff[1]), int(skimage_mode),
+          _ptr(applied), _ptr(wsb), wsb.numel())
     if want_sums:
         return out, applied, wsb[:8 * n].view(torch.int64).clone()
     return out, applied
@@ -222,9 +220,8 @@ def hed_augment_float(patches, sigma, bias, cutoff=(0.05, 0.95), skimage_mode=0)
     out = torch.empty_like(patches)
     applied = torch.empty((n,), dtype=torch.int32, device=dev)
     wsb = torch.empty(max(8 * n, 256), dtype=torch.uint8, device=dev)
-    _ffi.check(_ffi.lib().sl_hed_augment_f64(_ptr(patches), _ptr(out), n, h, w, _ptr(sigma), _ptr(bias), float(cutoff[0]),
-                                             float(cutoff[1]), int(skimage_mode), _ptr(applied), _ptr(wsb), wsb.numel(),
-                                             _stream()), "sl_hed_augment_f64")
+    _call("sl_hed_augment_f64", _ptr(patches), _ptr(out), n, h, w, _ptr(sigma), _ptr(bias), float(cutoff[0]), float(cutoff[1]),
+          int(skimage_mode), _ptr(applied), _ptr(wsb), wsb.numel())
     return out, applied
 
 
@@ -232,7 +229,7 @@ def rgb_to_od(rgb):
     """convert_RGB_to_OD materialised: (N,H,W,3) float64."""
     n, h, w = _check_tiles(rgb)
     od = torch.empty((n, h, w, 3), dtype=torch.float64, device=rgb.device)
-    _ffi.check(_ffi.lib().sl_rgb_to_od(_ptr(rgb), n, h, w, _ptr(od), _stream()), "sl_rgb_to_od")
+    _call("sl_rgb_to_od", _ptr(rgb), n, h, w, _ptr(od))
     return od
 
 
@@ -242,11 +239,9 @@ def stain_augment(rgb, M, alpha_beta, augment_background=False, params=None, out
     dev = rgb.device
     M = _f64(M, (n, 2, 3), dev)
     ab = _f64(alpha_beta, (n, 4), dev)
-    p = params if params is not None else _ffi.default_params()
     if out is None:
         out = torch.empty_like(rgb)
-    _ffi.check(_ffi.lib().sl_stain_augment(_ptr(rgb), _ptr(out), n, h, w, _ptr(M), _ptr(ab),
-                                           1 if augment_background else 0, C.byref(p), _stream()), "sl_stain_augment")
+    _call("sl_stain_augment", _ptr(rgb), _ptr(out), n, h, w, _ptr(M), _ptr(ab), 1 if augment_background else 0, _params(params))
     return out
 
 
@@ -256,7 +251,7 @@ def grayscale_augment(rgb, alpha_beta, out=None):
     ab = _f64(alpha_beta, (n, 2), rgb.device)
     if out is None:
         out = torch.empty_like(rgb)
-    _ffi.check(_ffi.lib().sl_grayscale_augment(_ptr(rgb), _ptr(out), n, h, w, _ptr(ab), _stream()), "sl_grayscale_augment")
+    _call("sl_grayscale_augment", _ptr(rgb), _ptr(out), n, h, w, _ptr(ab))
     return out
 
 
@@ -266,8 +261,7 @@ def tissue_mask(rgb, luminosity_threshold=0.8, want_mask=True):
     dev = rgb.device
     mask = torch.empty((n, h, w), dtype=torch.uint8, device=dev) if want_mask else None
     counts = torch.empty((n,), dtype=torch.int64, device=dev)
-    _ffi.check(_ffi.lib().sl_tissue_mask(_ptr(rgb), n, h, w, float(luminosity_threshold), _ptr(mask), _ptr(counts),
-                                         _stream()), "sl_tissue_mask")
+    _call("sl_tissue_mask", _ptr(rgb), n, h, w, float(luminosity_threshold), _ptr(mask), _ptr(counts))
     return mask, counts
 
 
@@ -277,8 +271,7 @@ def concentrations(rgb, M, lasso_lambda=0.01):
     dev = rgb.device
     M = _f64(M, (n, 2, 3), dev)
     Cout = torch.empty((n, h * w, 2), dtype=torch.float32, device=dev)
-    _ffi.check(_ffi.lib().sl_concentrations(_ptr(rgb), n, h, w, _ptr(M), float(lasso_lambda), _ptr(Cout), _stream()),
-               "sl_concentrations")
+    _call("sl_concentrations", _ptr(rgb), n, h, w, _ptr(M), float(lasso_lambda), _ptr(Cout))
     return Cout
 
 
@@ -288,7 +281,7 @@ def od_to_rgb(od):
         raise ValueError("expected a contiguous CUDA float64 tensor")
     out = torch.empty(od.shape, dtype=torch.uint8, device=od.device)
     neg = torch.zeros((1,), dtype=torch.int32, device=od.device)
-    _ffi.check(_ffi.lib().sl_od_to_rgb(_ptr(od), od.numel(), _ptr(out), _ptr(neg), _stream()), "sl_od_to_rgb")
+    _call("sl_od_to_rgb", _ptr(od), od.numel(), _ptr(out), _ptr(neg))
     return out, neg
 
 
@@ -297,7 +290,7 @@ def rgb_to_lab8(rgb):
     """cv2.cvtColor(COLOR_RGB2LAB) on uint8 tiles -> (N,H,W,3) uint8."""
     n, h, w = _check_tiles(rgb)
     out = torch.empty_like(rgb)
-    _ffi.check(_ffi.lib().sl_rgb_to_lab8(_ptr(rgb), _ptr(out), n, h, w, _stream()), "sl_rgb_to_lab8")
+    _call("sl_rgb_to_lab8", _ptr(rgb), _ptr(out), n, h, w)
     return out
 
 
@@ -305,7 +298,7 @@ def lab8_to_rgb(lab):
     """cv2.cvtColor(COLOR_LAB2RGB) on uint8 tiles."""
     n, h, w = _check_tiles(lab)
     out = torch.empty_like(lab)
-    _ffi.check(_ffi.lib().sl_lab8_to_rgb(_ptr(lab), _ptr(out), n, h, w, _stream()), "sl_lab8_to_rgb")
+    _call("sl_lab8_to_rgb", _ptr(lab), _ptr(out), n, h, w)
     return out
 
 
@@ -313,7 +306,7 @@ def lab_split(rgb):
     """lab_split: three (N,H,W) float32 planes L8/2.55, a8-128, b8-128."""
     n, h, w = _check_tiles(rgb)
     I1, I2, I3 = (torch.empty((n, h, w), dtype=torch.float32, device=rgb.device) for _ in range(3))
-    _ffi.check(_ffi.lib().sl_lab_split(_ptr(rgb), n, h, w, _ptr(I1), _ptr(I2), _ptr(I3), _stream()), "sl_lab_split")
+    _call("sl_lab_split", _ptr(rgb), n, h, w, _ptr(I1), _ptr(I2), _ptr(I3))
     return I1, I2, I3
 
 
@@ -324,8 +317,7 @@ def lab_merge(I1, I2, I3):
         raise ValueError("expected three contiguous CUDA (N, H, W) planes of one float dtype")
     n, h, w = I1.shape
     out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=I1.device)
-    _ffi.check(_ffi.lib().sl_lab_merge(_ptr(I1), _ptr(I2), _ptr(I3), 1 if I1.dtype == torch.float64 else 0, n, h, w, _ptr(out),
-                                       _stream()), "sl_lab_merge")
+    _call("sl_lab_merge", _ptr(I1), _ptr(I2), _ptr(I3), 1 if I1.dtype == torch.float64 else 0, n, h, w, _ptr(out))
     return out
 
 
@@ -336,8 +328,7 @@ def standardize_brightness(rgb, out=None, ws=None):
         out = torch.empty_like(rgb)
     p = torch.empty((n,), dtype=torch.float64, device=rgb.device)
     wsb = _scratch(ws, _ffi.OP_LAB_STATS, n, h, w, rgb.device)
-    _ffi.check(_ffi.lib().sl_standardize_brightness(_ptr(rgb), _ptr(out), n, h, w, _ptr(p), _ptr(wsb), wsb.numel(), _stream()),
-               "sl_standardize_brightness")
+    _call("sl_standardize_brightness", _ptr(rgb), _ptr(out), n, h, w, _ptr(p), _ptr(wsb), wsb.numel())
     return out, p
 
 
@@ -346,8 +337,7 @@ def reinhard_stats(rgb, standardize=True, ws=None):
     n, h, w = _check_tiles(rgb)
     st = torch.empty((n, 8), dtype=torch.float64, device=rgb.device)
     wsb = _scratch(ws, _ffi.OP_LAB_STATS, n, h, w, rgb.device)
-    _ffi.check(_ffi.lib().sl_reinhard_stats(_ptr(rgb), n, h, w, 1 if standardize else 0, _ptr(st), _ptr(wsb), wsb.numel(), _stream()),
-               "sl_reinhard_stats")
+    _call("sl_reinhard_stats", _ptr(rgb), n, h, w, 1 if standardize else 0, _ptr(st), _ptr(wsb), wsb.numel())
     return st
 
 
@@ -360,9 +350,8 @@ def reinhard_transform(rgb, target_means, target_stds, mask_background=False, lu
         out = torch.empty_like(rgb)
     st = torch.empty((n, 8), dtype=torch.float64, device=dev)
     wsb = _scratch(ws, _ffi.OP_LAB_STATS, n, h, w, dev)
-    _ffi.check(_ffi.lib().sl_reinhard_transform(_ptr(rgb), _ptr(out), n, h, w, _ptr(tm), _ptr(ts), 1 if mask_background else 0,
-                                                float(luminosity_threshold), _ptr(st), _ptr(wsb), wsb.numel(), _stream()),
-               "sl_reinhard_transform")
+    _call("sl_reinhard_transform", _ptr(rgb), _ptr(out), n, h, w, _ptr(tm), _ptr(ts), 1 if mask_background else 0,
+          float(luminosity_threshold), _ptr(st), _ptr(wsb), wsb.numel())
     return out, st
 
 
@@ -373,8 +362,7 @@ def luminosity_standardize(rgb, percentile=95, out=None, ws=None):
         out = torch.empty_like(rgb)
     p = torch.empty((n,), dtype=torch.float64, device=rgb.device)
     wsb = _scratch(ws, _ffi.OP_LAB_STATS, n, h, w, rgb.device)
-    _ffi.check(_ffi.lib().sl_luminosity_standardize(_ptr(rgb), _ptr(out), n, h, w, float(percentile), _ptr(p), _ptr(wsb),
-                                                    wsb.numel(), _stream()), "sl_luminosity_standardize")
+    _call("sl_luminosity_standardize", _ptr(rgb), _ptr(out), n, h, w, float(percentile), _ptr(p), _ptr(wsb), wsb.numel())
     return out, p
 
 
@@ -382,11 +370,9 @@ def luminosity_standardize(rgb, percentile=95, out=None, ws=None):
 def tile_moments(rgb, params=None, ws=None):
     """(n, 10) float64 per tile: tissue count, sum od[3], sum od od^T [xx, xy, xz, yy, yz, zz]  (sl_tile_moments)."""
     n, h, w = _check_tiles(rgb)
-    p = params if params is not None else _ffi.default_params()
     out = torch.empty((n, 10), dtype=torch.float64, device=rgb.device)
     wsb = _scratch(ws, _ffi.OP_TILE_MOMENTS, n, h, w, rgb.device)
-    _ffi.check(_ffi.lib().sl_tile_moments(_ptr(rgb), n, h, w, C.byref(p), _ptr(out), _ptr(wsb), wsb.numel(), _stream()),
-               "sl_tile_moments")
+    _call("sl_tile_moments", _ptr(rgb), n, h, w, _params(params), _ptr(out), _ptr(wsb), wsb.numel())
     return out
 
 
@@ -400,13 +386,11 @@ def slide_key_histogram(rgb, keyset, basis, prefixes, prefix_bits, hist=None, pa
     """Accumulate into hist ((2, 256) int64, device), for both targets of the key set, the next 8 key bits of this
     process's pixels whose key starts with prefixes[t]."""
     n, h, w = _check_tiles(rgb)
-    p = params if params is not None else _ffi.default_params()
     if hist is None:
         hist = torch.zeros((2, 256), dtype=torch.int64, device=rgb.device)
     keep, bp = _basis6(basis)
     pre = (C.c_uint32 * 2)(int(prefixes[0]) & 0xffffffff, int(prefixes[1]) & 0xffffffff)
-    _ffi.check(_ffi.lib().sl_slide_key_histogram(_ptr(rgb), n, h, w, C.byref(p), int(keyset), bp, pre, int(prefix_bits),
-                                                 _ptr(hist), _stream()), "sl_slide_key_histogram")
+    _call("sl_slide_key_histogram", _ptr(rgb), n, h, w, _params(params), int(keyset), bp, pre, int(prefix_bits), _ptr(hist))
     return hist
 
 
@@ -414,25 +398,22 @@ def slide_key_histogram16(rgb, keyset, basis, prefixes16, hist=None, params=None
     """Accumulate into hist ((2, 65536) int64, device), for both targets, the LOW 16 key bits of this process's pixels
     whose key's top 16 bits equal prefixes16[t] (the last two radix rounds in one sweep)."""
     n, h, w = _check_tiles(rgb)
-    p = params if params is not None else _ffi.default_params()
     if hist is None:
         hist = torch.zeros((2, 65536), dtype=torch.int64, device=rgb.device)
     keep, bp = _basis6(basis)
     pre = (C.c_uint32 * 2)(int(prefixes16[0]) & 0xffff, int(prefixes16[1]) & 0xffff)
-    _ffi.check(_ffi.lib().sl_slide_key_histogram16(_ptr(rgb), n, h, w, C.byref(p), int(keyset), bp, pre, _ptr(hist), _stream()),
-               "sl_slide_key_histogram16")
+    _call("sl_slide_key_histogram16", _ptr(rgb), n, h, w, _params(params), int(keyset), bp, pre, _ptr(hist))
     return hist
 
 
 def slide_key_histogram_sampled(rgb, keyset, basis, prefixes, prefix_bits, sample_log2, params=None):
     """slide_key_histogram over a stratified pixel sample (one 64-chunk row in 2**sample_log2); returns a fresh (2, 256) int64."""
     n, h, w = _check_tiles(rgb)
-    p = params if params is not None else _ffi.default_params()
     hist = torch.zeros((2, 256), dtype=torch.int64, device=rgb.device)
     keep, bp = _basis6(basis)
     pre = (C.c_uint32 * 2)(int(prefixes[0]) & 0xffffffff, int(prefixes[1]) & 0xffffffff)
-    _ffi.check(_ffi.lib().sl_slide_key_histogram_sampled(_ptr(rgb), n, h, w, C.byref(p), int(keyset), bp, pre, int(prefix_bits),
-                                                         int(sample_log2), _ptr(hist), _stream()), "sl_slide_key_histogram_sampled")
+    _call("sl_slide_key_histogram_sampled", _ptr(rgb), n, h, w, _params(params), int(keyset), bp, pre, int(prefix_bits), int(sample_log2),
+          _ptr(hist))
     return hist
 
 
@@ -440,49 +421,42 @@ def slide_key_window(rgb, keyset, basis, window_lo, params=None):
     """Per target: histogram of key - window_lo[t] over this process's keys inside [window_lo[t], window_lo[t] + 65536) and the
     number of its keys below the window.  Returns one (2 * 65536 + 2,) int64 device tensor: hist[0], hist[1], below[0], below[1]."""
     n, h, w = _check_tiles(rgb)
-    p = params if params is not None else _ffi.default_params()
     buf = torch.zeros((2 * 65536 + 2,), dtype=torch.int64, device=rgb.device)
     keep, bp = _basis6(basis)
     lo = (C.c_uint32 * 2)(int(window_lo[0]) & 0xffffffff, int(window_lo[1]) & 0xffffffff)
-    _ffi.check(_ffi.lib().sl_slide_key_window(_ptr(rgb), n, h, w, C.byref(p), int(keyset), bp, lo, _ptr(buf), _stream()),
-               "sl_slide_key_window")
+    _call("sl_slide_key_window", _ptr(rgb), n, h, w, _params(params), int(keyset), bp, lo, _ptr(buf))
     return buf
 
 
 # ---- device-driven pooled statistics (sl_pool_*): every step is enqueued, nothing is read back -------------------------------
 def pool_begin(moments11, state=None, params=None):
     """moments11: device float64 (11,) = the tile moments summed over all tiles and ranks + the pixel count.  Returns the state tensor."""
-    p = params if params is not None else _ffi.default_params()
     if state is None:
         state = torch.empty((_ffi.POOL_STATE_DOUBLES,), dtype=torch.float64, device=moments11.device)
-    _ffi.check(_ffi.lib().sl_pool_begin(_ptr(moments11), C.byref(p), _ptr(state), _stream()), "sl_pool_begin")
+    _call("sl_pool_begin", _ptr(moments11), _params(params), _ptr(state))
     return state
 
 
 def pool_histogram(rgb, keyset, state, rnd, sample_log2, hist, params=None):
     """This process's sampled (2, 256) histogram of radix round `rnd` under the prefixes in `state`, accumulated into hist (zeroed by the caller)."""
     n, h, w = _check_tiles(rgb)
-    p = params if params is not None else _ffi.default_params()
-    _ffi.check(_ffi.lib().sl_pool_histogram(_ptr(rgb), n, h, w, C.byref(p), int(keyset), _ptr(state), int(rnd), int(sample_log2), _ptr(hist),
-                                            _stream()), "sl_pool_histogram")
+    _call("sl_pool_histogram", _ptr(rgb), n, h, w, _params(params), int(keyset), _ptr(state), int(rnd), int(sample_log2), _ptr(hist))
     return hist
 
 
 def pool_pick(state, keyset, rnd, hist_reduced):
-    _ffi.check(_ffi.lib().sl_pool_pick(_ptr(state), int(keyset), int(rnd), _ptr(hist_reduced), _stream()), "sl_pool_pick")
+    _call("sl_pool_pick", _ptr(state), int(keyset), int(rnd), _ptr(hist_reduced))
 
 
 def pool_window(rgb, keyset, state, buf, params=None):
     """This process's window histogram + counts below ((2 * 65536 + 2,) int64, zeroed by the caller) around the windows in `state`."""
     n, h, w = _check_tiles(rgb)
-    p = params if params is not None else _ffi.default_params()
-    _ffi.check(_ffi.lib().sl_pool_window(_ptr(rgb), n, h, w, C.byref(p), int(keyset), _ptr(state), _ptr(buf), _stream()), "sl_pool_window")
+    _call("sl_pool_window", _ptr(rgb), n, h, w, _params(params), int(keyset), _ptr(state), _ptr(buf))
     return buf
 
 
 def pool_resolve(state, keyset, window_reduced, params=None):
-    p = params if params is not None else _ffi.default_params()
-    _ffi.check(_ffi.lib().sl_pool_resolve(_ptr(state), int(keyset), _ptr(window_reduced), C.byref(p), _stream()), "sl_pool_resolve")
+    _call("sl_pool_resolve", _ptr(state), int(keyset), _ptr(window_reduced), _params(params))
 
 
 # ---- the pooled statistics in ONE full sweep (sl_pool2_*): see include/stainlib_hip.h ------------------------------------------------
@@ -496,18 +470,15 @@ def pool2_workspace(n, h, w, sample_log2, device) -> torch.Tensor:
 def pool2_sample(rgb, sample_log2, ws, params=None):
     """S1: this process's sample (packed list in ws) and its moment sums -> (16,) float64 to be all-reduced."""
     n, h, w = _check_tiles(rgb)
-    p = params if params is not None else _ffi.default_params()
     out = torch.empty((16,), dtype=torch.float64, device=rgb.device)
-    _ffi.check(_ffi.lib().sl_pool2_sample(_ptr(rgb), n, h, w, C.byref(p), int(sample_log2), _ptr(ws), ws.numel(), _ptr(out), _stream()),
-               "sl_pool2_sample")
+    _call("sl_pool2_sample", _ptr(rgb), n, h, w, _params(params), int(sample_log2), _ptr(ws), ws.numel(), _ptr(out))
     return out
 
 
 def pool2_begin(moments16, sample_log2, state=None, params=None):
-    p = params if params is not None else _ffi.default_params()
     if state is None:
         state = torch.empty((_ffi.POOL2_STATE_DOUBLES,), dtype=torch.float64, device=moments16.device)
-    _ffi.check(_ffi.lib().sl_pool2_begin(_ptr(moments16), C.byref(p), int(sample_log2), _ptr(state), _stream()), "sl_pool2_begin")
+    _call("sl_pool2_begin", _ptr(moments16), _params(params), int(sample_log2), _ptr(state))
     return state
 
 
@@ -515,44 +486,39 @@ def pool2_hist(which, keyset, mode, shape, sample_log2, state, ws, hist, params=
     """A pass over the sample list (which=0, mode=0: a uniform grid) or the candidate list (which=1, mode=1: a window) of ws: the
     histogram of the key set under the constants in `state`, written into hist ((POOL2_HIST_WORDS,) int64)."""
     n, h, w = shape
-    p = params if params is not None else _ffi.default_params()
-    _ffi.check(_ffi.lib().sl_pool2_hist(int(which), int(keyset), int(mode), int(n), int(h), int(w), C.byref(p), int(sample_log2), _ptr(state),
-                                        _ptr(ws), ws.numel(), _ptr(hist), _stream()), "sl_pool2_hist")
+    _call("sl_pool2_hist", int(which), int(keyset), int(mode), int(n), int(h), int(w), _params(params), int(sample_log2), _ptr(state),
+          _ptr(ws), ws.numel(), _ptr(hist))
     return hist
 
 
 def pool2_bands(state, keyset, hist_reduced):
-    _ffi.check(_ffi.lib().sl_pool2_bands(_ptr(state), int(keyset), _ptr(hist_reduced), _stream()), "sl_pool2_bands")
+    _call("sl_pool2_bands", _ptr(state), int(keyset), _ptr(hist_reduced))
 
 
 def pool2_sweep(rgb, sample_log2, state, ws, params=None):
     """THE full sweep: exact moment sums + the raw candidates (into ws) -> (16,) float64 to be all-reduced."""
     n, h, w = _check_tiles(rgb)
-    p = params if params is not None else _ffi.default_params()
     out = torch.empty((16,), dtype=torch.float64, device=rgb.device)
-    _ffi.check(_ffi.lib().sl_pool2_sweep(_ptr(rgb), n, h, w, C.byref(p), int(sample_log2), _ptr(state), _ptr(ws), ws.numel(), _ptr(out),
-                                         _stream()), "sl_pool2_sweep")
+    _call("sl_pool2_sweep", _ptr(rgb), n, h, w, _params(params), int(sample_log2), _ptr(state), _ptr(ws), ws.numel(), _ptr(out))
     return out
 
 
 def pool2_exact(totals16, state):
-    _ffi.check(_ffi.lib().sl_pool2_exact(_ptr(totals16), _ptr(state), _stream()), "sl_pool2_exact")
+    _call("sl_pool2_exact", _ptr(totals16), _ptr(state))
 
 
 def pool2_local(rgb, sample_log2, ws, state=None, params=None):
     """The whole one-sweep chain on ONE process, enqueued by one call (sl_pool2_local).  Returns the state tensor."""
     n, h, w = _check_tiles(rgb)
-    p = params if params is not None else _ffi.default_params()
     if state is None:
         state = torch.empty((_ffi.POOL2_STATE_DOUBLES,), dtype=torch.float64, device=rgb.device)
-    _ffi.check(_ffi.lib().sl_pool2_local(_ptr(rgb), n, h, w, C.byref(p), int(sample_log2), _ptr(ws), ws.numel(), _ptr(state), _stream()),
-               "sl_pool2_local")
+    _call("sl_pool2_local", _ptr(rgb), n, h, w, _params(params), int(sample_log2), _ptr(ws), ws.numel(), _ptr(state))
     return state
 
 
 def pool2_step(state, keyset, hist_reduced):
     """One level of the exact selection on the candidates (see sl_pool2_step)."""
-    _ffi.check(_ffi.lib().sl_pool2_step(_ptr(state), int(keyset), _ptr(hist_reduced), _stream()), "sl_pool2_step")
+    _call("sl_pool2_step", _ptr(state), int(keyset), _ptr(hist_reduced))
 
 
 # ---- the pooled slide-level Vahadane dictionary (sl_sdict_*): rounds of sweep -> all-reduce -> step, nothing read back ----------------
@@ -565,10 +531,9 @@ def sdict_workspace(n, h, w, device) -> torch.Tensor:
 
 def sdict_begin(sample_log2, device, state=None, params=None):
     """The dictionary iteration at the Ruifrok start.  Returns the state tensor ((SDICT_STATE_DOUBLES,) float64)."""
-    p = params if params is not None else _ffi.default_params()
     if state is None:
         state = torch.empty((_ffi.SDICT_STATE_DOUBLES,), dtype=torch.float64, device=device)
-    _ffi.check(_ffi.lib().sl_sdict_begin(C.byref(p), int(sample_log2), _ptr(state), _stream()), "sl_sdict_begin")
+    _call("sl_sdict_begin", _params(params), int(sample_log2), _ptr(state))
     return state
 
 
@@ -578,27 +543,23 @@ def sdict_sweep(rgb, sample_log2, state, ws, sums=None, params=None):
             and rgb.is_contiguous()):
         raise ValueError("expected a contiguous CUDA uint8 tensor of shape (N, H, W, 3)")
     n, h, w, _ = rgb.shape
-    p = params if params is not None else _ffi.default_params()
     if sums is None:
         sums = torch.empty((_ffi.SDICT_SUMS,), dtype=torch.float64, device=rgb.device)
-    _ffi.check(_ffi.lib().sl_sdict_sweep(_ptr(rgb) if n else C.c_void_p(0), n, h, w, C.byref(p), int(sample_log2), _ptr(state), _ptr(ws),
-                                         ws.numel(), _ptr(sums), _stream()), "sl_sdict_sweep")
+    _call("sl_sdict_sweep", _ptr(rgb) if n else C.c_void_p(0), n, h, w, _params(params), int(sample_log2), _ptr(state), _ptr(ws),
+          ws.numel(), _ptr(sums))
     return sums
 
 
 def sdict_step(state, sums_reduced, params=None):
-    p = params if params is not None else _ffi.default_params()
-    _ffi.check(_ffi.lib().sl_sdict_step(_ptr(state), _ptr(sums_reduced), C.byref(p), _stream()), "sl_sdict_step")
+    _call("sl_sdict_step", _ptr(state), _ptr(sums_reduced), _params(params))
 
 
 def slide_key_next_above(rgb, keyset, basis, key_ords, params=None):
     """Per target: smallest key (ordered uint32, Python ints) above key_ords[t] among this process's pixels; 0xffffffff if none."""
     n, h, w = _check_tiles(rgb)
-    p = params if params is not None else _ffi.default_params()
     mn = torch.full((2,), -1, dtype=torch.int32, device=rgb.device)        # 0xffffffff
     keep, bp = _basis6(basis)
     ko = (C.c_uint32 * 2)(int(key_ords[0]) & 0xffffffff, int(key_ords[1]) & 0xffffffff)
-    _ffi.check(_ffi.lib().sl_slide_key_next_above(_ptr(rgb), n, h, w, C.byref(p), int(keyset), bp, ko, _ptr(mn), _stream()),
-               "sl_slide_key_next_above")
+    _call("sl_slide_key_next_above", _ptr(rgb), n, h, w, _params(params), int(keyset), bp, ko, _ptr(mn))
     v = mn.cpu().tolist()
     return [int(v[0]) & 0xffffffff, int(v[1]) & 0xffffffff]
