@@ -465,6 +465,58 @@ SL_API int sl_sdict_sweep(const uint8_t* rgb, int n, int h, int w, const SlParam
 /* the dictionary update from the ALL-REDUCED sums, the stopping rule, and at the end the stain matrix (vahadane_stain_extractor.py:36-43) */
 SL_API int sl_sdict_step(double* state, const double* sums_reduced, const SlParams* params, void* stream);
 
+/* ---- the pooled slide-level REINHARD / LUMINOSITY statistics (stainlib_amd/csrc/slide_lab.hip) ----------------------------------------
+ * ReinhardStainNormalizer.transform (normalization/normalizer.py:70-94) and LuminosityStandardizer.standardize with the LAB helpers
+ * (utils/stain_utils.py:52-67,146-194) on the concatenation: every tile of every rank is mapped with the statistics the reference computes
+ * from the vertical concatenation of all of them.  Everything those statistics need is a sum of integers -- the histogram of all bytes
+ * (p90, np.percentile linear), the histogram of L8 with sum a8, sum a8^2, sum b8, sum b8^2 (cv2.meanStdDev of the lab_split planes; the L
+ * percentile) -- so the pooled result is the reference's on the concatenation byte for byte: no sample, no bracket, no fallback route and
+ * no tolerance.  One computation is the chain
+ *     sl_slab_bytes                 -> all-reduce sums_a (SL_SLAB_SUMS_A uint64, SUM)  -> sl_slab_begin
+ *     sl_slab_lab                   -> all-reduce sums_b (SL_SLAB_SUMS_B uint64, SUM)  -> sl_slab_finish
+ *     sl_slab_map
+ * enqueued on one stream; every decision is taken on the device from all-reduced sums, so every rank reaches the same state without a
+ * broadcast.  LuminosityStandardizer (mode 1) does not standardise the brightness: no bytes sweep, sl_slab_begin(standardize = 0).
+ * n == 0 is legal in the two sum calls (a rank with an empty shard writes zeros).  A zero standard deviation follows numpy's inf / NaN
+ * arithmetic as the per-tile kernel does; it is not a status.
+ * Like the per-tile Lab family, OpenCV's 8-bit Lab conversions are RESTATED here (from the published RGB2Lab_b / Lab2RGBinteger), not
+ * pinned against a real cv2: PARITY UNPINNED against OpenCV itself; the reference's own arithmetic around them is what the tests pin.
+ * `state`: SL_SLAB_STATE_DOUBLES doubles of device memory owned by the caller. */
+#define SL_SLAB_STATE_DOUBLES 512
+#define SL_SLAB_SUMS_A 256        /* counts of the byte values 0 .. 255 over all three channels */
+#define SL_SLAB_SUMS_B 262        /* [0, 256) counts of L8 of the (standardised) pixels, [256] sum a8, [257] sum a8^2, [258] sum b8, [259] sum b8^2,
+                                     [260] tissue pixels at the threshold of sl_slab_lab, [261] pixels */
+#define SL_SLAB_P90 0             /* 90th percentile of all bytes of the slide (NaN when the chain does not standardise) */
+#define SL_SLAB_MEANS 1           /* mean L, a, b of the (standardised) slide as get_mean_std gives them */
+#define SL_SLAB_STDS 4            /* population standard deviations L, a, b */
+#define SL_SLAB_LPCT 7            /* mode 1: the percentile of L8 (NaN in mode 0) */
+#define SL_SLAB_TISSUE 8          /* the slide's tissue-pixel count at the threshold of sl_slab_lab */
+#define SL_SLAB_NPX 9             /* the slide's pixel count */
+#define SL_SLAB_STATUS 10         /* SL_TILE_OK; SL_TILE_EMPTY_MASK: the slide has no pixel, or (mode 0 with mask_background) no tissue pixel,
+                                     where the reference raises TissueMaskException (stain_utils.py:46-47) */
+#define SL_SLAB_TABLES 32         /* from here: the composed byte tables of the sweeps (private layout) */
+/* workspace bytes of sl_slab_bytes / sl_slab_lab (per-workgroup partial rows); 0 for bad arguments */
+SL_API size_t sl_slab_workspace_bytes(int n, int h, int w);
+/* this rank's byte counts (stain_utils.py:193: np.percentile(I, 90) needs the counts of the whole slide) */
+SL_API int sl_slab_bytes(const uint8_t* rgb, int n, int h, int w, void* workspace, size_t workspace_bytes,
+                         unsigned long long* sums_a_out, void* stream);
+/* p90 (np.percentile, linear) from the ALL-REDUCED counts, the brightness table uint8(clip(v * 255.0 / p90, 0, 255)) (stain_utils.py:194)
+ * and the gamma values behind it; standardize == 0: identity brightness, sums_a_reduced may be NULL.  Writes the whole state header. */
+SL_API int sl_slab_begin(double* state, const unsigned long long* sums_a_reduced, int standardize, void* stream);
+/* this rank's Lab sums of the (standardised) tiles (stain_utils.py:146-158,174-186; the luminosity test of stain_utils.py:42-43) */
+SL_API int sl_slab_lab(const uint8_t* rgb, int n, int h, int w, const double* state, double luminosity_threshold, void* workspace,
+                       size_t workspace_bytes, unsigned long long* sums_b_out, void* stream);
+/* from the ALL-REDUCED sums.  mode 0 (Reinhard): means / stds, the three byte tables of normalizer.py:81-83 -- the lookup index is the
+ * binary32 v / 2.55f (resp. v - 128.0f) promoted to binary64, ((x - mean) * (tstd / std)) + tmean in binary64 -- composed with merge_back
+ * (* 2.55 resp. + 128.0, clip, truncate) and the Lab -> RGB tables; target_means / target_stds: 3 doubles each (DEVICE).  mode 1
+ * (luminosity): the `percentile` of L8 and the table uint8(clip(255 * L8 / p, 0, 255)) (stain_utils.py:64-65).  Sets the status. */
+SL_API int sl_slab_finish(double* state, const unsigned long long* sums_b_reduced, int mode, const double* target_means,
+                          const double* target_stds, double percentile, int mask_background, void* stream);
+/* the map of this rank's tiles under the slide's tables; mode 0 with mask_background: pixels failing the luminosity test become L 254,
+ * a = b = 0 before merge_back (normalizer.py:86-90).  With a status other than SL_TILE_OK the tiles are copied through unchanged. */
+SL_API int sl_slab_map(const uint8_t* rgb, uint8_t* out, int n, int h, int w, const double* state, int mode, int mask_background,
+                       double luminosity_threshold, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

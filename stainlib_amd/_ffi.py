@@ -128,10 +128,19 @@ _SIGNATURES = {
     "sl_sdict_begin": (C.c_int, [C.POINTER(SlParams), C.c_int, _P, _P]),
     "sl_sdict_sweep": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(SlParams), C.c_int, _P, _P, C.c_size_t, _P, _P]),
     "sl_sdict_step": (C.c_int, [_P, _P, C.POINTER(SlParams), _P]),
+    # the pooled slide-level Reinhard / luminosity statistics (state: SLAB_STATE_DOUBLES doubles; workspace: sl_slab_workspace_bytes)
+    "sl_slab_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "sl_slab_bytes": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P, _P]),
+    "sl_slab_begin": (C.c_int, [_P, _P, C.c_int, _P]),
+    "sl_slab_lab": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_double, _P, C.c_size_t, _P, _P]),
+    "sl_slab_finish": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_double, C.c_int, _P]),
+    "sl_slab_map": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_double, _P]),
 }
 POOL_STATE_DOUBLES, POOL_M, POOL_MAXC, POOL_STATUS, POOL_MISS = 64, 0, 6, 8, 9
 POOL2_STATE_DOUBLES, POOL2_HIST_WORDS, POOL2_WHY = 256, 2 * 8192 + 8 * 32, 33
 SDICT_STATE_DOUBLES, SDICT_SUMS, SDICT_M, SDICT_STATUS, SDICT_SWEEPS, SDICT_ROUNDS, SDICT_MODE, SDICT_D, SDICT_NPX = 64, 32, 0, 6, 7, 8, 9, 10, 16
+SLAB_STATE_DOUBLES, SLAB_SUMS_A, SLAB_SUMS_B, SLAB_TABLES = 512, 256, 262, 32
+SLAB_P90, SLAB_MEANS, SLAB_STDS, SLAB_LPCT, SLAB_TISSUE, SLAB_NPX, SLAB_STATUS = 0, 1, 4, 7, 8, 9, 10
 EXPECTED_VERSION = 600     # the SL_VERSION this binding (SlParams, signatures) was written for
 EXPORTS = tuple(_SIGNATURES)
 

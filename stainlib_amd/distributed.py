@@ -26,6 +26,9 @@ This is an extension (the reference has no notion of a slide); its check is the 
     slide: under one shared dictionary a sweep reduces each rank's tiles to 31 class-moment sums, those are all-reduced (32 doubles
     with the pixel count), and one workgroup takes the update on every rank alike; a few such rounds reach the fixed point.  The 99th
     percentile of each concentration under that matrix is pinned by the same order-statistic machinery as Macenko's.
+    With a Reinhard normalizer (``PooledReinhardStatistics``) everything is a sum of integers -- the histogram of all bytes, the histogram
+    of L8 and four sums over a8 and b8 --, so two small all-reduces give the reference's result on the concatenation byte for byte;
+    ``slide_luminosity_standardize`` is LuminosityStandardizer on the concatenation from the same L8 histogram.
 """
 from __future__ import annotations
 
@@ -545,12 +548,86 @@ class PooledVahadaneStatistics(_PooledStatistics):
         return M, maxC
 
 
+class PooledReinhardStatistics:
+    """The statistics ReinhardStainNormalizer.transform / LuminosityStandardizer.standardize take from an image (normalizer.py:78-80,
+    stain_utils.py:64,188-194), of the tall image made of every tile on every rank (csrc/slide_lab.hip).
+
+    DEVICE-DRIVEN: the sums of this rank's tiles, the two all-reduces (256 and 262 int64) and the single-workgroup steps are enqueued on
+    the current stream; every step consumes all-reduced integer sums only, so every rank reaches the same state without a broadcast, and
+    the state is the reference's on the concatenation exactly -- there is no fallback route.  ``finish`` is the one read-back.  A rank may
+    hold no tile; it still takes part in both collectives."""
+
+    def __init__(self, group=None):
+        self.group = group
+        self.last_status = 0                 # SL_TILE_* of the last state read back
+        self.last_p90 = float("nan")         # 90th percentile of the slide's bytes (NaN for the luminosity chain)
+        self.last_percentile = float("nan")  # the L percentile of the luminosity chain
+        self.last_means = self.last_stds = None      # numpy (3,) float64
+        self.last_tissue = self.last_pixels = 0
+        self._ws = None
+
+    def _workspace(self, tiles_local):
+        from . import engine
+        n_local, h, w, _ = tiles_local.shape
+        key = (n_local, h, w, tiles_local.device)
+        if self._ws is None or self._ws[0] != key:
+            self._ws = (key, engine.slab_workspace(n_local, h, w, tiles_local.device))
+        return self._ws[1]
+
+    def enqueue(self, tiles_local: torch.Tensor, target_means, target_stds, mask_background=False, luminosity_threshold=0.8) -> torch.Tensor:
+        """The Reinhard chain: bytes -> all-reduce -> begin -> Lab sums -> all-reduce -> finish.  Returns the state (device float64,
+        _ffi.SLAB_STATE_DOUBLES); ``engine.slab_map(tiles, state, 0, ...)`` behind it maps the tiles."""
+        from . import engine
+        _, world = _world(self.group)
+        ws = self._workspace(tiles_local)
+        state = engine.slab_begin(_reduced(engine.slab_bytes(tiles_local, ws), world, self.group), True, tiles_local.device)
+        sums = _reduced(engine.slab_lab(tiles_local, state, luminosity_threshold, ws), world, self.group)
+        engine.slab_finish(state, sums, 0, target_means, target_stds, mask_background=mask_background)
+        return state
+
+    def enqueue_luminosity(self, tiles_local: torch.Tensor, percentile=95) -> torch.Tensor:
+        """The luminosity chain: identity brightness (no bytes sweep), Lab sums -> all-reduce -> finish(mode 1)."""
+        from . import engine
+        _, world = _world(self.group)
+        ws = self._workspace(tiles_local)
+        state = engine.slab_begin(None, False, tiles_local.device)
+        sums = _reduced(engine.slab_lab(tiles_local, state, 0.8, ws), world, self.group)
+        engine.slab_finish(state, sums, 1, percentile=percentile)
+        return state
+
+    def finish(self, state: torch.Tensor):
+        """The one read-back: the reported numbers into last_*; raises like the reference on an empty tissue mask (or an empty slide)."""
+        from . import _ffi
+        from .utils.excepts import TissueMaskException
+        s = state[:_ffi.SLAB_TABLES].cpu().numpy()
+        self.last_status = int(s[_ffi.SLAB_STATUS])
+        self.last_p90, self.last_percentile = float(s[_ffi.SLAB_P90]), float(s[_ffi.SLAB_LPCT])
+        self.last_means = s[_ffi.SLAB_MEANS:_ffi.SLAB_MEANS + 3].copy()
+        self.last_stds = s[_ffi.SLAB_STDS:_ffi.SLAB_STDS + 3].copy()
+        self.last_tissue, self.last_pixels = int(s[_ffi.SLAB_TISSUE]), int(s[_ffi.SLAB_NPX])
+        if self.last_status == _ffi.TILE_EMPTY_MASK:
+            raise TissueMaskException("Empty tissue mask computed")
+        return self.last_status
+
+
+def slide_luminosity_standardize(tiles_local: torch.Tensor, percentile=95, group=None, out: Optional[torch.Tensor] = None):
+    """LuminosityStandardizer.standardize (stain_utils.py:52-67) on the concatenation of every tile on every rank: (out, p), p the
+    `percentile` of the slide's L8 as a float.  One sweep for the L8 histogram, one small all-reduce, the map."""
+    from . import engine
+    stats = PooledReinhardStatistics(group)
+    state = stats.enqueue_luminosity(tiles_local, percentile)
+    out = engine.slab_map(tiles_local, state, 1, out=out)
+    stats.finish(state)
+    return out, stats.last_percentile
+
+
 class SlideNormalizer:
-    """Slide-level Macenko/Vahadane normalisation over a sharded set of tiles (see module docstring).
+    """Slide-level Macenko/Vahadane/Reinhard normalisation over a sharded set of tiles (see module docstring).
 
     mode="median" (default): per-tile fits, all-gather, element-wise median.  mode="pooled": the exact statistics
     of the concatenated slide -- ``PooledSlideStatistics`` for a Macenko normalizer, ``PooledVahadaneStatistics`` for a Vahadane one
-    (dispatched on ``normalizer.method``).
+    (dispatched on ``normalizer.method``), ``PooledReinhardStatistics`` for a ReinhardStainNormalizer (pooled mode only: mode="median" or
+    graph=True with one raises ValueError).
 
     graph=True (pooled mode on ONE process: no collective sits between the steps): the one-sweep chain and the apply pass behind it --
     some fifty launches -- are captured into a HIP graph the first time a (tiles buffer, out buffer) pair is seen and REPLAYED on every
@@ -564,6 +641,11 @@ class SlideNormalizer:
             raise ValueError("mode must be 'median' or 'pooled'")
         if graph and getattr(normalizer, "method", "macenko") == "vahadane":
             raise ValueError("graph=True is not supported with a Vahadane normalizer")
+        from .normalization.normalizer import ReinhardStainNormalizer
+        self._reinhard = isinstance(normalizer, ReinhardStainNormalizer)
+        self._reinhard_targets = None
+        if self._reinhard and (mode != "pooled" or graph):
+            raise ValueError("a Reinhard normalizer supports mode='pooled' without graph capture only")
         self.normalizer = normalizer          # a fitted stainlib_amd ExtractiveStainNormalizer
         self.group = group
         self.mode = mode
@@ -592,10 +674,18 @@ class SlideNormalizer:
         from . import _ffi
         return state[_ffi.POOL_M:_ffi.POOL_M + 6].reshape(2, 3), state[_ffi.POOL_MAXC:_ffi.POOL_MAXC + 2]
 
-    def transform_shard(self, tiles_local: torch.Tensor, out: Optional[torch.Tensor] = None, n_tiles_total: Optional[int] = None):
+    def transform_shard(self, tiles_local: torch.Tensor, out: Optional[torch.Tensor] = None, n_tiles_total: Optional[int] = None, *,
+                        mask_background=False, luminosity_threshold=0.8):
         """tiles_local: this rank's (n_local,H,W,3) uint8 device tensor.  Returns (out, M_slide, maxC_slide, status_local).
         n_tiles_total (pooled mode, optional): the slide's tile count over all ranks; saves the one tiny all-reduce that otherwise
-        agrees on the sample density.  On failure (TissueMaskException) `out` holds a copy of the input tiles."""
+        agrees on the sample density.  On failure (TissueMaskException) `out` holds a copy of the input tiles.
+        With a Reinhard normalizer: returns (out, means, stds, status_local) -- the slide's Lab means and standard deviations as device
+        float64 (3,) -- and sets ``last_p90``; mask_background / luminosity_threshold are ReinhardStainNormalizer.transform's (the
+        extractive normalizers have no such arguments: a non-default value with one raises ValueError)."""
+        if self._reinhard:
+            return self._transform_reinhard(tiles_local, out, mask_background, luminosity_threshold)
+        if mask_background or luminosity_threshold != 0.8:
+            raise ValueError("mask_background / luminosity_threshold apply to a Reinhard normalizer only")
         if self.mode == "median":
             return self._transform_median(tiles_local, out)
         if getattr(self.normalizer, "method", "macenko") == "vahadane":
@@ -690,3 +780,25 @@ class SlideNormalizer:
         if n:
             out = self._apply(tiles_local, M_s, maxC_s, *self._targets(dev), out)
         return out, M_s, maxC_s, torch.zeros((n,), dtype=torch.int32, device=dev)
+
+    def _transform_reinhard(self, tiles_local: torch.Tensor, out: Optional[torch.Tensor], mask_background, luminosity_threshold):
+        """Pooled mode with a Reinhard normalizer.  Device-driven: the statistics AND the map are enqueued before the one read-back; with
+        an unusable status (an empty tissue mask under mask_background, an empty slide) the map copies the tiles through."""
+        from . import engine, _ffi
+        stats = PooledReinhardStatistics(self.group)
+        tm, ts = self.normalizer._targets()
+        key = (str(tiles_local.device), tuple(tm), tuple(ts))         # the six target doubles on the device, uploaded once per fit (cf. _target_on)
+        if self._reinhard_targets is None or self._reinhard_targets[0] != key:
+            self._reinhard_targets = (key, torch.tensor(tm, dtype=torch.float64, device=tiles_local.device),
+                                      torch.tensor(ts, dtype=torch.float64, device=tiles_local.device))
+        _, tm, ts = self._reinhard_targets
+        state = stats.enqueue(tiles_local, tm, ts, mask_background, luminosity_threshold)
+        out = engine.slab_map(tiles_local, state, 0, mask_background, luminosity_threshold, out=out)
+        means = state[_ffi.SLAB_MEANS:_ffi.SLAB_MEANS + 3].clone()
+        stds = state[_ffi.SLAB_STDS:_ffi.SLAB_STDS + 3].clone()
+        try:
+            stats.finish(state)
+        finally:
+            self.last_p90 = stats.last_p90
+            self.last_tissue, self.last_pixels = stats.last_tissue, stats.last_pixels
+        return out, means, stds, torch.zeros((tiles_local.shape[0],), dtype=torch.int32, device=tiles_local.device)

@@ -554,6 +554,68 @@ def sdict_step(state, sums_reduced, params=None):
     _call("sl_sdict_step", _ptr(state), _ptr(sums_reduced), _params(params))
 
 
+# ---- the pooled slide-level Reinhard / luminosity statistics (sl_slab_*): two sums -> all-reduce -> step, then the map ----------------
+def _check_shard(rgb: torch.Tensor):
+    """like _check_tiles, for a shard that may hold no tile"""
+    if not (isinstance(rgb, torch.Tensor) and rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.dim() == 4 and rgb.shape[-1] == 3
+            and rgb.is_contiguous()):
+        raise ValueError("expected a contiguous CUDA uint8 tensor of shape (N, H, W, 3)")
+    n, h, w, _ = rgb.shape
+    return n, h, w
+
+
+def slab_workspace(n, h, w, device) -> torch.Tensor:
+    need = int(_ffi.lib().sl_slab_workspace_bytes(int(n), int(h), int(w)))
+    if need == 0:
+        raise ValueError("sl_slab_workspace_bytes: bad arguments")
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def slab_bytes(rgb, ws, sums=None):
+    """The byte counts of this process's tiles (n may be 0) -> (SLAB_SUMS_A,) int64 to be all-reduced."""
+    n, h, w = _check_shard(rgb)
+    if sums is None:
+        sums = torch.empty((_ffi.SLAB_SUMS_A,), dtype=torch.int64, device=rgb.device)
+    _call("sl_slab_bytes", _ptr(rgb) if n else C.c_void_p(0), n, h, w, _ptr(ws), ws.numel(), _ptr(sums))
+    return sums
+
+
+def slab_begin(sums_a_reduced, standardize, device, state=None):
+    """p90 and the brightness table from the all-reduced byte counts (standardize=False: identity brightness, no counts needed).
+    Returns the state tensor ((SLAB_STATE_DOUBLES,) float64)."""
+    if state is None:
+        state = torch.empty((_ffi.SLAB_STATE_DOUBLES,), dtype=torch.float64, device=device)
+    _call("sl_slab_begin", _ptr(state), _ptr(sums_a_reduced), 1 if standardize else 0)
+    return state
+
+
+def slab_lab(rgb, state, luminosity_threshold, ws, sums=None):
+    """The Lab sums of this process's (standardised) tiles (n may be 0) -> (SLAB_SUMS_B,) int64 to be all-reduced."""
+    n, h, w = _check_shard(rgb)
+    if sums is None:
+        sums = torch.empty((_ffi.SLAB_SUMS_B,), dtype=torch.int64, device=rgb.device)
+    _call("sl_slab_lab", _ptr(rgb) if n else C.c_void_p(0), n, h, w, _ptr(state), float(luminosity_threshold), _ptr(ws), ws.numel(), _ptr(sums))
+    return sums
+
+
+def slab_finish(state, sums_b_reduced, mode, target_means=None, target_stds=None, percentile=95.0, mask_background=False):
+    """The slide's statistics, tables and status from the all-reduced Lab sums.  mode 0: Reinhard (target_means / target_stds: 3 values
+    each), mode 1: luminosity (percentile)."""
+    tm = _f64(target_means, (3,), state.device) if target_means is not None else None
+    ts = _f64(target_stds, (3,), state.device) if target_stds is not None else None
+    _call("sl_slab_finish", _ptr(state), _ptr(sums_b_reduced), int(mode), _ptr(tm), _ptr(ts), float(percentile), 1 if mask_background else 0)
+
+
+def slab_map(rgb, state, mode, mask_background=False, luminosity_threshold=0.8, out=None):
+    """The map of this process's tiles under the slide's tables (a non-OK status copies them through).  An empty shard is returned as is."""
+    n, h, w = _check_shard(rgb)
+    if out is None:
+        out = torch.empty_like(rgb)
+    if n:
+        _call("sl_slab_map", _ptr(rgb), _ptr(out), n, h, w, _ptr(state), int(mode), 1 if mask_background else 0, float(luminosity_threshold))
+    return out
+
+
 def slide_key_next_above(rgb, keyset, basis, key_ords, params=None):
     """Per target: smallest key (ordered uint32, Python ints) above key_ords[t] among this process's pixels; 0xffffffff if none."""
     n, h, w = _check_tiles(rgb)
