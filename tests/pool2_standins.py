@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from stainlib_amd import distributed as sd
+from tests.standin_math import angle_keys, conc_keys, eig2, f2ord, matrix_from, moments, od_of, ord2f, tissue
 
 NB, TW, TP, WB, WBITS, KB, KBITS = 8192, 256, 8, 2048, 11, 4096, 12   # grid bins, tail words (TP per slot), coarse window bins and key bits per level, single keys of a last level
 K_T, K_NPX, K_VD, K_VF, K_K, K_G, K_TS, K_NS, K_SLOG, K_BRK, K_BR, K_WLO, K_RES, K_SH, K_DONE, K_LEVEL = \
@@ -22,63 +23,9 @@ K_T, K_NPX, K_VD, K_VF, K_K, K_G, K_TS, K_NS, K_SLOG, K_BRK, K_BR, K_WLO, K_RES,
 K_VH, K_MH, K_L = 34, 140, 150                         # (K_MH, K_L: private to the stand-ins -- the sample's stain matrix, the thresholds)
 
 
-def f2ord(a):
-    u = np.asarray(a, np.float32).view(np.uint32)
-    return np.where(u & 0x80000000, ~u, u | 0x80000000).astype(np.uint64)
-
-
-def ord2f(o):
-    o = int(o)
-    bits = (o & 0x7fffffff) if (o & 0x80000000) else (~o & 0xffffffff)
-    return float(np.array([bits], np.uint32).view(np.float32)[0])
-
-
 def install(all_tiles, break_it=False):
     from oracle import stain_oracle as so
     from stainlib_amd import _ffi, engine
-
-    def tissue(px):
-        return (so.lab_l8(px.reshape(1, -1, 3)) / 255.0 < 0.8).ravel()
-
-    def od_of(px):
-        return so.rgb_to_od(px.reshape(1, -1, 3)).reshape(-1, 3)
-
-    def eig2(m):
-        T = m[0]
-        mean = m[1:4] / T
-        S2 = np.array([[m[4], m[5], m[6]], [m[5], m[7], m[8]], [m[6], m[8], m[9]]])
-        _, V = np.linalg.eigh((S2 - T * np.outer(mean, mean)) / (T - 1.0))
-        V = V[:, [2, 1]].copy()
-        for i in range(2):
-            if V[0, i] < 0:
-                V[:, i] *= -1.0
-        return V
-
-    def angle_keys(od32, V):
-        th = od32 @ np.asarray(V, np.float64).astype(np.float32)
-        x, y = th[:, 0], th[:, 1]
-        d = np.abs(x) + np.abs(y)
-        p = np.where(d > 0, y / np.where(d > 0, d, 1), 0).astype(np.float32)
-        return np.where(x < 0, np.where(y >= 0, 2.0, -2.0).astype(np.float32) - p, p).astype(np.float32)
-
-    def conc_keys(od32, M):
-        return so.lasso2_nonneg(od32.astype(np.float64), np.asarray(M, np.float64).reshape(2, 3), 0.01).astype(np.float32)
-
-    def moments(od):
-        S = od.T @ od
-        return [float(len(od)), *od.sum(0), S[0, 0], S[0, 1], S[0, 2], S[1, 1], S[1, 2], S[2, 2]]
-
-    def ang(p):
-        if abs(p) <= 1.0:
-            return math.atan2(p, 1.0 - abs(p))
-        pp = 2.0 - p if p > 0 else -2.0 - p
-        return math.atan2(pp, -(1.0 - abs(pp)))
-
-    def matrix_from(V, pa0, pb0, g0, pa1, pb1, g1):
-        phis = [sd.np_lerp(ang(pa0), ang(pb0), g0), sd.np_lerp(ang(pa1), ang(pb1), g1)]
-        v1, v2 = V @ np.array([math.cos(phis[0]), math.sin(phis[0])]), V @ np.array([math.cos(phis[1]), math.sin(phis[1])])
-        M = np.array([v1, v2]) if v1[0] > v2[0] else np.array([v2, v1])
-        return M / np.linalg.norm(M, axis=1, keepdims=True)
 
     # what only the harness knows: the exact statistics of the whole slide
     tall = np.concatenate([t.reshape(-1, 3) for t in all_tiles])

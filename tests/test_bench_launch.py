@@ -9,12 +9,13 @@ import sys
 
 import pytest
 
+from tests.ranks import LAUNCHER_ENV, free_port
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _clean_env(**extra):
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT",
-                                                            "GROUP_RANK", "ROLE_RANK", "TORCHELASTIC_RUN_ID")}
+    env = {k: v for k, v in os.environ.items() if k not in LAUNCHER_ENV}
     env.update(extra)
     return env
 
@@ -76,7 +77,7 @@ def test_more_gpus_than_the_box_has_is_refused():
 
 def test_a_launcher_with_another_world_size_is_refused():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
-           "29641", "bench.py", "--gpus", "4", "--steps", "1", "--warmup", "0"]
+           str(free_port()), "bench.py", "--gpus", "4", "--steps", "1", "--warmup", "0"]
     r = subprocess.run(cmd, cwd=ROOT, env=_clean_env(SL_BENCH_DRY="1"), capture_output=True, text=True, timeout=600)
     assert r.returncode != 0 and "launcher started 2 rank(s)" in r.stderr, (r.returncode, r.stderr[-1500:])
 

@@ -4,13 +4,12 @@ ReinhardStainNormalizer, slide_luminosity_standardize) against the oracle on the
 The statistics are sums of integers, so the bar is equality: every output byte and p90 equal the oracle's; the means and standard
 deviations agree to the rounding of two different summation orders (rtol 1e-13 / 1e-12, the per-tile bars of tests/test_gpu_lab.py).
 The seeds are the first ones tried; the CPU gloo test runs the same class-b recipe and holds the equality there."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
 from oracle import stain_oracle as so
+from tests.ranks import run_ranks
 
 pytestmark = pytest.mark.gpu
 
@@ -184,41 +183,26 @@ def test_slide_luminosity_standardize_equals_the_oracle_on_the_concatenation(cls
     assert slide_luminosity_standardize(dev, percentile=80, group=False, out=out2)[0] is out2 and torch.equal(out2, out)
 
 
-def _two_rank_worker(rank, world, port, shards, q):
+def _two_rank_worker(rank, world, shards):
     """one of two processes that SHARE the GPU: its contiguous shard of the class-b slide through the product's chain, gloo carrying the
     two all-reduces of device tensors"""
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from stainlib_amd.distributed import SlideNormalizer, slide_luminosity_standardize
-        lo = sum(shards[:rank])
-        mine = _dev(_slide("b"))[lo:lo + shards[rank]].contiguous()
-        sn = SlideNormalizer(_normalizer(), mode="pooled")
-        out, m, s, _ = sn.transform_shard(mine, mask_background=True)
-        lum, p = slide_luminosity_standardize(mine, percentile=95)
-        q.put((rank, out.cpu().numpy(), m.cpu().numpy(), s.cpu().numpy(), sn.last_p90, lum.cpu().numpy(), p))
-    finally:
-        dist.destroy_process_group()
+    from stainlib_amd.distributed import SlideNormalizer, slide_luminosity_standardize
+    lo = sum(shards[:rank])
+    mine = _dev(_slide("b"))[lo:lo + shards[rank]].contiguous()
+    sn = SlideNormalizer(_normalizer(), mode="pooled")
+    out, m, s, _ = sn.transform_shard(mine, mask_background=True)
+    lum, p = slide_luminosity_standardize(mine, percentile=95)
+    return rank, out.cpu().numpy(), m.cpu().numpy(), s.cpu().numpy(), sn.last_p90, lum.cpu().numpy(), p
 
 
 def test_two_ranks_sharing_the_gpu_run_the_pooled_reinhard_chain_over_gloo():
     """Two processes on cuda:0 with an uneven split (3 + 2) and with a rank that holds no tile (5 + 0): both reach the oracle's bytes on
     the concatenation and report identical means, stds and p90 to the bit."""
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
     tall = np.concatenate(_slide("b"), axis=0)
     want = _target().transform(tall, mask_background=True)
     want_lum = so.luminosity_standardize(tall, 95)
-    for shards, port in (((3, 2), 29641), ((5, 0), 29642)):
-        q = ctx.Queue()
-        procs = [ctx.Process(target=_two_rank_worker, args=(r, 2, port, shards, q)) for r in range(2)]
-        for p in procs:
-            p.start()
-        res = sorted([q.get(timeout=600) for _ in procs], key=lambda t: t[0])
-        for p in procs:
-            p.join(timeout=120)
-            assert p.exitcode == 0
+    for shards in ((3, 2), (5, 0)):
+        res = run_ranks(_two_rank_worker, 2, shards, timeout=600)
         assert np.array_equal(np.concatenate([r[1] for r in res], axis=0).reshape(want.shape), want)
         assert np.array_equal(np.concatenate([r[5] for r in res], axis=0).reshape(want_lum.shape), want_lum)
         assert res[0][2].tobytes() == res[1][2].tobytes() and res[0][3].tobytes() == res[1][3].tobytes()

@@ -10,6 +10,7 @@ import torch
 
 from oracle import stain_oracle as so
 from tests.gpu_util import to_dev, u8_parity
+from tests.ranks import run_ranks
 
 pytestmark = pytest.mark.gpu
 V_ATOL = 1e-7
@@ -169,41 +170,23 @@ def test_sdict_entry_points_refuse_bad_arguments_and_accept_an_empty_shard():
     assert (got == 0).all()
 
 
-def _two_rank_worker(rank, world, port, shards, q):
+def _two_rank_worker(rank, world, shards):
     """one of two processes that SHARE the GPU: its contiguous shard of the slide through the product's Vahadane dictionary rounds,
     with gloo carrying the all-reduces of device tensors between the steps"""
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from stainlib_amd.distributed import PooledVahadaneStatistics
-        dev = torch.device("cuda", 0)
-        tiles = [so.synth_tile(256, 256, 120 + s) for s in range(sum(shards))]
-        lo = sum(shards[:rank])
-        mine = torch.from_numpy(np.stack(tiles)[lo:lo + shards[rank]].copy()).to(dev)
-        st = PooledVahadaneStatistics()
-        M, mc = st(mine)
-        q.put((rank, M, mc, st.last_rounds))
-    finally:
-        dist.destroy_process_group()
+    from stainlib_amd.distributed import PooledVahadaneStatistics
+    dev = torch.device("cuda", 0)
+    tiles = [so.synth_tile(256, 256, 120 + s) for s in range(sum(shards))]
+    lo = sum(shards[:rank])
+    mine = torch.from_numpy(np.stack(tiles)[lo:lo + shards[rank]].copy()).to(dev)
+    st = PooledVahadaneStatistics()
+    M, mc = st(mine)
+    return rank, M, mc, st.last_rounds
 
 
-@pytest.mark.parametrize("shards,port", [((2, 2), 29641), ((3, 2), 29642), ((5, 0), 29643)])
-def test_two_ranks_sharing_the_gpu_learn_the_slide_dictionary_over_gloo(shards, port):
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_two_rank_worker, args=(r, 2, port, shards, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    try:
-        res = sorted([q.get(timeout=600) for _ in procs], key=lambda t: t[0])
-    finally:
-        for p in procs:
-            p.join(timeout=120)
-            if p.exitcode is None:
-                p.kill()
-    assert all(p.exitcode == 0 for p in procs)
+# (the case ids are the ones these cases have always had: their numbers were rendezvous ports once, and name nothing now)
+@pytest.mark.parametrize("shards", [(2, 2), (3, 2), (5, 0)], ids=["shards0-29641", "shards1-29642", "shards2-29643"])
+def test_two_ranks_sharing_the_gpu_learn_the_slide_dictionary_over_gloo(shards):
+    res = run_ranks(_two_rank_worker, 2, shards, timeout=600)
     tiles = [so.synth_tile(256, 256, 120 + s) for s in range(sum(shards))]
     M1, mc1, _ = _pooled(to_dev(tiles))
     for rank, M, mc, rounds in res:

@@ -10,6 +10,8 @@ import sys
 import numpy as np
 import pytest
 
+from tests.ranks import free_port, run_ranks
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -17,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_under_the_launcher_with_a_one_rank_rccl_group():
     env = dict(os.environ, SL_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", "29611", "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--tiles", "48", "--size", "256",
+           "--master-port", str(free_port()), "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--tiles", "48", "--size", "256",
            "--full", "--no-cpu-baseline", "--no-secondary", "--slide-pooled"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
@@ -38,31 +40,25 @@ def test_bench_under_the_launcher_with_a_one_rank_rccl_group():
     np.testing.assert_allclose(np.asarray(sp["M_slide"]), M.reshape(-1), rtol=0, atol=2e-6)
 
 
-def _two_rank_worker(rank, world, port, n_tiles, q):
+def _two_rank_worker(rank, world, n_tiles):
     """one of two processes that SHARE the GPU: its contiguous shard of the slide through the product's one-sweep chain, with gloo
     carrying the all-reduces of device tensors between the steps"""
     import torch
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from stainlib_amd.distributed import PooledSlideStatistics, SlideNormalizer, shard_range
-        from tools.synth import synth_tiles
-        import stainlib_amd as sl
-        dev = torch.device("cuda", 0)
-        slide = synth_tiles(n_tiles, 256, 320, seed=21, device=dev)
-        lo, hi = shard_range(n_tiles, rank, world)
-        st = PooledSlideStatistics()
-        got = st.finish(st.enqueue_merged(slide[lo:hi], n_tiles_total=n_tiles))
-        miss = st.last_miss
-        nrm = sl.MacenkoNormalizer()
-        nrm.stain_matrix_target = np.array([[0.55, 0.75, 0.35], [0.10, 0.95, 0.20]]) / np.linalg.norm([[0.55, 0.75, 0.35], [0.10, 0.95, 0.20]], axis=1, keepdims=True)
-        nrm.maxC_target = np.array([[1.9, 1.1]])
-        sn = SlideNormalizer(nrm, mode="pooled")
-        out, M_s, mc_s, _ = sn.transform_shard(slide[lo:hi], n_tiles_total=n_tiles)
-        q.put((rank, None if got is None else (got[0], got[1]), miss, list(sn.last_path), M_s.cpu().numpy(), out.cpu().numpy()))
-    finally:
-        dist.destroy_process_group()
+    from stainlib_amd.distributed import PooledSlideStatistics, SlideNormalizer, shard_range
+    from tools.synth import synth_tiles
+    import stainlib_amd as sl
+    dev = torch.device("cuda", 0)
+    slide = synth_tiles(n_tiles, 256, 320, seed=21, device=dev)
+    lo, hi = shard_range(n_tiles, rank, world)
+    st = PooledSlideStatistics()
+    got = st.finish(st.enqueue_merged(slide[lo:hi], n_tiles_total=n_tiles))
+    miss = st.last_miss
+    nrm = sl.MacenkoNormalizer()
+    nrm.stain_matrix_target = np.array([[0.55, 0.75, 0.35], [0.10, 0.95, 0.20]]) / np.linalg.norm([[0.55, 0.75, 0.35], [0.10, 0.95, 0.20]], axis=1, keepdims=True)
+    nrm.maxC_target = np.array([[1.9, 1.1]])
+    sn = SlideNormalizer(nrm, mode="pooled")
+    out, M_s, mc_s, _ = sn.transform_shard(slide[lo:hi], n_tiles_total=n_tiles)
+    return rank, None if got is None else (got[0], got[1]), miss, list(sn.last_path), M_s.cpu().numpy(), out.cpu().numpy()
 
 
 def test_two_ranks_sharing_the_gpu_run_the_one_sweep_chain_over_gloo():
@@ -71,20 +67,11 @@ def test_two_ranks_sharing_the_gpu_run_the_one_sweep_chain_over_gloo():
     whole slide bit for bit (sums of integers and of binary64 partials in a fixed order per rank; the all-reduce adds two numbers),
     and the bytes of their shards must be those of the single-process transform."""
     import torch
-    import torch.multiprocessing as mp
     import stainlib_amd as sl
     from stainlib_amd.distributed import PooledSlideStatistics, SlideNormalizer
     from tools.synth import synth_tiles
-    ctx = mp.get_context("spawn")
-    for n_tiles, port in ((24, 29631), (23, 29632)):
-        q = ctx.Queue()
-        procs = [ctx.Process(target=_two_rank_worker, args=(r, 2, port, n_tiles, q)) for r in range(2)]
-        for p in procs:
-            p.start()
-        res = sorted([q.get(timeout=600) for _ in procs], key=lambda t: t[0])
-        for p in procs:
-            p.join(timeout=120)
-            assert p.exitcode == 0
+    for n_tiles in (24, 23):
+        res = run_ranks(_two_rank_worker, 2, n_tiles, timeout=600)
         slide = synth_tiles(n_tiles, 256, 320, seed=21, device=torch.device("cuda", 0))
         st = PooledSlideStatistics(group=False)
         want = st.finish(st.enqueue_merged(slide))

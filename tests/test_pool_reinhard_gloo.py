@@ -5,16 +5,12 @@ The orchestration under test is the product's: the two integer all-reduces, the 
 without tiles, the one read-back, the empty-mask contract.  The device steps are the numpy stand-ins of tests/pool_reinhard_standins.py
 (sums of THIS rank's tiles; begin / finish from reduced sums only).  The bar is the oracle's ReinhardStainNormalizer.transform /
 luminosity_standardize on the vertical concatenation of all tiles, byte for byte."""
-import os
-
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
 from stainlib_amd import distributed as sd
-from tests.test_distributed_gloo import _free_port
+from tests.ranks import run_ranks
 
 H, W = 61, 67
 
@@ -34,60 +30,41 @@ def _target():
     return ref
 
 
-def _worker(rank, world, port, shards, q):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    if world > 1:
-        dist.init_process_group("gloo", rank=rank, world_size=world)
+def _worker(rank, world, shards):
+    from tests import pool_reinhard_standins
+    calls = []
+    pool_reinhard_standins.install(calls)
+    import stainlib_amd
+    from stainlib_amd.utils.excepts import TissueMaskException
+    ref = _target()
+    nrm = stainlib_amd.ReinhardStainNormalizer(ref.target_means, ref.target_stds)
+    lo = sum(shards[:rank])
+    res = {"rank": rank}
+    mine = torch.from_numpy(np.stack(_slide("dark"))[lo:lo + shards[rank]].copy())
+    for name, kw in (("plain", {}), ("mask", dict(mask_background=True)), ("mask06", dict(mask_background=True, luminosity_threshold=0.6))):
+        sn = sd.SlideNormalizer(nrm, mode="pooled")
+        out, means, stds, status = sn.transform_shard(mine, **kw)
+        assert status.shape == (shards[rank],) and not status.any() and means.dtype == torch.float64 and means.shape == (3,)
+        res[name] = (out.numpy(), means.numpy(), stds.numpy(), sn.last_p90)
+    res["n_calls_reinhard"] = len(calls)
+    for pct in (95, 80):
+        out, p = sd.slide_luminosity_standardize(mine, percentile=pct)
+        res["lum%d" % pct] = (out.numpy(), p)
+    res["bytes_sweeps"] = calls.count("bytes")
+    white = torch.from_numpy(np.stack(_slide("white"))[lo:lo + shards[rank]].copy())
+    out = torch.zeros_like(white)
     try:
-        from tests import pool_reinhard_standins
-        calls = []
-        pool_reinhard_standins.install(calls)
-        import stainlib_amd
-        from stainlib_amd.utils.excepts import TissueMaskException
-        ref = _target()
-        nrm = stainlib_amd.ReinhardStainNormalizer(ref.target_means, ref.target_stds)
-        lo = sum(shards[:rank])
-        res = {"rank": rank}
-        mine = torch.from_numpy(np.stack(_slide("dark"))[lo:lo + shards[rank]].copy())
-        for name, kw in (("plain", {}), ("mask", dict(mask_background=True)), ("mask06", dict(mask_background=True, luminosity_threshold=0.6))):
-            sn = sd.SlideNormalizer(nrm, mode="pooled")
-            out, means, stds, status = sn.transform_shard(mine, **kw)
-            assert status.shape == (shards[rank],) and not status.any() and means.dtype == torch.float64 and means.shape == (3,)
-            res[name] = (out.numpy(), means.numpy(), stds.numpy(), sn.last_p90)
-        res["n_calls_reinhard"] = len(calls)
-        for pct in (95, 80):
-            out, p = sd.slide_luminosity_standardize(mine, percentile=pct)
-            res["lum%d" % pct] = (out.numpy(), p)
-        res["bytes_sweeps"] = calls.count("bytes")
-        white = torch.from_numpy(np.stack(_slide("white"))[lo:lo + shards[rank]].copy())
-        out = torch.zeros_like(white)
-        try:
-            sd.SlideNormalizer(nrm, mode="pooled").transform_shard(white, out=out, mask_background=True)
-            res["white"] = "no exception"
-        except TissueMaskException:
-            res["white"] = ("empty", bool(torch.equal(out, white)))
-        out, _, _, _ = sd.SlideNormalizer(nrm, mode="pooled").transform_shard(white)        # without the mask a white slide is just a slide
-        res["white_plain"] = out.numpy()
-        q.put(res)
-        if world > 1:
-            dist.barrier()
-    finally:
-        if world > 1:
-            dist.destroy_process_group()
+        sd.SlideNormalizer(nrm, mode="pooled").transform_shard(white, out=out, mask_background=True)
+        res["white"] = "no exception"
+    except TissueMaskException:
+        res["white"] = ("empty", bool(torch.equal(out, white)))
+    out, _, _, _ = sd.SlideNormalizer(nrm, mode="pooled").transform_shard(white)        # without the mask a white slide is just a slide
+    res["white_plain"] = out.numpy()
+    return res
 
 
 def _run(shards):
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, len(shards), port, shards, q)) for r in range(len(shards))]
-    for p in procs:
-        p.start()
-    res = sorted([q.get(timeout=300) for _ in procs], key=lambda t: t["rank"])
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
-    return res
+    return run_ranks(_worker, len(shards), shards, timeout=300)
 
 
 _WANT = {}

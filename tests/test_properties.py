@@ -6,6 +6,7 @@ from hypothesis import given, settings, strategies as st
 
 from oracle import stain_oracle as so
 from stainlib_amd import distributed as sd
+from tests.standin_math import f2ord as _f2ord
 
 
 def _random_M(rng, allow_negative_correlation):
@@ -48,11 +49,6 @@ def test_ordered_uint32_key_round_trip_and_order(v):
         return
     assert (oa < ob) == (a < b) or a == b
     assert sd.ord_to_float(oa) == a or (a == 0.0 and sd.ord_to_float(oa) == 0.0)
-
-
-def _f2ord(a):
-    u = np.asarray(a, np.float32).view(np.uint32)
-    return np.where(u & 0x80000000, ~u, u | 0x80000000).astype(np.uint32)
 
 
 def test_macenko_matrix_is_invariant_under_pixel_permutation_and_tiling():
