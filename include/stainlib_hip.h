@@ -10,7 +10,8 @@
  *
  * Conventions
  *   - every data pointer is a DEVICE pointer (HBM), e.g. torch tensor.data_ptr();
- *     SlParams is the only host pointer.
+ *     SlParams and SlTensorFormat are the only host structs (a few pooled-mode calls take small host arrays, named where
+ *     they are declared).
  *   - images: n tiles, each h x w x 3 interleaved RGB uint8, tiles contiguous
  *     (NHWC).  Stain matrices: row-major 2x3 double, row 0 = haematoxylin.
  *   - the caller owns every buffer including the workspace; the library keeps
@@ -516,6 +517,42 @@ SL_API int sl_slab_finish(double* state, const unsigned long long* sums_b_reduce
  * a = b = 0 before merge_back (normalizer.py:86-90).  With a status other than SL_TILE_OK the tiles are copied through unchanged. */
 SL_API int sl_slab_map(const uint8_t* rgb, uint8_t* out, int n, int h, int w, const double* state, int mode, int mask_background,
                        double luminosity_threshold, void* stream);
+
+/* ---- model-ready tensor output (stainlib_amd/csrc/tensor_out.hip; an extension: the reference ends at normalizer.py:50 with a uint8
+ * image, and every consumer then writes ((out.permute(0, 3, 1, 2).float() / 255) - mean) / std in its framework) -------------------------
+ * One definition everywhere, so that the fused pass and "convert afterwards" agree to the bit.  For channel c and a result byte b --
+ * the TRUNCATED uint8 the library produces today, never the value before the cast --
+ *     scale32[c] = (float)(1.0 / (255.0 * std[c]))        binary64 on the host, rounded to binary32 once
+ *     shift32[c] = (float)(-mean[c] / std[c])
+ *     v          = fmaf((float)b, scale32[c], shift32[c])   ONE fused multiply-add: one binary32 rounding
+ *     out        = v converted to the output type, round-to-nearest-even
+ * Layouts of `out` (n x 3 x h x w elements): SL_LAYOUT_NCHW -- plane c of tile i starts at element (3 i + c) h w; SL_LAYOUT_NHWC --
+ * interleaved like the input (torch's channels_last).  `out` needs the alignment of its element type only; stores are 16 bytes wide
+ * where `out` is 16-byte aligned and h w is a multiple of 4 (float32) or 8 (the half types) pixels, element-wise otherwise.
+ * SlTensorFormat is a HOST pointer, like SlParams. */
+#define SL_DTYPE_F32 0
+#define SL_DTYPE_F16 1
+#define SL_DTYPE_BF16 2
+#define SL_LAYOUT_NCHW 0
+#define SL_LAYOUT_NHWC 1
+typedef struct SlTensorFormat {
+    uint32_t struct_size;        /* sizeof(SlTensorFormat) of the caller's header: set by sl_default_tensor_format, checked by both entry
+                                    points (SL_ERR_BADARG on a mismatch) */
+    int32_t dtype;               /* SL_DTYPE_* */
+    int32_t layout;              /* SL_LAYOUT_* */
+    int32_t reserved;
+    double mean[3];              /* per channel, in units of [0, 1]; finite, else SL_ERR_BADARG */
+    double std[3];               /* finite and > 0, else SL_ERR_BADARG */
+} SlTensorFormat;
+/* float32, NCHW, mean 0, std 1 (the plain b / 255) */
+SL_API void sl_default_tensor_format(SlTensorFormat* f);
+/* Replaces the consumer's permute / cast / scale / shift passes behind any uint8 result: one streaming sweep, 3 B read and 6 or 12 B
+ * written per pixel.  rgb: n x h x w x 3 uint8; out: n x 3 x h x w elements of fmt->dtype in fmt->layout. */
+SL_API int sl_to_tensor(const uint8_t* rgb, void* out, int n, int h, int w, const SlTensorFormat* fmt, void* stream);
+/* sl_normalize_apply (normalization/normalizer.py:46-50) followed by sl_to_tensor in ONE pass: the bytes of the truncating cast are
+ * converted in registers and the uint8 image is never written; equal to sl_to_tensor(sl_normalize_apply(...)) bit for bit.  A tile whose
+ * fit failed (NaN M_src, maxC_src <= 0) is passed through as in sl_normalize_apply: its SOURCE bytes are converted. */
+SL_API int sl_normalize_apply_tensor(const uint8_t* rgb, void* out, int n, int h, int w, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, double lasso_lambda, const SlTensorFormat* fmt, void* stream);
 
 #ifdef __cplusplus
 }

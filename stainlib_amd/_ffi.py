@@ -54,6 +54,22 @@ class SlParams(C.Structure):
     ]
 
 
+class SlTensorFormat(C.Structure):
+    """The model-ready output of sl_to_tensor / sl_normalize_apply_tensor (a HOST struct, like SlParams)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("dtype", C.c_int32),
+        ("layout", C.c_int32),
+        ("reserved", C.c_int32),
+        ("mean", C.c_double * 3),
+        ("std", C.c_double * 3),
+    ]
+
+
+DTYPE_F32, DTYPE_F16, DTYPE_BF16 = range(3)
+LAYOUT_NCHW, LAYOUT_NHWC = range(2)
+
+
 class StainlibHipError(RuntimeError):
     pass
 
@@ -135,6 +151,10 @@ _SIGNATURES = {
     "sl_slab_lab": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_double, _P, C.c_size_t, _P, _P]),
     "sl_slab_finish": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_double, C.c_int, _P]),
     "sl_slab_map": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_double, _P]),
+    # model-ready tensor output (SlTensorFormat: a host struct)
+    "sl_default_tensor_format": (None, [C.POINTER(SlTensorFormat)]),
+    "sl_to_tensor": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(SlTensorFormat), _P]),
+    "sl_normalize_apply_tensor": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_double, C.POINTER(SlTensorFormat), _P]),
 }
 POOL_STATE_DOUBLES, POOL_M, POOL_MAXC, POOL_STATUS, POOL_MISS = 64, 0, 6, 8, 9
 POOL2_STATE_DOUBLES, POOL2_HIST_WORDS, POOL2_WHY = 256, 2 * 8192 + 8 * 32, 33
@@ -172,6 +192,12 @@ def lib() -> C.CDLL:
 def check(code: int, what: str) -> None:
     if code != 0:
         raise StainlibHipError(f"{what} failed: {lib().sl_error_string(code).decode()} (code {code})")
+
+
+def default_tensor_format() -> SlTensorFormat:
+    f = SlTensorFormat()
+    lib().sl_default_tensor_format(C.byref(f))
+    return f
 
 
 def default_params() -> SlParams:

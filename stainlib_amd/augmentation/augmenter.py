@@ -119,10 +119,15 @@ class HedColorAugmenter(ColorAugmenterBase):
             return patch                                              # augmenter.py:331
         return out[0].cpu().numpy()
 
-    def transform_batch(self, tiles, sigmas=None, biases=None, out=None):
+    def transform_batch(self, tiles, sigmas=None, biases=None, out=None, tensor_format=None):
         """Batched extension: (N,H,W,3) uint8 device tensor; per-tile (N,3) sigmas / biases (defaults: the
-        augmenter's current ones for every tile).  Returns (out, applied)."""
+        augmenter's current ones for every tile).  Returns (out, applied).
+        ``tensor_format``: a ``stainlib_amd.TensorFormat``; `out` is then the (N,3,H,W) tensor in that format (the augmentation writes
+        a uint8 scratch, ``tensor_format.convert`` reads it)."""
         from .. import engine
+        if tensor_format is not None:
+            u8, applied = self.transform_batch(tiles, sigmas, biases)
+            return tensor_format.convert(u8, out=out), applied
         n = tiles.shape[0]
         sigmas = [self._sigmas] * n if sigmas is None else sigmas
         biases = [self._biases] * n if biases is None else biases

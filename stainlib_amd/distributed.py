@@ -610,13 +610,19 @@ class PooledReinhardStatistics:
         return self.last_status
 
 
-def slide_luminosity_standardize(tiles_local: torch.Tensor, percentile=95, group=None, out: Optional[torch.Tensor] = None):
+def slide_luminosity_standardize(tiles_local: torch.Tensor, percentile=95, group=None, out: Optional[torch.Tensor] = None,
+                                 tensor_format=None):
     """LuminosityStandardizer.standardize (stain_utils.py:52-67) on the concatenation of every tile on every rank: (out, p), p the
-    `percentile` of the slide's L8 as a float.  One sweep for the L8 histogram, one small all-reduce, the map."""
+    `percentile` of the slide's L8 as a float.  One sweep for the L8 histogram, one small all-reduce, the map.
+    tensor_format: a stainlib_amd.TensorFormat; `out` is then the (n_local,3,H,W) tensor in that format (the map writes a uint8 scratch,
+    tensor_format.convert reads it)."""
     from . import engine
     stats = PooledReinhardStatistics(group)
     state = stats.enqueue_luminosity(tiles_local, percentile)
-    out = engine.slab_map(tiles_local, state, 1, out=out)
+    if tensor_format is not None:
+        out = tensor_format.convert(engine.slab_map(tiles_local, state, 1), out=out)
+    else:
+        out = engine.slab_map(tiles_local, state, 1, out=out)
     stats.finish(state)
     return out, stats.last_percentile
 
@@ -663,11 +669,15 @@ class SlideNormalizer:
         return self.normalizer.stain_matrix_target, self.normalizer.maxC_target.reshape(2)
 
     @staticmethod
-    def _apply(tiles_local, M_s, maxC_s, Mt, mct, out):
-        """The apply pass of every tile under the one slide matrix M_s (2, 3) and maxC_s (2,) (device float64)."""
+    def _apply(tiles_local, M_s, maxC_s, Mt, mct, out, fmt=None):
+        """The apply pass of every tile under the one slide matrix M_s (2, 3) and maxC_s (2,) (device float64); with a TensorFormat the
+        pass that converts its bytes in registers (no uint8 image is written)."""
         from . import engine
         n = tiles_local.shape[0]
-        return engine.normalize_apply(tiles_local, M_s.expand(n, 2, 3).contiguous(), maxC_s.expand(n, 2).contiguous(), Mt, mct, out=out)
+        M_n, maxC_n = M_s.expand(n, 2, 3).contiguous(), maxC_s.expand(n, 2).contiguous()
+        if fmt is not None:
+            return engine.normalize_apply_tensor(tiles_local, M_n, maxC_n, Mt, mct, fmt, out=out)
+        return engine.normalize_apply(tiles_local, M_n, maxC_n, Mt, mct, out=out)
 
     @staticmethod
     def _slide_stats(state):         # views of the slide's (M, maxC) in a pool state
@@ -675,31 +685,36 @@ class SlideNormalizer:
         return state[_ffi.POOL_M:_ffi.POOL_M + 6].reshape(2, 3), state[_ffi.POOL_MAXC:_ffi.POOL_MAXC + 2]
 
     def transform_shard(self, tiles_local: torch.Tensor, out: Optional[torch.Tensor] = None, n_tiles_total: Optional[int] = None, *,
-                        mask_background=False, luminosity_threshold=0.8):
+                        mask_background=False, luminosity_threshold=0.8, tensor_format=None):
         """tiles_local: this rank's (n_local,H,W,3) uint8 device tensor.  Returns (out, M_slide, maxC_slide, status_local).
         n_tiles_total (pooled mode, optional): the slide's tile count over all ranks; saves the one tiny all-reduce that otherwise
         agrees on the sample density.  On failure (TissueMaskException) `out` holds a copy of the input tiles.
         With a Reinhard normalizer: returns (out, means, stds, status_local) -- the slide's Lab means and standard deviations as device
         float64 (3,) -- and sets ``last_p90``; mask_background / luminosity_threshold are ReinhardStainNormalizer.transform's (the
-        extractive normalizers have no such arguments: a non-default value with one raises ValueError)."""
+        extractive normalizers have no such arguments: a non-default value with one raises ValueError).
+        tensor_format: a stainlib_amd.TensorFormat; `out` is then the (n_local,3,H,W) tensor in that format, bit for bit
+        tensor_format.convert of the uint8 result: the apply pass of the extractive normalizers converts its bytes in registers, the
+        Reinhard map writes a uint8 scratch that the converter reads.  Not with graph=True (ValueError)."""
+        if tensor_format is not None and self.graph:
+            raise ValueError("tensor_format is not supported with graph=True")
         if self._reinhard:
-            return self._transform_reinhard(tiles_local, out, mask_background, luminosity_threshold)
+            return self._transform_reinhard(tiles_local, out, mask_background, luminosity_threshold, tensor_format)
         if mask_background or luminosity_threshold != 0.8:
             raise ValueError("mask_background / luminosity_threshold apply to a Reinhard normalizer only")
         if self.mode == "median":
-            return self._transform_median(tiles_local, out)
+            return self._transform_median(tiles_local, out, tensor_format)
         if getattr(self.normalizer, "method", "macenko") == "vahadane":
-            return self._transform_vahadane(tiles_local, out, n_tiles_total)
-        return self._transform_macenko(tiles_local, out, n_tiles_total)
+            return self._transform_vahadane(tiles_local, out, n_tiles_total, tensor_format)
+        return self._transform_macenko(tiles_local, out, n_tiles_total, tensor_format)
 
-    def _transform_median(self, tiles_local: torch.Tensor, out: Optional[torch.Tensor]):
+    def _transform_median(self, tiles_local: torch.Tensor, out: Optional[torch.Tensor], fmt=None):
         """Per-tile fits, all-gathered; every tile normalised with their element-wise median."""
         M, maxC, status = self.normalizer.fit_batch_targets(tiles_local)
         M_s, maxC_s = slide_statistics(*gather_tile_stats(M, maxC, status, self.group))
-        out = self._apply(tiles_local, M_s, maxC_s, *self._targets(tiles_local.device), out)
+        out = self._apply(tiles_local, M_s, maxC_s, *self._targets(tiles_local.device), out, fmt)
         return out, M_s, maxC_s, status
 
-    def _transform_macenko(self, tiles_local: torch.Tensor, out: Optional[torch.Tensor], n_tiles_total: Optional[int]):
+    def _transform_macenko(self, tiles_local: torch.Tensor, out: Optional[torch.Tensor], n_tiles_total: Optional[int], fmt=None):
         """Pooled mode with a Macenko normalizer.  Device-driven: the statistics AND the apply pass are enqueued before anything is read
         back; the one read-back afterwards only confirms that both windows caught their ranks (else the next chain, or the host-driven
         rounds, and the pass again).  When a chain ends in an unusable state (a window miss, an empty tissue mask, a degenerate
@@ -718,12 +733,12 @@ class SlideNormalizer:
 
         def behind(st):                     # the apply pass behind each eager chain; the next route writes the same `out`
             nonlocal out
-            out = self._apply(tiles_local, *self._slide_stats(st), Mt, mct, out)
+            out = self._apply(tiles_local, *self._slide_stats(st), Mt, mct, out, fmt)
         M_np, maxC_np, state = stats.settle(tiles_local, n_tiles_total, self.merged, ws=self._pool2_ws, first=first, behind=behind)
         if state is None:                   # the host-driven rounds settled it: the pass again, under their numbers
             M_s = torch.as_tensor(M_np, dtype=torch.float64, device=dev)
             maxC_s = torch.as_tensor(maxC_np, dtype=torch.float64, device=dev)
-            out = self._apply(tiles_local, M_s, maxC_s, Mt, mct, out)
+            out = self._apply(tiles_local, M_s, maxC_s, Mt, mct, out, fmt)
         else:
             M_s, maxC_s = (t.clone() for t in self._slide_stats(state))
         self.last_path = stats.last_path             # per stage: "merged" (one sweep for both), "window" (one each) or "radix"
@@ -754,7 +769,7 @@ class SlideNormalizer:
             self._graphed = (key, engine.Graphed(captured), keep)
         return self._graphed[1], out
 
-    def _transform_vahadane(self, tiles_local: torch.Tensor, out: Optional[torch.Tensor], n_tiles_total: Optional[int]):
+    def _transform_vahadane(self, tiles_local: torch.Tensor, out: Optional[torch.Tensor], n_tiles_total: Optional[int], fmt=None):
         """Pooled mode with a Vahadane normalizer: the slide's dictionary and concentrations, then the apply pass of the Macenko mode."""
         from .utils.excepts import TissueMaskException
         if self.graph:
@@ -762,12 +777,19 @@ class SlideNormalizer:
         stats = PooledVahadaneStatistics(self.group)
         dev = tiles_local.device
         n = tiles_local.shape[0]
-        if out is None:
-            out = torch.empty_like(tiles_local)
+        if fmt is not None:
+            def through():             # "unchanged" in the format: the source bytes converted
+                return fmt.convert(tiles_local, out=out)
+        else:
+            if out is None:
+                out = torch.empty_like(tiles_local)
+
+            def through():
+                return out.copy_(tiles_local)
         try:
             M_np, maxC_np = stats(tiles_local, n_tiles_total=n_tiles_total)
         except TissueMaskException:
-            out.copy_(tiles_local)
+            through()
             raise
         finally:
             self.last_path = stats.last_path
@@ -775,13 +797,14 @@ class SlideNormalizer:
         M_s = torch.as_tensor(M_np, dtype=torch.float64, device=dev)
         maxC_s = torch.as_tensor(maxC_np, dtype=torch.float64, device=dev)
         if stats.last_status != 0:             # unusable statistics: the tiles go through unchanged, as k_apply does for a failed tile
-            out.copy_(tiles_local)
-            return out, M_s, maxC_s, torch.full((n,), stats.last_status, dtype=torch.int32, device=dev)
+            return through(), M_s, maxC_s, torch.full((n,), stats.last_status, dtype=torch.int32, device=dev)
         if n:
-            out = self._apply(tiles_local, M_s, maxC_s, *self._targets(dev), out)
+            out = self._apply(tiles_local, M_s, maxC_s, *self._targets(dev), out, fmt)
+        elif fmt is not None:
+            out = through()                    # an empty shard: the empty tensor in the format
         return out, M_s, maxC_s, torch.zeros((n,), dtype=torch.int32, device=dev)
 
-    def _transform_reinhard(self, tiles_local: torch.Tensor, out: Optional[torch.Tensor], mask_background, luminosity_threshold):
+    def _transform_reinhard(self, tiles_local: torch.Tensor, out: Optional[torch.Tensor], mask_background, luminosity_threshold, fmt=None):
         """Pooled mode with a Reinhard normalizer.  Device-driven: the statistics AND the map are enqueued before the one read-back; with
         an unusable status (an empty tissue mask under mask_background, an empty slide) the map copies the tiles through."""
         from . import engine, _ffi
@@ -793,7 +816,10 @@ class SlideNormalizer:
                                       torch.tensor(ts, dtype=torch.float64, device=tiles_local.device))
         _, tm, ts = self._reinhard_targets
         state = stats.enqueue(tiles_local, tm, ts, mask_background, luminosity_threshold)
-        out = engine.slab_map(tiles_local, state, 0, mask_background, luminosity_threshold, out=out)
+        if fmt is not None:                    # the map into a uint8 scratch, then the converter
+            out = fmt.convert(engine.slab_map(tiles_local, state, 0, mask_background, luminosity_threshold), out=out)
+        else:
+            out = engine.slab_map(tiles_local, state, 0, mask_background, luminosity_threshold, out=out)
         means = state[_ffi.SLAB_MEANS:_ffi.SLAB_MEANS + 3].clone()
         stds = state[_ffi.SLAB_STDS:_ffi.SLAB_STDS + 3].clone()
         try:

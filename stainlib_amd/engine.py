@@ -145,6 +145,63 @@ def normalize_apply(rgb, M_src, maxC_src, M_tgt, maxC_tgt, lasso_lambda=0.01, ou
     return (out, pre) if want_prequant else out
 
 
+# ---- model-ready tensor output (sl_to_tensor / sl_normalize_apply_tensor; see SlTensorFormat in include/stainlib_hip.h) --------------
+_TENSOR_DTYPES = {torch.float32: _ffi.DTYPE_F32, torch.float16: _ffi.DTYPE_F16, torch.bfloat16: _ffi.DTYPE_BF16}
+
+
+def _tensor_format(fmt):
+    """(SlTensorFormat, torch dtype, channels_last) of a stainlib_amd.TensorFormat."""
+    f = _ffi.default_tensor_format()
+    f.dtype = _TENSOR_DTYPES[fmt.dtype]
+    f.layout = _ffi.LAYOUT_NHWC if fmt.channels_last else _ffi.LAYOUT_NCHW
+    for c in range(3):
+        f.mean[c] = float(fmt.mean[c])
+        f.std[c] = float(fmt.std[c])
+    return f, fmt.dtype, bool(fmt.channels_last)
+
+
+def _tensor_out(out, n, h, w, dtype, channels_last, device):
+    """The (N, 3, H, W) result tensor in the format's memory layout: the caller's, checked, or a fresh one."""
+    if out is None:
+        return torch.empty((n, 3, h, w), dtype=dtype, device=device,
+                           memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+    # (strides, not is_contiguous(memory_format=...): that test ignores the strides of size-1 dimensions, the kernel does not)
+    want = (3 * h * w, 1, 3 * w, 3) if channels_last else (3 * h * w, h * w, w, 1)
+    if not (isinstance(out, torch.Tensor) and out.dtype == dtype and out.device == device and tuple(out.shape) == (n, 3, h, w)
+            and tuple(out.stride()) == want):
+        raise ValueError(f"out must be a {dtype} tensor of shape ({n}, 3, {h}, {w}) on {device} in "
+                         f"{'channels_last' if channels_last else 'contiguous'} memory format")
+    return out
+
+
+def to_tensor(rgb, fmt, out=None):
+    """(N,H,W,3) uint8 -> (N,3,H,W) tensor of fmt.dtype, contiguous or channels_last: fma(b, 1/(255 std), -mean/std) of every byte,
+    rounded to nearest even (sl_to_tensor).  fmt: a stainlib_amd.TensorFormat."""
+    n, h, w = _check_shard(rgb)
+    f, dtype, cl = _tensor_format(fmt)
+    out = _tensor_out(out, n, h, w, dtype, cl, rgb.device)
+    if n == 0:                   # an empty shard of the slide modes
+        return out
+    _call("sl_to_tensor", _ptr(rgb), _ptr(out), n, h, w, C.byref(f))
+    return out
+
+
+def normalize_apply_tensor(rgb, M_src, maxC_src, M_tgt, maxC_tgt, fmt, lasso_lambda=0.01, out=None):
+    """normalize_apply and to_tensor in one pass (sl_normalize_apply_tensor): equal to to_tensor(normalize_apply(...), fmt) bit for
+    bit, without the uint8 image in between."""
+    n, h, w = _check_tiles(rgb)
+    dev = rgb.device
+    M_src = _f64(M_src, (n, 2, 3), dev)
+    maxC_src = _f64(maxC_src, (n, 2), dev)
+    M_tgt = _f64(M_tgt, (2, 3), dev)
+    maxC_tgt = _f64(maxC_tgt, (2,), dev)
+    f, dtype, cl = _tensor_format(fmt)
+    out = _tensor_out(out, n, h, w, dtype, cl, dev)
+    _call("sl_normalize_apply_tensor", _ptr(rgb), _ptr(out), n, h, w, _ptr(M_src), _ptr(maxC_src), _ptr(M_tgt), _ptr(maxC_tgt),
+          float(lasso_lambda), C.byref(f))
+    return out
+
+
 def _fit(fn_name, op, rgb, params, ws, with_sweeps=False):
     n, h, w = _check_tiles(rgb)
     dev = rgb.device

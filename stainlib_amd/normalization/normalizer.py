@@ -23,6 +23,10 @@ _METHODS = ("macenko", "vahadane")
 # host-driven (~1.3 ms whatever the size), so it only pays from the measured crossover on (tools/big_image.py:
 # 4096^2 1.27 vs 1.58 ms, 6144^2 3.4 vs 1.9 ms).
 BIG_IMAGE_PIXELS = 5 << 22        # ~21 Mpx
+# transform_batch(tensor_format=...): "fused" = *_fit, then sl_normalize_apply_tensor; "convert" = *_transform into a uint8 scratch, then
+# sl_to_tensor.  Both give the same bits (tests/test_gpu_tensor_format.py).  NOT MEASURED yet (tools/tensor_format_time.py decides it at
+# 512 x 1024^2): "fused" on the byte count alone -- it saves the 3 B/px write and re-read of the scratch.
+TENSOR_ROUTE = "fused"
 
 
 def _row_bands(dev_img):
@@ -142,12 +146,27 @@ class ExtractiveStainNormalizer(object):
         """Per-tile (M, maxC, status) device tensors for a batch of candidate targets."""
         return self._fit_tiles(tiles, ws=ws)
 
-    def transform_batch(self, tiles, out=None, ws=None):
+    def transform_batch(self, tiles, out=None, ws=None, tensor_format=None, _tensor_route=None):
         """(N,H,W,3) uint8 device tensor -> (out, M_src, maxC_src, status) device tensors.  A tile whose
         status is non-zero (1 = empty tissue mask, 2 = degenerate, 3 = a zero 99th-percentile concentration) is passed through unchanged.
         ``ws``: an ``engine.Workspace`` to reuse (ONE stream at a time); by default every call takes its scratch from
-        torch's stream-ordered caching allocator, so concurrent streams / threads never share it."""
-        return self._transform_tiles(tiles, out=out, ws=ws)
+        torch's stream-ordered caching allocator, so concurrent streams / threads never share it.
+        ``tensor_format``: a ``stainlib_amd.TensorFormat``; `out` is then the (N,3,H,W) tensor in that format -- bit for bit
+        ``tensor_format.convert`` of the uint8 result (a passed-through tile: of its source bytes)."""
+        if tensor_format is None:
+            return self._transform_tiles(tiles, out=out, ws=ws)
+        from .. import engine
+        route = _tensor_route or TENSOR_ROUTE
+        if route == "fused":           # the fit, then the apply pass that converts its bytes in registers: no uint8 image
+            M, maxC, status = self._fit_tiles(tiles, ws=ws)
+            M_t, c_t = self._target_on(tiles.device)
+            x = engine.normalize_apply_tensor(tiles, M, maxC, M_t, c_t, tensor_format, out=out)
+        elif route == "convert":       # today's transform into a uint8 scratch, then the converter
+            u8, M, maxC, status = self._transform_tiles(tiles, ws=ws)
+            x = tensor_format.convert(u8, out=out)
+        else:
+            raise ValueError("_tensor_route must be 'fused' or 'convert'")
+        return x, M, maxC, status
 
     def state_dict(self):
         return {"method": self.method, "stain_matrix_target": np.array(self.stain_matrix_target),
@@ -205,8 +224,13 @@ class ReinhardStainNormalizer(object):
             raise TissueMaskException("Empty tissue mask computed")       # stain_utils.py:46-47 via normalizer.py:86
         return out[0].cpu().numpy()
 
-    def transform_batch(self, tiles, mask_background=False, luminosity_threshold=0.8, out=None, ws=None):
-        """Batched extension: (N,H,W,3) uint8 device tensor -> (out, stats (N,8): p90, means, stds, tissue pixels)."""
+    def transform_batch(self, tiles, mask_background=False, luminosity_threshold=0.8, out=None, ws=None, tensor_format=None):
+        """Batched extension: (N,H,W,3) uint8 device tensor -> (out, stats (N,8): p90, means, stds, tissue pixels).
+        ``tensor_format``: a ``stainlib_amd.TensorFormat``; `out` is then the (N,3,H,W) tensor in that format (the map writes a uint8
+        scratch, ``tensor_format.convert`` reads it)."""
         from .. import engine
         tm, ts = self._targets()
-        return engine.reinhard_transform(tiles, tm, ts, mask_background, luminosity_threshold, out=out, ws=ws)
+        if tensor_format is None:
+            return engine.reinhard_transform(tiles, tm, ts, mask_background, luminosity_threshold, out=out, ws=ws)
+        u8, st = engine.reinhard_transform(tiles, tm, ts, mask_background, luminosity_threshold, ws=ws)
+        return tensor_format.convert(u8, out=out), st
