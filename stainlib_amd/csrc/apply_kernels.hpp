@@ -232,6 +232,8 @@ __device__ __forceinline__ Chunk pack_trunc_general(const float (&t)[12]) {
 // The apply sweep over chunks [c0, c1) of one tile with `nthreads` cooperating threads, table values from the
 // row table.  Two chunks per trip; the next trip's chunks are in flight during the current one and the 12 table
 // gathers of a chunk are issued one chunk ahead of its arithmetic.
+// (A second loop shape beside pipelined_sweep of sweep_pipeline.hpp, shared with augment_sweep: per-lane loop control, no
+// tail instantiation, the store predicated on cc < c1.  Both keep their own gather: sweep_pipeline.hpp includes this header.)
 template <bool ALIGNED, bool FAST, class TR, bool STREAM = false>
 __device__ __forceinline__ void apply_sweep(const uint8_t* src, uint8_t* dst, int P, int c0, int c1, int t, int nthreads,
                                             const TR& T, const ApplyK& K) {

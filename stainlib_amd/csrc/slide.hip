@@ -17,6 +17,7 @@
 // two lasso concentrations (all pixels), as order-preserving uint32 of their binary32 value.  Nothing
 // per-pixel is stored: every round is one more sweep over the uint8 tiles.
 #include "stats_kernels.hpp"
+#include "sweep_pipeline.hpp"
 #include "sl_host.hpp"
 #include <cmath>
 #include <cstring>
@@ -118,7 +119,7 @@ __global__ __launch_bounds__(kSweepThreads, 4) void k_slide_keys(SlideArgs a, un
     auto process = [&](const Chunk& in, int cc, int c1) {
 #pragma unroll
         for (int px = 0; px < 4; ++px) {
-            bool have = (cc < c1) & (ALIGNED | ((size_t)cc * 4 + px < (size_t)a.P));
+            bool have = in_tile<ALIGNED>(cc, px, c1, a.P);
             uint32_t o0, o1;
             if (KEYSET == SL_KEYSET_ANGLE) {
                 const float2 er = T.gam_odf(T.addr(in, 3 * px)), eg = T.gam_odf(T.addr(in, 3 * px + 1)), eb = T.gam_odf(T.addr(in, 3 * px + 2));
@@ -251,25 +252,15 @@ template <int KEYSET, bool ALIGNED, int kTrip, bool STREAM>
 __device__ __forceinline__ void window_sweep(const uint8_t* src, int P, int c0, int c1, int t, const TabReaderB& T, const SlideArgs& a,
                                              const float* V, const LassoK& L, const float* thr, unsigned long long* hist, WinAcc& acc) {
     constexpr int nthreads = kSweepThreads;
-    const size_t nbytes = (size_t)P * 3;
-    const int lane = t & 63;
-    const int w0 = __builtin_amdgcn_readfirstlane(c0 + (t & ~63));
     const uint32_t wlo0 = a.window_lo[0], wlo1 = a.window_lo[1];
-    struct G { float2 v[12]; };
-    struct Gc { float v[12]; };
-    using GT = typename std::conditional<KEYSET == SL_KEYSET_ANGLE, G, Gc>::type;
+    constexpr bool kAngle = KEYSET == SL_KEYSET_ANGLE;
+    using GT = std::conditional_t<kAngle, GatherGamOd, GatherOd>;
     const float ylimf = in_vgpr(a.ylimf);
     uint32_t lc0 = 0, lc1 = 0;                  // per lane: pixels proven below window 0 / (angle: between the windows; conc: below window 1)
     auto g_at = [](const GT& g, int i) { return g.v[i]; };
-    auto fetch = [&](int cc) { return load_chunk_clamped<ALIGNED, STREAM>(src, nbytes, cc, c1); };
     auto gather = [&](const Chunk& ch) {
-        GT g;
-#pragma unroll
-        for (int i = 0; i < 12; ++i) {
-            if constexpr (KEYSET == SL_KEYSET_ANGLE) g.v[i] = T.gam_odf(T.addr(ch, i));
-            else g.v[i] = T.odf(T.addr(ch, i));
-        }
-        return g;
+        if constexpr (kAngle) return gather_gam_od(T, ch);
+        else return gather_od(T, ch);
     };
     auto exact = [&](uint32_t o0, uint32_t o1, bool counted0, bool counted1) {     // under the exec mask of the unproven lanes
         acc.l_nb0 += ((o0 < wlo0) & !counted0) ? 1u : 0u;
@@ -281,10 +272,10 @@ __device__ __forceinline__ void window_sweep(const uint8_t* src, int P, int c0, 
     // Scalar instructions are as scarce as vector ones here (one issue slot per SIMD visit), so the proven pixels are
     // counted per LANE (one add-with-carry off the compare's mask each) and the unproven ones are looked for once per
     // CHUNK: the exact path of a chunk's four pixels sits behind one branch.
-    auto compute = [&](auto tail_tag, const GT& g, int cc) {
+    auto compute = [&](auto tail_tag, const Chunk&, const GT& g, int cc) {
         constexpr bool TAIL = decltype(tail_tag)::value;
         bool flag[4], cnt0[4], cnt1[4];
-        auto inb = [&](int px) { return (cc < c1) & (ALIGNED | ((size_t)cc * 4 + px < (size_t)P)); };
+        auto inb = [&](int px) { return in_tile<ALIGNED>(cc, px, c1, P); };
         auto xy = [&](float odr, float odg, float odb, float& x, float& y) {                 // the operations of angle_key
             x = fmaf(V[4], odb, fmaf(V[2], odg, V[0] * odr));
             y = fmaf(V[5], odb, fmaf(V[3], odg, V[1] * odr));
@@ -336,30 +327,7 @@ __device__ __forceinline__ void window_sweep(const uint8_t* src, int P, int c0, 
             }
         }
     };
-    Chunk cur[kTrip], nx[kTrip];
-#pragma unroll
-    for (int k = 0; k < kTrip; ++k) { cur[k] = fetch(w0 + lane + k * nthreads); nx[k] = fetch(w0 + lane + (kTrip + k) * nthreads); }
-    GT g[2];
-    g[0] = gather(cur[0]);
-    auto trip = [&](auto tail_tag, int cb) {
-#pragma unroll
-        for (int k = 0; k < kTrip; ++k) {
-            if (k + 1 < kTrip) {
-                g[(k + 1) & 1] = gather(cur[k + 1]);
-            } else {
-#pragma unroll
-                for (int j = 0; j < kTrip; ++j) { cur[j] = nx[j]; nx[j] = fetch(cb + lane + (2 * kTrip + j) * nthreads); }
-                g[0] = gather(cur[0]);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            compute(tail_tag, g[k & 1], cb + k * nthreads + lane);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-    const int lim = ALIGNED ? c1 : min(c1, P >> 2);          // chunks made of in-range pixels only
-    int cb = w0;
-    for (; cb + (kTrip - 1) * nthreads + 64 <= lim; cb += nthreads * kTrip) trip(std::false_type{}, cb);
-    if (cb < c1) trip(std::true_type{}, cb);                    // at most one ragged trip per wave
+    pipelined_sweep<ALIGNED, kTrip, STREAM>(src, P, c0, c1, t, nthreads, gather, compute);
     // angle: window 1 lies above window 0, so "below window 1" = below window 0 or between the two
     acc.l_nb0 += lc0;
     acc.l_nb1 += KEYSET == SL_KEYSET_ANGLE ? lc0 + lc1 : lc1;

@@ -731,9 +731,7 @@ struct BlockSink {
     }
 };
 
-#ifndef P2_TRIP
-#define P2_TRIP 2          // chunks per lane and trip: with 4 (as the other sweeps) the kernel spilled 250 VGPRs and 19 SGPRs into its loop
-#endif
+constexpr int kP2Trip = 2;   // chunks per lane and trip: with 4 (as the other sweeps) the kernel spilled 250 VGPRs and 19 SGPRs into its loop
 struct P2SweepK {            // VGPR-resident
     float gH[3], gL[3], n[3], k1;
     float W[2][3], kt[2], eps[2], zeta[2], thr[2];
@@ -747,14 +745,9 @@ __device__ __forceinline__ void p2_sweep_part(const uint8_t* src, int P, int c0,
     const size_t nbytes = (size_t)P * 3;
     const int lane = t & 63;
     const int w0 = __builtin_amdgcn_readfirstlane(c0 + (t & ~63));
-    struct G { float2 v[12]; };
+    using G = GatherGamOd;
     auto fetch = [&](int cc) { return load_chunk_clamped<ALIGNED, STREAM>(src, nbytes, cc, c1); };
-    auto gather = [&](const Chunk& ch) {
-        G g;
-#pragma unroll
-        for (int i = 0; i < 12; ++i) g.v[i] = T.gam_odf(T.addr(ch, i));
-        return g;
-    };
+    auto gather = [&](const Chunk& ch) { return gather_gam_od(T, ch); };
     BurstMoments bm;
     uint32_t cnt_t = 0;                                        // wave-uniform, per part
     auto compute = [&](auto tail_tag, const Chunk& ch, const G& g, int cc) {
@@ -773,7 +766,7 @@ __device__ __forceinline__ void p2_sweep_part(const uint8_t* src, int P, int c0,
             const bool g1 = !(fmaf(K.zeta[0], fabsf(z), fmaf(K.eps[0], sa, a1)) < K.thr[0]), g2 = !(fmaf(K.zeta[1], fabsf(z), fmaf(K.eps[1], sa, a2)) < K.thr[1]);
             bool gc = g1 | g2;
             if (TAIL) {
-                const bool inb = (cc < c1) & (ALIGNED | ((size_t)cc * 4 + px < (size_t)P));
+                const bool inb = in_tile<ALIGNED>(cc, px, c1, P);
                 tc = tc & inb; gc = gc & inb;
             }
             const bool ga = tc & !pp;
@@ -781,11 +774,9 @@ __device__ __forceinline__ void p2_sweep_part(const uint8_t* src, int P, int c0,
             if (tc) bm.add(er.y, eg.y, eb.y);
             const uint32_t value = (chunk_pixel(ch, px) & 0xffffffu) | (ga ? kBitAng : 0u) | (gc ? kBitConc : 0u);
             sink.put_value(__builtin_amdgcn_ballot_w64(ga | gc), value);
-#ifdef P2_PXBAR
-            __builtin_amdgcn_sched_barrier(0);
-#endif
         }
     };
+    // A deliberate variant of pipelined_sweep (sweep_pipeline.hpp, the canonical form of this loop): no gather look-ahead, trips in pairs.
     // Two chunks per lane and trip (with the four of the other sweeps this kernel -- moments, staged candidates, 25 constants --
     // spilled 250 VGPRs and 19 SGPRs into its loop); a burst of the binary32 moment sums still spans 16 pixels per lane, the same
     // 16 as in moments_sweep_b: it is flushed after every SECOND trip, so the sums are bit-identical to sl_tile_moments'.
@@ -793,25 +784,10 @@ __device__ __forceinline__ void p2_sweep_part(const uint8_t* src, int P, int c0,
     Chunk cur[kTrip], nx[kTrip];
 #pragma unroll
     for (int k = 0; k < kTrip; ++k) { cur[k] = fetch(w0 + lane + k * nthreads); nx[k] = fetch(w0 + lane + (kTrip + k) * nthreads); }
-#ifdef P2_DBUF
-    G g[2];
-    g[0] = gather(cur[0]);
-#endif
     auto trip = [&](auto tail_tag, int cb) {
 #pragma unroll
         for (int k = 0; k < kTrip; ++k) {
             const Chunk ch = cur[k];
-#ifdef P2_DBUF
-            if (k + 1 < kTrip) {
-                g[(k + 1) & 1] = gather(cur[k + 1]);
-            } else {
-#pragma unroll
-                for (int j = 0; j < kTrip; ++j) { cur[j] = nx[j]; nx[j] = fetch(cb + lane + (2 * kTrip + j) * nthreads); }
-                g[0] = gather(cur[0]);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            compute(tail_tag, ch, g[k & 1], cb + k * nthreads + lane);
-#else
             const G g = gather(ch);
             if (k + 1 == kTrip) {
 #pragma unroll
@@ -819,7 +795,6 @@ __device__ __forceinline__ void p2_sweep_part(const uint8_t* src, int P, int c0,
             }
             __builtin_amdgcn_sched_barrier(0);
             compute(tail_tag, ch, g, cb + k * nthreads + lane);
-#endif
             __builtin_amdgcn_sched_barrier(0);
         }
     };
@@ -888,8 +863,8 @@ __global__ __launch_bounds__(kSweepThreads, 4) void k_p2_sweep(P2SweepArgs a) {
         int c0, c1;
         part_range((a.P + 3) >> 2, a.parts, part, c0, c1);
         if (c0 >= c1) continue;
-        if (stream) p2_sweep_part<ALIGNED, P2_TRIP, true>(src, a.P, c0, c1, tid, T, K, sink, mo, n_tissue);
-        else p2_sweep_part<ALIGNED, P2_TRIP, false>(src, a.P, c0, c1, tid, T, K, sink, mo, n_tissue);
+        if (stream) p2_sweep_part<ALIGNED, kP2Trip, true>(src, a.P, c0, c1, tid, T, K, sink, mo, n_tissue);
+        else p2_sweep_part<ALIGNED, kP2Trip, false>(src, a.P, c0, c1, tid, T, K, sink, mo, n_tissue);
     }
     sink.close(lane);
     double v[12];

@@ -271,7 +271,7 @@ __device__ __forceinline__ void select_sweep_cube(const uint8_t* src, int P, int
         for (int px = 0; px < 4; ++px) {
             unsigned long long m = __builtin_amdgcn_ballot_w64(amb[px]);
             if (TAIL) {
-                const bool inb = (cc < c1) & (ALIGNED | ((size_t)cc * 4 + px < (size_t)P));
+                const bool inb = in_tile<ALIGNED>(cc, px, c1, P);
                 m &= __builtin_amdgcn_ballot_w64(inb);
             }
             lds_append_masked(ring_lds, rn, m, p[px]);
@@ -279,6 +279,8 @@ __device__ __forceinline__ void select_sweep_cube(const uint8_t* src, int P, int
             if (px & 1) drain();                                 // at most 127 + 2 x 64 entries before it: kCubeRing holds them
         }
     };
+    // A deliberate variant of pipelined_sweep (sweep_pipeline.hpp, the canonical form of this loop): no table gather per chunk,
+    // so nothing to issue ahead and no scheduling barriers.
     Chunk cur[kTrip], nx[kTrip];
 #pragma unroll
     for (int k = 0; k < kTrip; ++k) { cur[k] = fetch(w0 + lane + k * nthreads); nx[k] = fetch(w0 + lane + (kTrip + k) * nthreads); }

@@ -120,26 +120,22 @@ __device__ __forceinline__ void dict_sweep_b(const uint8_t* src, int P, int c0, 
     const size_t nbytes = (size_t)P * 3;
     const int lane = t & 63;
     const int w0 = __builtin_amdgcn_readfirstlane(c0 + (t & ~63));
-    struct G { float2 v[12]; };
+    using G = GatherGamOd;
     auto fetch = [&](int cc) { return load_chunk_clamped<ALIGNED, STREAM>(src, nbytes, cc, c1); };
-    auto gather = [&](const Chunk& ch) {
-        G g;
-#pragma unroll
-        for (int i = 0; i < 12; ++i) g.v[i] = T.gam_odf(T.addr(ch, i));
-        return g;
-    };
+    auto gather = [&](const Chunk& ch) { return gather_gam_od(T, ch); };
     auto compute = [&](auto tail_tag, const G& g, int cc) {
         constexpr bool TAIL = decltype(tail_tag)::value;
 #pragma unroll
         for (int px = 0; px < 4; ++px) {
             const float2 er = g.v[3 * px], eg = g.v[3 * px + 1], eb = g.v[3 * px + 2];
             bool tissue = is_tissue_f(er.x, eg.x, eb.x, ylimf);
-            if (TAIL) tissue = tissue & (cc < c1) & (ALIGNED | ((size_t)cc * 4 + px < (size_t)P));
+            if (TAIL) tissue = tissue & in_tile<ALIGNED>(cc, px, c1, P);
             acc.pixel(L, tissue, er.y, eg.y, eb.y);
         }
     };
-    // (no gather look-ahead here: the 27 burst sums leave no room for a second set of table values, and the sweep is bound by
-    //  its ~60 vector instructions per pixel, not by the LDS latency the other waves of the SIMD cover)
+    // A deliberate variant of pipelined_sweep (sweep_pipeline.hpp, the canonical form of this loop): the bursts are flushed every
+    // kDictBurstTrips trips, and there is no gather look-ahead, because the 27 burst sums leave no room for a second set of table
+    // values and the sweep is bound by its ~60 vector instructions per pixel, not by the LDS latency the other waves of the SIMD cover.
     Chunk cur[kTrip], nx[kTrip];
 #pragma unroll
     for (int k = 0; k < kTrip; ++k) { cur[k] = fetch(w0 + lane + k * nthreads); nx[k] = fetch(w0 + lane + (kTrip + k) * nthreads); }

@@ -2,6 +2,7 @@
 // Part of stats_kernels.hpp (split by phase in round 4, no functional change); include that umbrella, not this file.
 #pragma once
 #include "stats_linalg.hpp"
+#include "sweep_pipeline.hpp"
 
 namespace sl {
 
@@ -69,14 +70,16 @@ __device__ __forceinline__ void sample_row(const Chunk& ch, int row0, int lane, 
         bool ok = true;
         if (TAIL) {
             const int cc = row0 + lane;
-            ok = (cc < c1) & (ALIGNED | ((size_t)cc * 4 + (last ? 3 : 0) < (size_t)P));
+            ok = (cc < c1) & (ALIGNED | ((size_t)cc * 4 + (last ? 3 : 0) < (size_t)P));      // in_tile, pixel 0 or 3
         }
         if (ok) as_global(samp)[((uint32_t)row0 >> cps_log2) + sl.idx] = v;
     }
 }
 
-// Sweep 1 on the layout-B table ({gamma, od32} per byte): the structure of select_sweep (gathers of a chunk issued one chunk
-// ahead of its arithmetic, next trip's chunks in flight), tissue test, binary32 burst sums flushed once per trip.
+// Sweep 1 on the layout-B table ({gamma, od32} per byte): the loop of pipelined_sweep (sweep_pipeline.hpp, the canonical form)
+// with the sample bookkeeping of a trip's rows before its arithmetic, tissue test, binary32 burst sums flushed once per trip.
+// It keeps a copy of that loop: on the driver (two per-trip hooks) fused_sweep1 changed its register use and with it the
+// allocation of the fused kernels that call it (tools/isa_diff.py), which the headline path does not allow.
 // c0 must be a multiple of 64; for schedule-independent bursts also of kTrip * nthreads (part_range guarantees it).
 template <bool ALIGNED, int kTrip, bool STREAM = false>
 __device__ __forceinline__ void moments_sweep_b(const uint8_t* src, int P, int c0, int c1, int t, int nthreads,
@@ -181,37 +184,25 @@ __device__ __forceinline__ float tissue_x_bound(const float* Vf /*[6]*/, float y
 //   concentration stage (g12 >= 0): c_i <= max(0, a_i) exactly, so  a1 < lo0 and a2 < lo1  =>  both
 //     keys lie below their brackets (needs lo > 0; otherwise nothing is plain)
 // The plain pixels are not even counted: their number is (valid pixels of the stage) - (raw candidates).
-// c0 must be a multiple of 64.  The LDS gathers of a chunk are issued one chunk ahead of its arithmetic.
-template <int STAGE> struct SelGather;
-template <> struct SelGather<kStageConc> { float v[12]; };        // od32 per byte
-template <> struct SelGather<kStageMerged> { float2 v[12]; };
-struct SelGatherOd { float v[12]; };                             // merged stage with the projection bound: od32 only
-
+// The loop itself is pipelined_sweep (sweep_pipeline.hpp); c0 must be a multiple of 64.
 // XBOUND (merged stage only): angle candidates are the pixels with t0 > K.xmin outside the plain cone instead of the tissue
 // pixels outside it -- a superset (the finish evaluates the tissue test of every candidate exactly) that costs three
 // instructions less per pixel and reads 4-byte table entries.
 template <int STAGE, bool ALIGNED, int kTrip, bool STREAM = false, bool XBOUND = false, class TR, class Sink>
 __device__ __forceinline__ void select_sweep(const uint8_t* src, int P, int c0, int c1, int t, int nthreads,
                                              const TR& T, float ylimf, const SelConsts& K, Sink& sink) {
-    const size_t nbytes = (size_t)P * 3;
     const int lane = t & 63;
     // thresholds of the cheap tests
     const float nhi0m = in_vgpr(-(K.hi0 + kAngleMargin)), nlo1m = in_vgpr(-(K.lo1 - kAngleMargin));
     const bool conc_ok = (K.L.g12 >= 0.0f) & (K.lo0 > 0.0f) & (K.lo1 > 0.0f);
     const float clo0 = conc_ok ? K.lo0 : -INFINITY, clo1 = conc_ok ? K.lo1 : -INFINITY;
-    const int w0 = __builtin_amdgcn_readfirstlane(c0 + (t & ~63));
-    auto fetch = [&](int cc) { return load_chunk_clamped<ALIGNED, STREAM>(src, nbytes, cc, c1); };   // dead lanes: see `live`
     static_assert(!XBOUND || STAGE == kStageMerged, "");
-    using GatherT = std::conditional_t<XBOUND, SelGatherOd, SelGather<STAGE>>;
+    constexpr bool kGamma = STAGE != kStageConc && !XBOUND;       // the concentration stage and the projection bound read od32 only
+    using GatherT = std::conditional_t<kGamma, GatherGamOd, GatherOd>;
     const float xmin = in_vgpr(K.xmin);
     auto gather = [&](const Chunk& ch) {
-        GatherT g;
-#pragma unroll
-        for (int i = 0; i < 12; ++i) {
-            if constexpr (STAGE != kStageConc && !XBOUND) g.v[i] = T.gam_odf(T.addr(ch, i));
-            else g.v[i] = T.odf(T.addr(ch, i));
-        }
-        return g;
+        if constexpr (kGamma) return gather_gam_od(T, ch);
+        else return gather_od(T, ch);
     };
     auto compute = [&](auto tail_tag, const Chunk& ch, const GatherT& g, int cc) {
         constexpr bool TAIL = decltype(tail_tag)::value;
@@ -256,37 +247,13 @@ __device__ __forceinline__ void select_sweep(const uint8_t* src, int P, int c0, 
                 m = __builtin_amdgcn_ballot_w64(g1) | __builtin_amdgcn_ballot_w64(g2);
             }
             if (TAIL) {
-                const bool inb = (cc < c1) & (ALIGNED | ((size_t)cc * 4 + px < (size_t)P));
+                const bool inb = in_tile<ALIGNED>(cc, px, c1, P);
                 m &= __builtin_amdgcn_ballot_w64(inb);
             }
             sink.put(m, ch, px, lane);
         }
     };
-    Chunk cur[kTrip], nx[kTrip];                             // see moments_sweep
-#pragma unroll
-    for (int k = 0; k < kTrip; ++k) { cur[k] = fetch(w0 + lane + k * nthreads); nx[k] = fetch(w0 + lane + (kTrip + k) * nthreads); }
-    GatherT g[2];
-    g[0] = gather(cur[0]);
-    auto trip = [&](auto tail_tag, int cb) {
-#pragma unroll
-        for (int k = 0; k < kTrip; ++k) {
-            const Chunk ch = cur[k];
-            if (k + 1 < kTrip) {
-                g[(k + 1) & 1] = gather(cur[k + 1]);
-            } else {
-#pragma unroll
-                for (int j = 0; j < kTrip; ++j) { cur[j] = nx[j]; nx[j] = fetch(cb + lane + (2 * kTrip + j) * nthreads); }
-                g[0] = gather(cur[0]);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            compute(tail_tag, ch, g[k & 1], cb + k * nthreads + lane);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-    const int lim = ALIGNED ? c1 : min(c1, P >> 2);          // chunks made of in-range pixels only
-    int cb = w0;
-    for (; cb + (kTrip - 1) * nthreads + 64 <= lim; cb += nthreads * kTrip) trip(std::false_type{}, cb);
-    if (cb < c1) trip(std::true_type{}, cb);                    // at most one ragged trip per wave
+    pipelined_sweep<ALIGNED, kTrip, STREAM>(src, P, c0, c1, t, nthreads, gather, compute);
 }
 
 }  // namespace sl

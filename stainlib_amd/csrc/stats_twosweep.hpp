@@ -294,14 +294,9 @@ __device__ __forceinline__ void ts_sweep(const uint8_t* src, int P, int c0, int 
     const size_t nbytes = (size_t)P * 3;
     const int lane = t & 63;
     const int w0 = __builtin_amdgcn_readfirstlane(c0 + (t & ~63));
-    struct G { float2 v[12]; };
+    using G = GatherGamOd;
     auto fetch = [&](int cc) { return load_chunk_clamped<ALIGNED, STREAM>(src, nbytes, cc, c1); };
-    auto gather = [&](const Chunk& ch) {
-        G g;
-#pragma unroll
-        for (int i = 0; i < 12; ++i) g.v[i] = T.gam_odf(T.addr(ch, i));
-        return g;
-    };
+    auto gather = [&](const Chunk& ch) { return gather_gam_od(T, ch); };
     BurstMoments bm;
     auto compute = [&](auto tail_tag, const G& g, int cc) {
         constexpr bool TAIL = decltype(tail_tag)::value;
@@ -313,7 +308,7 @@ __device__ __forceinline__ void ts_sweep(const uint8_t* src, int P, int c0, int 
                 n_tissue += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(tc));
                 if (tc) bm.add(er.y, eg.y, eb.y);
             } else {
-                const bool inb = (cc < c1) & (ALIGNED | ((size_t)cc * 4 + px < (size_t)P));
+                const bool inb = in_tile<ALIGNED>(cc, px, c1, P);
                 const unsigned long long m = __builtin_amdgcn_ballot_w64(tc) & __builtin_amdgcn_ballot_w64(inb);
                 n_tissue += (uint32_t)__popcll(m);
                 if (tc & inb) bm.add(er.y, eg.y, eb.y);
@@ -374,7 +369,7 @@ __device__ __forceinline__ void ts_sweep(const uint8_t* src, int P, int c0, int 
         for (int px = 0; px < 4; ++px) {
             unsigned long long m = __builtin_amdgcn_ballot_w64(amb[px]);
             if (TAIL) {
-                const bool inb = (cc < c1) & (ALIGNED | ((size_t)cc * 4 + px < (size_t)P));
+                const bool inb = in_tile<ALIGNED>(cc, px, c1, P);
                 m &= __builtin_amdgcn_ballot_w64(inb);
             }
             lds_append_masked(ring_lds, rn, m, p[px] & 0xffffffu);
@@ -382,6 +377,8 @@ __device__ __forceinline__ void ts_sweep(const uint8_t* src, int P, int c0, int 
             if (px & 1) drain();
         }
     };
+    // A deliberate variant of pipelined_sweep (sweep_pipeline.hpp, the canonical form of this loop): the cube test of the trip's
+    // chunks runs behind the trip's first gather, so the look-ahead buffers live inside the trip.
     Chunk cur[kTrip], nx[kTrip];
 #pragma unroll
     for (int k = 0; k < kTrip; ++k) { cur[k] = fetch(w0 + lane + k * nthreads); nx[k] = fetch(w0 + lane + (kTrip + k) * nthreads); }

@@ -2,7 +2,10 @@
     for lib in A B A B; do STAINLIB_HIP_LIB=$PWD/stainlib_amd/csrc/libstainlib_hip_$lib.so python tools/time_kernels.py; done
 prints one line: fused Macenko transform (512 x 1024^2), k_apply, per-phase transform at 128 tiles, StainAugmentor.pop and
 HED (1250 x 512^2), Vahadane transform (128 and 512 x 1024^2), and with `lab` the Lab family on 1250 x 512^2 (Reinhard
-transform, its statistics sweeps alone, LuminosityStandardizer, both plain conversions); milliseconds, median of `reps` launches."""
+transform, its statistics sweeps alone, LuminosityStandardizer, both plain conversions); with `sweeps` the kernels that run on
+csrc/sweep_pipeline.hpp and are not on the default route, each on 128 tiles of 1024^2 and of 512^2 (one-launch-per-phase fit:
+k_moments / k_select; sl_tile_moments; sl_slide_key_window for both key sets; the fused kernel with two_sweep = 1: fused_sweep1 /
+fused_select; the fused Vahadane fit: its fused_select) and the 1024-thread fused kernel on 192 tiles (schedule = 3); milliseconds, median of `reps` launches."""
 import os
 import sys
 import time
@@ -72,4 +75,18 @@ if "lab" in what:
     res["luminosity1250"] = med(lambda: engine.luminosity_standardize(t5, 95, out=o5, ws=ws))
     res["rgb2lab1250"] = med(lambda: engine.rgb_to_lab8(t5))
     res["lab2rgb1250"] = med(lambda: engine.lab8_to_rgb(t5))
+if "sweeps" in what:
+    V = np.linalg.qr(np.random.default_rng(3).normal(size=(3, 2)))[0].reshape(6)
+    Mn = (M[0] / M[0].norm(dim=1, keepdim=True)).cpu().numpy().reshape(6)
+    for tag, t in (("1024", rgb[:128]), ("512", rgb.view(-1, 512, 512, 3)[:128])):
+        res["fit_phase" + tag] = med(lambda: engine.macenko_fit(t, params=engine.make_params(schedule=1), ws=ws))
+        res["moments" + tag] = med(lambda: engine.tile_moments(t, ws=ws))
+        res["win_angle" + tag] = med(lambda: engine.slide_key_window(t, _ffi.KEYSET_ANGLE, V, (0x80000000, 0x80000000)))
+        res["win_conc" + tag] = med(lambda: engine.slide_key_window(t, _ffi.KEYSET_CONC, Mn, (0xBF800000, 0xBF800000)))   # keys around 1.0
+        res["fit_three" + tag] = med(lambda: engine.macenko_fit(t, params=engine.make_params(schedule=2, two_sweep=1), ws=ws))
+        res["vah_fit" + tag] = med(lambda: engine.vahadane_fit(t, params=engine.make_params(schedule=2, dl_tol=1e-6, dl_max_sweeps=100), ws=ws))
+    # the 1024-thread fused kernel (the default from 192 tiles of 1024^2 up to the CU count): its entry function is allocated around
+    # the out-of-line sweeps' register use
+    res["wide192"] = med(lambda: engine.macenko_transform(rgb[:192], Mt[0], mct[0], params=engine.make_params(schedule=3), out=out[:192], ws=ws))
+    res["wide_fit192"] = med(lambda: engine.macenko_fit(rgb[:192], params=engine.make_params(schedule=3, two_sweep=1), ws=ws))
 print(os.path.basename(_ffi.LIB_PATH), " ".join(f"{k} {v:.3f}" for k, v in res.items()))
