@@ -10,7 +10,7 @@
  *
  * Conventions
  *   - every data pointer is a DEVICE pointer (HBM), e.g. torch tensor.data_ptr();
- *     SlParams and SlTensorFormat are the only host structs (a few pooled-mode calls take small host arrays, named where
+ *     SlParams, SlTensorFormat and SlSeparateOut are the only host structs (a few pooled-mode calls take small host arrays, named where
  *     they are declared).
  *   - images: n tiles, each h x w x 3 interleaved RGB uint8, tiles contiguous
  *     (NHWC).  Stain matrices: row-major 2x3 double, row 0 = haematoxylin.
@@ -553,6 +553,39 @@ SL_API int sl_to_tensor(const uint8_t* rgb, void* out, int n, int h, int w, cons
  * converted in registers and the uint8 image is never written; equal to sl_to_tensor(sl_normalize_apply(...)) bit for bit.  A tile whose
  * fit failed (NaN M_src, maxC_src <= 0) is passed through as in sl_normalize_apply: its SOURCE bytes are converted. */
 SL_API int sl_normalize_apply_tensor(const uint8_t* rgb, void* out, int n, int h, int w, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, double lasso_lambda, const SlTensorFormat* fmt, void* stream);
+
+/* ---- stain separation (stainlib_amd/csrc/separate.hip; an extension: what torchstain's normalize(..., stains=True), staintools and
+ * HistomicsTK hand out beside the normalised image) ---------------------------------------------------------------------------------
+ * sl_normalize_apply's sweep with up to four outputs per pixel from ONE read of the tile and ONE lasso solve.  With c1, c2 the binary32
+ * concentrations of a pixel as sl_normalize_apply computes them under the tile's (M_src, maxC_src) -- carried scaled by 2^-k, k per
+ * tile -- and q[i][ch] = (float)(-log2(e) * ratio_i * M_tgt[i][ch] * 2^k), ratio_i = maxC_tgt[i] / maxC_src[i]:
+ *     norm      n x h x w x 3 uint8: the bytes of sl_normalize_apply, byte for byte
+ *     stain[i]  n x h x w x 3 uint8, i = 0 haematoxylin only, 1 eosin only: 255.0f * exp2f(c_i * q[i][ch]) through the cast of norm --
+ *               the bytes of sl_normalize_apply called with the OTHER row of M_tgt zeroed, wherever that call takes the same lasso
+ *               form (always when M_tgt has no negative entry or the source rows are negatively correlated; for the image of a row
+ *               that itself holds the negative entry)
+ *     conc      n x 2 x h x w elements of conc_dtype, planar, H plane first: c_i * (float)(ratio_i * 2^k), the normalised
+ *               concentration of normalizer.py:48, one binary32 multiply, converted round-to-nearest-even
+ * Without a target (M_tgt == NULL and maxC_tgt == NULL) every tile is reconstructed under its OWN stain matrix with ratio 1: norm is
+ * the tile's reconstruction, the stain images are its own H and E appearance, conc is the raw get_concentrations.
+ * A tile whose fit failed (NaN M_src, maxC_src <= 0): norm = its source bytes, both stain images 255 in every byte, conc +0.
+ * `conc` needs the alignment of its element type only; its stores are 16 bytes wide where it is 16-byte aligned and h w is a multiple
+ * of 4 (float32) or 8 (the half types) pixels and every uint8 pointer of the call is 4-byte aligned, element-wise otherwise.
+ * No workspace.  SlSeparateOut is a HOST struct; the pointers in it are DEVICE pointers. */
+typedef struct SlSeparateOut {
+    uint32_t struct_size;        /* sizeof(SlSeparateOut) of the caller's header: set by sl_default_separate_out, checked (SL_ERR_BADARG
+                                    on a mismatch) */
+    int32_t conc_dtype;          /* SL_DTYPE_F32 (default) / _F16 / _BF16; checked even when conc is NULL */
+    uint8_t* norm;               /* n x h x w x 3, or NULL */
+    uint8_t* stain[2];           /* H-only, E-only image, each n x h x w x 3, or NULL */
+    void* conc;                  /* n x 2 x h x w elements of conc_dtype, or NULL */
+} SlSeparateOut;
+/* all outputs NULL, float32 */
+SL_API void sl_default_separate_out(SlSeparateOut* o);
+/* SL_ERR_BADARG before anything is launched: a NULL rgb / M_src / maxC_src / outs; exactly one of M_tgt, maxC_tgt NULL; n, h or w <= 0
+ * or h w > 2^30; a struct_size mismatch; an unknown conc_dtype; no output requested; two outputs at one address or an output at rgb;
+ * conc not aligned to its element size. */
+SL_API int sl_stain_separate(const uint8_t* rgb, int n, int h, int w, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, double lasso_lambda, const SlSeparateOut* outs, void* stream);
 
 #ifdef __cplusplus
 }

@@ -3,6 +3,7 @@
 The export list mirrors stainlib/__init__.py:19-30.  ReinhardStainNormalizer and LuminosityStandardizer (SURVEY
 8f-3 / 8f-4) sit on OpenCV's 8-bit Lab conversions, restated in csrc/lab.hip: parity unpinned against cv2 itself.
 TensorFormat (an extension) turns the batched operators' uint8 results into model-ready float tensors.
+Separated (an extension) is what the normalizers' separate / separate_batch return: per-stain images and concentration maps.
 Importing the package does not need a GPU; calling anything numeric does, and fails loudly without the
 HIP library -- there is no CPU fallback.
 """
@@ -14,6 +15,7 @@ from .extraction.vahadane_stain_extractor import VahadaneStainExtractor  # noqa:
 from .normalization.normalizer import (ExtractiveStainNormalizer, MacenkoNormalizer,  # noqa: F401
                                        ReinhardStainNormalizer, VahadaneNormalizer)
 from .tensor_format import TensorFormat  # noqa: F401
+from .separated import Separated  # noqa: F401
 from .utils.stain_utils import LuminosityStandardizer  # noqa: F401
 from .utils.excepts import InvalidRangeError, TissueMaskException  # noqa: F401
 

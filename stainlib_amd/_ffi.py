@@ -66,6 +66,17 @@ class SlTensorFormat(C.Structure):
     ]
 
 
+class SlSeparateOut(C.Structure):
+    """The outputs of sl_stain_separate (a HOST struct; the pointers in it are DEVICE pointers, NULL = not wanted)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("conc_dtype", C.c_int32),
+        ("norm", C.c_void_p),
+        ("stain", C.c_void_p * 2),
+        ("conc", C.c_void_p),
+    ]
+
+
 DTYPE_F32, DTYPE_F16, DTYPE_BF16 = range(3)
 LAYOUT_NCHW, LAYOUT_NHWC = range(2)
 
@@ -155,6 +166,9 @@ _SIGNATURES = {
     "sl_default_tensor_format": (None, [C.POINTER(SlTensorFormat)]),
     "sl_to_tensor": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(SlTensorFormat), _P]),
     "sl_normalize_apply_tensor": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_double, C.POINTER(SlTensorFormat), _P]),
+    # stain separation (SlSeparateOut: a host struct of device pointers)
+    "sl_default_separate_out": (None, [C.POINTER(SlSeparateOut)]),
+    "sl_stain_separate": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_double, C.POINTER(SlSeparateOut), _P]),
 }
 POOL_STATE_DOUBLES, POOL_M, POOL_MAXC, POOL_STATUS, POOL_MISS = 64, 0, 6, 8, 9
 POOL2_STATE_DOUBLES, POOL2_HIST_WORDS, POOL2_WHY = 256, 2 * 8192 + 8 * 32, 33
@@ -198,6 +212,12 @@ def default_tensor_format() -> SlTensorFormat:
     f = SlTensorFormat()
     lib().sl_default_tensor_format(C.byref(f))
     return f
+
+
+def default_separate_out() -> SlSeparateOut:
+    o = SlSeparateOut()
+    lib().sl_default_separate_out(C.byref(o))
+    return o
 
 
 def default_params() -> SlParams:

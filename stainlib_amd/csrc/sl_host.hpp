@@ -51,6 +51,16 @@ inline bool aligned4(const void* p, long pixels_per_tile) {
     return ((uintptr_t)p & 3u) == 0 && (pixels_per_tile & 3) == 0;
 }
 
+inline size_t elem_bytes(int dtype) { return dtype == SL_DTYPE_F32 ? 4 : 2; }      // of an SL_DTYPE_*
+
+// The wide store path of the float outputs (tensor_out.hip, separate.hip) needs every tile's (NHWC) or every plane's (planar) first
+// element on a 16-byte boundary: the pointer itself and P elements (3 P for NHWC) a multiple of 16 bytes -- either way P a multiple
+// of the 4 (float32) or 8 (half types) pixels of a group.
+inline bool wide_ok(const void* out, long P, int dtype) {
+    const long px = 16 / (long)elem_bytes(dtype);
+    return ((uintptr_t)out & 15u) == 0 && P % px == 0;
+}
+
 // Launches k_aligned when `aligned` (aligned4 of every tile pointer the kernel reads or writes), else k_unaligned: the two
 // instantiations of one sweep kernel, with the same geometry and arguments.
 template <class K, class... Args>

@@ -28,15 +28,6 @@ TensorK tensor_k(const SlTensorFormat& f) {
     return k;
 }
 
-size_t elem_bytes(int dtype) { return dtype == SL_DTYPE_F32 ? 4 : 2; }
-
-// The wide store path needs every tile's (NHWC) or every plane's (NCHW) first element on a 16-byte boundary: the pointer itself and
-// P elements (3 P for NHWC) a multiple of 16 bytes -- either way P a multiple of the 4 (float32) or 8 (half types) pixels of a group.
-bool wide_ok(const void* out, long P, int dtype) {
-    const long px = 16 / (long)elem_bytes(dtype);
-    return ((uintptr_t)out & 15u) == 0 && P % px == 0;
-}
-
 // f(dtype tag, layout tag, aligned tag, wide tag) for the runtime format
 template <class F>
 void with_format(int dtype, int layout, bool aligned, bool wide, F&& f) {

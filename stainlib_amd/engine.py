@@ -11,6 +11,7 @@ import ctypes as C
 import torch
 
 from . import _ffi
+from .separated import Separated
 
 
 def _stream() -> int:
@@ -200,6 +201,81 @@ def normalize_apply_tensor(rgb, M_src, maxC_src, M_tgt, maxC_tgt, fmt, lasso_lam
     _call("sl_normalize_apply_tensor", _ptr(rgb), _ptr(out), n, h, w, _ptr(M_src), _ptr(maxC_src), _ptr(M_tgt), _ptr(maxC_tgt),
           float(lasso_lambda), C.byref(f))
     return out
+
+
+# ---- stain separation (sl_stain_separate; see SlSeparateOut in include/stainlib_hip.h) -------------------------------------------------
+
+def _separate_want(want, conc_dtype):
+    """The wanted outputs as a tuple of field names, checked (no device needed)."""
+    if isinstance(want, str):
+        want = (want,)
+    try:
+        want = tuple(want)
+    except TypeError:
+        raise ValueError("want must be a sequence of 'norm', 'h', 'e', 'conc'") from None
+    if not want or len(set(want)) != len(want) or any(not isinstance(k, str) or k not in Separated._fields for k in want):
+        raise ValueError(f"want must name at least one of {Separated._fields}, each once; got {want!r}")
+    if conc_dtype not in _TENSOR_DTYPES:
+        raise ValueError("conc_dtype must be torch.float32, torch.float16 or torch.bfloat16")
+    return want
+
+
+def _separate_out_fields(out, want, conc_dtype):
+    """What can be said about `out` without the tiles (no device needed): its form, and per field presence and dtype."""
+    if out is None:
+        return
+    if not (isinstance(out, tuple) and len(out) == 4):
+        raise ValueError("out must be an engine.Separated of caller buffers (None where the library allocates)")
+    for name, t in zip(Separated._fields, out):
+        if t is None:
+            continue
+        if name not in want:
+            raise ValueError(f"out.{name} is given but {name!r} is not in want")
+        dtype = conc_dtype if name == "conc" else torch.uint8
+        if not (isinstance(t, torch.Tensor) and t.dtype == dtype):
+            raise ValueError(f"out.{name} must be a {dtype} tensor")
+
+
+def _separate_out(out, want, n, h, w, conc_dtype, device):
+    """The four result tensors (None where not wanted): the caller's, checked, or fresh ones."""
+    res = []
+    for k, name in enumerate(Separated._fields):
+        shape, dtype = ((n, 2, h, w), conc_dtype) if name == "conc" else ((n, h, w, 3), torch.uint8)
+        t = out[k] if out is not None else None
+        if name not in want:
+            res.append(None)
+        elif t is None:
+            res.append(torch.empty(shape, dtype=dtype, device=device))
+        elif not (t.device == device and tuple(t.shape) == shape and t.is_contiguous()):
+            raise ValueError(f"out.{name} must be a contiguous {dtype} tensor of shape {shape} on {device}")
+        else:
+            res.append(t)
+    return Separated(*res)
+
+
+def stain_separate(rgb, M_src, maxC_src, M_tgt=None, maxC_tgt=None, lasso_lambda=0.01, want=("norm", "h", "e", "conc"),
+                   conc_dtype=torch.float32, out=None):
+    """normalize_apply's pass with up to four outputs from one read and one lasso solve per pixel (sl_stain_separate) -> Separated:
+    norm = normalize_apply's bytes; h / e = the image of one stain alone (normalize_apply with the other row of M_tgt zeroed);
+    conc = the normalised concentrations C * maxC_tgt / maxC_src as (N,2,H,W) planes of conc_dtype.
+    M_tgt=None (and maxC_tgt=None): no target -- every tile under its own M_src, conc = the raw get_concentrations."""
+    want = _separate_want(want, conc_dtype)
+    if (M_tgt is None) != (maxC_tgt is None):
+        raise ValueError("M_tgt and maxC_tgt go together: both, or neither (no target)")
+    _separate_out_fields(out, want, conc_dtype)
+    n, h, w = _check_tiles(rgb)
+    dev = rgb.device
+    res = _separate_out(out, want, n, h, w, conc_dtype, dev)
+    M_src = _f64(M_src, (n, 2, 3), dev)
+    maxC_src = _f64(maxC_src, (n, 2), dev)
+    if M_tgt is not None:
+        M_tgt = _f64(M_tgt, (2, 3), dev)
+        maxC_tgt = _f64(maxC_tgt, (2,), dev)
+    o = _ffi.default_separate_out()
+    o.conc_dtype = _TENSOR_DTYPES[conc_dtype]
+    o.norm, o.stain[0], o.stain[1], o.conc = (t.data_ptr() if t is not None else None for t in res)
+    _call("sl_stain_separate", _ptr(rgb), n, h, w, _ptr(M_src), _ptr(maxC_src), _ptr(M_tgt), _ptr(maxC_tgt), float(lasso_lambda), C.byref(o))
+    return res
 
 
 def _fit(fn_name, op, rgb, params, ws, with_sweeps=False):

@@ -168,6 +168,46 @@ class ExtractiveStainNormalizer(object):
             raise ValueError("_tensor_route must be 'fused' or 'convert'")
         return x, M, maxC, status
 
+    # -- stain separation (an extension: torchstain's normalize(..., stains=True), the concentration maps of staintools) ----
+    def separate_batch(self, tiles, want=("norm", "h", "e", "conc"), conc_dtype=None, normalize=True, ws=None):
+        """(N,H,W,3) uint8 device tensor -> (Separated, M_src, maxC_src, status): the per-tile fit, then ONE pass that writes what
+        ``want`` names -- norm (transform_batch's image), h / e (the haematoxylin-only / eosin-only image, (N,H,W,3) uint8) and conc
+        (the normalised concentrations, (N,2,H,W) planes of ``conc_dtype``: float32 by default, float16 or bfloat16).
+        ``normalize=False``: no target (no fit() needed) -- every tile under its own stain matrix, conc = the raw concentrations.
+        A tile whose status is non-zero: norm = the tile, h = e = white, conc = 0."""
+        import torch
+        from .. import engine
+        conc_dtype = torch.float32 if conc_dtype is None else conc_dtype
+        want = engine._separate_want(want, conc_dtype)
+        if normalize and not hasattr(self, "stain_matrix_target"):
+            raise ValueError("separate_batch(normalize=True) needs a fitted target: call fit() first, or pass normalize=False")
+        M, maxC, status = self._fit_tiles(tiles, ws=ws)
+        M_t, c_t = self._target_on(tiles.device) if normalize else (None, None)
+        sep = engine.stain_separate(tiles, M, maxC, M_t, c_t, want=want, conc_dtype=conc_dtype)
+        return sep, M, maxC, status
+
+    def separate(self, I, normalize=True):
+        """An image (RGB uint8) -> Separated of numpy arrays: norm (= transform(I)), h, e ((H,W,3) uint8) and conc ((2,H,W) float32)."""
+        assert is_uint8_image(I), _UINT8_MSG
+        from .. import engine
+        dev = _to_device(I)
+        if normalize:
+            M_t, c_t = self._target_on(dev.device)
+        else:
+            M_t = c_t = None
+        big = self._big_image_statistics(dev)
+        if big is not None:
+            sep = engine.stain_separate(dev, big[0][None], big[1][None], M_t, c_t)
+        else:
+            M, maxC, status = self._fit_tiles(dev)
+            st = int(status[0])
+            raise_for_status(st)
+            if st != 0:
+                warnings.warn("99th-percentile concentration of the source is zero; the reference divides by it",
+                              RuntimeWarning)
+            sep = engine.stain_separate(dev, M, maxC, M_t, c_t)
+        return engine.Separated(*(t[0].cpu().numpy() for t in sep))
+
     def state_dict(self):
         return {"method": self.method, "stain_matrix_target": np.array(self.stain_matrix_target),
                 "maxC_target": np.array(self.maxC_target)}
