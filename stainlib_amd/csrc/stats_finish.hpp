@@ -275,9 +275,20 @@ __device__ __forceinline__ void wg_pick2(const float* cand0, const float* cand1,
 
 // Both brackets of a selection stage: the one-pass path where the bracket covers the wanted ranks and its member list is
 // complete, the windowed / whole-tile paths of stage_order_stats otherwise.  lt[b] = pixels below bracket b (proven or counted).
-template <bool TWO_COLS, class TileKeyAt>
+// make_tile_key(b): the whole-tile key functor of bracket b (a few values captured BY VALUE), made only where the windowed / whole-tile
+// paths run, and those out of line: built beforehand, the key's two dozen constants stayed live across the one-pass path and went to
+// scratch there, and its copies for the out-of-line selection passes were scratch traffic in the caller's body.
+struct ColdStats { float xa, xb; int fallbacks; };
+template <class MakeTileKey>
+__device__ __noinline__ ColdStats stage_order_stats_cold(const float* cand, uint32_t n_in, uint32_t cap_list, int complete, float lo, float hi, long long lt, int P,
+                                                         MakeTileKey make_tile_key, int b, uint32_t n, long long k, SelScratch* S) {
+    ColdStats r{0.0f, 0.0f, 0};
+    stage_order_stats(cand, n_in, cap_list, complete != 0, lo, hi, lt, P, make_tile_key(b), n, k, r.xa, r.xb, r.fallbacks, *S);
+    return r;
+}
+template <class MakeTileKey>
 __device__ __forceinline__ void stage_pick2(const float* cand0, const float* cand1, const uint32_t* n_in, uint32_t cap_list, bool complete,
-                                            const float* lo, const float* hi, const long long* lt, int P, TileKeyAt tile_key_at, uint32_t n,
+                                            const float* lo, const float* hi, const long long* lt, int P, MakeTileKey make_tile_key, uint32_t n,
                                             const long long* k, const PickScale& ps, float* res /*[4]: xa0, xb0, xa1, xb1*/, int& fallbacks, SelScratch& S) {
     bool fast[2], has2[2];
     uint32_t krel[2];
@@ -297,8 +308,8 @@ __device__ __forceinline__ void stage_pick2(const float* cand0, const float* can
         if (done[b]) {
             if (!has2[b]) xb[b] = xa[b];
         } else {
-            if constexpr (TWO_COLS) tile_key_at.col = b;
-            stage_order_stats(b ? cand1 : cand0, n_in[b], cap_list, complete, lo[b], hi[b], lt[b], P, tile_key_at, n, k[b], xa[b], xb[b], fallbacks, S);
+            const ColdStats c = stage_order_stats_cold(b ? cand1 : cand0, n_in[b], cap_list, complete ? 1 : 0, lo[b], hi[b], lt[b], P, make_tile_key, b, n, k[b], &S);
+            xa[b] = c.xa; xb[b] = c.xb; fallbacks += c.fallbacks;
         }
         res[2 * b] = xa[b]; res[2 * b + 1] = xb[b];
     }

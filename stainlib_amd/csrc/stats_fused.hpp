@@ -103,6 +103,7 @@ __device__ __forceinline__ void fused_lds_origin(const FusedShared<NT>& sh) {
                   offsetof(FusedShared<NT>, S) == FusedLds<NT>::hist && offsetof(SelScratch, hist) == 0, "");
     if (lds_address(&sh) != 0u) __builtin_trap();
 }
+static_assert(sizeof(FusedShared<kFusedThreads>) <= 81920, "two 512-thread workgroups share a CU's 160 KB of LDS");
 
 // (the finish steps inlined into the kernel again: measured +3.7 %)
 #define SL_FINISH_ATTR __noinline__
@@ -426,18 +427,24 @@ __device__ SL_FINISH_ATTR int fused_finish2(FusedShared<NT>* shp, const uint8_t*
     // ---------------- finish 2: exact angular percentiles -> M  (see "Finish 2 of the fused kernel" above wg_refine_s)
     const uint32_t T = (uint32_t)sh.sum[0];
     long long k[2];
-    double gfrac[2];
-    percentile_pos((double)T, 100.0 - pct, k[0], gfrac[0]);
-    percentile_pos((double)T, pct, k[1], gfrac[1]);
+    {
+        double g;                                                 // (the fractions: taken again where M is made, not carried there)
+        percentile_pos((double)T, 100.0 - pct, k[0], g);
+        percentile_pos((double)T, pct, k[1], g);
+    }
     fin_tab_build(sh.tab);                                        // the row table's space: one-copy table + member staging
     const FinTab FT{FusedLds<NT>::tab};
     const uint32_t stage_lds = FusedLds<NT>::tab + kFinTabBytes + (uint32_t)wave * fin_stage_bytes(NT);
     const uint32_t stage_entries = fin_stage_bytes(NT) / 8u;      // two lists per wave
-    AngleTileKey tkey;
-    tkey.src = src; tkey.tab = FT.view(); tkey.ylimf = ylimf;
+    const auto tile_angle_key = [shp, src, ylimf](int) {          // (exact fallback: sh.Vf is the tile's for the whole step)
+        AngleTileKey tkey;
+        tkey.src = src; tkey.tab = FinTab{FusedLds<NT>::tab}.view(); tkey.ylimf = ylimf;
+        for (int i = 0; i < 6; ++i) tkey.V[i] = shp->Vf[i];
+        return tkey;
+    };
     WordAngleKey rkey;
     rkey.T = FT; rkey.ylimf = ylimf;
-    for (int i = 0; i < 6; ++i) { tkey.V[i] = sh.Vf[i]; rkey.V[i] = sh.Vf[i]; }
+    for (int i = 0; i < 6; ++i) rkey.V[i] = sh.Vf[i];
     const bool complete = sh.n_raw <= (uint32_t)cap_raw && sh.overflow == 0;
     const uint32_t n_raw = sh.n_raw < (uint32_t)cap_raw ? sh.n_raw : (uint32_t)cap_raw;
     // the list the angular pass reads: the cube sweep's own (every tissue pixel outside the plain cone), else the mixed one
@@ -467,14 +474,18 @@ __device__ SL_FINISH_ATTR int fused_finish2(FusedShared<NT>* shp, const uint8_t*
             }
         }
         float res[4];
-        stage_pick2<false>(cand0, cand1, ra.n_in, (uint32_t)cap_list, complete_a, los, his, lt, P, tkey, T, k, ra.ps, res, fallbacks, sh.S);
+        stage_pick2(cand0, cand1, ra.n_in, (uint32_t)cap_list, complete_a, los, his, lt, P, tile_angle_key, T, k, ra.ps, res, fallbacks, sh.S);
         if (tid == 0) { sh.res[0] = res[0]; sh.res[1] = res[1]; sh.res[2] = res[2]; sh.res[3] = res[3]; }
         __syncthreads();
     }
     SL_SUB(5);
     if (tid < 64) {
         double M[6];
-        stain_matrix_from_angles(sh.Vd, sh.res, gfrac, M, tid);
+        long long kd;
+        double g0, g1;
+        percentile_pos((double)T, 100.0 - pct, kd, g0);
+        percentile_pos((double)T, pct, kd, g1);
+        stain_matrix_from_angles(sh.Vd, sh.res, g0, g1, M, tid);
         if (tid == 0) {
             for (int i = 0; i < 6; ++i) sh.M[i] = M[i];
             if (stain_matrix_singular(M)) sh.status = SL_TILE_DEGENERATE_COV;
@@ -512,11 +523,14 @@ __device__ SL_FINISH_ATTR int fused_finish2(FusedShared<NT>* shp, const uint8_t*
         for (int col = 0; col < 2; ++col)
             covered = covered & (kc >= clt[col]) & (kc2 < clt[col] + (long long)rc.n_in[col]) & (rc.n_in[col] <= (uint32_t)cap_list);
         if (covered) {
-            ConcTileKey ctk;
-            ctk.src = src; ctk.tab = FT.view(); ctk.L = sh.L; ctk.col = 0;
+            const auto tile_conc_key = [shp, src](int col) {     // (exact fallback: sh.L is what the M step left)
+                ConcTileKey ctk;
+                ctk.src = src; ctk.tab = FinTab{FusedLds<NT>::tab}.view(); ctk.L = shp->L; ctk.col = col;
+                return ctk;
+            };
             const long long kk[2] = {kc, kc};
             float res[4];
-            stage_pick2<true>(cand0, cand1, rc.n_in, (uint32_t)cap_list, true, cl, chh, clt, P, ctk, (uint32_t)P, kk, rc.ps, res, fallbacks, sh.S);
+            stage_pick2(cand0, cand1, rc.n_in, (uint32_t)cap_list, true, cl, chh, clt, P, tile_conc_key, (uint32_t)P, kk, rc.ps, res, fallbacks, sh.S);
             if (tid == 0) {
                 sh.maxC[0] = np_lerp((double)res[0], (double)res[1], gc);   // normalizer.py:36,47
                 sh.maxC[1] = np_lerp((double)res[2], (double)res[3], gc);
@@ -536,18 +550,19 @@ __device__ SL_FINISH_ATTR int fused_finish2(FusedShared<NT>* shp, const uint8_t*
 // ------------------------------------------------------------------------------------------
 // two-sweep schedule (stats_twosweep.hpp): phase 0 and the merged sweep, out of line like every other phase
 // ------------------------------------------------------------------------------------------
-// Phase 0: the cluster sample of the tile (into registers, and into samp[0 .. n_lines * kClusterPx) for the routes that fall back),
+// Phase 0: the cluster sample of the tile (into samp[0 .. n_lines * kClusterPx): read back by the passes below, SampleRows, and by the routes
+// that fall back),
 // its eigenvectors, the angular brackets under them, the two half-spaces of the plain cone, the box of stain matrices with its tilts, the
 // concentration brackets under the box centre and the colour-cube mask of the merged sweep (S.hist).  Leaves sh.ts (ts.ok: sweep 1
 // collects candidates), sh.mk, and sh.use_cube (share).
 // Every workgroup of a launch starts here at the same moment and nothing streams meanwhile, so this phase is written for LATENCY: the
-// sample words stay in registers (thread t holds entries t, t + NT, ...), each bracket set costs one evaluation of the keys into a
+// sample words are a thread's own (thread t holds entries t, t + NT, ...: kBrkBatch of them at a time, the next batch in flight -- all 32
+// in registers across the whole phase put it at 128 VGPRs with ~108 spills in its body), each bracket set costs one evaluation of the keys into a
 // fixed-range histogram and one wave_locate per rank (the register-resident windowed search of finish 1 needs four passes and three
 // times the barriers: 33-45 us per set where this takes ~15; its brackets are tighter by a histogram bin -- 0.002 of pseudo-angle,
 // ~1 % of a concentration -- which costs this schedule a few hundred candidates), and the fourth moments ride in the angle pass.
 // Phase 0, one thread: the sample's eigenvectors, the plane's normal and the Gaussian tilt bound from sh.sum (out of line: the binary64
-// Jacobi sweep wants three dozen registers of its own while every thread of fused_phase0 holds its 32 sample words -- inlined, 28 of
-// them went to scratch around it; out of line they sit in callee-saved registers).
+// Jacobi sweep wants three dozen registers of its own; inlined, it pushed what fused_phase0 holds into scratch around it).
 template <int NT>
 __device__ __noinline__ void phase0_estimate(FusedShared<NT>* shp, int mode_) {
     FusedShared<NT>& sh = *shp;
@@ -613,6 +628,33 @@ __device__ __noinline__ void phase0_cone_and_box(FusedShared<NT>* shp, float hi0
     ts_box(sh.ts.Vd, sh.ts.nd, sh.ts.tau, sh.box, lam, tid, sh.mk);
 }
 
+// Phase 0 reads its sample back in batches of kBrkBatch words per thread (thread t: entries t, t + NT, ...; row j0 + u of the batch is entry
+// (j0 + u) NT + t, clamped to the last entry like the gather) from the copy the gather wrote for the fallback routes: every thread reads
+// the words it wrote itself, the next batch is in flight while the current one is evaluated.  Held in registers across the whole phase
+// (32 per lane) the sample cost every sub-step scratch round trips; phase 0 runs with nothing to hide them behind.
+template <int NT>
+struct SampleRows {
+    const uint32_t* samp;
+    int n_sample, tid;
+    uint32_t nx[kBrkBatch];
+    // (the thread's index behind an empty asm, as lane_id() of k_fused: from one `tid` the compiler shares the 32 row addresses between
+    //  the passes and parks them in scratch from one to the next)
+    __device__ __forceinline__ SampleRows(const uint32_t* s, int n, int t) : samp(s), n_sample(n), tid(t) {
+        asm volatile("" : "+v"(tid));
+        load(0);
+    }
+    __device__ __forceinline__ void load(int j0) {
+#pragma unroll
+        for (int u = 0; u < kBrkBatch; ++u) nx[u] = as_global(samp)[min((j0 + u) * NT + tid, n_sample - 1)];
+    }
+    // the batch of rows j0 .. j0 + kBrkBatch - 1 into w; starts the loads of the batch behind it
+    __device__ __forceinline__ void next(uint32_t* w, int j0) {
+#pragma unroll
+        for (int u = 0; u < kBrkBatch; ++u) w[u] = nx[u];
+        if (j0 + kBrkBatch < kMaxSample / NT) load(j0 + kBrkBatch);
+    }
+};
+
 constexpr int kP0Bins = 1024;            // angle keys: pseudo-angle [-1, 1) in 1024 bins; concentrations: 512 bins per stain of c / (c + 1)
 template <int NT>
 __device__ SL_FINISH_ATTR void fused_phase0(FusedShared<NT>* shp, const uint8_t* src_, uint32_t* samp_, int P_, int n_lines_, float ylimf_, double pct_, double lam_,
@@ -633,8 +675,7 @@ __device__ SL_FINISH_ATTR void fused_phase0(FusedShared<NT>* shp, const uint8_t*
     SL_SUB(0);
     if (tid == 0) { sh.ts.ok = 0; sh.ts.why = kTsNoEstimate; sh.mk.ok = 0; sh.use_cube = 0; }
     const TabView tab = view_of_b(sh.tab);
-    // ---------------- the sample: gathered into registers (8 loads in flight), written out for the fallback routes, summed on the way
-    uint32_t w[KPT];
+    // ---------------- the sample: gathered kBrkBatch loads at a time, written out (for the passes below and the fallback routes), summed on the way
     Moments mo;
     BurstMoments bm;                                              // (binary32 sums of a thread's <= 32 entries: the estimate needs no more)
     double cnt = 0.0;
@@ -642,18 +683,19 @@ __device__ SL_FINISH_ATTR void fused_phase0(FusedShared<NT>* shp, const uint8_t*
         const uint32_t nl = (uint32_t)(((3ll * P) >> 7) < 1 ? 1 : ((3ll * P) >> 7));
         const uint32_t wl = nl / (uint32_t)n_lines;                // lines per stratum (>= 1)
 #pragma unroll
-        for (int j0 = 0; j0 < KPT; j0 += 8) {
+        for (int j0 = 0; j0 < KPT; j0 += kBrkBatch) {
+            uint32_t w[kBrkBatch];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) {
+            for (int u = 0; u < kBrkBatch; ++u) {
                 const int b = min((j0 + u) * NT + tid, n_sample - 1);      // (clamped, never predicated)
-                w[j0 + u] = cluster_word(src, P, wl, (uint32_t)b);
+                w[u] = cluster_word(src, P, wl, (uint32_t)b);
             }
 #pragma unroll
-            for (int u = 0; u < 8; ++u) {
+            for (int u = 0; u < kBrkBatch; ++u) {
                 const int b = (j0 + u) * NT + tid;
                 if (b < n_sample) {
-                    as_global(samp)[b] = w[j0 + u];
-                    const uint32_t r = w[j0 + u] & 255u, g = (w[j0 + u] >> 8) & 255u, bl = (w[j0 + u] >> 16) & 255u;
+                    as_global(samp)[b] = w[u];
+                    const uint32_t r = w[u] & 255u, g = (w[u] >> 8) & 255u, bl = (w[u] >> 16) & 255u;
                     if (is_tissue_f(tab.gam(r), tab.gam(g), tab.gam(bl), ylimf)) {
                         bm.add(tab.odf(r), tab.odf(g), tab.odf(bl));
                         cnt += 1.0;
@@ -696,21 +738,27 @@ __device__ SL_FINISH_ATTR void fused_phase0(FusedShared<NT>* shp, const uint8_t*
         for (int c = 0; c < 3; ++c) nf[c] = sh.ts.fn[c];
         const float mx = sh.res[1], my = sh.res[2], mz = sh.res[3];
         float q1 = 0.0f, q2 = 0.0f;
+        SampleRows<NT> rows(samp, n_sample, tid);
 #pragma unroll
-        for (int j = 0; j < KPT; ++j) {
-            const int b = j * NT + tid;
-            const uint32_t r = w[j] & 255u, g = (w[j] >> 8) & 255u, bl = (w[j] >> 16) & 255u;
-            const float ox = tab.odf(r), oy = tab.odf(g), oz = tab.odf(bl);
-            const bool tissue = (b < n_sample) & is_tissue_f(tab.gam(r), tab.gam(g), tab.gam(bl), ylimf);
-            if (tissue) {
-                const float key = angle_key(V, ox, oy, oz);
-                const int bin = min(kP0Bins - 1, max(0, (int)((key + 1.0f) * (0.5f * kP0Bins))));
-                atomicAdd(&sh.S.hist[bin], 1u);
-                const float dx = ox - mx, dy = oy - my, dz = oz - mz;
-                const float a1 = fmaf(V[4], dz, fmaf(V[2], dy, V[0] * dx)), a2 = fmaf(V[5], dz, fmaf(V[3], dy, V[1] * dx));
-                const float a3 = fmaf(nf[2], dz, fmaf(nf[1], dy, nf[0] * dx));
-                q1 = fmaf(a1 * a3, a1 * a3, q1);
-                q2 = fmaf(a2 * a3, a2 * a3, q2);
+        for (int j0 = 0; j0 < KPT; j0 += kBrkBatch) {
+            uint32_t w[kBrkBatch];
+            rows.next(w, j0);
+#pragma unroll
+            for (int u = 0; u < kBrkBatch; ++u) {
+                const int b = (j0 + u) * NT + tid;
+                const uint32_t r = w[u] & 255u, g = (w[u] >> 8) & 255u, bl = (w[u] >> 16) & 255u;
+                const float ox = tab.odf(r), oy = tab.odf(g), oz = tab.odf(bl);
+                const bool tissue = (b < n_sample) & is_tissue_f(tab.gam(r), tab.gam(g), tab.gam(bl), ylimf);
+                if (tissue) {
+                    const float key = angle_key(V, ox, oy, oz);
+                    const int bin = min(kP0Bins - 1, max(0, (int)((key + 1.0f) * (0.5f * kP0Bins))));
+                    atomicAdd(&sh.S.hist[bin], 1u);
+                    const float dx = ox - mx, dy = oy - my, dz = oz - mz;
+                    const float a1 = fmaf(V[4], dz, fmaf(V[2], dy, V[0] * dx)), a2 = fmaf(V[5], dz, fmaf(V[3], dy, V[1] * dx));
+                    const float a3 = fmaf(nf[2], dz, fmaf(nf[1], dy, nf[0] * dx));
+                    q1 = fmaf(a1 * a3, a1 * a3, q1);
+                    q2 = fmaf(a2 * a3, a2 * a3, q2);
+                }
             }
         }
         double d1 = wave_sum((double)q1), d2 = wave_sum((double)q2);
@@ -779,20 +827,26 @@ __device__ SL_FINISH_ATTR void fused_phase0(FusedShared<NT>* shp, const uint8_t*
     if (sh.mk.ok) {                                               // block-uniform
         LassoK L = sh.mk.Lc;
         uint32_t nz1 = 0, nz2 = 0;                                // wave-uniform
+        SampleRows<NT> rows(samp, n_sample, tid);
 #pragma unroll
-        for (int j = 0; j < KPT; ++j) {
-            const int b = j * NT + tid;
-            float c1, c2;
-            lasso2(L, tab.odf(w[j] & 255u), tab.odf((w[j] >> 8) & 255u), tab.odf((w[j] >> 16) & 255u), c1, c2);
-            const int b1 = min(511, max(0, (int)(512.0f * c1 * __builtin_amdgcn_rcpf(c1 + 1.0f))));
-            const int b2 = min(511, max(0, (int)(512.0f * c2 * __builtin_amdgcn_rcpf(c2 + 1.0f))));
-            // (background pixels all have concentration 0: thousands of atomics on ONE bin took most of this step -- entries of bin 0 are
-            //  counted off the ballot instead, one add per wave and row)
-            const bool in = b < n_sample;
-            const unsigned long long z1 = __builtin_amdgcn_ballot_w64(in & (b1 == 0)), z2 = __builtin_amdgcn_ballot_w64(in & (b2 == 0));
-            if (in & (b1 != 0)) atomicAdd(&sh.S.hist[b1], 1u);
-            if (in & (b2 != 0)) atomicAdd(&sh.S.hist[512 + b2], 1u);
-            nz1 += (uint32_t)__popcll(z1); nz2 += (uint32_t)__popcll(z2);
+        for (int j0 = 0; j0 < KPT; j0 += kBrkBatch) {
+            uint32_t w[kBrkBatch];
+            rows.next(w, j0);
+#pragma unroll
+            for (int u = 0; u < kBrkBatch; ++u) {
+                const int b = (j0 + u) * NT + tid;
+                float c1, c2;
+                lasso2(L, tab.odf(w[u] & 255u), tab.odf((w[u] >> 8) & 255u), tab.odf((w[u] >> 16) & 255u), c1, c2);
+                const int b1 = min(511, max(0, (int)(512.0f * c1 * __builtin_amdgcn_rcpf(c1 + 1.0f))));
+                const int b2 = min(511, max(0, (int)(512.0f * c2 * __builtin_amdgcn_rcpf(c2 + 1.0f))));
+                // (background pixels all have concentration 0: thousands of atomics on ONE bin took most of this step -- entries of bin 0
+                //  are counted off the ballot instead, one add per wave and row)
+                const bool in = b < n_sample;
+                const unsigned long long z1 = __builtin_amdgcn_ballot_w64(in & (b1 == 0)), z2 = __builtin_amdgcn_ballot_w64(in & (b2 == 0));
+                if (in & (b1 != 0)) atomicAdd(&sh.S.hist[b1], 1u);
+                if (in & (b2 != 0)) atomicAdd(&sh.S.hist[512 + b2], 1u);
+                nz1 += (uint32_t)__popcll(z1); nz2 += (uint32_t)__popcll(z2);
+            }
         }
         if (lane == 0) { if (nz1) atomicAdd(&sh.S.hist[0], nz1); if (nz2) atomicAdd(&sh.S.hist[512], nz2); }
         __syncthreads();
@@ -869,12 +923,12 @@ __device__ SL_FINISH_ATTR void fused_phase0(FusedShared<NT>* shp, const uint8_t*
         const TsCubeConsts cc = ts_cube_tables(view_of_b(sh.tab), sh.ts, ctab, tid);
         if (tid == 0) sh.S.misc[33] = 0;
         __syncthreads();
-        // the share of the sample in ambiguous cells, from two of the register rows (1/16 of the entries)
+        // the share of the sample in ambiguous cells, from two of the thread's rows (1/16 of the entries)
         uint32_t amb = 0, seen = 0;
 #pragma unroll
         for (int j = 0; j < KPT; j += KPT / 2) {
             if (j * NT + tid < n_sample) {
-                amb += ts_cell_plain(ctab, cc, ylimf, w[j]) ? 0u : 1u;
+                amb += ts_cell_plain(ctab, cc, ylimf, as_global(samp)[j * NT + tid]) ? 0u : 1u;
                 ++seen;
             }
         }

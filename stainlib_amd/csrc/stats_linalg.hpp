@@ -103,10 +103,11 @@ __device__ __forceinline__ bool stain_matrix_singular(const double* M) {
 // pseudo-angle order statistics -> stain matrix (macenko_stain_extractor.py:33-44).  Called by a whole wave (the result is
 // valid in every lane): the four arctan2 run in lanes 0-3 at once and the two sincos in lanes 0-1 -- this one-lane chain
 // of binary64 library calls was 31 us of every tile's finish step; the same calls on the same arguments, bit for bit.
-__device__ __forceinline__ void stain_matrix_from_angles(const double* Vd, const float* xs /*[4]*/, const double* gfrac, double* M, int lane) {
+// (g0, g1: the interpolation fractions of minPhi and maxPhi, as two values: an array of them is indexed by the lane and lives in scratch)
+__device__ __forceinline__ void stain_matrix_from_angles(const double* Vd, const float* xs /*[4]*/, double g0, double g1, double* M, int lane) {
     const double ang = angle_of_pseudo((double)xs[lane & 3]);
     const int pair = (lane & 1) * 2;                      // even lanes: minPhi (xs[0], xs[1]); odd lanes: maxPhi (xs[2], xs[3])
-    const double phi = np_lerp(__shfl(ang, pair, 64), __shfl(ang, pair + 1, 64), (lane & 1) ? gfrac[1] : gfrac[0]);
+    const double phi = np_lerp(__shfl(ang, pair, 64), __shfl(ang, pair + 1, 64), (lane & 1) ? g1 : g0);
     double s, c;
     sincos(phi, &s, &c);
     const double s1 = __shfl(s, 0, 64), c1 = __shfl(c, 0, 64), s2 = __shfl(s, 1, 64), c2 = __shfl(c, 1, 64);
@@ -124,6 +125,9 @@ __device__ __forceinline__ void stain_matrix_from_angles(const double* Vd, const
     const double ne = sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
 #pragma unroll
     for (int c = 0; c < 3; ++c) { M[c] = h[c] / nh; M[3 + c] = e[c] / ne; }   // :44
+}
+__device__ __forceinline__ void stain_matrix_from_angles(const double* Vd, const float* xs /*[4]*/, const double* gfrac, double* M, int lane) {
+    stain_matrix_from_angles(Vd, xs, gfrac[0], gfrac[1], M, lane);
 }
 
 // ------------------------------------------------------------------------------------------
