@@ -587,6 +587,32 @@ SL_API void sl_default_separate_out(SlSeparateOut* o);
  * conc not aligned to its element size. */
 SL_API int sl_stain_separate(const uint8_t* rgb, int n, int h, int w, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, double lasso_lambda, const SlSeparateOut* outs, void* stream);
 
+/* ---- stain jitter in the apply pass (stainlib_amd/csrc/jitter.hip; an extension: a training loader normalises, normalization/normalizer.py:46-50,
+ * and then perturbs the stains, augmentation/augmenter.py:428-447 -- which re-fits the NORMALISED image to learn what the apply pass already
+ * holds: after normalisation the stain basis of every tile is the target's and its concentrations are C * maxC_tgt / maxC_src) ---------------
+ * sl_normalize_apply's sweep with StainAugmentor.pop's affine map on the concentrations, ONE pass: 3 B/px read, the uint8 image or the
+ * model-ready tensor written.  Per tile t, with K the constants sl_normalize_apply builds from (M_src[t], maxC_src[t]) and (M_tgt, maxC_tgt),
+ * 2^k its per-tile scale, ratio_i = maxC_tgt[i] / maxC_src[t][i], and c1, c2 the binary32 concentrations of a pixel (carried scaled by 2^-k; the
+ * lasso form is chosen by the sign of the source rows' correlation alone, as in sl_stain_augment):
+ *     al_i = (float)alpha_i,  be_i = (float)(beta_i / ratio_i * 2^-k)
+ *     c_i' = fmaf(c_i, al_i, be_i) on tissue pixels (all pixels when augment_background), else c_i
+ *            -- alpha and beta act on the NORMALISED concentration c_i ratio_i, in the target's units: the same beta means the same on every tile
+ *     value = 255.0f * exp2(fmaf(c1', q[0][ch], c2' * q[1][ch])),  q[i][ch] = (float)(-log2(e) * ratio_i * M_tgt[i][ch] * 2^k)
+ *     byte  = the SATURATING truncation, np.clip(., 0, 255).astype(uint8) of augmenter.py:447 -- never modulo 256
+ * "Tissue" is the luminosity test of the SOURCE pixel under params->luminosity_threshold (utils/stain_utils.py:32-48), as in sl_stain_augment.
+ * Without a target (M_tgt == NULL and maxC_tgt == NULL) every tile is perturbed under its OWN stain matrix with ratio exactly 1: the bytes of
+ * sl_stain_augment, byte for byte (StainAugmentor.pop's definition).  With alpha = 1 and beta = 0 the bytes are sl_normalize_apply's wherever
+ * its values stay in [0, 255] (M_tgt without a negative entry).
+ *   alpha_beta  n x 4 double (device): alpha0, beta0, alpha1, beta1 per tile (the reference's draw order, augmenter.py:435-437)
+ *   params      NULL (defaults) or an SlParams: lasso_lambda and luminosity_threshold are read
+ *   fmt         NULL: out is the n x h x w x 3 uint8 image.  Otherwise out is the tensor of sl_normalize_apply_tensor in that format, equal to
+ *               sl_to_tensor of the uint8 result bit for bit
+ * A tile whose fit failed (NaN M_src, maxC_src <= 0) is passed through: its source bytes, converted when a format is given.
+ * SL_ERR_BADARG before anything is launched: a NULL rgb / out / M_src / maxC_src / alpha_beta; exactly one of M_tgt, maxC_tgt NULL; n, h or
+ * w <= 0 or h w > 2^30; an SlParams of another struct_size; a format sl_to_tensor refuses (struct_size, dtype, layout, a non-finite value,
+ * std <= 0).  out == rgb is not supported.  No workspace; capture-safe like the rest (no allocation, no synchronisation, no memset). */
+SL_API int sl_normalize_jitter(const uint8_t* rgb, void* out, int n, int h, int w, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, const double* alpha_beta, int augment_background, const SlParams* params, const SlTensorFormat* fmt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

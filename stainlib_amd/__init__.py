@@ -3,13 +3,14 @@
 The export list mirrors stainlib/__init__.py:19-30.  ReinhardStainNormalizer and LuminosityStandardizer (SURVEY
 8f-3 / 8f-4) sit on OpenCV's 8-bit Lab conversions, restated in csrc/lab.hip: parity unpinned against cv2 itself.
 TensorFormat (an extension) turns the batched operators' uint8 results into model-ready float tensors.
+StainJitter (an extension) draws the per-tile (alpha, beta) of the augment_batch methods: stain jitter inside the apply pass.
 Separated (an extension) is what the normalizers' separate / separate_batch return: per-stain images and concentration maps.
 Importing the package does not need a GPU; calling anything numeric does, and fails loudly without the
 HIP library -- there is no CPU fallback.
 """
 from . import _ffi  # noqa: F401
 from .augmentation.augmenter import (HedLightColorAugmenter, HedLighterColorAugmenter,  # noqa: F401
-                                     HedStrongColorAugmenter, StainAugmentor, GrayscaleAugmentor)
+                                     HedStrongColorAugmenter, StainAugmentor, GrayscaleAugmentor, StainJitter)
 from .extraction.macenko_stain_extractor import MacenkoStainExtractor  # noqa: F401
 from .extraction.vahadane_stain_extractor import VahadaneStainExtractor  # noqa: F401
 from .normalization.normalizer import (ExtractiveStainNormalizer, MacenkoNormalizer,  # noqa: F401

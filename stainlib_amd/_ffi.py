@@ -169,6 +169,9 @@ _SIGNATURES = {
     # stain separation (SlSeparateOut: a host struct of device pointers)
     "sl_default_separate_out": (None, [C.POINTER(SlSeparateOut)]),
     "sl_stain_separate": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_double, C.POINTER(SlSeparateOut), _P]),
+    # stain jitter in the apply pass (SlParams and SlTensorFormat: host structs, either may be NULL)
+    "sl_normalize_jitter": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, C.POINTER(SlParams),
+                                      C.POINTER(SlTensorFormat), _P]),
 }
 POOL_STATE_DOUBLES, POOL_M, POOL_MAXC, POOL_STATUS, POOL_MISS = 64, 0, 6, 8, 9
 POOL2_STATE_DOUBLES, POOL2_HIST_WORDS, POOL2_WHY = 256, 2 * 8192 + 8 * 32, 33

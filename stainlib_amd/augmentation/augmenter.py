@@ -4,7 +4,8 @@ Public behaviour kept from the reference: class names, ``keyword``/``shapes``, t
 users peek at (``_sigmas``, ``_biases``, ``_sigma_ranges``, ``_bias_ranges``, ``_cutoff_range``), the
 range validation and its ``InvalidRangeError`` titles, the order in which ``randomize()`` / ``pop()``
 consume the GLOBAL ``np.random`` stream, and the "un-randomized augmenter applies the lower bounds"
-quirk (augmenter.py:194-198, 246-250).  The arithmetic is ``sl_hed_augment`` / ``sl_stain_augment``.
+quirk (augmenter.py:194-198, 246-250).  The arithmetic is ``sl_hed_augment`` / ``sl_stain_augment``
+(``sl_normalize_jitter`` for the batched ``StainAugmentor.augment_batch``).
 """
 from __future__ import annotations
 
@@ -200,6 +201,7 @@ class StainAugmentor(object):
             self.extractor = VahadaneStainExtractor
         else:
             raise Exception('Method not recognized.')                  # augmenter.py:411
+        self._method = name
         self.sigma1 = sigma1
         self.sigma2 = sigma2
         self.augment_background = augment_background
@@ -245,6 +247,50 @@ class StainAugmentor(object):
         from .. import engine
         out = engine.stain_augment(self._dev, self.stain_matrix[None], [alpha_beta], self.augment_background)
         return out[0].cpu().numpy()
+
+    def augment_batch(self, tiles, alpha_beta=None, tensor_format=None):
+        """Batched extension: (N,H,W,3) uint8 device tensor -> (out, M, maxC, status) device tensors: every tile perturbed under its OWN
+        stain matrix (this augmentor's extractor, fitted per tile) -- n fit() / pop() pairs in one fit and ONE pass, nothing through the
+        host.  alpha_beta: (N, 4) = alpha0, beta0, alpha1, beta1 per tile; by default drawn from the global numpy stream exactly as N
+        successive pop() calls would (StainJitter.draw).  A tile whose status is non-zero comes back unchanged.
+        ``tensor_format``: a ``stainlib_amd.TensorFormat``; `out` is then the (N,3,H,W) tensor in that format.
+        fit() / pop() are untouched by it."""
+        from .. import engine
+        jitter = StainJitter(self.sigma1, self.sigma2, self.augment_background)
+        engine._jitter_args(None, None, alpha_beta if alpha_beta is not None else np.empty((0, 4)), None, tensor_format, None)
+        n = engine._check_tiles(tiles)[0]
+        if self._method == "macenko":
+            M, maxC, status = engine.macenko_fit(tiles)
+        else:
+            M, maxC, status, _ = engine.vahadane_fit(tiles)
+        if alpha_beta is None:
+            alpha_beta = jitter.draw(n)
+        out = engine.normalize_jitter(tiles, M, maxC, None, None, alpha_beta, self.augment_background, fmt=tensor_format)
+        return out, M, maxC, status
+
+
+class StainJitter(object):
+    """The draws of StainAugmentor.pop (augmenter.py:435-437) for a batch: what engine.normalize_jitter and the augment_batch methods
+    take as ``alpha_beta``.  alpha_i ~ U(1 - sigma1, 1 + sigma1) scales, beta_i ~ U(-sigma2, sigma2) shifts the concentration of stain i
+    (0 haematoxylin, 1 eosin)."""
+
+    def __init__(self, sigma1=0.2, sigma2=0.2, augment_background=False):
+        self.sigma1 = sigma1
+        self.sigma2 = sigma2
+        self.augment_background = augment_background
+
+    def draw(self, n):
+        """(n, 4) float64: alpha0, beta0, alpha1, beta1 per tile, from the GLOBAL numpy stream in the order of n successive
+        StainAugmentor.pop() calls (the convention of HedColorAugmenter.randomize_batch)."""
+        n = int(n)
+        if n < 0:
+            raise ValueError("n must be >= 0")
+        ab = np.empty((n, 4), dtype=np.float64)
+        for t in range(n):
+            for i in range(2):
+                ab[t, 2 * i] = np.random.uniform(1 - self.sigma1, 1 + self.sigma1)
+                ab[t, 2 * i + 1] = np.random.uniform(-self.sigma2, self.sigma2)
+        return ab
 
 
 class GrayscaleAugmentor(object):

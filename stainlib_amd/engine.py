@@ -278,6 +278,70 @@ def stain_separate(rgb, M_src, maxC_src, M_tgt=None, maxC_tgt=None, lasso_lambda
     return res
 
 
+# ---- stain jitter in the apply pass (sl_normalize_jitter; see include/stainlib_hip.h) ---------------------------------------------------
+
+def _jitter_args(M_tgt, maxC_tgt, alpha_beta, params, fmt, out):
+    """What can be said about a normalize_jitter call without the tiles (no device needed)."""
+    from .tensor_format import TensorFormat
+    if (M_tgt is None) != (maxC_tgt is None):
+        raise ValueError("M_tgt and maxC_tgt go together: both, or neither (no target)")
+    if alpha_beta is None:
+        raise ValueError("alpha_beta must hold (alpha0, beta0, alpha1, beta1) per tile: an (N, 4) array (StainJitter.draw)")
+    if not isinstance(alpha_beta, torch.Tensor):
+        import numpy as np
+        try:
+            shape = np.asarray(alpha_beta, dtype=np.float64).shape
+        except (TypeError, ValueError):
+            raise ValueError("alpha_beta must hold (alpha0, beta0, alpha1, beta1) per tile: an (N, 4) array") from None
+    else:
+        shape = tuple(alpha_beta.shape)
+    if len(shape) != 2 or shape[1] != 4:
+        raise ValueError(f"alpha_beta must hold (alpha0, beta0, alpha1, beta1) per tile: an (N, 4) array, not one of shape {shape}")
+    if params is not None and not isinstance(params, _ffi.SlParams):
+        raise ValueError("params must be an SlParams (engine.make_params) or None")
+    if fmt is not None and not isinstance(fmt, TensorFormat):
+        raise ValueError("fmt must be a stainlib_amd.TensorFormat or None (the uint8 image)")
+    if out is not None:
+        dtype = fmt.dtype if fmt is not None else torch.uint8
+        if not (isinstance(out, torch.Tensor) and out.dtype == dtype):
+            raise ValueError(f"out must be a {dtype} tensor")
+    return shape[0]
+
+
+def normalize_jitter(rgb, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, augment_background=False, params=None, fmt=None, out=None):
+    """normalize_apply and StainAugmentor.pop's perturbation in ONE pass (sl_normalize_jitter): per tile C_i * alpha_i + beta_i on the
+    NORMALISED concentrations C * maxC_tgt / maxC_src of tissue pixels (all pixels with augment_background), reconstructed under the
+    target, clipped.  alpha_beta: (N, 4) = alpha0, beta0, alpha1, beta1 per tile (StainJitter.draw).
+    M_tgt=None (and maxC_tgt=None): no target -- every tile under its own M_src: stain_augment's bytes.
+    fmt: a stainlib_amd.TensorFormat -> the (N,3,H,W) tensor, bit for bit fmt.convert of the uint8 result; None -> (N,H,W,3) uint8.
+    params: lasso_lambda and luminosity_threshold are read."""
+    n_ab = _jitter_args(M_tgt, maxC_tgt, alpha_beta, params, fmt, out)
+    n, h, w = _check_tiles(rgb)
+    if n_ab != n:
+        raise ValueError(f"alpha_beta has {n_ab} rows for {n} tiles")
+    dev = rgb.device
+    M_src = _f64(M_src, (n, 2, 3), dev)
+    maxC_src = _f64(maxC_src, (n, 2), dev)
+    if M_tgt is not None:
+        M_tgt = _f64(M_tgt, (2, 3), dev)
+        maxC_tgt = _f64(maxC_tgt, (2,), dev)
+    ab = _f64(alpha_beta, (n, 4), dev)
+    if fmt is None:
+        f = None
+        if out is None:
+            out = torch.empty_like(rgb)
+        elif not (out.device == dev and tuple(out.shape) == (n, h, w, 3) and out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous uint8 tensor of shape {(n, h, w, 3)} on {dev}")
+        if out.data_ptr() == rgb.data_ptr():
+            raise ValueError("out must not be the input (no in-place jitter)")
+    else:
+        f, dtype, cl = _tensor_format(fmt)
+        out = _tensor_out(out, n, h, w, dtype, cl, dev)
+    _call("sl_normalize_jitter", _ptr(rgb), _ptr(out), n, h, w, _ptr(M_src), _ptr(maxC_src), _ptr(M_tgt), _ptr(maxC_tgt), _ptr(ab),
+          1 if augment_background else 0, C.byref(params) if params is not None else None, C.byref(f) if f is not None else None)
+    return out
+
+
 def _fit(fn_name, op, rgb, params, ws, with_sweeps=False):
     n, h, w = _check_tiles(rgb)
     dev = rgb.device

@@ -186,6 +186,24 @@ class ExtractiveStainNormalizer(object):
         sep = engine.stain_separate(tiles, M, maxC, M_t, c_t, want=want, conc_dtype=conc_dtype)
         return sep, M, maxC, status
 
+    # -- stain jitter in the apply pass (an extension: RandStainNA / StainAugmentor-style augmentation of the normalised tiles) ----
+    def augment_batch(self, tiles, alpha_beta, augment_background=False, normalize=True, out=None, ws=None, tensor_format=None):
+        """(N,H,W,3) uint8 device tensor -> (out, M_src, maxC_src, status): the per-tile fit, then ONE pass that normalises every tile
+        and perturbs its stains: C_i * alpha_i + beta_i on the normalised concentrations of tissue pixels (every pixel with
+        ``augment_background``), under the target's stain matrix, clipped.  ``alpha_beta``: (N, 4) = alpha0, beta0, alpha1, beta1 per
+        tile (``stainlib_amd.StainJitter(...).draw(N)``).  With alpha = 1, beta = 0 the result is transform_batch's.
+        ``normalize=False``: no target (no fit() needed) -- every tile perturbed under its own stain matrix, a batched StainAugmentor.
+        ``tensor_format``: a ``stainlib_amd.TensorFormat``; `out` is then the (N,3,H,W) tensor in that format, bit for bit
+        ``tensor_format.convert`` of the uint8 result.  A tile whose status is non-zero comes back as its own bytes (their conversion)."""
+        from .. import engine
+        engine._jitter_args(None, None, alpha_beta, None, tensor_format, out)
+        if normalize and not hasattr(self, "stain_matrix_target"):
+            raise ValueError("augment_batch(normalize=True) needs a fitted target: call fit() first, or pass normalize=False")
+        M, maxC, status = self._fit_tiles(tiles, ws=ws)
+        M_t, c_t = self._target_on(tiles.device) if normalize else (None, None)
+        x = engine.normalize_jitter(tiles, M, maxC, M_t, c_t, alpha_beta, augment_background, fmt=tensor_format, out=out)
+        return x, M, maxC, status
+
     def separate(self, I, normalize=True):
         """An image (RGB uint8) -> Separated of numpy arrays: norm (= transform(I)), h, e ((H,W,3) uint8) and conc ((2,H,W) float32)."""
         assert is_uint8_image(I), _UINT8_MSG
