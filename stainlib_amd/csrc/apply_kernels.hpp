@@ -1,6 +1,7 @@
 // apply.hip -- the per-pixel "OD + reconstruction" family of sweeps (gfx950).
 //
-//   k_apply          normalizer.py:46-50   u8 -> OD -> 2-atom lasso -> rescale -> 255*exp(-C@Mt) -> u8
+//   k_apply          normalizer.py:46-50   u8 -> OD -> 2-atom lasso -> rescale -> 255*exp(-C@Mt) -> u8  (its per-pixel pieces;
+//                                          the kernel: apply_pass.hpp)
 //   k_stain_augment  augmenter.py:428-449  same skeleton, C*alpha+beta on tissue, clip
 //   k_concentrations stain_utils.py:69-78  materialise C (only for the Python attribute)
 //   k_tissue_mask    stain_utils.py:32-48  materialise the mask / count it
@@ -155,8 +156,9 @@ __device__ __forceinline__ float fnma_clamp01(float r, float m, float a) {     /
     return o;
 }
 
-__device__ __forceinline__ void apply_consts(const double* M_src, const double* maxC_src, const double* M_tgt,
-                                             const double* maxC_tgt, double lam, ApplyK& K) {
+// Returns 2^k, the unit the concentrations of K are carried in (c_true = c * 2^k).
+__device__ __forceinline__ double apply_consts(const double* M_src, const double* maxC_src, const double* M_tgt,
+                                               const double* maxC_tgt, double lam, ApplyK& K) {
     lasso_consts(M_src, lam, K.L);
     const double sc = lasso_unit_scale(K.L), inv = 1.0 / sc;       // powers of two
     scale_lasso(K.L, (float)sc);
@@ -173,13 +175,27 @@ __device__ __forceinline__ void apply_consts(const double* M_src, const double* 
     }
     K.fast = (bool)__builtin_amdgcn_readfirstlane((int)(nonpos & (K.L.g12 >= 0.0f)));
     vgpr(K.L);
+    return inv;
+}
+
+// the two concentrations of one pixel (scaled by 2^-k) from its optical densities
+template <bool FAST>
+__device__ __forceinline__ void apply_conc(const ApplyK& K, float x, float y, float z, float& c1, float& c2) {
+    if (FAST) {                                    // g12 >= 0: branch-free lasso (see lasso2)
+        float a1, a2;
+        lasso_interior(K.L, x, y, z, a1, a2);
+        c1 = fnma_clamp01(K.L.r1, neg_part01(a2), a1);
+        c2 = fnma_clamp01(K.L.r2, neg_part01(a1), a2);
+    } else {
+        lasso2(K.L, x, y, z, c1, c2);
+    }
 }
 
 // 255 * exp(-C @ M_tgt) of one pixel, before the cast
 template <bool FAST>
 __device__ __forceinline__ void apply_px(const ApplyK& K, float x, float y, float z, float (&t)[3]) {
     float c1, c2;
-    if (FAST) {                                    // g12 >= 0: branch-free lasso (see lasso2)
+    if (FAST) {                                    // (apply_conc restated: through the call the fused kernels allocate other registers)
         float a1, a2;
         lasso_interior(K.L, x, y, z, a1, a2);
         c1 = fnma_clamp01(K.L.r1, neg_part01(a2), a1);
@@ -281,83 +297,6 @@ __device__ __forceinline__ void apply_sweep(const uint8_t* src, uint8_t* dst, in
 }
 
 constexpr int kU = 4;       // chunks in flight per lane per trip (plain sweeps: 4 x 12 B loads issued back to back)
-constexpr int kUApply = 2;  // k_apply: 2 chunks per trip with the following trip prefetched
-
-template <bool ALIGNED, bool PREQ>
-static __global__ __launch_bounds__(kWG) void k_apply(const uint8_t* __restrict__ rgb, uint8_t* __restrict__ out,
-                                               int P, int parts, const double* __restrict__ M_src,
-                                               const double* __restrict__ maxC_src,
-                                               const double* __restrict__ M_tgt,
-                                               const double* __restrict__ maxC_tgt, double lam,
-                                               float* __restrict__ prequant) {
-    __shared__ float s_od[256 * kRepl];
-    fill_od_lut(s_od);
-    const int tile = blockIdx.x / parts, part = blockIdx.x % parts;
-    const int tid = threadIdx.x;
-    const uint32_t lane32 = tid & (kRepl - 1);   // which LDS copy of the table this lane reads
-
-    // per-tile constants, computed redundantly in binary64 by every lane
-    ApplyK K;
-    apply_consts(M_src + 6 * (size_t)tile, maxC_src + 2 * (size_t)tile, M_tgt, maxC_tgt, lam, K);
-    __syncthreads();
-
-    const size_t nbytes = (size_t)P * 3;
-    const uint8_t* src = rgb + (size_t)tile * nbytes;
-    uint8_t* dst = out + (size_t)tile * nbytes;
-    const int nch = (P + 3) >> 2;
-    const int span = (nch + parts - 1) / parts;
-    const int c0 = part * span;
-    const int c1 = min(nch, c0 + span);
-
-    // A tile whose fit failed (empty tissue mask / degenerate covariance: M is NaN; a zero 99th-percentile concentration,
-    // which the reference divides by, normalizer.py:48) is passed through unchanged; the caller sees why in status[].
-    // (Block-uniform branch.)
-    if (!(M_src[6 * (size_t)tile] == M_src[6 * (size_t)tile]) || !(maxC_src[2 * (size_t)tile] > 0.0) || !(maxC_src[2 * (size_t)tile + 1] > 0.0)) {
-        for (int c = c0 + tid; c < c1; c += kWG) store_chunk<ALIGNED>(dst, nbytes, c, load_chunk<ALIGNED>(src, nbytes, c));
-        return;
-    }
-
-    // software pipeline: the next trip's chunks are requested before this trip's arithmetic (measured +5 %)
-    auto fetch = [&](int cc) { return load_chunk_clamped<ALIGNED, true>(src, nbytes, cc, c1); };    // single pass: non-temporal
-    auto sweep = [&](auto fast_tag) {
-        constexpr bool FAST = decltype(fast_tag)::value;
-        Chunk nxt[kUApply];
-#pragma unroll
-        for (int u = 0; u < kUApply; ++u) nxt[u] = fetch(c0 + tid + u * kWG);
-        for (int c = c0 + tid; c < c1; c += kWG * kUApply) {
-            Chunk in[kUApply];
-#pragma unroll
-            for (int u = 0; u < kUApply; ++u) {
-                in[u] = nxt[u];
-                nxt[u] = fetch(c + (kUApply + u) * kWG);
-            }
-#pragma unroll
-            for (int u = 0; u < kUApply; ++u) {
-                const int cc = c + u * kWG;
-                float t[12];
-#pragma unroll
-                for (int px = 0; px < 4; ++px) {
-                    const float x = lut(s_od, chunk_byte(in[u], 3 * px + 0), lane32);
-                    const float y = lut(s_od, chunk_byte(in[u], 3 * px + 1), lane32);
-                    const float z = lut(s_od, chunk_byte(in[u], 3 * px + 2), lane32);
-                    float v[3];
-                    apply_px<FAST>(K, x, y, z, v);
-                    t[3 * px] = v[0]; t[3 * px + 1] = v[1]; t[3 * px + 2] = v[2];
-                    if (PREQ) {
-                        const size_t pix = (size_t)cc * 4 + px;
-                        if (cc < c1 && pix < (size_t)P) {
-                            float* pq = prequant + ((size_t)tile * P + pix) * 3;
-                            pq[0] = v[0]; pq[1] = v[1]; pq[2] = v[2];
-                        }
-                    }
-                }
-                const Chunk o = FAST ? pack_trunc_fast(t) : pack_trunc_general(t);
-                if (cc < c1) store_chunk<ALIGNED, true>(dst, nbytes, cc, o);
-            }
-        }
-    };
-    if (K.fast) sweep(std::true_type{}); else sweep(std::false_type{});
-}
 
 // StainAugmentor.pop: own stain matrix both ways, affine on the concentrations of tissue pixels
 // (augmenter.py:435-443), clip (augmenter.py:447).  Persistent 512-thread workgroups over (tile, part) items with the

@@ -13,15 +13,14 @@ extern "C" int sl_normalize_jitter(const uint8_t* rgb, void* out, int n, int h, 
     if (!params_ok(params)) return SL_ERR_BADARG;
     if (fmt && !format_ok(fmt)) return SL_ERR_BADARG;
     const SlParams p = params_or_defaults(params);
-    const long P = (long)h * w;
-    const int parts = parts_for(P);
-    const dim3 grid((unsigned)((long)n * parts)), block(kWG);
+    const TileLaunch L(n, h, w, kWG);
+    const long P = L.P;
     const float ylimf = tissue_ylimf(p);
     hipStream_t s = (hipStream_t)stream;
     auto launch = [&](auto dt, auto lay, auto al, auto wide) {
         auto go = [&](auto all) {
             hipLaunchKernelGGL((k_apply_jitter<decltype(dt)::value, decltype(lay)::value, decltype(al)::value, decltype(wide)::value, decltype(all)::value>),
-                               grid, block, 0, s, rgb, out, (int)P, parts, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, p.lasso_lambda, ylimf,
+                               L.grid, L.block, 0, s, rgb, out, (int)P, L.parts, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, p.lasso_lambda, ylimf,
                                fmt ? tensor_k(*fmt) : TensorK{});
         };
         if (augment_background) go(std::true_type{}); else go(std::false_type{});

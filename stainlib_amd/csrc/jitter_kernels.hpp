@@ -1,12 +1,12 @@
 // jitter_kernels.hpp -- stain jitter in the apply pass (an extension: the reference normalises, normalizer.py:46-50, and perturbs,
 // augmenter.py:428-447, in two passes with a re-fit of the normalised image between them).
 //
-//   k_apply_jitter   k_apply's sweep with StainAugmentor.pop's affine map on the concentrations it holds in registers, written
+//   k_apply_jitter   k_apply's sweep (prologue, failed-fit rule and pipeline of apply_pass.hpp) with StainAugmentor.pop's affine map on the concentrations it holds in registers, written
 //                    as the uint8 image or, through the converter of tensor_kernels.hpp, as the model-ready tensor
 //
 // Definition (include/stainlib_hip.h, sl_normalize_jitter), written so that the pass equals its two neighbours bit for bit.  For
 // one tile let K be the ApplyK that apply_consts builds from the tile's (M_src, maxC_src) and the target (M_tgt, maxC_tgt),
-// 2^k = apply_unit(M_src, lam), ratio_i = maxC_tgt[i] / maxC_src[i], and c1, c2 the binary32 concentrations of apply_conc (carried
+// 2^k the unit apply_consts reports, ratio_i = maxC_tgt[i] / maxC_src[i], and c1, c2 the binary32 concentrations of apply_conc (carried
 // scaled by 2^-k), in the lasso form K.L.g12 >= 0 selects -- k_stain_augment's rule, not K.fast.
 //   jitter   al_i = (float)alpha_i, be_i = (float)(beta_i / ratio_i * 2^-k); c_i' = fmaf(c_i, al_i, be_i) on tissue pixels (the
 //            luminosity test of the SOURCE pixel, is_tissue_f as k_stain_augment makes it), on every pixel when ALL, else c_i' = c_i:
@@ -26,7 +26,7 @@
 // Roofline: HBM, 3 B read + 3 B (uint8) or 6 / 12 B (tensor) written per pixel; per pixel the tissue test adds 3 FMA-class
 // instructions and a compare, the jitter 2 FMAs and 2 selects to k_apply's count.
 #pragma once
-#include "separate_kernels.hpp"      // apply_conc, apply_unit; tensor_kernels.hpp (the converter) through it
+#include "tensor_kernels.hpp"        // the converter; apply_pass.hpp (prologue, driver) through it
 
 namespace sl {
 
@@ -52,70 +52,41 @@ static __global__ __launch_bounds__(kWG) void k_apply_jitter(const uint8_t* __re
     static_assert(U >= 1, "a group is at most kUApply chunks");
     __shared__ float2 s_tab[256];
     fill_gam_od_lut(s_tab);
-    const int tile = blockIdx.x / parts, part = blockIdx.x % parts;
     const int tid = threadIdx.x;
-
-    // per-tile constants; without a target the tile's own statistics stand in for it (ratio exactly 1)
-    const double* Ms = M_src + 6 * (size_t)tile;
-    const double* mcs = maxC_src + 2 * (size_t)tile;
-    const double* Mt = M_tgt ? M_tgt : Ms;
-    const double* mct = M_tgt ? maxC_tgt : mcs;
-    ApplyK K;
-    apply_consts(Ms, mcs, Mt, mct, lam, K);
-    const double sc = 1.0 / apply_unit(Ms, lam);               // 2^-k (a power of two: exact)
+    const ApplyTile<G> A(blockIdx.x, parts, P, rgb, M_src, maxC_src, M_tgt, maxC_tgt, lam);
+    const ApplyK& K = A.K;
+    const double sc = 1.0 / A.unit;                            // 2^-k (a power of two: exact)
     JitterK J;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-        J.al[i] = in_vgpr(uni((float)alpha_beta[4 * (size_t)tile + 2 * i]));
-        J.be[i] = in_vgpr(uni((float)(alpha_beta[4 * (size_t)tile + 2 * i + 1] / (mct[i] / mcs[i]) * sc)));
+        J.al[i] = in_vgpr(uni((float)alpha_beta[4 * (size_t)A.tile + 2 * i]));
+        J.be[i] = in_vgpr(uni((float)(alpha_beta[4 * (size_t)A.tile + 2 * i + 1] / (A.mct[i] / A.mcs[i]) * sc)));
     }
     J.ylimf = in_vgpr(ylimf);
     const TensorK F = tensor_consts(fmt);
     __syncthreads();
+    if (A.empty()) return;
 
-    const size_t nbytes = (size_t)P * 3;
-    const uint8_t* src = rgb + (size_t)tile * nbytes;
-    uint8_t* const d_u8 = (uint8_t*)out + (size_t)tile * nbytes;
-    T* const d_t = (T*)out + (size_t)tile * nbytes;
-    const int nch = (P + 3) >> 2;
-    int g0, g1;
-    group_span<SDT>(P, parts, part, g0, g1);
-    if (g0 >= g1) return;
+    const size_t nbytes = A.nbytes;
+    const int nch = A.nch, g1 = A.g1;
+    uint8_t* const d_u8 = (uint8_t*)out + (size_t)A.tile * nbytes;
+    T* const d_t = (T*)out + (size_t)A.tile * nbytes;
 
-    // A failed fit (k_apply's rule, block-uniform): the source bytes, converted when a format is given.
-    if (!(Ms[0] == Ms[0]) || !(mcs[0] > 0.0) || !(mcs[1] > 0.0)) {
-        if (TENSOR) {
-            convert_sweep<SDT, LAYOUT, ALIGNED, WIDE>(src, d_t, P, g0, g1, tid, F);
-        } else {
-            for (int c = g0 + tid; c < g1; c += kWG) store_chunk<ALIGNED>(d_u8, nbytes, c, load_chunk<ALIGNED>(src, nbytes, c));
-        }
+    if (SL_FIT_FAILED(A)) {                          // the source bytes, converted when a format is given
+        if (TENSOR) convert_sweep<SDT, LAYOUT, ALIGNED, WIDE>(A.src, d_t, P, A.g0, g1, tid, F);
+        else copy_chunks<ALIGNED>(A.src, d_u8, nbytes, A.g0, g1, tid);
         return;
     }
 
-    // k_apply_tensor's pipeline: U groups per lane and trip, the following trip in flight; lanes past the end re-read the last group
-    auto fetch = [&](int gg, int j) {
-        const int gc = gg < g1 ? gg : g1 - 1;
-        return load_chunk_clamped<ALIGNED, true>(src, nbytes, G * gc + j, nch);
-    };
     auto sweep = [&](auto fast_tag) {
         constexpr bool FAST = decltype(fast_tag)::value;
-        Chunk nxt[U][G];
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int j = 0; j < G; ++j) nxt[u][j] = fetch(g0 + tid + u * kWG, j);
-        for (int g = g0 + tid; g < g1; g += kWG * U) {
-            Chunk in[U][G];
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int j = 0; j < G; ++j) {
-                    in[u][j] = nxt[u][j];
-                    nxt[u][j] = fetch(g + (U + u) * kWG, j);
-                }
+        GroupPipe<U, ALIGNED, G> pipe(A, tid);
+        for (int g = A.g0 + tid; g < g1; g += kWG * U) {
+            pipe.advance(g);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int gg = g + u * kWG;
+                const Chunk (&inu)[G] = pipe.in[u];
                 float v[12 * G];
 #pragma unroll
                 for (int j = 0; j < G; ++j) {
@@ -123,9 +94,9 @@ static __global__ __launch_bounds__(kWG) void k_apply_jitter(const uint8_t* __re
                     float t[12];
 #pragma unroll
                     for (int px = 0; px < 4; ++px) {
-                        const float2 er = s_tab[chunk_byte(in[u][j], 3 * px + 0)];      // x = gamma, y = od32
-                        const float2 eg = s_tab[chunk_byte(in[u][j], 3 * px + 1)];
-                        const float2 eb = s_tab[chunk_byte(in[u][j], 3 * px + 2)];
+                        const float2 er = s_tab[chunk_byte(inu[j], 3 * px + 0)];      // x = gamma, y = od32
+                        const float2 eg = s_tab[chunk_byte(inu[j], 3 * px + 1)];
+                        const float2 eb = s_tab[chunk_byte(inu[j], 3 * px + 2)];
                         float c1, c2;
                         apply_conc<FAST>(K, er.y, eg.y, eb.y, c1, c2);
                         if (ALL) {

@@ -36,10 +36,11 @@ extern "C" void sl_default_separate_out(SlSeparateOut* o) {
 extern "C" int sl_stain_separate(const uint8_t* rgb, int n, int h, int w, const double* M_src, const double* maxC_src,
                                  const double* M_tgt, const double* maxC_tgt, double lasso_lambda, const SlSeparateOut* outs,
                                  void* stream) {
-    if (!rgb || !M_src || !maxC_src || !outs || n <= 0 || h <= 0 || w <= 0) return SL_ERR_BADARG;
+    if (const int rc = check_shape(rgb, n, h, w)) return rc;
+    if (!outs || !M_src || !maxC_src) return SL_ERR_BADARG;
     if ((M_tgt == nullptr) != (maxC_tgt == nullptr)) return SL_ERR_BADARG;       // both: a target; neither: every tile's own matrix
-    const long P = (long)h * w;
-    if (P > (1L << 30)) return SL_ERR_BADARG;
+    const TileLaunch L(n, h, w, kWG);
+    const long P = L.P;
     if (outs->struct_size != (uint32_t)sizeof(SlSeparateOut)) return SL_ERR_BADARG;       // (before any other field is read)
     const SlSeparateOut o = *outs;
     if (o.conc_dtype < SL_DTYPE_F32 || o.conc_dtype > SL_DTYPE_BF16) return SL_ERR_BADARG;
@@ -57,12 +58,10 @@ extern "C" int sl_stain_separate(const uint8_t* rgb, int n, int h, int w, const 
     bool aligned = aligned4(rgb, P);
     for (int i = 0; i < 3; ++i) aligned = aligned && (!ptrs[i] || aligned4(ptrs[i], P));
     if (o.conc) aligned = aligned && wide_ok(o.conc, P, o.conc_dtype);
-    const int parts = parts_for(P);
-    const dim3 grid((unsigned)((long)n * parts)), block(kWG);
     const SeparateOut d{o.norm, {o.stain[0], o.stain[1]}, o.conc};
     with_outputs(o.norm != nullptr, o.stain[0] || o.stain[1], o.conc ? o.conc_dtype : kDtNone, aligned, [&](auto nt, auto st, auto dt, auto al) {
-        hipLaunchKernelGGL((k_separate<decltype(nt)::value, decltype(st)::value, decltype(dt)::value, decltype(al)::value>), grid, block, 0,
-                           (hipStream_t)stream, rgb, d, (int)P, parts, M_src, maxC_src, M_tgt, maxC_tgt, lasso_lambda);
+        hipLaunchKernelGGL((k_separate<decltype(nt)::value, decltype(st)::value, decltype(dt)::value, decltype(al)::value>), L.grid, L.block, 0,
+                           (hipStream_t)stream, rgb, d, (int)P, L.parts, M_src, maxC_src, M_tgt, maxC_tgt, lasso_lambda);
     });
     return launch_status();
 }

@@ -1,11 +1,11 @@
 // separate_kernels.hpp -- stain separation (an extension: the reference ends at normalizer.py:50 with the recombined image).
 //
-//   k_separate   k_apply's sweep with up to four outputs per pixel from ONE read of the tile and ONE lasso solve:
+//   k_separate   k_apply's sweep (prologue, failed-fit rule and pipeline of apply_pass.hpp) with up to four outputs per pixel from ONE read of the tile and ONE lasso solve:
 //                the normalised image, the haematoxylin-only and eosin-only images, the two concentration planes
 //
 // Definitions (include/stainlib_hip.h, SlSeparateOut), written so that "separate" equals "compose it yourself", bit for bit.
 // For one tile let K be the ApplyK that apply_consts builds from the tile's (M_src, maxC_src) and the target (M_tgt, maxC_tgt), and
-// c1, c2 the binary32 concentrations apply_px computes (apply_conc below: carried scaled by 2^-k, in the lasso form K.fast selects).
+// c1, c2 the binary32 concentrations apply_px computes (apply_conc: carried scaled by 2^-k, in the lasso form K.fast selects).
 //   norm      k_apply's bytes: 255 * exp2(fmaf(c1, q[0][ch], c2 * q[1][ch])), pack_trunc_fast when K.fast, else pack_trunc_general.
 //   stain[i]  t = 255.0f * exp2f(c_i * K.q[i][ch]): one binary32 multiply, the hardware exp2, one multiply; the cast of norm.
 //             Wherever sl_normalize_apply, called with the OTHER row of M_tgt replaced by zeros, makes the same K.fast decision, it
@@ -38,26 +38,6 @@ struct SeparateOut {                    // device pointers, NULL = not wanted
     uint8_t* stain[2];
     void* conc;
 };
-
-// The two concentrations of apply_px (apply_kernels.hpp), which keeps them to itself: the same statements, so the same bits.
-template <bool FAST>
-__device__ __forceinline__ void apply_conc(const ApplyK& K, float x, float y, float z, float& c1, float& c2) {
-    if (FAST) {                                    // g12 >= 0: branch-free lasso (see lasso2)
-        float a1, a2;
-        lasso_interior(K.L, x, y, z, a1, a2);
-        c1 = fnma_clamp01(K.L.r1, neg_part01(a2), a1);
-        c2 = fnma_clamp01(K.L.r2, neg_part01(a1), a2);
-    } else {
-        lasso2(K.L, x, y, z, c1, c2);
-    }
-}
-
-// 2^k of apply_consts (which folds it into K and does not hand it out): the same two calls on the same matrix
-__device__ __forceinline__ double apply_unit(const double* M_src, double lam) {
-    LassoK L;
-    lasso_consts(M_src, lam, L);
-    return 1.0 / lasso_unit_scale(L);
-}
 
 // Group g of a tile (pixels [4 G g, 4 G (g + 1))), v[i][p] = plane i of its pixel p, to the tile's planes at `base` (element i P + p).
 // WIDE (the host checked: every plane of every tile starts on a 16-byte boundary, which makes P a multiple of 4 G -- no ragged
@@ -101,46 +81,34 @@ static __global__ __launch_bounds__(kWG) void k_separate(const uint8_t* __restri
     static_assert(U >= 1, "a group is at most kUApply chunks");
     __shared__ float s_od[256 * kRepl];
     fill_od_lut(s_od);
-    const int tile = blockIdx.x / parts, part = blockIdx.x % parts;
     const int tid = threadIdx.x;
     const uint32_t lane32 = tid & (kRepl - 1);
-
-    // per-tile constants; without a target the tile's own statistics stand in for it (ratio exactly 1)
-    const double* Ms = M_src + 6 * (size_t)tile;
-    const double* mcs = maxC_src + 2 * (size_t)tile;
-    const double* Mt = M_tgt ? M_tgt : Ms;
-    const double* mct = M_tgt ? maxC_tgt : mcs;
-    ApplyK K;
-    apply_consts(Ms, mcs, Mt, mct, lam, K);
-    const double inv = CONC ? apply_unit(Ms, lam) : 1.0;
+    const ApplyTile<G> A(blockIdx.x, parts, P, rgb, M_src, maxC_src, M_tgt, maxC_tgt, lam);
+    const ApplyK& K = A.K;
     float s[2] = {0.0f, 0.0f};
     if (CONC) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) s[i] = in_vgpr(uni((float)(mct[i] / mcs[i] * inv)));
+        for (int i = 0; i < 2; ++i) s[i] = in_vgpr(uni((float)(A.mct[i] / A.mcs[i] * A.unit)));
     }
     __syncthreads();
+    if (A.empty()) return;
 
-    const size_t nbytes = (size_t)P * 3;
-    const uint8_t* src = rgb + (size_t)tile * nbytes;
-    uint8_t* const d_norm = NORM ? out.norm + (size_t)tile * nbytes : nullptr;
-    uint8_t* const d_st[2] = {STAINS && out.stain[0] ? out.stain[0] + (size_t)tile * nbytes : nullptr,
-                              STAINS && out.stain[1] ? out.stain[1] + (size_t)tile * nbytes : nullptr};
-    T* const d_conc = CONC ? (T*)out.conc + (size_t)tile * 2 * P : nullptr;
-    const int nch = (P + 3) >> 2;
-    int g0, g1;
-    group_span<SDT>(P, parts, part, g0, g1);
-    if (g0 >= g1) return;
+    const size_t nbytes = A.nbytes;
+    const int nch = A.nch, g1 = A.g1;
+    uint8_t* const d_norm = NORM ? out.norm + (size_t)A.tile * nbytes : nullptr;
+    uint8_t* const d_st[2] = {STAINS && out.stain[0] ? out.stain[0] + (size_t)A.tile * nbytes : nullptr,
+                              STAINS && out.stain[1] ? out.stain[1] + (size_t)A.tile * nbytes : nullptr};
+    T* const d_conc = CONC ? (T*)out.conc + (size_t)A.tile * 2 * P : nullptr;
 
-    // A failed fit (k_apply's rule, block-uniform): the source bytes, zero concentration.
-    if (!(Ms[0] == Ms[0]) || !(mcs[0] > 0.0) || !(mcs[1] > 0.0)) {
+    if (SL_FIT_FAILED(A)) {                          // the source bytes, zero concentration
         const Chunk white{0xffffffffu, 0xffffffffu, 0xffffffffu};
         const float zero[2][4 * G] = {};
-        for (int g = g0 + tid; g < g1; g += kWG) {
+        for (int g = A.g0 + tid; g < g1; g += kWG) {
 #pragma unroll
             for (int j = 0; j < G; ++j) {
                 const int cc = G * g + j;
                 if (cc >= nch) continue;
-                if (NORM) store_chunk<ALIGNED>(d_norm, nbytes, cc, load_chunk<ALIGNED>(src, nbytes, cc));
+                if (NORM) store_chunk<ALIGNED>(d_norm, nbytes, cc, load_chunk<ALIGNED>(A.src, nbytes, cc));
                 if (STAINS) {
 #pragma unroll
                     for (int i = 0; i < 2; ++i)
@@ -152,30 +120,15 @@ static __global__ __launch_bounds__(kWG) void k_separate(const uint8_t* __restri
         return;
     }
 
-    // k_apply_tensor's pipeline: U groups per lane and trip, the following trip in flight
-    auto fetch = [&](int gg, int j) {
-        const int gc = gg < g1 ? gg : g1 - 1;
-        return load_chunk_clamped<ALIGNED, true>(src, nbytes, G * gc + j, nch);
-    };
     auto sweep = [&](auto fast_tag) {
         constexpr bool FAST = decltype(fast_tag)::value;
-        Chunk nxt[U][G];
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int j = 0; j < G; ++j) nxt[u][j] = fetch(g0 + tid + u * kWG, j);
-        for (int g = g0 + tid; g < g1; g += kWG * U) {
-            Chunk in[U][G];
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int j = 0; j < G; ++j) {
-                    in[u][j] = nxt[u][j];
-                    nxt[u][j] = fetch(g + (U + u) * kWG, j);
-                }
+        GroupPipe<U, ALIGNED, G> pipe(A, tid);
+        for (int g = A.g0 + tid; g < g1; g += kWG * U) {
+            pipe.advance(g);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int gg = g + u * kWG;
+                const Chunk (&inu)[G] = pipe.in[u];
                 float cv[2][4 * G];
 #pragma unroll
                 for (int j = 0; j < G; ++j) {
@@ -184,10 +137,8 @@ static __global__ __launch_bounds__(kWG) void k_separate(const uint8_t* __restri
                     float tn[12], th[12], te[12];
 #pragma unroll
                     for (int px = 0; px < 4; ++px) {
-                        const float x = lut(s_od, chunk_byte(in[u][j], 3 * px + 0), lane32);
-                        const float y = lut(s_od, chunk_byte(in[u][j], 3 * px + 1), lane32);
-                        const float z = lut(s_od, chunk_byte(in[u][j], 3 * px + 2), lane32);
-                        float c1, c2;
+                        float x, y, z, c1, c2;
+                        od_of_pixel(s_od, inu[j], px, lane32, x, y, z);
                         apply_conc<FAST>(K, x, y, z, c1, c2);
 #pragma unroll
                         for (int ch = 0; ch < 3; ++ch) {

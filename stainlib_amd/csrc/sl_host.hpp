@@ -47,6 +47,14 @@ int zero_async(void* p, size_t bytes, hipStream_t s);
 // workspace of the Lab family (lab.hip)
 size_t lab_workspace_bytes(int n_tiles);
 
+// The shape checks every per-tile entry point starts with: the input, a positive batch and tile, at most 2^30 pixels per tile.
+inline int check_shape(const void* rgb, int n, int h, int w) {
+    if (!rgb || n <= 0 || h <= 0 || w <= 0) return SL_ERR_BADARG;
+    if ((long)h * w > (1L << 30)) return SL_ERR_BADARG;
+    return SL_OK;
+}
+inline int check_shape(const void* rgb, const void* out, int n, int h, int w) { return out ? check_shape(rgb, n, h, w) : SL_ERR_BADARG; }
+
 inline bool aligned4(const void* p, long pixels_per_tile) {
     return ((uintptr_t)p & 3u) == 0 && (pixels_per_tile & 3) == 0;
 }
@@ -75,6 +83,15 @@ inline int parts_for(long P) {
     long p = (P + 32767) / 32768;
     return (int)(p < 1 ? 1 : p);
 }
+
+// The geometry of the launchers that give every (tile, part) a workgroup of its own.  `threads` is always kWG: a parameter only
+// because kWG lives in sl_device.hpp, which this host-side header does not include (common.hip builds without it).
+struct TileLaunch {
+    long P;
+    int parts;
+    dim3 grid, block;
+    TileLaunch(int n, int h, int w, int threads) : P((long)h * w), parts(parts_for(P)), grid((unsigned)((long)n * parts)), block(threads) {}
+};
 
 // parts_for(P) for n tiles walked by max_grid persistent workgroups: no more parts than it takes to give every workgroup ~4 items.
 // (n <= 0 is taken as one tile: workspace sizing asks before the tile count is checked.)

@@ -40,10 +40,4 @@ inline void with_format(int dtype, int layout, bool aligned, bool wide, F&& f) {
     else l2(std::integral_constant<int, kDtBF16>{});
 }
 
-inline int check_shape(const void* rgb, const void* out, int n, int h, int w) {
-    if (!rgb || !out || n <= 0 || h <= 0 || w <= 0) return SL_ERR_BADARG;
-    if ((long)h * w > (1L << 30)) return SL_ERR_BADARG;
-    return SL_OK;
-}
-
 }  // namespace sl

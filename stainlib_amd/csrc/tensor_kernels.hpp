@@ -13,7 +13,7 @@
 // issue, not by bytes: a lane owns a GROUP of G adjacent chunks (G = 1 for float32, 2 for the half types -- 8 pixels) so
 // that every store of the wide path is 16 bytes: one per plane (NCHW), three per group (NHWC).
 #pragma once
-#include "apply_kernels.hpp"
+#include "apply_pass.hpp"
 
 namespace sl {
 
@@ -114,6 +114,8 @@ __device__ __forceinline__ void store_group(typename Elem<DT>::type* base, int P
 }
 
 // the groups [g0, g1) of one tile, plain conversion of the source bytes (k_to_tensor; the pass-through of k_apply_tensor)
+// (A loop of its own beside GroupPipe of apply_pass.hpp: no prefetch -- there is no arithmetic to hide a load behind -- and
+// U = 4 / G groups per trip, kU chunks issued back to back, not kUApply.)
 template <int DT, int LAYOUT, bool ALIGNED, bool WIDE>
 __device__ __forceinline__ void convert_sweep(const uint8_t* src, typename Elem<DT>::type* dst, int P, int g0, int g1, int tid,
                                               const TensorK& K) {
@@ -138,30 +140,21 @@ __device__ __forceinline__ void convert_sweep(const uint8_t* src, typename Elem<
     }
 }
 
-// the tile split of parts_for, in groups
-template <int DT>
-__device__ __forceinline__ void group_span(int P, int parts, int part, int& g0, int& g1) {
-    constexpr int G = group_chunks<DT>();
-    const int nch = (P + 3) >> 2;
-    const int ngr = (nch + G - 1) / G;
-    const int span = (ngr + parts - 1) / parts;
-    g0 = part * span;
-    g1 = min(ngr, g0 + span);
-}
-
 template <int DT, int LAYOUT, bool ALIGNED, bool WIDE>
 static __global__ __launch_bounds__(kWG) void k_to_tensor(const uint8_t* __restrict__ rgb, void* __restrict__ out, int P, int parts, TensorK fmt) {
     typedef typename Elem<DT>::type T;
     const int tile = blockIdx.x / parts, part = blockIdx.x % parts;
     const TensorK K = tensor_consts(fmt);
     int g0, g1;
-    group_span<DT>(P, parts, part, g0, g1);
+    group_span<group_chunks<DT>()>(P, parts, part, g0, g1);
     if (g0 >= g1) return;
     convert_sweep<DT, LAYOUT, ALIGNED, WIDE>(rgb + (size_t)tile * 3 * P, (T*)out + (size_t)tile * 3 * P, P, g0, g1, threadIdx.x, K);
 }
 
-// k_apply (apply_kernels.hpp) with the converter's store path behind the cast: the same per-tile constants, the same pipelined fetch
-// (two chunks per lane and trip, the following trip in flight), the same K.fast / general split, apply_px and pack_trunc_* as they are.
+// k_apply (apply_pass.hpp) with the converter's store path behind the cast: the same constants, pipelined fetch (kUApply chunks per lane
+// and trip), K.fast / general split, apply_px and pack_trunc_*.  A deliberate variant: it keeps its own prologue and its own copy of
+// GroupPipe's loop.  On the shared frame float32 NCHW aligned + wide (the same instructions in another order) measured 0.5 % slower on
+// an MI355X, outside the run-to-run spread; as written here all 24 instantiations are unchanged function for function (tools/isa_diff.py).
 template <int DT, int LAYOUT, bool ALIGNED, bool WIDE>
 static __global__ __launch_bounds__(kWG) void k_apply_tensor(const uint8_t* __restrict__ rgb, void* __restrict__ out, int P, int parts,
                                                              const double* __restrict__ M_src, const double* __restrict__ maxC_src,
@@ -186,7 +179,7 @@ static __global__ __launch_bounds__(kWG) void k_apply_tensor(const uint8_t* __re
     T* dst = (T*)out + (size_t)tile * nbytes;
     const int nch = (P + 3) >> 2;
     int g0, g1;
-    group_span<DT>(P, parts, part, g0, g1);
+    group_span<G>(P, parts, part, g0, g1);
     if (g0 >= g1) return;
 
     // k_apply's pass-through rule (a failed fit: NaN M_src, a non-positive maxC_src): the SOURCE bytes are converted.  (Block-uniform.)
@@ -224,9 +217,9 @@ static __global__ __launch_bounds__(kWG) void k_apply_tensor(const uint8_t* __re
                     float t[12];
 #pragma unroll
                     for (int px = 0; px < 4; ++px) {
-                        const float x = lut(s_od, chunk_byte(in[u][j], 3 * px + 0), lane32);
-                        const float y = lut(s_od, chunk_byte(in[u][j], 3 * px + 1), lane32);
-                        const float z = lut(s_od, chunk_byte(in[u][j], 3 * px + 2), lane32);
+                        const float x = lut(s_od, chunk_byte(in[u][j], 3 * px + 0), lane32);       // (od_of_pixel, written out:
+                        const float y = lut(s_od, chunk_byte(in[u][j], 3 * px + 1), lane32);       //  through the call 4 of the 24
+                        const float z = lut(s_od, chunk_byte(in[u][j], 3 * px + 2), lane32);       //  instantiations change)
                         float r[3];
                         apply_px<FAST>(K, x, y, z, r);
                         t[3 * px] = r[0]; t[3 * px + 1] = r[1]; t[3 * px + 2] = r[2];

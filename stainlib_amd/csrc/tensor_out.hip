@@ -15,13 +15,11 @@ extern "C" void sl_default_tensor_format(SlTensorFormat* f) {
 extern "C" int sl_to_tensor(const uint8_t* rgb, void* out, int n, int h, int w, const SlTensorFormat* fmt, void* stream) {
     if (const int rc = check_shape(rgb, out, n, h, w)) return rc;
     if (!format_ok(fmt)) return SL_ERR_BADARG;
-    const long P = (long)h * w;
-    const int parts = parts_for(P);
-    const dim3 grid((unsigned)((long)n * parts)), block(kWG);
+    const TileLaunch L(n, h, w, kWG);
     const TensorK k = tensor_k(*fmt);
-    with_format(fmt->dtype, fmt->layout, aligned4(rgb, P), wide_ok(out, P, fmt->dtype), [&](auto dt, auto lay, auto al, auto wide) {
-        hipLaunchKernelGGL((k_to_tensor<decltype(dt)::value, decltype(lay)::value, decltype(al)::value, decltype(wide)::value>), grid, block, 0,
-                           (hipStream_t)stream, rgb, out, (int)P, parts, k);
+    with_format(fmt->dtype, fmt->layout, aligned4(rgb, L.P), wide_ok(out, L.P, fmt->dtype), [&](auto dt, auto lay, auto al, auto wide) {
+        hipLaunchKernelGGL((k_to_tensor<decltype(dt)::value, decltype(lay)::value, decltype(al)::value, decltype(wide)::value>), L.grid, L.block, 0,
+                           (hipStream_t)stream, rgb, out, (int)L.P, L.parts, k);
     });
     return launch_status();
 }
@@ -32,13 +30,11 @@ extern "C" int sl_normalize_apply_tensor(const uint8_t* rgb, void* out, int n, i
     if (const int rc = check_shape(rgb, out, n, h, w)) return rc;
     if (!M_src || !maxC_src || !M_tgt || !maxC_tgt) return SL_ERR_BADARG;
     if (!format_ok(fmt)) return SL_ERR_BADARG;
-    const long P = (long)h * w;
-    const int parts = parts_for(P);
-    const dim3 grid((unsigned)((long)n * parts)), block(kWG);
+    const TileLaunch L(n, h, w, kWG);
     const TensorK k = tensor_k(*fmt);
-    with_format(fmt->dtype, fmt->layout, aligned4(rgb, P), wide_ok(out, P, fmt->dtype), [&](auto dt, auto lay, auto al, auto wide) {
-        hipLaunchKernelGGL((k_apply_tensor<decltype(dt)::value, decltype(lay)::value, decltype(al)::value, decltype(wide)::value>), grid, block, 0,
-                           (hipStream_t)stream, rgb, out, (int)P, parts, M_src, maxC_src, M_tgt, maxC_tgt, lasso_lambda, k);
+    with_format(fmt->dtype, fmt->layout, aligned4(rgb, L.P), wide_ok(out, L.P, fmt->dtype), [&](auto dt, auto lay, auto al, auto wide) {
+        hipLaunchKernelGGL((k_apply_tensor<decltype(dt)::value, decltype(lay)::value, decltype(al)::value, decltype(wide)::value>), L.grid, L.block, 0,
+                           (hipStream_t)stream, rgb, out, (int)L.P, L.parts, M_src, maxC_src, M_tgt, maxC_tgt, lasso_lambda, k);
     });
     return launch_status();
 }
