@@ -613,6 +613,31 @@ SL_API int sl_stain_separate(const uint8_t* rgb, int n, int h, int w, const doub
  * std <= 0).  out == rgb is not supported.  No workspace; capture-safe like the rest (no allocation, no synchronisation, no memset). */
 SL_API int sl_normalize_jitter(const uint8_t* rgb, void* out, int n, int h, int w, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, const double* alpha_beta, int augment_background, const SlParams* params, const SlTensorFormat* fmt, void* stream);
 
+/* ---- random crop, flip and quarter turn in the apply pass (stainlib_amd/csrc/view.hip; an extension: the geometric half of a training
+ * loader's augmentation -- 224^2 out of 256^2, a flip, a turn, different for every tile -- otherwise runs behind the call, on the widest
+ * data type, over pixels that were computed and written for nothing) ---------------------------------------------------------------------
+ * For tile t let full[t] be the h x w x 3 uint8 image an existing pass writes:
+ *     alpha_beta != NULL                   sl_normalize_jitter with the same augment_background, params and target (or no target)
+ *     alpha_beta == NULL, M_src != NULL    sl_normalize_apply with lasso_lambda = params->lasso_lambda, its general cast included
+ *     M_src == NULL                        none: the source bytes themselves
+ * (a tile whose fit failed -- NaN M_src, maxC_src <= 0 --: its source bytes, as in both passes).  The statistics are those of the WHOLE
+ * tile; only the apply is restricted to the window: "normalise, then crop".
+ * A view is windows[t] = (y0, x0, d), three int32 per tile on the device; the output size (oh, ow) is one for the whole call:
+ *     d' = d & d_mask,  k = d' & 3 quarter turns,  f = d' & 4 flip
+ *     (wh, ww) = (oh, ow) for even k, (ow, oh) for odd k: the window in the tile
+ *     y0' = clamp(y0, 0, h - wh),  x0' = clamp(x0, 0, w - ww), clamped on the device: no window can leave the tile
+ *     view[t] = rot90(flip_w_if(f, full[t][y0' : y0' + wh, x0' : x0' + ww]), k)
+ * with rot90 = torch.rot90(., k, dims=(0, 1)) (counter-clockwise) and the flip = torch.flip(., dims=(1,)), applied BEFORE the turn.
+ *   out   fmt == NULL: n x oh x ow x 3 uint8.  Otherwise the n x 3 x oh x ow tensor sl_to_tensor makes of view, bit for bit, in fmt->dtype
+ *         and fmt->layout; `out` needs the alignment of its element type only
+ * Only window pixels are read (3 B), computed and written.
+ * SL_ERR_BADARG before anything is launched: what sl_normalize_jitter refuses of rgb, out, n, h, w, a one-sided target, params and fmt;
+ * NULL windows; oh or ow < 1, oh > h or ow > w; d_mask outside 0..7; d_mask & 1 with ow > h or oh > w (the transposed window must fit
+ * too); M_src == NULL with a non-NULL M_tgt, maxC_src or alpha_beta; M_src without maxC_src; M_src without both a target and alpha_beta
+ * (sl_normalize_apply needs a target); more than 2^31 - 1 (tile, 64 x 64 patch) pairs.  out == rgb is not supported.  No workspace;
+ * capture-safe like the rest (no allocation, no synchronisation, no memset). */
+SL_API int sl_normalize_view(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, const double* alpha_beta, int augment_background, const SlParams* params, const SlTensorFormat* fmt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -172,6 +172,9 @@ _SIGNATURES = {
     # stain jitter in the apply pass (SlParams and SlTensorFormat: host structs, either may be NULL)
     "sl_normalize_jitter": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, C.POINTER(SlParams),
                                       C.POINTER(SlTensorFormat), _P]),
+    # crop / flip / rot90 in the apply pass (windows: n x 3 int32 on the device; M_src, alpha_beta, SlParams, SlTensorFormat may be NULL)
+    "sl_normalize_view": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, C.c_int,
+                                    C.POINTER(SlParams), C.POINTER(SlTensorFormat), _P]),
 }
 POOL_STATE_DOUBLES, POOL_M, POOL_MAXC, POOL_STATUS, POOL_MISS = 64, 0, 6, 8, 9
 POOL2_STATE_DOUBLES, POOL2_HIST_WORDS, POOL2_WHY = 256, 2 * 8192 + 8 * 32, 33

@@ -248,23 +248,33 @@ class StainAugmentor(object):
         out = engine.stain_augment(self._dev, self.stain_matrix[None], [alpha_beta], self.augment_background)
         return out[0].cpu().numpy()
 
-    def augment_batch(self, tiles, alpha_beta=None, tensor_format=None):
+    def augment_batch(self, tiles, alpha_beta=None, tensor_format=None, view=None, windows=None):
         """Batched extension: (N,H,W,3) uint8 device tensor -> (out, M, maxC, status) device tensors: every tile perturbed under its OWN
         stain matrix (this augmentor's extractor, fitted per tile) -- n fit() / pop() pairs in one fit and ONE pass, nothing through the
         host.  alpha_beta: (N, 4) = alpha0, beta0, alpha1, beta1 per tile; by default drawn from the global numpy stream exactly as N
         successive pop() calls would (StainJitter.draw).  A tile whose status is non-zero comes back unchanged.
         ``tensor_format``: a ``stainlib_amd.TensorFormat``; `out` is then the (N,3,H,W) tensor in that format.
+        ``view``: a ``stainlib_amd.TileView`` -- per tile only the window ``windows[t]`` of that result, flipped and turned, from the
+        same pass (engine.normalize_view); `out` is (N,oh,ow,3) or (N,3,oh,ow) and the call returns (out, M, maxC, status, windows).
+        ``windows`` defaults to ``view.draw(N, H, W)``, drawn AFTER the alpha_beta of the call.
         fit() / pop() are untouched by it."""
         from .. import engine
         jitter = StainJitter(self.sigma1, self.sigma2, self.augment_background)
         engine._jitter_args(None, None, alpha_beta if alpha_beta is not None else np.empty((0, 4)), None, tensor_format, None)
-        n = engine._check_tiles(tiles)[0]
+        if view is not None or windows is not None:
+            engine._view_call(view, windows, tiles, draw=False)
+        n, h, w = engine._check_tiles(tiles)
         if self._method == "macenko":
             M, maxC, status = engine.macenko_fit(tiles)
         else:
             M, maxC, status, _ = engine.vahadane_fit(tiles)
         if alpha_beta is None:
             alpha_beta = jitter.draw(n)
+        if view is not None or windows is not None:
+            size, d_mask, windows = engine._view_call(view, windows, tiles)
+            out = engine.normalize_view(tiles, windows, size, d_mask, M, maxC, None, None, alpha_beta, self.augment_background,
+                                        fmt=tensor_format)
+            return out, M, maxC, status, windows
         out = engine.normalize_jitter(tiles, M, maxC, None, None, alpha_beta, self.augment_background, fmt=tensor_format)
         return out, M, maxC, status
 

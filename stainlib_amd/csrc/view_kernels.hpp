@@ -1,0 +1,276 @@
+// view_kernels.hpp -- random crop, flip and quarter turn fused into the output sweep of the apply pass (an extension: a training loader
+// crops / flips / rotates every tile differently BEHIND our call, one or two more trips over the widest data type).
+//
+//   k_view   per tile a window of the image that sl_normalize_jitter / sl_normalize_apply would write (or of the source bytes
+//            themselves), flipped and turned by the tile's dihedral code, as the uint8 image or the model-ready tensor
+//
+// Definition (include/stainlib_hip.h, sl_normalize_view): the result is "the same bits, elsewhere" -- the tensor value is defined on
+// the truncated byte and a dihedral transform is a permutation -- so the pixel arithmetic below is k_apply's / k_apply_jitter's
+// statement for statement (apply_consts, apply_px, apply_conc, the two casts, JitterK, is_tissue_f, cvt_chunk) on the same constants.
+//
+// Shape: ONE workgroup = one tile and one patch of kViewB x kViewB OUTPUT pixels.  The dihedral code (block-uniform, read once, a
+// run-time value) decides which kViewB x kViewB block of the source window that is; the two sides meet in LDS:
+//   read side   walks the SOURCE block along source rows: 16 lanes per row, a 12-byte chunk (4 pixels) each, 16 rows per pass, 4 passes,
+//               all four loads issued before the first arithmetic.  A row segment starts at byte 3 (y w + x0), any residue mod 4: the
+//               loads are dwordx3 at byte addresses (full speed on gfx950, as in the unaligned k_apply), never predicated -- rows and
+//               chunks past the block re-read its last row / chunk, a chunk that would pass the tile's end starts early and is shifted
+//               into place (load12: load_chunk's rule at an arbitrary byte) -- and the LDS write is masked instead.
+//   LDS         one packed dword r | g << 8 | b << 16 per pixel (the three TRUNCATED bytes), in SOURCE orientation, row pitch
+//               kViewPitch = 65 dwords.
+//   write side  walks OUTPUT rows: 16 lanes per row, 4 adjacent output pixels each -> one 12-byte chunk -> cvt_chunk -> 12 / 16 / 24 /
+//               48 contiguous bytes per lane and plane, vector stores at element alignment; the ragged last lane of a row stores
+//               element by element.  The dihedral code is only the affine map (a0, ai, aj) from output to LDS index.
+// LDS banking (ds_write_b32 / ds_read_b32: bank (a / 4) % 32 within each 32-lane half; a half = 2 rows x 16 lanes): with the odd
+// pitch the bank of pixel (r, x) is (r + x) % 32.  A lane's instruction s touches x = 4 c + s (c = 0..15), so on the row-wise side
+// lanes c and c + 8 of a row share a bank and the next row is shifted by one: 2-way.  On the column-wise side (odd codes) the lane
+// stride is 4 pitches = 4 banks, the same picture: 2-way, where an even pitch would make it 16-way.  Chosen: pitch 65 with this plain
+// 4-pixels-per-lane assignment; the remaining 2-way conflict on 8 of the ~20 LDS instructions of a chunk could be rotated away
+// (instruction s takes pixel (s + rot) & 3, rot per lane) at 16 selects per chunk -- not done, the pass is not LDS bound.
+#pragma once
+#include "jitter_kernels.hpp"        // JitterK, the {gamma, od32} table; tensor_kernels.hpp and apply_pass.hpp through it
+
+namespace sl {
+
+constexpr int kViewB = 64;                       // patch edge in pixels
+constexpr int kViewPitch = kViewB + 1;           // LDS row pitch in dwords (odd: see above)
+constexpr int kViewRaw = 0, kViewApply = 1, kViewJitTissue = 2, kViewJitAll = 3;     // which pass `full` is
+
+typedef uint32_t sl_u32x2u __attribute__((ext_vector_type(2), aligned(1)));
+typedef uint32_t sl_u32x4u __attribute__((ext_vector_type(4), aligned(1)));
+
+// The 12 bytes at byte `base` (< nbytes) of a tile, bytes past the tile's end as zeros: load_chunk's unaligned rule (start early enough
+// to stay inside, shift into place) at an arbitrary byte.  No predicated load; a tile of fewer than 12 bytes goes byte by byte.
+__device__ __forceinline__ Chunk load12(const uint8_t* tile, size_t nbytes, size_t base) {
+    if (nbytes < 12) return load_chunk<false>(tile + base, nbytes - base, 0);      // (uniform; its byte path clamps every address)
+    const size_t lim = nbytes - 12;
+    const size_t at = base < lim ? base : lim;
+    const sl_u32x3u u = *(SL_GLOBAL const sl_u32x3u*)(as_global(tile) + at);
+    const uint32_t d = (uint32_t)(base - at);                // 0 except at the tile's end (1..11 bytes too early)
+    const uint32_t step = d >> 2, sh = 8u * (d & 3u);
+    const uint32_t a0 = step == 0 ? u.x : (step == 1 ? u.y : u.z);
+    const uint32_t a1 = step == 0 ? u.y : (step == 1 ? u.z : 0u);
+    const uint32_t a2 = step == 0 ? u.z : 0u;
+    Chunk r;
+    r.w0 = (uint32_t)((((unsigned long long)a1 << 32) | a0) >> sh);
+    r.w1 = (uint32_t)((((unsigned long long)a2 << 32) | a1) >> sh);
+    r.w2 = a2 >> sh;
+    return r;
+}
+
+// 4 output pixels (v[3 px + c], cvt_chunk's order) of one output row at pixel `pix` of the tile's oh x ow output; nvalid of them
+// exist (1..4).  NCHW: `base` = the tile's plane 0, planes PO elements apart; NHWC: `base` = the tile's first element.
+template <int DT, int LAYOUT>
+__device__ __forceinline__ void store_view4(typename Elem<DT>::type* base, size_t PO, size_t pix, int nvalid, const float* v) {
+    typedef Elem<DT> E;
+    typedef typename E::type T;
+    if (nvalid == 4) {
+        if (LAYOUT == kLayNCHW) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float pl[4] = {v[c], v[3 + c], v[6 + c], v[9 + c]};
+                T* p = base + (size_t)c * PO + pix;
+                if (DT == kDtF32) {
+                    sl_u32x4u o; o.x = E::word(pl); o.y = E::word(pl + 1); o.z = E::word(pl + 2); o.w = E::word(pl + 3);
+                    *(SL_GLOBAL sl_u32x4u*)as_global((uint8_t*)p) = o;
+                } else {
+                    sl_u32x2u o; o.x = E::word(pl); o.y = E::word(pl + 2);
+                    *(SL_GLOBAL sl_u32x2u*)as_global((uint8_t*)p) = o;
+                }
+            }
+        } else {
+            uint8_t* p = (uint8_t*)(base + 3 * pix);
+            if (DT == kDtF32) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    sl_u32x4u o; o.x = E::word(v + 4 * k); o.y = E::word(v + 4 * k + 1); o.z = E::word(v + 4 * k + 2); o.w = E::word(v + 4 * k + 3);
+                    *(SL_GLOBAL sl_u32x4u*)as_global(p + 16 * k) = o;
+                }
+            } else {
+                sl_u32x4u o; o.x = E::word(v); o.y = E::word(v + 2); o.z = E::word(v + 4); o.w = E::word(v + 6);
+                *(SL_GLOBAL sl_u32x4u*)as_global(p) = o;
+                sl_u32x2u o2; o2.x = E::word(v + 8); o2.y = E::word(v + 10);
+                *(SL_GLOBAL sl_u32x2u*)as_global(p + 16) = o2;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int px = 0; px < 3; ++px) {
+            if (px < nvalid) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+                    as_global(base)[LAYOUT == kLayNCHW ? (size_t)c * PO + pix + px : 3 * (pix + px) + c] = E::one(v[3 * px + c]);
+            }
+        }
+    }
+}
+
+// DT: kDtU8 or a tensor type; LAYOUT: tensor only; MODE: kView*.  npx: patches per output row, npatch: per tile.
+template <int DT, int LAYOUT, int MODE>
+static __global__ __launch_bounds__(kWG) void k_view(const uint8_t* __restrict__ rgb, void* __restrict__ out, int h, int w, int oh, int ow,
+                                                     int npx, int npatch, const int32_t* __restrict__ windows, int d_mask,
+                                                     const double* __restrict__ M_src, const double* __restrict__ maxC_src,
+                                                     const double* M_tgt, const double* maxC_tgt, const double* __restrict__ alpha_beta,
+                                                     double lam, float ylimf, TensorK fmt) {
+    constexpr bool TENSOR = DT != kDtU8;
+    constexpr int SDT = TENSOR ? DT : kDtF32;
+    typedef typename Elem<SDT>::type T;
+    constexpr int B = kViewB, PITCH = kViewPitch;
+    static_assert(kWG == 256 && B == 64, "16 lanes x 4 pixels per row, 16 rows per pass, 4 passes");
+    __shared__ float2 s_tab[256];
+    __shared__ uint32_t s_px[B * PITCH];
+    if (MODE != kViewRaw) fill_gam_od_lut(s_tab);
+    const int tid = threadIdx.x;
+    const int lr = tid >> 4, lc = tid & 15;
+    const int tile = blockIdx.x / npatch, patch = blockIdx.x % npatch;
+    const int P = h * w;
+    const size_t nbytes = (size_t)P * 3;
+    const uint8_t* const src = rgb + (size_t)tile * nbytes;
+
+    // the view of this tile (block-uniform) and the source block of this patch
+    const int d = __builtin_amdgcn_readfirstlane(windows[3 * (size_t)tile + 2]) & d_mask;
+    const int k = d & 3;
+    const bool tr = k & 1, ry = (k >> 1) & 1, rx = ((k >> 1) ^ k ^ (d >> 2)) & 1;
+    const int wh = tr ? ow : oh, ww = tr ? oh : ow;
+    const int y0 = max(0, min(__builtin_amdgcn_readfirstlane(windows[3 * (size_t)tile + 0]), h - wh));
+    const int x0 = max(0, min(__builtin_amdgcn_readfirstlane(windows[3 * (size_t)tile + 1]), w - ww));
+    const int i0 = (patch / npx) * B, j0 = (patch % npx) * B;                  // the patch, in output pixels
+    const int bh = min(B, oh - i0), bw = min(B, ow - j0);
+    const int u0 = tr ? j0 : i0, nu = tr ? bw : bh;                           // its rows and columns in the (flipped, turned) window
+    const int v0 = tr ? i0 : j0, nv = tr ? bh : bw;
+    const int ys = y0 + (ry ? wh - u0 - nu : u0), xs = x0 + (rx ? ww - v0 - nv : v0);   // the source block: nu rows of nv pixels
+    // output pixel (il, jl) of the patch is LDS pixel a0 + il ai + jl aj
+    const int su = ry ? -PITCH : PITCH, sv = rx ? -1 : 1;
+    const int a0 = (ry ? (nu - 1) * PITCH : 0) + (rx ? nv - 1 : 0);
+    const int ai = tr ? sv : su, aj = tr ? su : sv;
+
+    // ---- read side: the four chunks of this lane, requested before any arithmetic
+    Chunk in[4];
+    {
+        const int cc = min(lc, (nv - 1) >> 2);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int r = min(16 * q + lr, nu - 1);
+            in[q] = load12(src, nbytes, 3 * ((size_t)(ys + r) * w + xs) + 12 * cc);
+        }
+    }
+    auto stage = [&](auto compute) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int r = 16 * q + lr;
+            uint32_t px[4];
+            compute(in[q], px);
+#pragma unroll
+            for (int p = 0; p < 4; ++p)
+                if (r < nu && 4 * lc + p < nv) s_px[r * PITCH + 4 * lc + p] = px[p];
+        }
+    };
+    auto unpack = [](const Chunk& o, uint32_t (&px)[4]) {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) px[p] = chunk_pixel(o, p) & 0xffffffu;
+    };
+    auto raw = [&](const Chunk& c, uint32_t (&px)[4]) { unpack(c, px); };
+
+    if (MODE == kViewRaw) {
+        stage(raw);
+    } else {
+        const ApplyTile<1> A(blockIdx.x, npatch, P, rgb, M_src, maxC_src, M_tgt, maxC_tgt, lam);
+        const ApplyK& K = A.K;
+        JitterK J;
+        if (MODE != kViewApply) {                                   // k_apply_jitter's constants
+            const double sc = 1.0 / A.unit;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                J.al[i] = in_vgpr(uni((float)alpha_beta[4 * (size_t)A.tile + 2 * i]));
+                J.be[i] = in_vgpr(uni((float)(alpha_beta[4 * (size_t)A.tile + 2 * i + 1] / (A.mct[i] / A.mcs[i]) * sc)));
+            }
+            J.ylimf = in_vgpr(ylimf);
+        }
+        __syncthreads();                                            // the table
+        if (SL_FIT_FAILED(A)) {                                     // the view of the source bytes
+            stage(raw);
+        } else if (MODE == kViewApply) {                            // k_apply: K.fast picks the lasso form and the cast
+            auto sweep = [&](auto fast_tag) {
+                constexpr bool FAST = decltype(fast_tag)::value;
+                stage([&](const Chunk& c, uint32_t (&px)[4]) {
+                    float t[12];
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) {
+                        const float x = s_tab[chunk_byte(c, 3 * p + 0)].y, y = s_tab[chunk_byte(c, 3 * p + 1)].y,
+                                    z = s_tab[chunk_byte(c, 3 * p + 2)].y;
+                        float v[3];
+                        apply_px<FAST>(K, x, y, z, v);
+                        t[3 * p] = v[0]; t[3 * p + 1] = v[1]; t[3 * p + 2] = v[2];
+                    }
+                    unpack(FAST ? pack_trunc_fast(t) : pack_trunc_general(t), px);
+                });
+            };
+            if (K.fast) sweep(std::true_type{}); else sweep(std::false_type{});
+        } else {                                                    // k_apply_jitter: g12 picks the lasso form, the cast saturates
+            auto sweep = [&](auto fast_tag) {
+                constexpr bool FAST = decltype(fast_tag)::value;
+                stage([&](const Chunk& c, uint32_t (&px)[4]) {
+                    float t[12];
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) {
+                        const float2 er = s_tab[chunk_byte(c, 3 * p + 0)];      // x = gamma, y = od32
+                        const float2 eg = s_tab[chunk_byte(c, 3 * p + 1)];
+                        const float2 eb = s_tab[chunk_byte(c, 3 * p + 2)];
+                        float c1, c2;
+                        apply_conc<FAST>(K, er.y, eg.y, eb.y, c1, c2);
+                        if (MODE == kViewJitAll) {
+                            c1 = fmaf(c1, J.al[0], J.be[0]);
+                            c2 = fmaf(c2, J.al[1], J.be[1]);
+                        } else {
+                            const bool tissue = is_tissue_f(er.x, eg.x, eb.x, J.ylimf);
+                            c1 = tissue ? fmaf(c1, J.al[0], J.be[0]) : c1;
+                            c2 = tissue ? fmaf(c2, J.al[1], J.be[1]) : c2;
+                        }
+#pragma unroll
+                        for (int ch = 0; ch < 3; ++ch)
+                            t[3 * p + ch] = 255.0f * __builtin_amdgcn_exp2f(fmaf(c1, K.q[0][ch], c2 * K.q[1][ch]));
+                    }
+                    unpack(pack_trunc_fast(t), px);
+                });
+            };
+            if (K.L.g12 >= 0.0f) sweep(std::true_type{}); else sweep(std::false_type{});
+        }
+    }
+    __syncthreads();
+
+    // ---- write side: output rows, 4 adjacent pixels per lane
+    const TensorK F = tensor_consts(fmt);
+    const size_t PO = (size_t)oh * ow;
+    const int jl = 4 * lc;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int il = 16 * q + lr;
+        const int row = a0 + min(il, bh - 1) * ai;
+        uint32_t px[4];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) px[p] = s_px[row + min(jl + p, bw - 1) * aj];
+        Chunk o;
+        o.w0 = px[0] | (px[1] << 24);
+        o.w1 = (px[1] >> 8) | (px[2] << 16);
+        o.w2 = (px[2] >> 16) | (px[3] << 8);
+        const int nvalid = min(4, bw - jl);
+        if (il < bh && nvalid > 0) {
+            const size_t pix = (size_t)(i0 + il) * ow + (j0 + jl);
+            if (TENSOR) {
+                float v[12];
+                cvt_chunk(o, F, v);
+                T* const base = (T*)out + (size_t)tile * 3 * PO;
+                store_view4<SDT, LAYOUT>(base, PO, pix, nvalid, v);
+            } else {
+                uint8_t* const p = (uint8_t*)out + ((size_t)tile * PO + pix) * 3;
+                if (nvalid == 4) {
+                    sl_u32x3u u; u.x = o.w0; u.y = o.w1; u.z = o.w2;
+                    *(SL_GLOBAL sl_u32x3u*)as_global(p) = u;
+                } else {
+                    for (int i = 0; i < 3 * nvalid; ++i) as_global(p)[i] = (uint8_t)chunk_byte(o, i);
+                }
+            }
+        }
+    }
+}
+
+}  // namespace sl

@@ -342,6 +342,122 @@ def normalize_jitter(rgb, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, augment_
     return out
 
 
+# ---- crop / flip / rot90 in the apply pass (sl_normalize_view; see include/stainlib_hip.h and stainlib_amd/tile_view.py) -------------------
+
+def _view_windows(windows, n, h, w, oh, ow, d_mask):
+    """The (n, 3) int32 windows of a normalize_view call (no device needed).  numpy / CPU windows are range-checked here (ValueError) and
+    come back as numpy; device windows are taken as they are -- the kernel masks the code and clamps the corner, nothing is read back."""
+    import numpy as np
+    if windows is None:
+        raise ValueError("windows must hold (y0, x0, d) per tile: an (N, 3) int32 array (TileView.draw)")
+    if isinstance(windows, torch.Tensor) and windows.is_cuda:
+        if not (windows.dtype == torch.int32 and tuple(windows.shape) == (n, 3) and windows.is_contiguous()):
+            raise ValueError(f"device windows must be a contiguous int32 tensor of shape ({n}, 3)")
+        return windows
+    try:
+        win = windows.numpy() if isinstance(windows, torch.Tensor) else np.asarray(windows)
+        if win.dtype.kind not in "iu":
+            raise TypeError
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError("windows must hold (y0, x0, d) per tile: an (N, 3) integer array") from None
+    if win.shape != (n, 3):
+        raise ValueError(f"windows must hold (y0, x0, d) per tile: an ({n}, 3) array, not one of shape {win.shape}")
+    win = win.astype(np.int64)
+    d = win[:, 2]
+    bad = (d < 0) | (d > 7) | ((d & ~int(d_mask)) != 0)
+    if bad.any():
+        raise ValueError(f"windows: tile {int(np.argmax(bad))} has the code {int(d[np.argmax(bad)])}, outside d_mask = {d_mask}")
+    odd = (d & 1) != 0
+    wh, ww = np.where(odd, ow, oh), np.where(odd, oh, ow)
+    bad = (win[:, 0] < 0) | (win[:, 0] > h - wh) | (win[:, 1] < 0) | (win[:, 1] > w - ww)
+    if bad.any():
+        t = int(np.argmax(bad))
+        raise ValueError(f"windows: tile {t} has its {int(wh[t])} x {int(ww[t])} window at ({int(win[t, 0])}, {int(win[t, 1])}), "
+                         f"outside the {h} x {w} tile")
+    return np.ascontiguousarray(win.astype(np.int32))
+
+
+def normalize_view(rgb, windows, size, d_mask=7, M_src=None, maxC_src=None, M_tgt=None, maxC_tgt=None, alpha_beta=None,
+                   augment_background=False, params=None, fmt=None, out=None):
+    """A crop, flip and quarter turn per tile INSIDE the apply pass (sl_normalize_view): per tile the window windows[t] = (y0, x0, d) of
+    the image that normalize_jitter (alpha_beta given), normalize_apply (M_src given) or nothing (M_src=None: the tiles' own bytes)
+    writes, flipped along the width when d & 4 and then turned d & 3 quarter turns counter-clockwise -- torch.rot90(torch.flip(
+    full[t][y0:y0+wh, x0:x0+ww], (1,)) if d & 4 else ..., d & 3, (0, 1)), bit for bit, without the pixels outside the window.
+    size: (oh, ow) of the OUTPUT, an int, or None (the full tile); a code with odd d & 3 takes an (ow, oh) window.
+    d_mask: the bits of d that count (7: everything; 6: no quarter turns -- the size need not fit transposed).
+    windows: (N, 3) int32 (TileView.draw).  numpy or CPU tensor: range-checked, ValueError.  Device tensor: taken as it is, the kernel
+    clamps every window into the tile; nothing is synchronised.
+    fmt: a stainlib_amd.TensorFormat -> the (N,3,oh,ow) tensor, else (N,oh,ow,3) uint8.  The statistics are the WHOLE tile's."""
+    from .tensor_format import TensorFormat
+    from .tile_view import check_size
+    if not (isinstance(rgb, torch.Tensor) and rgb.dim() == 4 and rgb.shape[-1] == 3):
+        raise ValueError("expected a contiguous CUDA uint8 tensor of shape (N, H, W, 3)")
+    n, h, w = (int(v) for v in rgb.shape[:3])
+    oh, ow = check_size(size, h, w, d_mask)
+    win = _view_windows(windows, n, h, w, oh, ow, d_mask)
+    if (M_tgt is None) != (maxC_tgt is None):
+        raise ValueError("M_tgt and maxC_tgt go together: both, or neither (no target)")
+    if M_src is None:
+        if not (maxC_src is None and M_tgt is None and alpha_beta is None):
+            raise ValueError("M_src=None is the view of the tiles' own bytes: maxC_src, M_tgt, maxC_tgt and alpha_beta must be None too")
+    elif maxC_src is None:
+        raise ValueError("M_src and maxC_src go together")
+    elif alpha_beta is None and M_tgt is None:
+        raise ValueError("without alpha_beta the view is normalize_apply's, which needs a target: pass M_tgt and maxC_tgt")
+    if alpha_beta is not None and _jitter_args(M_tgt, maxC_tgt, alpha_beta, None, None, None) != n:
+        raise ValueError(f"alpha_beta must have one row per tile ({n})")
+    if params is not None and not isinstance(params, _ffi.SlParams):
+        raise ValueError("params must be an SlParams (engine.make_params) or None")
+    if fmt is not None and not isinstance(fmt, TensorFormat):
+        raise ValueError("fmt must be a stainlib_amd.TensorFormat or None (the uint8 image)")
+    _check_tiles(rgb)
+    dev = rgb.device
+    if not isinstance(win, torch.Tensor):
+        win = torch.from_numpy(win).to(dev)
+    if win.device != dev:
+        raise ValueError(f"windows must be on {dev}")
+    if M_src is not None:
+        M_src = _f64(M_src, (n, 2, 3), dev)
+        maxC_src = _f64(maxC_src, (n, 2), dev)
+    if M_tgt is not None:
+        M_tgt = _f64(M_tgt, (2, 3), dev)
+        maxC_tgt = _f64(maxC_tgt, (2,), dev)
+    ab = _f64(alpha_beta, (n, 4), dev) if alpha_beta is not None else None
+    if fmt is None:
+        f = None
+        if out is None:
+            out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=dev)
+        elif not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and out.device == dev and tuple(out.shape) == (n, oh, ow, 3)
+                  and out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous uint8 tensor of shape {(n, oh, ow, 3)} on {dev}")
+        if out.data_ptr() == rgb.data_ptr():
+            raise ValueError("out must not be the input (no in-place view)")
+    else:
+        f, dtype, cl = _tensor_format(fmt)
+        out = _tensor_out(out, n, oh, ow, dtype, cl, dev)
+    _call("sl_normalize_view", _ptr(rgb), _ptr(out), n, h, w, oh, ow, _ptr(win), int(d_mask), _ptr(M_src), _ptr(maxC_src), _ptr(M_tgt),
+          _ptr(maxC_tgt), _ptr(ab), 1 if augment_background else 0, C.byref(params) if params is not None else None,
+          C.byref(f) if f is not None else None)
+    return out
+
+
+def _view_call(view, windows, tiles, draw=True):
+    """(size, d_mask, windows) of the view= / windows= pair of a batch method, checked without a device (ValueError): the windows as
+    given, or drawn (TileView.draw; draw=False: left None for a later call)."""
+    from .tile_view import TileView
+    if not isinstance(view, TileView):
+        raise ValueError("view must be a stainlib_amd.TileView" + (" (windows= goes with view=)" if view is None else ""))
+    if not (isinstance(tiles, torch.Tensor) and tiles.dim() == 4 and tiles.shape[-1] == 3):
+        raise ValueError("expected a contiguous CUDA uint8 tensor of shape (N, H, W, 3)")
+    n, h, w = (int(v) for v in tiles.shape[:3])
+    oh, ow = view.out_size(h, w)
+    if windows is not None:
+        _view_windows(windows, n, h, w, oh, ow, view.d_mask)
+    elif draw:
+        windows = view.draw(n, h, w)
+    return view.size, view.d_mask, windows
+
+
 def _fit(fn_name, op, rgb, params, ws, with_sweeps=False):
     n, h, w = _check_tiles(rgb)
     dev = rgb.device

@@ -146,16 +146,25 @@ class ExtractiveStainNormalizer(object):
         """Per-tile (M, maxC, status) device tensors for a batch of candidate targets."""
         return self._fit_tiles(tiles, ws=ws)
 
-    def transform_batch(self, tiles, out=None, ws=None, tensor_format=None, _tensor_route=None):
+    def transform_batch(self, tiles, out=None, ws=None, tensor_format=None, _tensor_route=None, view=None, windows=None):
         """(N,H,W,3) uint8 device tensor -> (out, M_src, maxC_src, status) device tensors.  A tile whose
         status is non-zero (1 = empty tissue mask, 2 = degenerate, 3 = a zero 99th-percentile concentration) is passed through unchanged.
         ``ws``: an ``engine.Workspace`` to reuse (ONE stream at a time); by default every call takes its scratch from
         torch's stream-ordered caching allocator, so concurrent streams / threads never share it.
         ``tensor_format``: a ``stainlib_amd.TensorFormat``; `out` is then the (N,3,H,W) tensor in that format -- bit for bit
-        ``tensor_format.convert`` of the uint8 result (a passed-through tile: of its source bytes)."""
+        ``tensor_format.convert`` of the uint8 result (a passed-through tile: of its source bytes).
+        ``view``: a ``stainlib_amd.TileView`` -- the unchanged fit of the WHOLE tiles, then ONE pass that writes per tile only the window
+        ``windows[t]`` (default: ``view.draw(N, H, W)``) of that result, flipped and turned (engine.normalize_view): `out` is
+        (N,oh,ow,3) uint8 or the (N,3,oh,ow) tensor, and the call returns (out, M_src, maxC_src, status, windows)."""
+        from .. import engine
+        if view is not None or windows is not None:
+            size, d_mask, windows = engine._view_call(view, windows, tiles)
+            M, maxC, status = self._fit_tiles(tiles, ws=ws)
+            M_t, c_t = self._target_on(tiles.device)
+            x = engine.normalize_view(tiles, windows, size, d_mask, M, maxC, M_t, c_t, fmt=tensor_format, out=out)
+            return x, M, maxC, status, windows
         if tensor_format is None:
             return self._transform_tiles(tiles, out=out, ws=ws)
-        from .. import engine
         route = _tensor_route or TENSOR_ROUTE
         if route == "fused":           # the fit, then the apply pass that converts its bytes in registers: no uint8 image
             M, maxC, status = self._fit_tiles(tiles, ws=ws)
@@ -187,20 +196,29 @@ class ExtractiveStainNormalizer(object):
         return sep, M, maxC, status
 
     # -- stain jitter in the apply pass (an extension: RandStainNA / StainAugmentor-style augmentation of the normalised tiles) ----
-    def augment_batch(self, tiles, alpha_beta, augment_background=False, normalize=True, out=None, ws=None, tensor_format=None):
+    def augment_batch(self, tiles, alpha_beta, augment_background=False, normalize=True, out=None, ws=None, tensor_format=None, view=None,
+                      windows=None):
         """(N,H,W,3) uint8 device tensor -> (out, M_src, maxC_src, status): the per-tile fit, then ONE pass that normalises every tile
         and perturbs its stains: C_i * alpha_i + beta_i on the normalised concentrations of tissue pixels (every pixel with
         ``augment_background``), under the target's stain matrix, clipped.  ``alpha_beta``: (N, 4) = alpha0, beta0, alpha1, beta1 per
         tile (``stainlib_amd.StainJitter(...).draw(N)``).  With alpha = 1, beta = 0 the result is transform_batch's.
         ``normalize=False``: no target (no fit() needed) -- every tile perturbed under its own stain matrix, a batched StainAugmentor.
         ``tensor_format``: a ``stainlib_amd.TensorFormat``; `out` is then the (N,3,H,W) tensor in that format, bit for bit
-        ``tensor_format.convert`` of the uint8 result.  A tile whose status is non-zero comes back as its own bytes (their conversion)."""
+        ``tensor_format.convert`` of the uint8 result.  A tile whose status is non-zero comes back as its own bytes (their conversion).
+        ``view``, ``windows``: as in transform_batch -- the crop / flip / quarter turn of every tile in the same pass; the call then
+        returns (out, M_src, maxC_src, status, windows)."""
         from .. import engine
         engine._jitter_args(None, None, alpha_beta, None, tensor_format, out)
         if normalize and not hasattr(self, "stain_matrix_target"):
             raise ValueError("augment_batch(normalize=True) needs a fitted target: call fit() first, or pass normalize=False")
+        if view is not None or windows is not None:
+            size, d_mask, windows = engine._view_call(view, windows, tiles)
         M, maxC, status = self._fit_tiles(tiles, ws=ws)
         M_t, c_t = self._target_on(tiles.device) if normalize else (None, None)
+        if view is not None:
+            x = engine.normalize_view(tiles, windows, size, d_mask, M, maxC, M_t, c_t, alpha_beta, augment_background, fmt=tensor_format,
+                                      out=out)
+            return x, M, maxC, status, windows
         x = engine.normalize_jitter(tiles, M, maxC, M_t, c_t, alpha_beta, augment_background, fmt=tensor_format, out=out)
         return x, M, maxC, status
 

@@ -55,10 +55,16 @@ class TensorFormat(object):
             raise ValueError(f"{what} must be three finite numbers, not {x!r}")
         return v
 
-    def convert(self, tiles_u8, out=None):
+    def convert(self, tiles_u8, out=None, view=None, windows=None):
         """(N, H, W, 3) uint8 device tensor -> (N, 3, H, W) tensor in this format (one streaming sweep, engine.to_tensor).
-        ``out``: a tensor of that shape, dtype and memory format to write into."""
+        ``out``: a tensor of that shape, dtype and memory format to write into.
+        ``view``: a ``stainlib_amd.TileView`` -- per tile only the window ``windows[t]`` (default: ``view.draw(N, H, W)``), flipped and
+        turned, converted in the same sweep (engine.normalize_view): the crop / flip / rot90 behind ANY uint8 result (Reinhard, HED,
+        luminosity ...).  Returns (the (N, 3, oh, ow) tensor, windows)."""
         from . import engine
+        if view is not None or windows is not None:
+            size, d_mask, windows = engine._view_call(view, windows, tiles_u8)
+            return engine.normalize_view(tiles_u8, windows, size, d_mask, fmt=self, out=out), windows
         return engine.to_tensor(tiles_u8, self, out=out)
 
     def __repr__(self):
