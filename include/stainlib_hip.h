@@ -638,6 +638,35 @@ SL_API int sl_normalize_jitter(const uint8_t* rgb, void* out, int n, int h, int 
  * capture-safe like the rest (no allocation, no synchronisation, no memset). */
 SL_API int sl_normalize_view(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, const double* alpha_beta, int augment_background, const SlParams* params, const SlTensorFormat* fmt, void* stream);
 
+/* ---- HED augmentation behind the apply pass, inside the view pass (stainlib_amd/csrc/hed_view.hip; an extension: a loader that normalises,
+ * HED-jitters (HedColorAugmenter, augmentation/augmenter.py:276-331), crops / flips and converts otherwise writes and re-reads two full-tile
+ * uint8 images, most of whose pixels the crop throws away) ---------------------------------------------------------------------------------
+ * In both calls full[t] is what sl_normalize_view defines by its pointer pattern: the h x w x 3 uint8 image that nothing (M_src == NULL: the
+ * source bytes), sl_normalize_apply (M_src and a target, no alpha_beta) or sl_normalize_jitter (alpha_beta, with or without a target,
+ * augment_background) writes for the WHOLE tile; a tile whose fit failed (NaN M_src, maxC_src <= 0) is its own bytes.
+ *
+ * sl_normalize_sums: HedColorAugmenter's cutoff test needs the mean of its whole input before any pixel is transformed; behind
+ * normalisation that input is an image nobody wants to write.  One read-only sweep (3 B/px read, n words written):
+ *     sums[t]    = the exact integer sum of the 3 h w bytes of full[t]   (uint64, device, 8-byte aligned; cleared by the call itself)
+ *     applied[t] = (cutoff_lo <= m && m <= cutoff_hi), m = (double)sums[t] / (3.0 * h w) / 255.0   (int32, device; may be NULL)
+ * -- sl_hed_augment's own test on its own sums, so applied equals what sl_hed_augment(full, ..) reports.  Integer atomics: the result does not
+ * depend on the order of the workgroups.  No workspace; capture-safe (no allocation, no synchronisation, no memset).
+ * SL_ERR_BADARG before anything is launched: what sl_normalize_view refuses of rgb, n, h, w, the statistics pattern and params; a NULL or
+ * misaligned sums; cutoff_lo <= cutoff_hi false (a NaN too; infinities are fine: -inf, +inf never fails). */
+SL_API int sl_normalize_sums(const uint8_t* rgb, int n, int h, int w, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, const double* alpha_beta, int augment_background, const SlParams* params, double cutoff_lo, double cutoff_hi, uint64_t* sums, int32_t* applied, void* stream);
+
+/* sl_normalize_hed_view: sl_normalize_view's parameters and its result -- the window, flip and quarter turn per tile, as the uint8 image or
+ * the tensor -- taken of
+ *     hed_applied[t] ? HED(full[t]) : full[t]
+ * where HED(.) is sl_hed_augment with hed_sigma[t], hed_bias[t] (n x 3 double each, device: H, E, D), skimage_mode and a cutoff that never
+ * fails: the bytes of that chain, bit for bit, without a pixel outside the window being read, computed or written.  The decision
+ * hed_applied (n int32, device) is an INPUT: sl_normalize_sums gives it, and a caller may overrule it between the two calls (the Python
+ * layer does, for a tile whose mean lies on a cutoff bound).
+ * skimage_mode: SL_HED_SKIMAGE_018 only.  The other three SL_HED_* modes are refused with SL_ERR_BADARG; use the chain for them.
+ * SL_ERR_BADARG before anything is launched: what sl_normalize_view refuses; a NULL hed_sigma, hed_bias or hed_applied; a skimage_mode
+ * outside the SL_HED_* range or other than SL_HED_SKIMAGE_018.  out == rgb is not supported.  No workspace; capture-safe like the rest. */
+SL_API int sl_normalize_hed_view(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, const double* alpha_beta, int augment_background, const SlParams* params, const SlTensorFormat* fmt, const double* hed_sigma, const double* hed_bias, const int32_t* hed_applied, int skimage_mode, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

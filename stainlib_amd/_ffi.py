@@ -175,6 +175,12 @@ _SIGNATURES = {
     # crop / flip / rot90 in the apply pass (windows: n x 3 int32 on the device; M_src, alpha_beta, SlParams, SlTensorFormat may be NULL)
     "sl_normalize_view": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, C.c_int,
                                     C.POINTER(SlParams), C.POINTER(SlTensorFormat), _P]),
+    # HED augmentation behind the apply pass: the byte sums of the image a route would write (sums: n uint64, applied: n int32 or NULL, both
+    # on the device), and the view pass with the HED stage (sl_normalize_view's parameters, then sigma, bias, applied, skimage_mode)
+    "sl_normalize_sums": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, C.POINTER(SlParams), C.c_double, C.c_double,
+                                    _P, _P, _P]),
+    "sl_normalize_hed_view": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, C.c_int,
+                                        C.POINTER(SlParams), C.POINTER(SlTensorFormat), _P, _P, _P, C.c_int, _P]),
 }
 POOL_STATE_DOUBLES, POOL_M, POOL_MAXC, POOL_STATUS, POOL_MISS = 64, 0, 6, 8, 9
 POOL2_STATE_DOUBLES, POOL2_HIST_WORDS, POOL2_WHY = 256, 2 * 8192 + 8 * 32, 33

@@ -5,7 +5,8 @@ users peek at (``_sigmas``, ``_biases``, ``_sigma_ranges``, ``_bias_ranges``, ``
 range validation and its ``InvalidRangeError`` titles, the order in which ``randomize()`` / ``pop()``
 consume the GLOBAL ``np.random`` stream, and the "un-randomized augmenter applies the lower bounds"
 quirk (augmenter.py:194-198, 246-250).  The arithmetic is ``sl_hed_augment`` / ``sl_stain_augment``
-(``sl_normalize_jitter`` for the batched ``StainAugmentor.augment_batch``).
+(``sl_normalize_jitter`` for the batched ``StainAugmentor.augment_batch``; ``sl_normalize_sums`` + ``sl_normalize_hed_view`` for
+``HedColorAugmenter.transform_batch(view=)`` and the ``hed=`` stage of the batch methods).
 """
 from __future__ import annotations
 
@@ -120,12 +121,25 @@ class HedColorAugmenter(ColorAugmenterBase):
             return patch                                              # augmenter.py:331
         return out[0].cpu().numpy()
 
-    def transform_batch(self, tiles, sigmas=None, biases=None, out=None, tensor_format=None):
+    def transform_batch(self, tiles, sigmas=None, biases=None, out=None, tensor_format=None, view=None, windows=None):
         """Batched extension: (N,H,W,3) uint8 device tensor; per-tile (N,3) sigmas / biases (defaults: the
         augmenter's current ones for every tile).  Returns (out, applied).
         ``tensor_format``: a ``stainlib_amd.TensorFormat``; `out` is then the (N,3,H,W) tensor in that format (the augmentation writes
-        a uint8 scratch, ``tensor_format.convert`` reads it)."""
+        a uint8 scratch, ``tensor_format.convert`` reads it).
+        ``view``: a ``stainlib_amd.TileView`` -- per tile only the window ``windows[t]`` (default: ``view.draw(N, H, W)``) of that result,
+        flipped and turned: a read-only pass for the cutoff test (engine.normalize_sums), then ONE pass that transforms, crops and
+        converts (engine.normalize_hed_view), bit for bit ``tensor_format.convert(transform_batch(tiles, ...)[0], view=view,
+        windows=windows)``.  Returns (out, applied, windows)."""
         from .. import engine
+        if view is not None or windows is not None:
+            engine._view_call(view, windows, tiles, draw=False)
+            n = int(tiles.shape[0])
+            sigmas = [self._sigmas] * n if sigmas is None else sigmas
+            biases = [self._biases] * n if biases is None else biases
+            engine._hed_call(self, sigmas, biases, tiles)
+            engine._check_tiles(tiles)
+            x, windows, draw = engine.hed_stage(tiles, self, sigmas, biases, view, windows, {}, fmt=tensor_format, out=out)
+            return x, draw.applied, windows
         if tensor_format is not None:
             u8, applied = self.transform_batch(tiles, sigmas, biases)
             return tensor_format.convert(u8, out=out), applied
@@ -248,7 +262,7 @@ class StainAugmentor(object):
         out = engine.stain_augment(self._dev, self.stain_matrix[None], [alpha_beta], self.augment_background)
         return out[0].cpu().numpy()
 
-    def augment_batch(self, tiles, alpha_beta=None, tensor_format=None, view=None, windows=None):
+    def augment_batch(self, tiles, alpha_beta=None, tensor_format=None, view=None, windows=None, hed=None, hed_sigmas=None, hed_biases=None):
         """Batched extension: (N,H,W,3) uint8 device tensor -> (out, M, maxC, status) device tensors: every tile perturbed under its OWN
         stain matrix (this augmentor's extractor, fitted per tile) -- n fit() / pop() pairs in one fit and ONE pass, nothing through the
         host.  alpha_beta: (N, 4) = alpha0, beta0, alpha1, beta1 per tile; by default drawn from the global numpy stream exactly as N
@@ -257,12 +271,18 @@ class StainAugmentor(object):
         ``view``: a ``stainlib_amd.TileView`` -- per tile only the window ``windows[t]`` of that result, flipped and turned, from the
         same pass (engine.normalize_view); `out` is (N,oh,ow,3) or (N,3,oh,ow) and the call returns (out, M, maxC, status, windows).
         ``windows`` defaults to ``view.draw(N, H, W)``, drawn AFTER the alpha_beta of the call.
+        ``hed``: a ``HedColorAugmenter`` -- its transform (ranges, cutoff, skimage_mode) on every perturbed tile, in the SAME pass as the
+        view and the conversion (engine.normalize_sums for its cutoff test, then engine.normalize_hed_view): bit for bit
+        ``hed.transform_batch`` of the result above, then the view.  ``hed_sigmas``, ``hed_biases``: (N, 3) each; by default
+        ``hed.randomize_batch(N)``, drawn after alpha_beta and BEFORE the windows.  The call then returns one more element at the end,
+        ``engine.HedDraw(sigmas, biases, applied)``.
         fit() / pop() are untouched by it."""
         from .. import engine
         jitter = StainJitter(self.sigma1, self.sigma2, self.augment_background)
         engine._jitter_args(None, None, alpha_beta if alpha_beta is not None else np.empty((0, 4)), None, tensor_format, None)
         if view is not None or windows is not None:
             engine._view_call(view, windows, tiles, draw=False)
+        with_hed = engine._hed_call(hed, hed_sigmas, hed_biases, tiles)
         n, h, w = engine._check_tiles(tiles)
         if self._method == "macenko":
             M, maxC, status = engine.macenko_fit(tiles)
@@ -270,6 +290,10 @@ class StainAugmentor(object):
             M, maxC, status, _ = engine.vahadane_fit(tiles)
         if alpha_beta is None:
             alpha_beta = jitter.draw(n)
+        if with_hed:
+            route = dict(M_src=M, maxC_src=maxC, alpha_beta=alpha_beta, augment_background=self.augment_background)
+            out, windows, draw = engine.hed_stage(tiles, hed, hed_sigmas, hed_biases, view, windows, route, fmt=tensor_format)
+            return (out, M, maxC, status) + ((windows,) if view is not None else ()) + (draw,)
         if view is not None or windows is not None:
             size, d_mask, windows = engine._view_call(view, windows, tiles)
             out = engine.normalize_view(tiles, windows, size, d_mask, M, maxC, None, None, alpha_beta, self.augment_background,

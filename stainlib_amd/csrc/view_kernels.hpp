@@ -7,6 +7,7 @@
 // Definition (include/stainlib_hip.h, sl_normalize_view): the result is "the same bits, elsewhere" -- the tensor value is defined on
 // the truncated byte and a dihedral transform is a permutation -- so the pixel arithmetic below is k_apply's / k_apply_jitter's
 // statement for statement (apply_consts, apply_px, apply_conc, the two casts, JitterK, is_tissue_f, cvt_chunk) on the same constants.
+// The kernel's body is view_body: k_view instantiates it as it stands, k_hed_view (hed_view_kernels.hpp) with the HED stage.
 //
 // Shape: ONE workgroup = one tile and one patch of kViewB x kViewB OUTPUT pixels.  The dihedral code (block-uniform, read once, a
 // run-time value) decides which kViewB x kViewB block of the source window that is; the two sides meet in LDS:
@@ -104,13 +105,27 @@ __device__ __forceinline__ void store_view4(typename Elem<DT>::type* base, size_
     }
 }
 
-// DT: kDtU8 or a tensor type; LAYOUT: tensor only; MODE: kView*.  npx: patches per output row, npatch: per tile.
-template <int DT, int LAYOUT, int MODE>
-static __global__ __launch_bounds__(kWG) void k_view(const uint8_t* __restrict__ rgb, void* __restrict__ out, int h, int w, int oh, int ow,
-                                                     int npx, int npatch, const int32_t* __restrict__ windows, int d_mask,
-                                                     const double* __restrict__ M_src, const double* __restrict__ maxC_src,
-                                                     const double* M_tgt, const double* maxC_tgt, const double* __restrict__ alpha_beta,
-                                                     double lam, float ylimf, TensorK fmt) {
+// A further stage between the truncation to bytes and the LDS write, on the four packed pixels `stage` holds.  HED = 0: none -- the
+// primary template is empty and k_view's code is what it was without it (tools/isa_diff.py); HED = 1: the HED augmentation of
+// sl_normalize_hed_view (hed_view_kernels.hpp specialises it; its arguments arrive in HedViewArgs).
+struct HedViewArgs {
+    const double *sigma, *bias;      // n x 3 each (device)
+    const int32_t* applied;          // n (device): the tile takes the stage or not
+    double H[9], R[9];               // hed_from_rgb, rgb_from_hed (row-major)
+};
+template <int HED>
+struct HedStage {
+    __device__ __forceinline__ void init(int, int, const HedViewArgs*) {}
+    __device__ __forceinline__ void apply(uint32_t (&)[4]) const {}
+};
+
+// DT: kDtU8 or a tensor type; LAYOUT: tensor only; MODE: kView*; HED: the stage above.  npx: patches per output row, npatch: per tile.
+template <int DT, int LAYOUT, int MODE, int HED>
+__device__ __forceinline__ void view_body(const uint8_t* rgb, void* out, int h, int w, int oh, int ow,
+                                          int npx, int npatch, const int32_t* windows, int d_mask,
+                                          const double* M_src, const double* maxC_src,
+                                          const double* M_tgt, const double* maxC_tgt, const double* alpha_beta,
+                                          double lam, float ylimf, TensorK fmt, const HedViewArgs* hv) {
     constexpr bool TENSOR = DT != kDtU8;
     constexpr int SDT = TENSOR ? DT : kDtF32;
     typedef typename Elem<SDT>::type T;
@@ -125,6 +140,8 @@ static __global__ __launch_bounds__(kWG) void k_view(const uint8_t* __restrict__
     const int P = h * w;
     const size_t nbytes = (size_t)P * 3;
     const uint8_t* const src = rgb + (size_t)tile * nbytes;
+    HedStage<HED> hed;
+    hed.init(tid, tile, hv);
 
     // the view of this tile (block-uniform) and the source block of this patch
     const int d = __builtin_amdgcn_readfirstlane(windows[3 * (size_t)tile + 2]) & d_mask;
@@ -159,6 +176,7 @@ static __global__ __launch_bounds__(kWG) void k_view(const uint8_t* __restrict__
             const int r = 16 * q + lr;
             uint32_t px[4];
             compute(in[q], px);
+            hed.apply(px);
 #pragma unroll
             for (int p = 0; p < 4; ++p)
                 if (r < nu && 4 * lc + p < nv) s_px[r * PITCH + 4 * lc + p] = px[p];
@@ -171,6 +189,7 @@ static __global__ __launch_bounds__(kWG) void k_view(const uint8_t* __restrict__
     auto raw = [&](const Chunk& c, uint32_t (&px)[4]) { unpack(c, px); };
 
     if (MODE == kViewRaw) {
+        if (HED != 0) __syncthreads();                              // the stage's table
         stage(raw);
     } else {
         const ApplyTile<1> A(blockIdx.x, npatch, P, rgb, M_src, maxC_src, M_tgt, maxC_tgt, lam);
@@ -271,6 +290,16 @@ static __global__ __launch_bounds__(kWG) void k_view(const uint8_t* __restrict__
             }
         }
     }
+}
+
+template <int DT, int LAYOUT, int MODE>
+static __global__ __launch_bounds__(kWG) void k_view(const uint8_t* __restrict__ rgb, void* __restrict__ out, int h, int w, int oh, int ow,
+                                                     int npx, int npatch, const int32_t* __restrict__ windows, int d_mask,
+                                                     const double* __restrict__ M_src, const double* __restrict__ maxC_src,
+                                                     const double* M_tgt, const double* maxC_tgt, const double* __restrict__ alpha_beta,
+                                                     double lam, float ylimf, TensorK fmt) {
+    view_body<DT, LAYOUT, MODE, 0>(rgb, out, h, w, oh, ow, npx, npatch, windows, d_mask, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, lam,
+                                   ylimf, fmt, nullptr);
 }
 
 }  // namespace sl

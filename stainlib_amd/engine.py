@@ -6,6 +6,7 @@ device tensors without synchronising.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 
 import torch
@@ -377,17 +378,10 @@ def _view_windows(windows, n, h, w, oh, ow, d_mask):
     return np.ascontiguousarray(win.astype(np.int32))
 
 
-def normalize_view(rgb, windows, size, d_mask=7, M_src=None, maxC_src=None, M_tgt=None, maxC_tgt=None, alpha_beta=None,
-                   augment_background=False, params=None, fmt=None, out=None):
-    """A crop, flip and quarter turn per tile INSIDE the apply pass (sl_normalize_view): per tile the window windows[t] = (y0, x0, d) of
-    the image that normalize_jitter (alpha_beta given), normalize_apply (M_src given) or nothing (M_src=None: the tiles' own bytes)
-    writes, flipped along the width when d & 4 and then turned d & 3 quarter turns counter-clockwise -- torch.rot90(torch.flip(
-    full[t][y0:y0+wh, x0:x0+ww], (1,)) if d & 4 else ..., d & 3, (0, 1)), bit for bit, without the pixels outside the window.
-    size: (oh, ow) of the OUTPUT, an int, or None (the full tile); a code with odd d & 3 takes an (ow, oh) window.
-    d_mask: the bits of d that count (7: everything; 6: no quarter turns -- the size need not fit transposed).
-    windows: (N, 3) int32 (TileView.draw).  numpy or CPU tensor: range-checked, ValueError.  Device tensor: taken as it is, the kernel
-    clamps every window into the tile; nothing is synchronised.
-    fmt: a stainlib_amd.TensorFormat -> the (N,3,oh,ow) tensor, else (N,oh,ow,3) uint8.  The statistics are the WHOLE tile's."""
+def _view_prepare(rgb, windows, size, d_mask, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, params, fmt, out, before_device=None):
+    """The checks of normalize_view (ValueError, in its order, nothing on the device before they pass; before_device(n): a caller's own
+    checks at the end of them) and its arguments on the device -> (n, h, w, oh, ow, windows, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta,
+    SlTensorFormat or None, out)."""
     from .tensor_format import TensorFormat
     from .tile_view import check_size
     if not (isinstance(rgb, torch.Tensor) and rgb.dim() == 4 and rgb.shape[-1] == 3):
@@ -410,6 +404,8 @@ def normalize_view(rgb, windows, size, d_mask=7, M_src=None, maxC_src=None, M_tg
         raise ValueError("params must be an SlParams (engine.make_params) or None")
     if fmt is not None and not isinstance(fmt, TensorFormat):
         raise ValueError("fmt must be a stainlib_amd.TensorFormat or None (the uint8 image)")
+    if before_device is not None:
+        before_device(n)
     _check_tiles(rgb)
     dev = rgb.device
     if not isinstance(win, torch.Tensor):
@@ -435,10 +431,204 @@ def normalize_view(rgb, windows, size, d_mask=7, M_src=None, maxC_src=None, M_tg
     else:
         f, dtype, cl = _tensor_format(fmt)
         out = _tensor_out(out, n, oh, ow, dtype, cl, dev)
+    return n, h, w, oh, ow, win, M_src, maxC_src, M_tgt, maxC_tgt, ab, f, out
+
+
+def normalize_view(rgb, windows, size, d_mask=7, M_src=None, maxC_src=None, M_tgt=None, maxC_tgt=None, alpha_beta=None,
+                   augment_background=False, params=None, fmt=None, out=None):
+    """A crop, flip and quarter turn per tile INSIDE the apply pass (sl_normalize_view): per tile the window windows[t] = (y0, x0, d) of
+    the image that normalize_jitter (alpha_beta given), normalize_apply (M_src given) or nothing (M_src=None: the tiles' own bytes)
+    writes, flipped along the width when d & 4 and then turned d & 3 quarter turns counter-clockwise -- torch.rot90(torch.flip(
+    full[t][y0:y0+wh, x0:x0+ww], (1,)) if d & 4 else ..., d & 3, (0, 1)), bit for bit, without the pixels outside the window.
+    size: (oh, ow) of the OUTPUT, an int, or None (the full tile); a code with odd d & 3 takes an (ow, oh) window.
+    d_mask: the bits of d that count (7: everything; 6: no quarter turns -- the size need not fit transposed).
+    windows: (N, 3) int32 (TileView.draw).  numpy or CPU tensor: range-checked, ValueError.  Device tensor: taken as it is, the kernel
+    clamps every window into the tile; nothing is synchronised.
+    fmt: a stainlib_amd.TensorFormat -> the (N,3,oh,ow) tensor, else (N,oh,ow,3) uint8.  The statistics are the WHOLE tile's."""
+    n, h, w, oh, ow, win, M_src, maxC_src, M_tgt, maxC_tgt, ab, f, out = _view_prepare(
+        rgb, windows, size, d_mask, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, params, fmt, out)
     _call("sl_normalize_view", _ptr(rgb), _ptr(out), n, h, w, oh, ow, _ptr(win), int(d_mask), _ptr(M_src), _ptr(maxC_src), _ptr(M_tgt),
           _ptr(maxC_tgt), _ptr(ab), 1 if augment_background else 0, C.byref(params) if params is not None else None,
           C.byref(f) if f is not None else None)
     return out
+
+
+# ---- HED augmentation behind the apply pass (sl_normalize_sums, sl_normalize_hed_view; see include/stainlib_hip.h) ------------------------
+
+HedDraw = collections.namedtuple("HedDraw", ["sigmas", "biases", "applied"])
+HedDraw.__doc__ = """What the hed= stage of a batch method did: the (N, 3) sigmas and biases it used (given or drawn) and applied, the (N,)
+int32 device tensor of the cutoff test's decisions (0: the tile came back without the HED transform)."""
+
+
+def _route_check(M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, params):
+    """normalize_view's checks of the arguments that name `full` (no device needed) -> the rows of alpha_beta, or None."""
+    if (M_tgt is None) != (maxC_tgt is None):
+        raise ValueError("M_tgt and maxC_tgt go together: both, or neither (no target)")
+    if M_src is None:
+        if not (maxC_src is None and M_tgt is None and alpha_beta is None):
+            raise ValueError("M_src=None is the view of the tiles' own bytes: maxC_src, M_tgt, maxC_tgt and alpha_beta must be None too")
+    elif maxC_src is None:
+        raise ValueError("M_src and maxC_src go together")
+    elif alpha_beta is None and M_tgt is None:
+        raise ValueError("without alpha_beta the view is normalize_apply's, which needs a target: pass M_tgt and maxC_tgt")
+    n_ab = _jitter_args(M_tgt, maxC_tgt, alpha_beta, None, None, None) if alpha_beta is not None else None
+    if params is not None and not isinstance(params, _ffi.SlParams):
+        raise ValueError("params must be an SlParams (engine.make_params) or None")
+    return n_ab
+
+
+def _cutoff(cutoff):
+    try:
+        lo, hi = (float(v) for v in cutoff)
+    except (TypeError, ValueError):
+        raise ValueError("cutoff must be a pair (lo, hi) with lo <= hi") from None
+    if not lo <= hi:
+        raise ValueError("cutoff must be a pair (lo, hi) with lo <= hi")
+    return lo, hi
+
+
+def normalize_sums(rgb, M_src=None, maxC_src=None, M_tgt=None, maxC_tgt=None, alpha_beta=None, augment_background=False, params=None,
+                   cutoff=(0.05, 0.95)):
+    """The exact byte sums of the image an apply-pass route WOULD write, without writing it (sl_normalize_sums: 3 B/px read) ->
+    (sums (N,) int64, applied (N,) int32).  The route is normalize_view's: nothing (M_src=None: the tiles' own bytes), normalize_apply
+    (M_src and a target) or normalize_jitter (alpha_beta).  applied[t] = cutoff[0] <= sums[t] / (3 H W) / 255 <= cutoff[1]: what
+    hed_augment(full, ..., cutoff=cutoff) reports for that image."""
+    n_ab = _route_check(M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, params)
+    lo, hi = _cutoff(cutoff)
+    if n_ab is not None and isinstance(rgb, torch.Tensor) and rgb.dim() == 4 and n_ab != rgb.shape[0]:
+        raise ValueError(f"alpha_beta must have one row per tile ({rgb.shape[0]})")
+    n, h, w = _check_tiles(rgb)
+    dev = rgb.device
+    if M_src is not None:
+        M_src = _f64(M_src, (n, 2, 3), dev)
+        maxC_src = _f64(maxC_src, (n, 2), dev)
+    if M_tgt is not None:
+        M_tgt = _f64(M_tgt, (2, 3), dev)
+        maxC_tgt = _f64(maxC_tgt, (2,), dev)
+    ab = _f64(alpha_beta, (n, 4), dev) if alpha_beta is not None else None
+    sums = torch.empty((n,), dtype=torch.int64, device=dev)
+    applied = torch.empty((n,), dtype=torch.int32, device=dev)
+    _call("sl_normalize_sums", _ptr(rgb), n, h, w, _ptr(M_src), _ptr(maxC_src), _ptr(M_tgt), _ptr(maxC_tgt), _ptr(ab),
+          1 if augment_background else 0, C.byref(params) if params is not None else None, lo, hi, _ptr(sums), _ptr(applied))
+    return sums, applied
+
+
+def _full_image(rgb, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, augment_background, params):
+    """`full` of a view route, materialised by the existing entry point (the chain the fused passes are defined by)."""
+    if M_src is None:
+        return rgb
+    if alpha_beta is None:
+        lam = params.lasso_lambda if params is not None else _ffi.default_params().lasso_lambda
+        return normalize_apply(rgb, M_src, maxC_src, M_tgt, maxC_tgt, lasso_lambda=lam)
+    return normalize_jitter(rgb, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, augment_background, params=params)
+
+
+def _hed_rows(x, what):
+    """The rows of an (N, 3) sigma / bias argument (no device needed)."""
+    import numpy as np
+    try:
+        shape = tuple(x.shape) if isinstance(x, torch.Tensor) else np.asarray(x, dtype=np.float64).shape
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must hold (H, E, D) per tile: an (N, 3) array") from None
+    if len(shape) != 2 or shape[1] != 3:
+        raise ValueError(f"{what} must hold (H, E, D) per tile: an (N, 3) array, not one of shape {shape}")
+    return shape[0]
+
+
+def normalize_hed_view(rgb, windows, size, d_mask, hed_sigma, hed_bias, hed_applied, skimage_mode=0, M_src=None, maxC_src=None, M_tgt=None,
+                       maxC_tgt=None, alpha_beta=None, augment_background=False, params=None, fmt=None, out=None):
+    """normalize_view of hed_applied[t] ? HED(full[t]) : full[t] in ONE pass (sl_normalize_hed_view): `full` is normalize_view's (the
+    route arguments are the same), HED(.) is hed_augment with the tile's hed_sigma / hed_bias ((N, 3) each), skimage_mode and a cutoff that
+    never fails -- bit for bit hed_augment then normalize_view of the result, without a pixel outside the window being touched.
+    hed_applied: (N,) int32, the decision per tile (normalize_sums gives it).
+    skimage_mode 0 ("0.18", the pinned one) runs in the kernel; the other three go through that chain (same bits, two more passes)."""
+    def hed_checks(n):
+        for x, what in ((hed_sigma, "hed_sigma"), (hed_bias, "hed_bias")):
+            if _hed_rows(x, what) != n:
+                raise ValueError(f"{what} must have one row per tile ({n})")
+        if skimage_mode not in (_ffi.HED_SKIMAGE_018, _ffi.HED_SKIMAGE_019, _ffi.HED_SKIMAGE_017, _ffi.HED_EXPERIMENTAL_LOG10):
+            raise ValueError("skimage_mode must be one of the HED_* modes (0..3)")
+        if hed_applied is None:
+            raise ValueError("hed_applied must hold the decision per tile: (N,) int32 (normalize_sums)")
+    n, h, w, oh, ow, win, M_src, maxC_src, M_tgt, maxC_tgt, ab, f, out = _view_prepare(
+        rgb, windows, size, d_mask, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, params, fmt, out, before_device=hed_checks)
+    dev = rgb.device
+    sigma = _f64(hed_sigma, (n, 3), dev)
+    bias = _f64(hed_bias, (n, 3), dev)
+    applied = torch.as_tensor(hed_applied, device=dev).to(torch.int32).reshape(n).contiguous()
+    if skimage_mode != _ffi.HED_SKIMAGE_018:                 # the chain itself
+        full = _full_image(rgb, M_src, maxC_src, M_tgt, maxC_tgt, ab, augment_background, params)
+        aug, _ = hed_augment(full, sigma, bias, cutoff=(-float("inf"), float("inf")), skimage_mode=skimage_mode)
+        img = torch.where((applied != 0).view(n, 1, 1, 1), aug, full)
+        return normalize_view(img, win, size, d_mask, fmt=fmt, out=out)
+    _call("sl_normalize_hed_view", _ptr(rgb), _ptr(out), n, h, w, oh, ow, _ptr(win), int(d_mask), _ptr(M_src), _ptr(maxC_src), _ptr(M_tgt),
+          _ptr(maxC_tgt), _ptr(ab), 1 if augment_background else 0, C.byref(params) if params is not None else None,
+          C.byref(f) if f is not None else None, _ptr(sigma), _ptr(bias), _ptr(applied), int(skimage_mode))
+    return out
+
+
+def _hed_call(hed, hed_sigmas, hed_biases, tiles):
+    """The hed= / hed_sigmas= / hed_biases= arguments of a batch method, checked without a device (ValueError).  True when the call has a
+    HED stage."""
+    from .augmentation.augmenter import HedColorAugmenter
+    if hed is None:
+        if hed_sigmas is not None or hed_biases is not None:
+            raise ValueError("hed_sigmas= and hed_biases= go with hed= (a HedColorAugmenter)")
+        return False
+    if not isinstance(hed, HedColorAugmenter):
+        raise ValueError("hed must be a stainlib_amd HedColorAugmenter (its ranges, cutoff and skimage_mode are used)")
+    if (hed_sigmas is None) != (hed_biases is None):
+        raise ValueError("hed_sigmas and hed_biases go together: both, or neither (drawn: hed.randomize_batch)")
+    if not (isinstance(tiles, torch.Tensor) and tiles.dim() == 4 and tiles.shape[-1] == 3):
+        raise ValueError("expected a contiguous CUDA uint8 tensor of shape (N, H, W, 3)")
+    n = int(tiles.shape[0])
+    for x, what in ((hed_sigmas, "hed_sigmas"), (hed_biases, "hed_biases")):
+        if x is not None and _hed_rows(x, what) != n:
+            raise ValueError(f"{what} must have one row per tile ({n})")
+    return True
+
+
+def hed_decide(tiles, cutoff, M_src=None, maxC_src=None, M_tgt=None, maxC_tgt=None, alpha_beta=None, augment_background=False, params=None):
+    """HedColorAugmenter's cutoff decision per tile for the image a route would write -> applied (N,) int32 on the device: normalize_sums,
+    then the knife-edge rule of HedColorAugmenter.transform_batch -- a tile whose EXACT mean lies within _CUTOFF_BAND of a bound is
+    decided by the reference's own float32 mean (augmenter.py:291-293) on the host; only for such a tile is `full` materialised (that one
+    tile, by the existing entry point).  One 8-byte-per-tile read-back per call."""
+    import numpy as np
+    from .augmentation.augmenter import _CUTOFF_BAND
+    lo, hi = _cutoff(cutoff)
+    sums, applied = normalize_sums(tiles, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, augment_background, params, cutoff=(lo, hi))
+    n, h, w = (int(v) for v in tiles.shape[:3])
+    exact = sums.to(torch.float64) / float(h * w * 3) / 255.0
+    band = _CUTOFF_BAND * max(abs(lo), abs(hi), 1e-30)
+    near = torch.nonzero(torch.minimum((exact - lo).abs(), (exact - hi).abs()) <= band).reshape(-1).tolist()
+    for i in near:
+        one = lambda x: x[i:i + 1] if x is not None else None        # noqa: E731
+        ab = None if alpha_beta is None else _f64(alpha_beta, (n, 4), tiles.device)
+        Ms = None if M_src is None else _f64(M_src, (n, 2, 3), tiles.device)
+        mcs = None if maxC_src is None else _f64(maxC_src, (n, 2), tiles.device)
+        patch = _full_image(tiles[i:i + 1], one(Ms), one(mcs), M_tgt, maxC_tgt, one(ab), augment_background, params)[0].cpu().numpy()
+        ref_mean = np.mean(a=patch.astype(dtype=np.float32)) / 255.0
+        applied[i] = 1 if bool(lo <= ref_mean <= hi) else 0
+    return applied
+
+
+def hed_stage(tiles, hed, hed_sigmas, hed_biases, view, windows, route, fmt=None, out=None):
+    """The hed= stage of the batch methods, behind their fit and their own draws, on arguments _hed_call / _view_call(draw=False) have
+    accepted: the draws the caller left open -- hed.randomize_batch(N), THEN view.draw --, the cutoff decision (hed_decide) and ONE fused
+    pass (normalize_hed_view).  route: normalize_view's keyword arguments that name `full` ({}: the tiles themselves).  Without a view
+    the result is the full tile, code 0.  -> (out, windows or None, HedDraw)."""
+    import numpy as np
+    n = int(tiles.shape[0])
+    if hed_sigmas is None:
+        hed_sigmas, hed_biases = hed.randomize_batch(n)
+    if view is not None:
+        size, d_mask, windows = _view_call(view, windows, tiles)
+        win = windows
+    else:
+        size, d_mask, windows, win = None, 0, None, np.zeros((n, 3), dtype=np.int32)
+    applied = hed_decide(tiles, hed._cutoff_range, **route)
+    x = normalize_hed_view(tiles, win, size, d_mask, hed_sigmas, hed_biases, applied, hed._skimage_mode, fmt=fmt, out=out, **route)
+    return x, windows, HedDraw(hed_sigmas, hed_biases, applied)
 
 
 def _view_call(view, windows, tiles, draw=True):

@@ -146,7 +146,22 @@ class ExtractiveStainNormalizer(object):
         """Per-tile (M, maxC, status) device tensors for a batch of candidate targets."""
         return self._fit_tiles(tiles, ws=ws)
 
-    def transform_batch(self, tiles, out=None, ws=None, tensor_format=None, _tensor_route=None, view=None, windows=None):
+    def _hed_batch(self, tiles, hed, hed_sigmas, hed_biases, view, windows, out, ws, tensor_format, target, jitter=None):
+        """The hed= route of transform_batch / augment_batch (arguments already accepted by engine._hed_call): the checks that are left,
+        the fit, then engine.hed_stage -- its draws, the read-only sums pass for the cutoff test and ONE pass that normalises (and
+        perturbs), HED-transforms, crops / flips and converts.  -> (out, M_src, maxC_src, status[, windows], HedDraw)."""
+        from .. import engine
+        if view is not None or windows is not None:
+            engine._view_call(view, windows, tiles, draw=False)
+        engine._check_tiles(tiles)
+        M, maxC, status = self._fit_tiles(tiles, ws=ws)
+        M_t, c_t = self._target_on(tiles.device) if target else (None, None)
+        route = dict(M_src=M, maxC_src=maxC, M_tgt=M_t, maxC_tgt=c_t, **(jitter or {}))
+        x, windows, draw = engine.hed_stage(tiles, hed, hed_sigmas, hed_biases, view, windows, route, fmt=tensor_format, out=out)
+        return (x, M, maxC, status) + ((windows,) if view is not None else ()) + (draw,)
+
+    def transform_batch(self, tiles, out=None, ws=None, tensor_format=None, _tensor_route=None, view=None, windows=None, hed=None,
+                        hed_sigmas=None, hed_biases=None):
         """(N,H,W,3) uint8 device tensor -> (out, M_src, maxC_src, status) device tensors.  A tile whose
         status is non-zero (1 = empty tissue mask, 2 = degenerate, 3 = a zero 99th-percentile concentration) is passed through unchanged.
         ``ws``: an ``engine.Workspace`` to reuse (ONE stream at a time); by default every call takes its scratch from
@@ -155,8 +170,15 @@ class ExtractiveStainNormalizer(object):
         ``tensor_format.convert`` of the uint8 result (a passed-through tile: of its source bytes).
         ``view``: a ``stainlib_amd.TileView`` -- the unchanged fit of the WHOLE tiles, then ONE pass that writes per tile only the window
         ``windows[t]`` (default: ``view.draw(N, H, W)``) of that result, flipped and turned (engine.normalize_view): `out` is
-        (N,oh,ow,3) uint8 or the (N,3,oh,ow) tensor, and the call returns (out, M_src, maxC_src, status, windows)."""
+        (N,oh,ow,3) uint8 or the (N,3,oh,ow) tensor, and the call returns (out, M_src, maxC_src, status, windows).
+        ``hed``: a ``HedColorAugmenter`` -- its transform (ranges, cutoff, skimage_mode) on every normalised tile in that same pass
+        (engine.normalize_sums for its cutoff test on the image nobody writes, then engine.normalize_hed_view): bit for bit
+        ``hed.transform_batch`` of the uint8 result, then the view and the conversion.  ``hed_sigmas``, ``hed_biases``: (N, 3) each; by
+        default ``hed.randomize_batch(N)``, drawn BEFORE the windows.  Works with or without ``view`` / ``tensor_format``; the call then
+        returns one more element at the end, ``engine.HedDraw(sigmas, biases, applied)``."""
         from .. import engine
+        if engine._hed_call(hed, hed_sigmas, hed_biases, tiles):
+            return self._hed_batch(tiles, hed, hed_sigmas, hed_biases, view, windows, out, ws, tensor_format, target=True)
         if view is not None or windows is not None:
             size, d_mask, windows = engine._view_call(view, windows, tiles)
             M, maxC, status = self._fit_tiles(tiles, ws=ws)
@@ -197,7 +219,7 @@ class ExtractiveStainNormalizer(object):
 
     # -- stain jitter in the apply pass (an extension: RandStainNA / StainAugmentor-style augmentation of the normalised tiles) ----
     def augment_batch(self, tiles, alpha_beta, augment_background=False, normalize=True, out=None, ws=None, tensor_format=None, view=None,
-                      windows=None):
+                      windows=None, hed=None, hed_sigmas=None, hed_biases=None):
         """(N,H,W,3) uint8 device tensor -> (out, M_src, maxC_src, status): the per-tile fit, then ONE pass that normalises every tile
         and perturbs its stains: C_i * alpha_i + beta_i on the normalised concentrations of tissue pixels (every pixel with
         ``augment_background``), under the target's stain matrix, clipped.  ``alpha_beta``: (N, 4) = alpha0, beta0, alpha1, beta1 per
@@ -206,11 +228,16 @@ class ExtractiveStainNormalizer(object):
         ``tensor_format``: a ``stainlib_amd.TensorFormat``; `out` is then the (N,3,H,W) tensor in that format, bit for bit
         ``tensor_format.convert`` of the uint8 result.  A tile whose status is non-zero comes back as its own bytes (their conversion).
         ``view``, ``windows``: as in transform_batch -- the crop / flip / quarter turn of every tile in the same pass; the call then
-        returns (out, M_src, maxC_src, status, windows)."""
+        returns (out, M_src, maxC_src, status, windows).
+        ``hed``, ``hed_sigmas``, ``hed_biases``: as in transform_batch -- the HedColorAugmenter's transform of the perturbed tile in the
+        same pass; one more element at the end of the returned tuple, ``engine.HedDraw``."""
         from .. import engine
         engine._jitter_args(None, None, alpha_beta, None, tensor_format, out)
         if normalize and not hasattr(self, "stain_matrix_target"):
             raise ValueError("augment_batch(normalize=True) needs a fitted target: call fit() first, or pass normalize=False")
+        if engine._hed_call(hed, hed_sigmas, hed_biases, tiles):
+            return self._hed_batch(tiles, hed, hed_sigmas, hed_biases, view, windows, out, ws, tensor_format, target=normalize,
+                                   jitter=dict(alpha_beta=alpha_beta, augment_background=augment_background))
         if view is not None or windows is not None:
             size, d_mask, windows = engine._view_call(view, windows, tiles)
         M, maxC, status = self._fit_tiles(tiles, ws=ws)
