@@ -105,14 +105,9 @@ class HedColorAugmenter(ColorAugmenterBase):
         out, applied, sums = engine.hed_augment(dev, [self._sigmas], [self._biases], cutoff=self._cutoff_range,
                                                 skimage_mode=self._skimage_mode, want_sums=True)
         ok = bool(int(applied[0]))
-        # The device tests the EXACT mean (integer byte sum); the reference tests np.mean of the float32 image / 255
-        # (augmenter.py:291-293), whose pairwise binary32 sum can be off by ~2e-6 relative on a large patch.  Within _CUTOFF_BAND of
-        # a bound the reference's own value decides (one host mean, only then).
-        exact = float(int(sums[0])) / patch.size / 255.0
-        lo, hi = self._cutoff_range
-        if min(abs(exact - lo), abs(exact - hi)) <= _CUTOFF_BAND * max(abs(lo), abs(hi), 1e-30):
-            ref_mean = np.mean(a=patch.astype(dtype=np.float32)) / 255.0
-            ref_ok = bool(lo <= ref_mean <= hi)
+        # the knife-edge rule (engine._near_cutoff): near a bound the reference's own value decides (one host mean, only then)
+        if engine._near_cutoff(sums, patch.shape[0] * patch.shape[1], self._cutoff_range):
+            ref_ok = engine._reference_cutoff_test(patch, self._cutoff_range)
             if ref_ok and not ok:                                     # transform after all: no cutoff this time
                 out, _ = engine.hed_augment(dev, [self._sigmas], [self._biases], cutoff=(-np.inf, np.inf),
                                             skimage_mode=self._skimage_mode)
@@ -148,18 +143,9 @@ class HedColorAugmenter(ColorAugmenterBase):
         biases = [self._biases] * n if biases is None else biases
         out, applied, sums = engine.hed_augment(tiles, sigmas, biases, cutoff=self._cutoff_range,
                                                 skimage_mode=self._skimage_mode, out=out, want_sums=True)
-        # The same knife-edge rule as transform(): a tile whose EXACT mean lies within _CUTOFF_BAND of a cutoff bound is decided by
-        # the reference's own expression (the float32 mean, augmenter.py:291-293) on the host, so that a tile gets the same answer
-        # alone and in a batch.  Costs one 8-byte-per-tile read-back per call; tiles near a bound are rare.
-        import torch
-        lo, hi = self._cutoff_range
-        exact = sums.to(torch.float64) / float(tiles.shape[1] * tiles.shape[2] * 3) / 255.0
-        band = _CUTOFF_BAND * max(abs(lo), abs(hi), 1e-30)
-        near = torch.nonzero(torch.minimum((exact - lo).abs(), (exact - hi).abs()) <= band).reshape(-1).tolist()
-        for i in near:
-            patch = tiles[i].cpu().numpy()
-            ref_mean = np.mean(a=patch.astype(dtype=np.float32)) / 255.0
-            ref_ok = bool(lo <= ref_mean <= hi)
+        # the same knife-edge rule as transform()
+        for i in engine._near_cutoff(sums, tiles.shape[1] * tiles.shape[2], self._cutoff_range):
+            ref_ok = engine._reference_cutoff_test(tiles[i].cpu().numpy(), self._cutoff_range)
             if ref_ok and not int(applied[i]):
                 engine.hed_augment(tiles[i:i + 1], [sigmas[i]], [biases[i]], cutoff=(-np.inf, np.inf), skimage_mode=self._skimage_mode,
                                    out=out[i:i + 1])
@@ -284,23 +270,11 @@ class StainAugmentor(object):
             engine._view_call(view, windows, tiles, draw=False)
         with_hed = engine._hed_call(hed, hed_sigmas, hed_biases, tiles)
         n, h, w = engine._check_tiles(tiles)
-        if self._method == "macenko":
-            M, maxC, status = engine.macenko_fit(tiles)
-        else:
-            M, maxC, status, _ = engine.vahadane_fit(tiles)
+        fit = (engine.macenko_fit if self._method == "macenko" else engine.vahadane_fit)(tiles)[:3]
         if alpha_beta is None:
             alpha_beta = jitter.draw(n)
-        if with_hed:
-            route = dict(M_src=M, maxC_src=maxC, alpha_beta=alpha_beta, augment_background=self.augment_background)
-            out, windows, draw = engine.hed_stage(tiles, hed, hed_sigmas, hed_biases, view, windows, route, fmt=tensor_format)
-            return (out, M, maxC, status) + ((windows,) if view is not None else ()) + (draw,)
-        if view is not None or windows is not None:
-            size, d_mask, windows = engine._view_call(view, windows, tiles)
-            out = engine.normalize_view(tiles, windows, size, d_mask, M, maxC, None, None, alpha_beta, self.augment_background,
-                                        fmt=tensor_format)
-            return out, M, maxC, status, windows
-        out = engine.normalize_jitter(tiles, M, maxC, None, None, alpha_beta, self.augment_background, fmt=tensor_format)
-        return out, M, maxC, status
+        route = dict(M_tgt=None, maxC_tgt=None, alpha_beta=alpha_beta, augment_background=self.augment_background)
+        return engine.route_stage(tiles, fit, route, tensor_format, None, view, windows, (hed, hed_sigmas, hed_biases) if with_hed else None)
 
 
 class StainJitter(object):

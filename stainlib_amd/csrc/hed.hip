@@ -222,16 +222,6 @@ static __global__ __launch_bounds__(kWG) void k_rgb_to_od(const uint8_t* __restr
 
 using namespace sl;
 
-namespace {
-void inv3(const double* m, double* o) {
-    const double a = m[0], b = m[1], c = m[2], d = m[3], e = m[4], f = m[5], g = m[6], h = m[7], i = m[8];
-    const double det = a * (e * i - f * h) - b * (d * i - f * g) + c * (d * h - e * g);
-    o[0] = (e * i - f * h) / det; o[1] = (c * h - b * i) / det; o[2] = (b * f - c * e) / det;
-    o[3] = (f * g - d * i) / det; o[4] = (a * i - c * g) / det; o[5] = (c * d - a * f) / det;
-    o[6] = (d * h - e * g) / det; o[7] = (b * g - a * h) / det; o[8] = (a * e - b * d) / det;
-}
-}  // namespace
-
 extern "C" int sl_hed_augment(const uint8_t* rgb, uint8_t* out, int n, int h, int w, const double* sigma,
                               const double* bias, double cutoff_lo, double cutoff_hi, int skimage_mode,
                               int32_t* applied, void* workspace, size_t workspace_bytes, void* stream) {
@@ -242,10 +232,7 @@ extern "C" int sl_hed_augment(const uint8_t* rgb, uint8_t* out, int n, int h, in
     if (!workspace || workspace_bytes < sizeof(unsigned long long) * (size_t)n || ((uintptr_t)workspace & 7u))
         return SL_ERR_WORKSPACE;
     HedConst hc;
-    // skimage.color.rgb_from_hed (colorconv.py:475-478), hed_from_rgb = inv(.)
-    const double R[9] = {0.65, 0.70, 0.29, 0.07, 0.99, 0.11, 0.27, 0.57, 0.78};
-    for (int i = 0; i < 9; ++i) hc.R[i] = R[i];
-    inv3(R, hc.H);
+    hed_matrices(hc.R, hc.H);
     hc.log2_base = skimage_mode == SL_HED_EXPERIMENTAL_LOG10 ? 3.321928094887362 : 1.4426950408889634;
     hipStream_t s = (hipStream_t)stream;
     unsigned long long* sums = (unsigned long long*)workspace;
@@ -273,9 +260,7 @@ extern "C" int sl_hed_augment_f64(const double* rgb, double* out, int n, int h, 
     if (P > (1L << 30)) return SL_ERR_BADARG;
     if (!workspace || workspace_bytes < sizeof(double) * (size_t)n || ((uintptr_t)workspace & 7u)) return SL_ERR_WORKSPACE;
     HedConst hc;
-    const double R[9] = {0.65, 0.70, 0.29, 0.07, 0.99, 0.11, 0.27, 0.57, 0.78};
-    for (int i = 0; i < 9; ++i) hc.R[i] = R[i];
-    inv3(R, hc.H);
+    hed_matrices(hc.R, hc.H);
     hc.log2_base = 0.0;
     hipStream_t s = (hipStream_t)stream;
     double* sums = (double*)workspace;

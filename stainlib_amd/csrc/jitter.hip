@@ -1,6 +1,6 @@
 // jitter.hip -- C-ABI launcher of the stain jitter in the apply pass (kernel: jitter_kernels.hpp).
 #include "jitter_kernels.hpp"
-#include "tensor_host.hpp"
+#include "route_host.hpp"
 
 using namespace sl;
 
@@ -25,13 +25,7 @@ extern "C" int sl_normalize_jitter(const uint8_t* rgb, void* out, int n, int h, 
         };
         if (augment_background) go(std::true_type{}); else go(std::false_type{});
     };
-    if (fmt) {          // the ALIGNED / WIDE decisions of sl_normalize_apply_tensor
-        with_format(fmt->dtype, fmt->layout, aligned4(rgb, P), wide_ok(out, P, fmt->dtype), launch);
-    } else {            // the uint8 image: ALIGNED as in sl_normalize_apply; layout and WIDE do not apply
-        const std::integral_constant<int, kDtU8> u8{};
-        const std::integral_constant<int, kLayNHWC> lay{};
-        if (aligned4(rgb, P) && aligned4(out, P)) launch(u8, lay, std::true_type{}, std::false_type{});
-        else launch(u8, lay, std::false_type{}, std::false_type{});
-    }
+    // a format: the ALIGNED / WIDE decisions of sl_normalize_apply_tensor; the uint8 image: ALIGNED as in sl_normalize_apply
+    with_format_or_u8(fmt, aligned4(rgb, P) && (fmt || aligned4(out, P)), fmt && wide_ok(out, P, fmt->dtype), launch);
     return launch_status();
 }

@@ -1,0 +1,57 @@
+// route_host.hpp -- host-side helpers of the entry points on the apply-pass frame (jitter.hip, view.hip, hed_view.hip).
+// The *route* is the pointer pattern (M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, augment_background) by which a call names the
+// image it would write: the tiles' own bytes, sl_normalize_apply's, the jitter under a target or the jitter under the tile's own matrix.
+#pragma once
+#include "view_kernels.hpp"        // kView*, kViewB
+#include "tensor_host.hpp"
+
+namespace sl {
+
+// SL_OK and the kView* mode of a route, or SL_ERR_BADARG.  (sl_normalize_apply, sl_normalize_apply_tensor, sl_normalize_jitter and
+// sl_stain_separate each accept one fixed part of this pattern and keep their own, narrower rule.)
+inline int route_of(const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, const double* alpha_beta,
+                    int augment_background, int& mode) {
+    if ((M_tgt == nullptr) != (maxC_tgt == nullptr)) return SL_ERR_BADARG;
+    if (!M_src) {                                                                // the source bytes themselves: nothing else applies
+        if (M_tgt || maxC_src || alpha_beta) return SL_ERR_BADARG;
+    } else {
+        if (!maxC_src) return SL_ERR_BADARG;
+        if (!alpha_beta && !M_tgt) return SL_ERR_BADARG;                         // sl_normalize_apply has no "no target"
+    }
+    mode = !M_src ? kViewRaw : (!alpha_beta ? kViewApply : (augment_background ? kViewJitAll : kViewJitTissue));
+    return SL_OK;
+}
+
+// f(mode tag) for the runtime mode
+template <class F>
+inline void with_mode(int mode, F&& f) {
+    if (mode == kViewRaw) f(std::integral_constant<int, kViewRaw>{});
+    else if (mode == kViewApply) f(std::integral_constant<int, kViewApply>{});
+    else if (mode == kViewJitTissue) f(std::integral_constant<int, kViewJitTissue>{});
+    else f(std::integral_constant<int, kViewJitAll>{});
+}
+
+// The geometry of a view of n tiles of h x w (check_shape has accepted them): SL_OK and the patches per output row and per tile, or
+// SL_ERR_BADARG.
+inline int view_geometry(int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, long& npx, long& npatch) {
+    if (!windows || oh < 1 || ow < 1 || oh > h || ow > w) return SL_ERR_BADARG;
+    if (d_mask < 0 || d_mask > 7) return SL_ERR_BADARG;
+    if ((d_mask & 1) && (ow > h || oh > w)) return SL_ERR_BADARG;               // the transposed window must fit too
+    npx = (ow + kViewB - 1) / kViewB;
+    npatch = npx * ((oh + kViewB - 1) / kViewB);
+    if ((long)n * npatch > 0x7fffffffL) return SL_ERR_BADARG;                    // one workgroup per (tile, patch)
+    return SL_OK;
+}
+
+// f(dtype tag, layout tag, aligned tag, wide tag) for a format format_ok has accepted (with_format), or for the uint8 image when there
+// is none: kDtU8 / kLayNHWC -- its layout and the wide stores do not apply.
+template <class F>
+inline void with_format_or_u8(const SlTensorFormat* fmt, bool aligned, bool wide, F&& f) {
+    if (fmt) return with_format(fmt->dtype, fmt->layout, aligned, wide, f);
+    const std::integral_constant<int, kDtU8> u8{};
+    const std::integral_constant<int, kLayNHWC> lay{};
+    if (aligned) f(u8, lay, std::true_type{}, std::false_type{});
+    else f(u8, lay, std::false_type{}, std::false_type{});
+}
+
+}  // namespace sl

@@ -69,7 +69,23 @@ inline bool wide_ok(const void* out, long P, int dtype) {
     return ((uintptr_t)out & 15u) == 0 && P % px == 0;
 }
 
-// Launches k_aligned when `aligned` (aligned4 of every tile pointer the kernel reads or writes), else k_unaligned: the two
+inline void inv3(const double* m, double* o) {
+    const double a = m[0], b = m[1], c = m[2], d = m[3], e = m[4], f = m[5], g = m[6], h = m[7], i = m[8];
+    const double det = a * (e * i - f * h) - b * (d * i - f * g) + c * (d * h - e * g);
+    o[0] = (e * i - f * h) / det; o[1] = (c * h - b * i) / det; o[2] = (b * f - c * e) / det;
+    o[3] = (f * g - d * i) / det; o[4] = (a * i - c * g) / det; o[5] = (c * d - a * f) / det;
+    o[6] = (d * h - e * g) / det; o[7] = (b * g - a * h) / det; o[8] = (a * e - b * d) / det;
+}
+
+// The constants of every HED kernel (hed.hip, hed_view.hip), row-major: R = skimage.color.rgb_from_hed (colorconv.py:475-478),
+// H = hed_from_rgb = inv(R).
+inline void hed_matrices(double* R, double* H) {
+    const double m[9] = {0.65, 0.70, 0.29, 0.07, 0.99, 0.11, 0.27, 0.57, 0.78};
+    for (int k = 0; k < 9; ++k) R[k] = m[k];
+    inv3(m, H);
+}
+
+// Launches k_aligned when `aligned`(aligned4 of every tile pointer the kernel reads or writes), else k_unaligned: the two
 // instantiations of one sweep kernel, with the same geometry and arguments.
 template <class K, class... Args>
 inline void launch_aligned(bool aligned, K k_aligned, K k_unaligned, dim3 grid, dim3 block, unsigned lds, hipStream_t s, Args... args) {

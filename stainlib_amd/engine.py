@@ -28,6 +28,11 @@ def _params(params):
     return C.byref(params if params is not None else _ffi.default_params())
 
 
+def _byref(struct):
+    """ctypes reference to an optional SlParams / SlTensorFormat: NULL for None."""
+    return C.byref(struct) if struct is not None else None
+
+
 def _call(name, *args):
     """lib().<name>(*args, current stream); an error code raises StainlibHipError("<name> failed: ...")."""
     _ffi.check(getattr(_ffi.lib(), name)(*args, _stream()), name)
@@ -47,6 +52,14 @@ def _f64(x, shape, device):
         x = np.asarray(x, dtype=np.float64)
     t = torch.as_tensor(x, dtype=torch.float64, device=device).reshape(shape)
     return t.contiguous()
+
+
+def _route_upload(n, device, M_src, maxC_src, M_tgt=None, maxC_tgt=None, alpha_beta=None):
+    """The statistics of an apply-pass route as device float64 tensors of the shapes the C ABI reads, None staying None ->
+    (M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta)."""
+    def up(x, shape):
+        return _f64(x, shape, device) if x is not None else None
+    return up(M_src, (n, 2, 3)), up(maxC_src, (n, 2)), up(M_tgt, (2, 3)), up(maxC_tgt, (2,)), up(alpha_beta, (n, 4))
 
 
 def make_params(**kw) -> _ffi.SlParams:
@@ -85,8 +98,7 @@ class Workspace:
 
 def _ws_need(op, n, h, w, params=None) -> int:
     """what THIS call needs (sl_workspace_bytes_for: the schedule its SlParams select), not the maximum over every SlParams"""
-    import ctypes as C
-    return int(_ffi.lib().sl_workspace_bytes_for(op, n, h, w, C.byref(params) if params is not None else None))
+    return int(_ffi.lib().sl_workspace_bytes_for(op, n, h, w, _byref(params)))
 
 
 def _scratch(ws, op, n, h, w, device, params=None) -> torch.Tensor:
@@ -135,10 +147,7 @@ def normalize_apply(rgb, M_src, maxC_src, M_tgt, maxC_tgt, lasso_lambda=0.01, ou
     """OD + reconstruction pass (sl_normalize_apply).  Returns out, or (out, prequant)."""
     n, h, w = _check_tiles(rgb)
     dev = rgb.device
-    M_src = _f64(M_src, (n, 2, 3), dev)
-    maxC_src = _f64(maxC_src, (n, 2), dev)
-    M_tgt = _f64(M_tgt, (2, 3), dev)
-    maxC_tgt = _f64(maxC_tgt, (2,), dev)
+    M_src, maxC_src, M_tgt, maxC_tgt, _ = _route_upload(n, dev, M_src, maxC_src, M_tgt, maxC_tgt)
     if out is None:
         out = torch.empty_like(rgb)
     pre = torch.empty((n, h, w, 3), dtype=torch.float32, device=dev) if want_prequant else None
@@ -176,6 +185,23 @@ def _tensor_out(out, n, h, w, dtype, channels_last, device):
     return out
 
 
+def _image_out(out, rgb, n, h, w, fmt, what):
+    """(SlTensorFormat or None, out) of a pass that writes n images of h x w from rgb: without a format the (n, h, w, 3) uint8 `out`,
+    checked or fresh, and not the input (what: "jitter" / "view", for that message); else _tensor_out's."""
+    dev = rgb.device
+    if fmt is not None:
+        f, dtype, cl = _tensor_format(fmt)
+        return f, _tensor_out(out, n, h, w, dtype, cl, dev)
+    if out is None:
+        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and out.device == dev and tuple(out.shape) == (n, h, w, 3)
+              and out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous uint8 tensor of shape {(n, h, w, 3)} on {dev}")
+    if out.data_ptr() == rgb.data_ptr():
+        raise ValueError(f"out must not be the input (no in-place {what})")
+    return None, out
+
+
 def to_tensor(rgb, fmt, out=None):
     """(N,H,W,3) uint8 -> (N,3,H,W) tensor of fmt.dtype, contiguous or channels_last: fma(b, 1/(255 std), -mean/std) of every byte,
     rounded to nearest even (sl_to_tensor).  fmt: a stainlib_amd.TensorFormat."""
@@ -193,10 +219,7 @@ def normalize_apply_tensor(rgb, M_src, maxC_src, M_tgt, maxC_tgt, fmt, lasso_lam
     bit, without the uint8 image in between."""
     n, h, w = _check_tiles(rgb)
     dev = rgb.device
-    M_src = _f64(M_src, (n, 2, 3), dev)
-    maxC_src = _f64(maxC_src, (n, 2), dev)
-    M_tgt = _f64(M_tgt, (2, 3), dev)
-    maxC_tgt = _f64(maxC_tgt, (2,), dev)
+    M_src, maxC_src, M_tgt, maxC_tgt, _ = _route_upload(n, dev, M_src, maxC_src, M_tgt, maxC_tgt)
     f, dtype, cl = _tensor_format(fmt)
     out = _tensor_out(out, n, h, w, dtype, cl, dev)
     _call("sl_normalize_apply_tensor", _ptr(rgb), _ptr(out), n, h, w, _ptr(M_src), _ptr(maxC_src), _ptr(M_tgt), _ptr(maxC_tgt),
@@ -267,11 +290,7 @@ def stain_separate(rgb, M_src, maxC_src, M_tgt=None, maxC_tgt=None, lasso_lambda
     n, h, w = _check_tiles(rgb)
     dev = rgb.device
     res = _separate_out(out, want, n, h, w, conc_dtype, dev)
-    M_src = _f64(M_src, (n, 2, 3), dev)
-    maxC_src = _f64(maxC_src, (n, 2), dev)
-    if M_tgt is not None:
-        M_tgt = _f64(M_tgt, (2, 3), dev)
-        maxC_tgt = _f64(maxC_tgt, (2,), dev)
+    M_src, maxC_src, M_tgt, maxC_tgt, _ = _route_upload(n, dev, M_src, maxC_src, M_tgt, maxC_tgt)
     o = _ffi.default_separate_out()
     o.conc_dtype = _TENSOR_DTYPES[conc_dtype]
     o.norm, o.stain[0], o.stain[1], o.conc = (t.data_ptr() if t is not None else None for t in res)
@@ -309,6 +328,27 @@ def _jitter_args(M_tgt, maxC_tgt, alpha_beta, params, fmt, out):
     return shape[0]
 
 
+def _route_check(M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, params, n=None):
+    """The checks of the arguments by which normalize_view, normalize_hed_view and normalize_sums name `full` -- the tiles' own bytes
+    (M_src=None), normalize_apply's image (M_src and a target) or normalize_jitter's (alpha_beta) -- and of params (no device needed) ->
+    the rows of alpha_beta, or None.  n: the rows alpha_beta must have."""
+    if (M_tgt is None) != (maxC_tgt is None):
+        raise ValueError("M_tgt and maxC_tgt go together: both, or neither (no target)")
+    if M_src is None:
+        if not (maxC_src is None and M_tgt is None and alpha_beta is None):
+            raise ValueError("M_src=None is the view of the tiles' own bytes: maxC_src, M_tgt, maxC_tgt and alpha_beta must be None too")
+    elif maxC_src is None:
+        raise ValueError("M_src and maxC_src go together")
+    elif alpha_beta is None and M_tgt is None:
+        raise ValueError("without alpha_beta the view is normalize_apply's, which needs a target: pass M_tgt and maxC_tgt")
+    n_ab = _jitter_args(M_tgt, maxC_tgt, alpha_beta, None, None, None) if alpha_beta is not None else None
+    if n is not None and n_ab is not None and n_ab != n:
+        raise ValueError(f"alpha_beta must have one row per tile ({n})")
+    if params is not None and not isinstance(params, _ffi.SlParams):
+        raise ValueError("params must be an SlParams (engine.make_params) or None")
+    return n_ab
+
+
 def normalize_jitter(rgb, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, augment_background=False, params=None, fmt=None, out=None):
     """normalize_apply and StainAugmentor.pop's perturbation in ONE pass (sl_normalize_jitter): per tile C_i * alpha_i + beta_i on the
     NORMALISED concentrations C * maxC_tgt / maxC_src of tissue pixels (all pixels with augment_background), reconstructed under the
@@ -320,26 +360,10 @@ def normalize_jitter(rgb, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, augment_
     n, h, w = _check_tiles(rgb)
     if n_ab != n:
         raise ValueError(f"alpha_beta has {n_ab} rows for {n} tiles")
-    dev = rgb.device
-    M_src = _f64(M_src, (n, 2, 3), dev)
-    maxC_src = _f64(maxC_src, (n, 2), dev)
-    if M_tgt is not None:
-        M_tgt = _f64(M_tgt, (2, 3), dev)
-        maxC_tgt = _f64(maxC_tgt, (2,), dev)
-    ab = _f64(alpha_beta, (n, 4), dev)
-    if fmt is None:
-        f = None
-        if out is None:
-            out = torch.empty_like(rgb)
-        elif not (out.device == dev and tuple(out.shape) == (n, h, w, 3) and out.is_contiguous()):
-            raise ValueError(f"out must be a contiguous uint8 tensor of shape {(n, h, w, 3)} on {dev}")
-        if out.data_ptr() == rgb.data_ptr():
-            raise ValueError("out must not be the input (no in-place jitter)")
-    else:
-        f, dtype, cl = _tensor_format(fmt)
-        out = _tensor_out(out, n, h, w, dtype, cl, dev)
+    M_src, maxC_src, M_tgt, maxC_tgt, ab = _route_upload(n, rgb.device, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta)
+    f, out = _image_out(out, rgb, n, h, w, fmt, "jitter")
     _call("sl_normalize_jitter", _ptr(rgb), _ptr(out), n, h, w, _ptr(M_src), _ptr(maxC_src), _ptr(M_tgt), _ptr(maxC_tgt), _ptr(ab),
-          1 if augment_background else 0, C.byref(params) if params is not None else None, C.byref(f) if f is not None else None)
+          1 if augment_background else 0, _byref(params), _byref(f))
     return out
 
 
@@ -389,19 +413,7 @@ def _view_prepare(rgb, windows, size, d_mask, M_src, maxC_src, M_tgt, maxC_tgt, 
     n, h, w = (int(v) for v in rgb.shape[:3])
     oh, ow = check_size(size, h, w, d_mask)
     win = _view_windows(windows, n, h, w, oh, ow, d_mask)
-    if (M_tgt is None) != (maxC_tgt is None):
-        raise ValueError("M_tgt and maxC_tgt go together: both, or neither (no target)")
-    if M_src is None:
-        if not (maxC_src is None and M_tgt is None and alpha_beta is None):
-            raise ValueError("M_src=None is the view of the tiles' own bytes: maxC_src, M_tgt, maxC_tgt and alpha_beta must be None too")
-    elif maxC_src is None:
-        raise ValueError("M_src and maxC_src go together")
-    elif alpha_beta is None and M_tgt is None:
-        raise ValueError("without alpha_beta the view is normalize_apply's, which needs a target: pass M_tgt and maxC_tgt")
-    if alpha_beta is not None and _jitter_args(M_tgt, maxC_tgt, alpha_beta, None, None, None) != n:
-        raise ValueError(f"alpha_beta must have one row per tile ({n})")
-    if params is not None and not isinstance(params, _ffi.SlParams):
-        raise ValueError("params must be an SlParams (engine.make_params) or None")
+    _route_check(M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, params, n)
     if fmt is not None and not isinstance(fmt, TensorFormat):
         raise ValueError("fmt must be a stainlib_amd.TensorFormat or None (the uint8 image)")
     if before_device is not None:
@@ -412,26 +424,8 @@ def _view_prepare(rgb, windows, size, d_mask, M_src, maxC_src, M_tgt, maxC_tgt, 
         win = torch.from_numpy(win).to(dev)
     if win.device != dev:
         raise ValueError(f"windows must be on {dev}")
-    if M_src is not None:
-        M_src = _f64(M_src, (n, 2, 3), dev)
-        maxC_src = _f64(maxC_src, (n, 2), dev)
-    if M_tgt is not None:
-        M_tgt = _f64(M_tgt, (2, 3), dev)
-        maxC_tgt = _f64(maxC_tgt, (2,), dev)
-    ab = _f64(alpha_beta, (n, 4), dev) if alpha_beta is not None else None
-    if fmt is None:
-        f = None
-        if out is None:
-            out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=dev)
-        elif not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and out.device == dev and tuple(out.shape) == (n, oh, ow, 3)
-                  and out.is_contiguous()):
-            raise ValueError(f"out must be a contiguous uint8 tensor of shape {(n, oh, ow, 3)} on {dev}")
-        if out.data_ptr() == rgb.data_ptr():
-            raise ValueError("out must not be the input (no in-place view)")
-    else:
-        f, dtype, cl = _tensor_format(fmt)
-        out = _tensor_out(out, n, oh, ow, dtype, cl, dev)
-    return n, h, w, oh, ow, win, M_src, maxC_src, M_tgt, maxC_tgt, ab, f, out
+    stats = _route_upload(n, dev, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta)
+    return (n, h, w, oh, ow, win) + stats + _image_out(out, rgb, n, oh, ow, fmt, "view")
 
 
 def normalize_view(rgb, windows, size, d_mask=7, M_src=None, maxC_src=None, M_tgt=None, maxC_tgt=None, alpha_beta=None,
@@ -448,8 +442,7 @@ def normalize_view(rgb, windows, size, d_mask=7, M_src=None, maxC_src=None, M_tg
     n, h, w, oh, ow, win, M_src, maxC_src, M_tgt, maxC_tgt, ab, f, out = _view_prepare(
         rgb, windows, size, d_mask, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, params, fmt, out)
     _call("sl_normalize_view", _ptr(rgb), _ptr(out), n, h, w, oh, ow, _ptr(win), int(d_mask), _ptr(M_src), _ptr(maxC_src), _ptr(M_tgt),
-          _ptr(maxC_tgt), _ptr(ab), 1 if augment_background else 0, C.byref(params) if params is not None else None,
-          C.byref(f) if f is not None else None)
+          _ptr(maxC_tgt), _ptr(ab), 1 if augment_background else 0, _byref(params), _byref(f))
     return out
 
 
@@ -458,23 +451,6 @@ def normalize_view(rgb, windows, size, d_mask=7, M_src=None, maxC_src=None, M_tg
 HedDraw = collections.namedtuple("HedDraw", ["sigmas", "biases", "applied"])
 HedDraw.__doc__ = """What the hed= stage of a batch method did: the (N, 3) sigmas and biases it used (given or drawn) and applied, the (N,)
 int32 device tensor of the cutoff test's decisions (0: the tile came back without the HED transform)."""
-
-
-def _route_check(M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, params):
-    """normalize_view's checks of the arguments that name `full` (no device needed) -> the rows of alpha_beta, or None."""
-    if (M_tgt is None) != (maxC_tgt is None):
-        raise ValueError("M_tgt and maxC_tgt go together: both, or neither (no target)")
-    if M_src is None:
-        if not (maxC_src is None and M_tgt is None and alpha_beta is None):
-            raise ValueError("M_src=None is the view of the tiles' own bytes: maxC_src, M_tgt, maxC_tgt and alpha_beta must be None too")
-    elif maxC_src is None:
-        raise ValueError("M_src and maxC_src go together")
-    elif alpha_beta is None and M_tgt is None:
-        raise ValueError("without alpha_beta the view is normalize_apply's, which needs a target: pass M_tgt and maxC_tgt")
-    n_ab = _jitter_args(M_tgt, maxC_tgt, alpha_beta, None, None, None) if alpha_beta is not None else None
-    if params is not None and not isinstance(params, _ffi.SlParams):
-        raise ValueError("params must be an SlParams (engine.make_params) or None")
-    return n_ab
 
 
 def _cutoff(cutoff):
@@ -499,17 +475,11 @@ def normalize_sums(rgb, M_src=None, maxC_src=None, M_tgt=None, maxC_tgt=None, al
         raise ValueError(f"alpha_beta must have one row per tile ({rgb.shape[0]})")
     n, h, w = _check_tiles(rgb)
     dev = rgb.device
-    if M_src is not None:
-        M_src = _f64(M_src, (n, 2, 3), dev)
-        maxC_src = _f64(maxC_src, (n, 2), dev)
-    if M_tgt is not None:
-        M_tgt = _f64(M_tgt, (2, 3), dev)
-        maxC_tgt = _f64(maxC_tgt, (2,), dev)
-    ab = _f64(alpha_beta, (n, 4), dev) if alpha_beta is not None else None
+    M_src, maxC_src, M_tgt, maxC_tgt, ab = _route_upload(n, dev, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta)
     sums = torch.empty((n,), dtype=torch.int64, device=dev)
     applied = torch.empty((n,), dtype=torch.int32, device=dev)
     _call("sl_normalize_sums", _ptr(rgb), n, h, w, _ptr(M_src), _ptr(maxC_src), _ptr(M_tgt), _ptr(maxC_tgt), _ptr(ab),
-          1 if augment_background else 0, C.byref(params) if params is not None else None, lo, hi, _ptr(sums), _ptr(applied))
+          1 if augment_background else 0, _byref(params), lo, hi, _ptr(sums), _ptr(applied))
     return sums, applied
 
 
@@ -562,8 +532,8 @@ def normalize_hed_view(rgb, windows, size, d_mask, hed_sigma, hed_bias, hed_appl
         img = torch.where((applied != 0).view(n, 1, 1, 1), aug, full)
         return normalize_view(img, win, size, d_mask, fmt=fmt, out=out)
     _call("sl_normalize_hed_view", _ptr(rgb), _ptr(out), n, h, w, oh, ow, _ptr(win), int(d_mask), _ptr(M_src), _ptr(maxC_src), _ptr(M_tgt),
-          _ptr(maxC_tgt), _ptr(ab), 1 if augment_background else 0, C.byref(params) if params is not None else None,
-          C.byref(f) if f is not None else None, _ptr(sigma), _ptr(bias), _ptr(applied), int(skimage_mode))
+          _ptr(maxC_tgt), _ptr(ab), 1 if augment_background else 0, _byref(params), _byref(f), _ptr(sigma), _ptr(bias), _ptr(applied),
+          int(skimage_mode))
     return out
 
 
@@ -588,27 +558,39 @@ def _hed_call(hed, hed_sigmas, hed_biases, tiles):
     return True
 
 
+def _near_cutoff(sums, pixels, cutoff):
+    """The knife-edge rule of HedColorAugmenter's cutoff test -> the indices of the tiles it applies to: those whose EXACT mean, the byte
+    sum sums[t] (an (N,) int64 tensor) / (3 pixels) / 255, lies within _CUTOFF_BAND (relative) of a bound of cutoff = (lo, hi).
+    The device tests that exact mean; the reference tests np.mean of the float32 image / 255 (augmenter.py:291-293), whose pairwise
+    binary32 sum can be off by ~2e-6 relative on a large patch.  For the tiles named here the reference's own value decides
+    (_reference_cutoff_test), so that a tile gets the same answer alone and in a batch.  One 8-byte-per-tile read-back; such tiles are rare."""
+    from .augmentation.augmenter import _CUTOFF_BAND
+    lo, hi = cutoff
+    exact = sums.to(torch.float64) / float(pixels * 3) / 255.0
+    band = _CUTOFF_BAND * max(abs(lo), abs(hi), 1e-30)
+    return torch.nonzero(torch.minimum((exact - lo).abs(), (exact - hi).abs()) <= band).reshape(-1).tolist()
+
+
+def _reference_cutoff_test(patch, cutoff):
+    """The reference's own cutoff test (augmenter.py:291-293) of a host patch ((H, W, 3) uint8 ndarray): its float32 mean inside cutoff."""
+    import numpy as np
+    return bool(cutoff[0] <= np.mean(a=patch.astype(dtype=np.float32)) / 255.0 <= cutoff[1])
+
+
 def hed_decide(tiles, cutoff, M_src=None, maxC_src=None, M_tgt=None, maxC_tgt=None, alpha_beta=None, augment_background=False, params=None):
     """HedColorAugmenter's cutoff decision per tile for the image a route would write -> applied (N,) int32 on the device: normalize_sums,
-    then the knife-edge rule of HedColorAugmenter.transform_batch -- a tile whose EXACT mean lies within _CUTOFF_BAND of a bound is
-    decided by the reference's own float32 mean (augmenter.py:291-293) on the host; only for such a tile is `full` materialised (that one
-    tile, by the existing entry point).  One 8-byte-per-tile read-back per call."""
-    import numpy as np
-    from .augmentation.augmenter import _CUTOFF_BAND
-    lo, hi = _cutoff(cutoff)
-    sums, applied = normalize_sums(tiles, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, augment_background, params, cutoff=(lo, hi))
+    then the knife-edge rule (_near_cutoff); only for a tile it names is `full` materialised (that one tile, by the existing entry point)
+    and tested on the host."""
+    cutoff = _cutoff(cutoff)
+    sums, applied = normalize_sums(tiles, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, augment_background, params, cutoff=cutoff)
     n, h, w = (int(v) for v in tiles.shape[:3])
-    exact = sums.to(torch.float64) / float(h * w * 3) / 255.0
-    band = _CUTOFF_BAND * max(abs(lo), abs(hi), 1e-30)
-    near = torch.nonzero(torch.minimum((exact - lo).abs(), (exact - hi).abs()) <= band).reshape(-1).tolist()
+    near = _near_cutoff(sums, h * w, cutoff)
+    if near:
+        M_src, maxC_src, M_tgt, maxC_tgt, ab = _route_upload(n, tiles.device, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta)
     for i in near:
         one = lambda x: x[i:i + 1] if x is not None else None        # noqa: E731
-        ab = None if alpha_beta is None else _f64(alpha_beta, (n, 4), tiles.device)
-        Ms = None if M_src is None else _f64(M_src, (n, 2, 3), tiles.device)
-        mcs = None if maxC_src is None else _f64(maxC_src, (n, 2), tiles.device)
-        patch = _full_image(tiles[i:i + 1], one(Ms), one(mcs), M_tgt, maxC_tgt, one(ab), augment_background, params)[0].cpu().numpy()
-        ref_mean = np.mean(a=patch.astype(dtype=np.float32)) / 255.0
-        applied[i] = 1 if bool(lo <= ref_mean <= hi) else 0
+        patch = _full_image(tiles[i:i + 1], one(M_src), one(maxC_src), M_tgt, maxC_tgt, one(ab), augment_background, params)[0].cpu().numpy()
+        applied[i] = 1 if _reference_cutoff_test(patch, cutoff) else 0
     return applied
 
 
@@ -646,6 +628,23 @@ def _view_call(view, windows, tiles, draw=True):
     elif draw:
         windows = view.draw(n, h, w)
     return view.size, view.d_mask, windows
+
+
+def route_stage(tiles, fit, route, fmt=None, out=None, view=None, windows=None, hed=None):
+    """The tail of the batch methods, behind their fit and their own draws, on arguments _jitter_args / _view_call(draw=False) / _hed_call
+    have accepted: ONE pass over the tiles and the tuple the method returns, (out, M_src, maxC_src, status[, windows][, HedDraw]).
+    fit: the fit's (M_src, maxC_src, status); route: the other arguments that name `full` (M_tgt, maxC_tgt and, for a jitter, alpha_beta
+    and augment_background).  hed = (HedColorAugmenter, hed_sigmas, hed_biases): hed_stage; else with a view: normalize_view, the
+    windows drawn here if not given; else normalize_jitter."""
+    M, maxC, status = fit
+    route = dict(M_src=M, maxC_src=maxC, **route)
+    if hed is not None:
+        x, windows, draw = hed_stage(tiles, *hed, view, windows, route, fmt=fmt, out=out)
+        return (x, M, maxC, status) + ((windows,) if view is not None else ()) + (draw,)
+    if view is not None:
+        size, d_mask, windows = _view_call(view, windows, tiles)
+        return normalize_view(tiles, windows, size, d_mask, fmt=fmt, out=out, **route), M, maxC, status, windows
+    return normalize_jitter(tiles, fmt=fmt, out=out, **route), M, maxC, status
 
 
 def _fit(fn_name, op, rgb, params, ws, with_sweeps=False):

@@ -146,19 +146,18 @@ class ExtractiveStainNormalizer(object):
         """Per-tile (M, maxC, status) device tensors for a batch of candidate targets."""
         return self._fit_tiles(tiles, ws=ws)
 
-    def _hed_batch(self, tiles, hed, hed_sigmas, hed_biases, view, windows, out, ws, tensor_format, target, jitter=None):
-        """The hed= route of transform_batch / augment_batch (arguments already accepted by engine._hed_call): the checks that are left,
-        the fit, then engine.hed_stage -- its draws, the read-only sums pass for the cutoff test and ONE pass that normalises (and
-        perturbs), HED-transforms, crops / flips and converts.  -> (out, M_src, maxC_src, status[, windows], HedDraw)."""
+    def _route_batch(self, tiles, target, jitter, out, ws, tensor_format, view, windows, hed):
+        """The view= / hed= routes of transform_batch and all of augment_batch: the checks that are left (every one before the fit and
+        before any draw), the fit of the whole tiles, then engine.route_stage -- ONE pass under the target (target=True) or every tile's
+        own matrix, with the jitter's alpha_beta / augment_background ({}: none).  hed: None, or (hed, hed_sigmas, hed_biases) that
+        engine._hed_call has accepted.  -> (out, M_src, maxC_src, status[, windows][, HedDraw])."""
         from .. import engine
         if view is not None or windows is not None:
             engine._view_call(view, windows, tiles, draw=False)
         engine._check_tiles(tiles)
-        M, maxC, status = self._fit_tiles(tiles, ws=ws)
+        fit = self._fit_tiles(tiles, ws=ws)
         M_t, c_t = self._target_on(tiles.device) if target else (None, None)
-        route = dict(M_src=M, maxC_src=maxC, M_tgt=M_t, maxC_tgt=c_t, **(jitter or {}))
-        x, windows, draw = engine.hed_stage(tiles, hed, hed_sigmas, hed_biases, view, windows, route, fmt=tensor_format, out=out)
-        return (x, M, maxC, status) + ((windows,) if view is not None else ()) + (draw,)
+        return engine.route_stage(tiles, fit, dict(M_tgt=M_t, maxC_tgt=c_t, **jitter), tensor_format, out, view, windows, hed)
 
     def transform_batch(self, tiles, out=None, ws=None, tensor_format=None, _tensor_route=None, view=None, windows=None, hed=None,
                         hed_sigmas=None, hed_biases=None):
@@ -177,14 +176,9 @@ class ExtractiveStainNormalizer(object):
         default ``hed.randomize_batch(N)``, drawn BEFORE the windows.  Works with or without ``view`` / ``tensor_format``; the call then
         returns one more element at the end, ``engine.HedDraw(sigmas, biases, applied)``."""
         from .. import engine
-        if engine._hed_call(hed, hed_sigmas, hed_biases, tiles):
-            return self._hed_batch(tiles, hed, hed_sigmas, hed_biases, view, windows, out, ws, tensor_format, target=True)
-        if view is not None or windows is not None:
-            size, d_mask, windows = engine._view_call(view, windows, tiles)
-            M, maxC, status = self._fit_tiles(tiles, ws=ws)
-            M_t, c_t = self._target_on(tiles.device)
-            x = engine.normalize_view(tiles, windows, size, d_mask, M, maxC, M_t, c_t, fmt=tensor_format, out=out)
-            return x, M, maxC, status, windows
+        with_hed = engine._hed_call(hed, hed_sigmas, hed_biases, tiles)
+        if with_hed or view is not None or windows is not None:
+            return self._route_batch(tiles, True, {}, out, ws, tensor_format, view, windows, (hed, hed_sigmas, hed_biases) if with_hed else None)
         if tensor_format is None:
             return self._transform_tiles(tiles, out=out, ws=ws)
         route = _tensor_route or TENSOR_ROUTE
@@ -235,19 +229,9 @@ class ExtractiveStainNormalizer(object):
         engine._jitter_args(None, None, alpha_beta, None, tensor_format, out)
         if normalize and not hasattr(self, "stain_matrix_target"):
             raise ValueError("augment_batch(normalize=True) needs a fitted target: call fit() first, or pass normalize=False")
-        if engine._hed_call(hed, hed_sigmas, hed_biases, tiles):
-            return self._hed_batch(tiles, hed, hed_sigmas, hed_biases, view, windows, out, ws, tensor_format, target=normalize,
-                                   jitter=dict(alpha_beta=alpha_beta, augment_background=augment_background))
-        if view is not None or windows is not None:
-            size, d_mask, windows = engine._view_call(view, windows, tiles)
-        M, maxC, status = self._fit_tiles(tiles, ws=ws)
-        M_t, c_t = self._target_on(tiles.device) if normalize else (None, None)
-        if view is not None:
-            x = engine.normalize_view(tiles, windows, size, d_mask, M, maxC, M_t, c_t, alpha_beta, augment_background, fmt=tensor_format,
-                                      out=out)
-            return x, M, maxC, status, windows
-        x = engine.normalize_jitter(tiles, M, maxC, M_t, c_t, alpha_beta, augment_background, fmt=tensor_format, out=out)
-        return x, M, maxC, status
+        with_hed = engine._hed_call(hed, hed_sigmas, hed_biases, tiles)
+        return self._route_batch(tiles, normalize, dict(alpha_beta=alpha_beta, augment_background=augment_background), out, ws,
+                                 tensor_format, view, windows, (hed, hed_sigmas, hed_biases) if with_hed else None)
 
     def separate(self, I, normalize=True):
         """An image (RGB uint8) -> Separated of numpy arrays: norm (= transform(I)), h, e ((H,W,3) uint8) and conc ((2,H,W) float32)."""

@@ -2,13 +2,7 @@
  * error code before anything is launched or dereferenced.  Built and run under AddressSanitizer by `make -C stainlib_amd/csrc asan`
  * (tests/test_host_api.py::test_c_abi_argument_checks_under_asan).  All data pointers of the ABI are DEVICE pointers: the host side
  * never reads through them, so the non-null ones below are deliberately wild. */
-#include <stdio.h>
-#include <string.h>
-#include "../include/stainlib_hip.h"
-
-static int checks = 0, failed = 0;
-#define EXPECT(expr, want) do { long long got_ = (long long)(expr); ++checks; \
-    if (got_ != (long long)(want)) { ++failed; printf("FAIL line %d: %s = %lld, expected %lld\n", __LINE__, #expr, got_, (long long)(want)); } } while (0)
+#include "abi_argcheck.h"
 
 int main(void) {
     uint8_t* rgb = (uint8_t*)0x100000;  uint8_t* out = (uint8_t*)0x200000;
@@ -113,6 +107,5 @@ int main(void) {
     EXPECT(sl_grayscale_augment(rgb, 0, n, h, w, d2, 0), SL_ERR_BADARG);
     EXPECT(sl_rgb_to_lab8(0, out, n, h, w, 0), SL_ERR_BADARG);
     EXPECT(sl_lab8_to_rgb(rgb, 0, n, h, w, 0), SL_ERR_BADARG);
-    printf("%s: %d checks, %d failed\n", failed ? "FAILED" : "OK", checks, failed);
-    return failed ? 1 : 0;
+    return report();
 }

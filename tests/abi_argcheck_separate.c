@@ -4,14 +4,7 @@
  * The data pointers are DEVICE pointers the host side never reads through: the non-null ones below are deliberately wild.
  * SlSeparateOut is a host pointer: the undersized copy below sits at the very end of its heap block, so a library that read a
  * caller's struct before checking struct_size would be caught reading past it. */
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include "../include/stainlib_hip.h"
-
-static int checks = 0, failed = 0;
-#define EXPECT(expr, want) do { long long got_ = (long long)(expr); ++checks; \
-    if (got_ != (long long)(want)) { ++failed; printf("FAIL line %d: %s = %lld, expected %lld\n", __LINE__, #expr, got_, (long long)(want)); } } while (0)
+#include "abi_argcheck.h"
 
 int main(void) {
     uint8_t* rgb = (uint8_t*)0x100000;
@@ -53,10 +46,7 @@ int main(void) {
         g.struct_size = 0;                         SEP(rgb, n, h, w, d6, d2, d6, d2, &g);
         g.struct_size = sizeof(SlSeparateOut) - 8; SEP(rgb, n, h, w, d6, d2, d6, d2, &g);
         g.struct_size = sizeof(SlSeparateOut) + 8; SEP(rgb, n, h, w, d6, d2, d6, d2, &g);
-        /* a caller built against a smaller struct: 16 bytes (the header fields and one pointer) at the end of a heap block */
-        char* blk = (char*)malloc(16);
-        memcpy(blk, &f, 16);
-        ((SlSeparateOut*)blk)->struct_size = 16;
+        void* blk = undersized(&f);                /* (the header fields and one pointer) */
         SEP(rgb, n, h, w, d6, d2, d6, d2, (const SlSeparateOut*)blk);
         SEP(rgb, n, h, w, d6, d2, 0, 0, (const SlSeparateOut*)blk);
         free(blk);
@@ -101,6 +91,5 @@ int main(void) {
         g.conc_dtype = SL_DTYPE_F32;                             SEP(rgb, n, h, w, d6, d2, d6, d2, &g);
         g.conc = (char*)cc + 2;                                  SEP(rgb, n, h, w, d6, d2, d6, d2, &g);
     }
-    printf("%s: %d checks, %d failed\n", failed ? "FAILED" : "OK", checks, failed);
-    return failed ? 1 : 0;
+    return report();
 }

@@ -4,15 +4,7 @@
  * (tests/test_tensor_format_host.py).  The data pointers are DEVICE pointers the host side never reads through: the non-null ones
  * below are deliberately wild.  SlTensorFormat is a host pointer: the undersized copy below sits at the very end of its heap block, so
  * a library that read a caller's struct before checking struct_size would be caught reading past it. */
-#include <math.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include "../include/stainlib_hip.h"
-
-static int checks = 0, failed = 0;
-#define EXPECT(expr, want) do { long long got_ = (long long)(expr); ++checks; \
-    if (got_ != (long long)(want)) { ++failed; printf("FAIL line %d: %s = %lld, expected %lld\n", __LINE__, #expr, got_, (long long)(want)); } } while (0)
+#include "abi_argcheck.h"
 
 int main(void) {
     uint8_t* rgb = (uint8_t*)0x100000;  void* out = (void*)0x200000;
@@ -52,10 +44,7 @@ int main(void) {
         g.struct_size = 0;                          BOTH(rgb, out, n, h, w, &g);
         g.struct_size = sizeof(SlTensorFormat) - 8; BOTH(rgb, out, n, h, w, &g);
         g.struct_size = sizeof(SlTensorFormat) + 8; BOTH(rgb, out, n, h, w, &g);
-        /* a caller built against a smaller struct: 16 bytes at the end of a heap block */
-        char* blk = (char*)malloc(16);
-        memcpy(blk, &f, 16);
-        ((SlTensorFormat*)blk)->struct_size = 16;
+        void* blk = undersized(&f);
         BOTH(rgb, out, n, h, w, (const SlTensorFormat*)blk);
         free(blk);
     }
@@ -82,6 +71,5 @@ int main(void) {
             g.std[c] = bad_std[i];  BOTH(rgb, out, n, h, w, &g);
         }
     }
-    printf("%s: %d checks, %d failed\n", failed ? "FAILED" : "OK", checks, failed);
-    return failed ? 1 : 0;
+    return report();
 }

@@ -4,15 +4,7 @@
  * The data pointers are DEVICE pointers the host side never reads through: the non-null ones below are deliberately wild.
  * SlParams and SlTensorFormat are host pointers: the undersized copies below sit at the very end of their heap blocks, so a library
  * that read a caller's struct before checking struct_size would be caught reading past it. */
-#include <math.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include "../include/stainlib_hip.h"
-
-static int checks = 0, failed = 0;
-#define EXPECT(expr, want) do { long long got_ = (long long)(expr); ++checks; \
-    if (got_ != (long long)(want)) { ++failed; printf("FAIL line %d: %s = %lld, expected %lld\n", __LINE__, #expr, got_, (long long)(want)); } } while (0)
+#include "abi_argcheck.h"
 
 int main(void) {
     uint8_t* rgb = (uint8_t*)0x100000;
@@ -81,10 +73,7 @@ int main(void) {
         q.struct_size = sizeof(SlParams) - 8;      VIEW(rgb, out, n, h, w, oh, ow, win, 7, d6, d2, d6, d2, 0, 0, &q, &f);
         q.struct_size = sizeof(SlParams) + 8;      VIEW(rgb, out, n, h, w, oh, ow, win, 7, 0, 0, 0, 0, 0, 0, &q, 0);
         q = p; q.two_sweep = 9;                    VIEW(rgb, out, n, h, w, oh, ow, win, 7, d6, d2, 0, 0, ab, 1, &q, 0);
-        /* a caller built against a smaller struct: 16 bytes at the end of a heap block */
-        char* blk = (char*)malloc(16);
-        memcpy(blk, &p, 16);
-        ((SlParams*)blk)->struct_size = 16;
+        void* blk = undersized(&p);
         VIEW(rgb, out, n, h, w, oh, ow, win, 7, d6, d2, d6, d2, ab, 0, (const SlParams*)blk, 0);
         VIEW(rgb, out, n, h, w, oh, ow, win, 6, 0, 0, 0, 0, 0, 0, (const SlParams*)blk, &f);
         free(blk);
@@ -95,9 +84,7 @@ int main(void) {
         g.struct_size = 0;                               VIEW(rgb, out, n, h, w, oh, ow, win, 7, d6, d2, d6, d2, ab, 0, 0, &g);
         g.struct_size = sizeof(SlTensorFormat) - 8;      VIEW(rgb, out, n, h, w, oh, ow, win, 7, d6, d2, d6, d2, 0, 0, &p, &g);
         g.struct_size = sizeof(SlTensorFormat) + 8;      VIEW(rgb, out, n, h, w, oh, ow, win, 7, 0, 0, 0, 0, 0, 0, 0, &g);
-        char* blk = (char*)malloc(16);
-        memcpy(blk, &f, 16);
-        ((SlTensorFormat*)blk)->struct_size = 16;
+        void* blk = undersized(&f);
         VIEW(rgb, out, n, h, w, oh, ow, win, 7, d6, d2, d6, d2, ab, 0, 0, (const SlTensorFormat*)blk);
         VIEW(rgb, out, n, h, w, oh, ow, win, 7, 0, 0, 0, 0, 0, 0, 0, (const SlTensorFormat*)blk);
         free(blk);
@@ -115,6 +102,5 @@ int main(void) {
             g = f; g.mean[c] = -INFINITY;                VIEW(rgb, out, n, h, w, oh, ow, win, 7, 0, 0, 0, 0, 0, 0, 0, &g);
         }
     }
-    printf("%s: %d checks, %d failed\n", failed ? "FAILED" : "OK", checks, failed);
-    return failed ? 1 : 0;
+    return report();
 }

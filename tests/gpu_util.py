@@ -1,8 +1,17 @@
-"""Helpers for the -m gpu parity tests (oracle = checker, HIP engine = thing under test)."""
+"""Helpers for the -m gpu parity tests (oracle = checker, HIP engine = thing under test), and the argument patterns the host-side tests
+of the route entry points share."""
 import numpy as np
 import torch
 
 from oracle import stain_oracle as so
+
+# Keyword patterns of the _v / _s wrappers of tests/test_view_host.py and tests/test_hed_view_host.py (None = a null pointer).
+# The four routes: jitter under a target, normalize_apply, jitter under the tile's own matrix, the tiles' own bytes.
+ROUTES = [dict(), dict(ab=None), dict(mt=None, ct=None), dict(ms=None, cs=None, mt=None, ct=None, ab=None)]
+BAD_STATS = [dict(cs=None), dict(mt=None), dict(ct=None), dict(ab=None, mt=None, ct=None), dict(ms=None), dict(ms=None, cs=None),
+             dict(ms=None, cs=None, ab=None), dict(ms=None, cs=None, mt=None, ct=None), dict(ms=None, mt=None, ct=None, ab=None),
+             dict(ms=None, cs=None, ab=None, ct=None), dict(ms=None, cs=None, ab=None, mt=None)]
+BAD_SHAPES = [dict(rgb=None), dict(n=0), dict(n=-1), dict(h=0), dict(w=-5), dict(h=65536, w=65536), dict(h=32768, w=32769)]
 
 
 def to_dev(tiles):

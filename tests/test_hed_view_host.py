@@ -12,6 +12,7 @@ import torch
 
 import stainlib_amd
 from stainlib_amd import _ffi, engine
+from tests.gpu_util import BAD_SHAPES, BAD_STATS, ROUTES
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BADARG = -1
@@ -31,13 +32,6 @@ def _v(rgb=RGB, out=OUT, n=N, h=H, w=W, oh=OH, ow=OW, win=WIN, d_mask=7, ms=D6, 
     return _ffi.lib().sl_normalize_hed_view(rgb, out, n, h, w, oh, ow, win, d_mask, ms, cs, mt, ct, ab, bg,
                                             C.byref(params) if params is not None else None, C.byref(fmt) if fmt is not None else None,
                                             sg, bs, ap, mode, None)
-
-
-ROUTES = [dict(), dict(ab=None), dict(mt=None, ct=None), dict(ms=None, cs=None, mt=None, ct=None, ab=None)]       # jitter, apply, own, raw
-BAD_STATS = [dict(cs=None), dict(mt=None), dict(ct=None), dict(ab=None, mt=None, ct=None), dict(ms=None), dict(ms=None, cs=None),
-             dict(ms=None, cs=None, ab=None), dict(ms=None, cs=None, mt=None, ct=None), dict(ms=None, mt=None, ct=None, ab=None),
-             dict(ms=None, cs=None, ab=None, ct=None), dict(ms=None, cs=None, ab=None, mt=None)]
-BAD_SHAPES = [dict(rgb=None), dict(n=0), dict(n=-1), dict(h=0), dict(w=-5), dict(h=65536, w=65536), dict(h=32768, w=32769)]
 
 
 # ---- the C entry points -------------------------------------------------------------------------------------------------------------------

@@ -12,6 +12,7 @@ import torch
 
 import stainlib_amd
 from stainlib_amd import _ffi, engine
+from tests.gpu_util import BAD_SHAPES, BAD_STATS, ROUTES
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BADARG = -1
@@ -99,14 +100,10 @@ def test_header_and_binding_agree():
     assert _ffi.lib().sl_version() == 600                    # an extension of ABI 600: no existing struct changes
 
 
-ROUTES = [dict(), dict(ab=None), dict(mt=None, ct=None), dict(ms=None, cs=None, mt=None, ct=None, ab=None)]       # jitter, apply, own, raw
-
-
-@pytest.mark.parametrize("kw", [dict(rgb=None), dict(out=None), dict(win=None), dict(n=0), dict(n=-1), dict(h=0), dict(w=-5),
-                                dict(h=65536, w=65536), dict(h=32768, w=32769), dict(oh=0), dict(ow=0), dict(oh=-1), dict(oh=H + 1),
-                                dict(ow=W + 1), dict(d_mask=-1), dict(d_mask=8), dict(d_mask=1 << 20),
-                                dict(oh=H, ow=W, d_mask=7), dict(oh=H, ow=W, d_mask=1), dict(oh=W + 1, ow=W, d_mask=5),
-                                dict(n=1 << 22, h=32768, w=32768, oh=32768, ow=32768)], ids=str)
+@pytest.mark.parametrize("kw", BAD_SHAPES + [dict(out=None), dict(win=None), dict(oh=0), dict(ow=0), dict(oh=-1), dict(oh=H + 1),
+                                             dict(ow=W + 1), dict(d_mask=-1), dict(d_mask=8), dict(d_mask=1 << 20),
+                                             dict(oh=H, ow=W, d_mask=7), dict(oh=H, ow=W, d_mask=1), dict(oh=W + 1, ow=W, d_mask=5),
+                                             dict(n=1 << 22, h=32768, w=32768, oh=32768, ow=32768)], ids=str)
 def test_bad_pointers_shapes_sizes_and_masks_are_refused(kw):
     for route in ROUTES:
         args = {**route, **kw}
@@ -114,10 +111,7 @@ def test_bad_pointers_shapes_sizes_and_masks_are_refused(kw):
         assert _v(**args, bg=1, params=_ffi.default_params(), fmt=_ffi.default_tensor_format()) == BADARG, args
 
 
-@pytest.mark.parametrize("kw", [dict(cs=None), dict(mt=None), dict(ct=None), dict(ab=None, mt=None, ct=None),
-                                dict(ms=None), dict(ms=None, cs=None), dict(ms=None, cs=None, ab=None),
-                                dict(ms=None, cs=None, mt=None, ct=None), dict(ms=None, mt=None, ct=None, ab=None),
-                                dict(ms=None, cs=None, ab=None, ct=None), dict(ms=None, cs=None, ab=None, mt=None)], ids=str)
+@pytest.mark.parametrize("kw", BAD_STATS, ids=str)
 def test_bad_statistics_are_refused(kw):
     assert _v(**kw) == BADARG and _v(**kw, d_mask=6, oh=H, ow=W, fmt=_ffi.default_tensor_format()) == BADARG
 
@@ -224,6 +218,28 @@ def test_bad_statistics_format_and_view_are_value_errors():
     after = np.random.uniform()
     np.random.seed(3)
     assert np.random.uniform() == after
+
+
+def test_route_upload_keeps_none_and_shapes_the_rest():
+    """engine._route_upload with the CPU as its device: under each of the four routes what is None stays None, and everything else comes
+    back as a contiguous float64 tensor of the shape the C ABI reads, with the caller's values"""
+    n = 3
+    given = dict(M_src=np.arange(n * 6.0).reshape(n, 6), maxC_src=[[1.0, 2.0]] * n, M_tgt=torch.arange(6, dtype=torch.float32),
+                 maxC_tgt=(1.5, 1.1), alpha_beta=np.ones((n, 4)))
+    shapes = dict(M_src=(n, 2, 3), maxC_src=(n, 2), M_tgt=(2, 3), maxC_tgt=(2,), alpha_beta=(n, 4))
+    cpu = torch.device("cpu")
+    for drop in ((), ("alpha_beta",), ("M_tgt", "maxC_tgt"), tuple(given)):                  # jitter, apply, own, raw
+        got = engine._route_upload(n, cpu, **{k: None if k in drop else v for k, v in given.items()})
+        assert len(got) == 5
+        for (k, v), t in zip(given.items(), got):
+            if k in drop:
+                assert t is None, (drop, k)
+            else:
+                assert t.dtype == torch.float64 and t.device == cpu and tuple(t.shape) == shapes[k] and t.is_contiguous(), (drop, k)
+                assert np.array_equal(t.numpy().ravel(), np.asarray(v, dtype=np.float64).ravel()), (drop, k)
+    M = torch.zeros((n, 2, 3), dtype=torch.float64)
+    got = engine._route_upload(n, cpu, M, given["maxC_src"])                                  # the short form of the callers without a route
+    assert got[0].data_ptr() == M.data_ptr() and got[2:] == (None, None, None)                # (already in place: not copied)
 
 
 def test_c_abi_argument_checks_of_the_view_entry_point_under_asan():
