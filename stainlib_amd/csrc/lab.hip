@@ -35,12 +35,8 @@ static __global__ __launch_bounds__(kLabWG) void k_byte_hist(const uint8_t* __re
     const int nch = (P + 3) >> 2;
     const int span = (nch + parts - 1) / parts;
     const int c0 = part * span, c1 = min(nch, c0 + span);
-    for (int c = c0 + (int)threadIdx.x; c < c1; c += kLabWG) {
-        const Chunk in = load_chunk<ALIGNED>(src, nbytes, c);
-#pragma unroll
-        for (int i = 0; i < 12; ++i)
-            if (ALIGNED || (size_t)c * 12 + i < nbytes) atomicAdd(&h[chunk_byte(in, i)], 1u);
-    }
+    for (int c = c0 + (int)threadIdx.x; c < c1; c += kLabWG)
+        count_chunk_bytes<ALIGNED>(h, load_chunk<ALIGNED>(src, nbytes, c), c, nbytes);
     __syncthreads();
     const int v = threadIdx.x;
     unsigned long long t = 0;
@@ -49,38 +45,21 @@ static __global__ __launch_bounds__(kLabWG) void k_byte_hist(const uint8_t* __re
     if (t) atomicAdd(&sc[tile].bytes[v], t);
 }
 
-// the brightness table of a tile: uint8(clip(v * 255.0 / p, 0, 255)) (stain_utils.py:193-194); identity when !standardize
-__device__ __forceinline__ void fill_brightness_lut(uint8_t* lut, const LabScratch& sc, int standardize, double* s_p) {
-    if (threadIdx.x == 0) *s_p = standardize ? percentile_of_hist(sc.bytes, 90.0) : nan("");
-    __syncthreads();
-    const double p = *s_p;
-    for (int v = threadIdx.x; v < 256; v += blockDim.x)
-        lut[v] = standardize ? (uint8_t)clip_trunc_u8((double)v * 255.0 / p) : (uint8_t)v;
-    __syncthreads();
-}
-
 // Per-tile composed tables (workspace, behind the LabScratch array): written ONCE per tile by k_lab_pre / k_lab_tables and loaded by every
 // workgroup of the sweeps that follow.  (Round 5: until then every workgroup of k_lab_hist / k_lab_map rebuilt them -- a serial
 // percentile over 256 global counters, three mean/std loops in binary64, five table passes -- before it touched a pixel: ~20 us of a
 // workgroup's ~450, which also kept the sweeps from being cut into workgroups small enough to fill the last round.)
-struct LabTileTabs {
-    uint16_t g[256];          // byte -> gamma value, through the brightness table where the op standardises
-    uint32_t yf[256];         // L8 -> (y, f(y)) of the MAPPED L byte, packed
-    int ad[256], bd[256];     // a8 / b8 -> the mapped byte on abToXZ's scale (MODE 0)
-    uint8_t lut[256];         // the brightness table (identity when the op does not standardise)
+struct LabTileTabs : LabMapTabs {
     double p;                 // the percentile the op reports (p90 of the bytes / the L percentile of MODE 1)
     double pad_;
 };
+static_assert(sizeof(LabTileTabs) == sizeof(LabMapTabs) + 16, "the workspace sizes rest on it");
 
 // after sweep A: the brightness table and the gamma values behind it (what sweep B needs)
 static __global__ __launch_bounds__(256) void k_lab_pre(const LabScratch* __restrict__ sc, int standardize, LabTileTabs* __restrict__ tt) {
-    __shared__ uint8_t s_lut[256];
-    __shared__ double s_p;
-    const int tile = blockIdx.x, tid = threadIdx.x;
-    fill_brightness_lut(s_lut, sc[tile], standardize, &s_p);
-    tt[tile].lut[tid] = s_lut[tid];
-    tt[tile].g[tid] = (uint16_t)d_gamma[s_lut[tid]];
-    if (tid == 0) tt[tile].p = s_p;
+    const int tile = blockIdx.x;
+    const double p = lab_begin_tables(tt[tile], sc[tile].bytes, standardize);
+    if (threadIdx.x == 0) tt[tile].p = p;
 }
 
 // ---- sweep B: histograms of the Lab bytes of the (standardised) tile ------------------------------------------------
@@ -159,12 +138,10 @@ struct LabMapArgs {
     double* p_out;                                              // MODE 1 / 2 (may be NULL)
 };
 
-// The per-tile tables of the map sweep, one workgroup per tile (what every workgroup of the sweep used to rebuild): normalizer.py:81-83 /
-// stain_utils.py:65 evaluated in binary64 on the 256 possible bytes, composed with the conversion tables the pixel path would
-// look up next.  MODE 0: needs k_lab_pre's brightness table; MODE 1: identity brightness.
+// The per-tile tables of the map sweep, one workgroup per tile (what every workgroup of the sweep used to rebuild): the tile's
+// statistics, then lab_finish_tables.  MODE 0: needs k_lab_pre's brightness table; MODE 1: identity brightness.
 template <int MODE>
 static __global__ __launch_bounds__(256) void k_lab_tables(LabMapArgs a) {
-    __shared__ uint8_t s_ch[3][256];          // per-channel Lab byte tables (MODE 0: all three; MODE 1: L only)
     __shared__ double s_p;
     __shared__ double s_ms[6];
     const int tile = blockIdx.x, tid = threadIdx.x;
@@ -176,31 +153,16 @@ static __global__ __launch_bounds__(256) void k_lab_tables(LabMapArgs a) {
             mean_std_of_scratch(sc, tid, m, s);
             s_ms[tid] = m; s_ms[3 + tid] = s;
         }
-        __syncthreads();
-        // normalizer.py:81-83 in binary64: ((x - mean) * (tstd / std)) + tmean; merge_back (stain_utils.py:168-171): * 2.55 resp.
-        // + 128.0, clip, truncate.  x is the binary32 value lab_split produced, promoted.
-        for (int ch = 0; ch < 3; ++ch) {
-            const double ratio = a.target_stds[ch] / s_ms[3 + ch];
-            const double x = ch == 0 ? (double)((float)tid / 2.55f) : (double)((float)tid - 128.0f);
-            const double nrm = ((x - s_ms[ch]) * ratio) + a.target_means[ch];
-            s_ch[ch][tid] = (uint8_t)clip_trunc_u8(ch == 0 ? nrm * 2.55 : nrm + 128.0);
-        }
     } else {
-        if (tid == 0) s_p = percentile_of_hist(sc.lab_l, a.percentile);
-        __syncthreads();
-        s_ch[0][tid] = (uint8_t)clip_trunc_u8(255.0 * (double)tid / s_p);          // stain_utils.py:65: 255 * L_float / p
-        if (tid == 0) tt.p = s_p;
+        if (tid == 0) tt.p = s_p = percentile_of_hist(sc.lab_l, a.percentile);
         tt.g[tid] = (uint16_t)d_gamma[tid];
         tt.lut[tid] = (uint8_t)tid;
     }
     __syncthreads();
-    const int L2 = s_ch[0][tid], A2 = MODE == 0 ? s_ch[1][tid] : tid, B2 = MODE == 0 ? s_ch[2][tid] : tid;
-    tt.yf[tid] = (uint32_t)d_lab_yf[2 * L2] | ((uint32_t)d_lab_yf[2 * L2 + 1] << 16);
-    tt.ad[tid] = lab_adiv(A2);
-    tt.bd[tid] = lab_bdiv(B2);
+    lab_finish_tables(tt, MODE, s_ms, a.target_means, a.target_stds, s_p);
 }
 
-// The sweep: per-tile tables from k_lab_pre / k_lab_tables; two chunks per lane in flight.
+// The sweep: per-tile tables from k_lab_pre / k_lab_tables; two chunks per lane in flight (lab_sweep2).
 template <int MODE, bool ALIGNED>
 static __global__ __launch_bounds__(kLabWG) void k_lab_map(LabMapArgs a) {
     __shared__ LabCbrtInv s_t;
@@ -221,47 +183,24 @@ static __global__ __launch_bounds__(kLabWG) void k_lab_map(LabMapArgs a) {
     if (MODE != 0 && part == 0 && tid == 0 && a.p_out) a.p_out[tile] = tt.p;
     __syncthreads();
     const int lim = MODE == 0 ? l8_limit(a.thr) : 256;
-    // background (normalizer.py:86-90): 254 + 0 on the L/2.55 scale -> clips to 255; a = b = 0 + 128
-    const uint32_t yf_bg = (uint32_t)d_lab_yf[2 * 255] | ((uint32_t)d_lab_yf[2 * 255 + 1] << 16);
-    const int ad_bg = lab_adiv(128), bd_bg = lab_bdiv(128);
+    const LabBackground bg = lab_background();
     const bool mask_bg = MODE == 0 && a.mask_background;
     const size_t nbytes = (size_t)a.P * 3;
-    const uint8_t* src = a.rgb + (size_t)tile * nbytes;
-    uint8_t* dst = a.out + (size_t)tile * nbytes;
     const int nch = (a.P + 3) >> 2;
     const int span = (nch + a.parts - 1) / a.parts;
-    const int c0 = part * span, c1 = min(nch, c0 + span);
-    if (c0 >= c1) return;
-    auto one = [&](const Chunk& in, int c) {
-        uint32_t ob[12];
+    const int c0 = part * span;
+    const ChunkSpan s{a.rgb + (size_t)tile * nbytes, (size_t)tile * nbytes, nbytes, min(nch, c0 + span)};      // the tile, up to this part's end
+    uint8_t* dst = a.out + s.off;
+    lab_sweep2<ALIGNED, true, kLabWG>(s, c0, [&](const Chunk& in, int c) {
+        if constexpr (MODE != 2) {
+            store_chunk<ALIGNED>(dst, s.nbytes, c, lab_map_chunk<MODE == 0>(s_t, s_g, s_yf, s_ad, s_bd, in, mask_bg, lim, bg));
+        } else {
+            uint32_t ob[12];
 #pragma unroll
-        for (int px = 0; px < 4; ++px) {
-            const uint32_t r = chunk_byte(in, 3 * px), g = chunk_byte(in, 3 * px + 1), b = chunk_byte(in, 3 * px + 2);
-            if (MODE == 2) {
-                ob[3 * px] = s_lut[r]; ob[3 * px + 1] = s_lut[g]; ob[3 * px + 2] = s_lut[b];
-                continue;
-            }
-            int L, A, B;
-            gamma_to_lab8(s_t, s_g[r], s_g[g], s_g[b], L, A, B);
-            uint32_t yf = s_yf[L];
-            int ad = MODE == 0 ? s_ad[A] : lab_adiv(A), bd = MODE == 0 ? s_bd[B] : lab_bdiv(B);     // (MODE 1 leaves a and b alone: three operations each)
-            if (mask_bg) {
-                const bool bg = !(L < lim);
-                yf = bg ? yf_bg : yf; ad = bg ? ad_bg : ad; bd = bg ? bd_bg : bd;
-            }
-            yf_to_rgb(s_t, (int)(yf & 0xffffu), (int)(yf >> 16), ad, bd, ob[3 * px], ob[3 * px + 1], ob[3 * px + 2]);
+            for (int i = 0; i < 12; ++i) ob[i] = s_lut[chunk_byte(in, i)];
+            store_chunk<ALIGNED>(dst, s.nbytes, c, pack12(ob));
         }
-        store_chunk<ALIGNED>(dst, nbytes, c, pack12(ob));
-    };
-    // (the next trip's two chunks are requested before this trip's arithmetic; clamped loads, never predicated)
-    Chunk n0 = load_chunk_clamped<ALIGNED, true>(src, nbytes, c0 + tid, c1), n1 = load_chunk_clamped<ALIGNED, true>(src, nbytes, c0 + tid + kLabWG, c1);
-    for (int c = c0 + tid; c < c1; c += 2 * kLabWG) {
-        const Chunk i0 = n0, i1 = n1;
-        n0 = load_chunk_clamped<ALIGNED, true>(src, nbytes, c + 2 * kLabWG, c1);
-        n1 = load_chunk_clamped<ALIGNED, true>(src, nbytes, c + 3 * kLabWG, c1);
-        one(i0, c);
-        if (c + kLabWG < c1) one(i1, c + kLabWG);
-    }
+    });
 }
 
 // ---- plain conversions -------------------------------------------------------------------------------------------
@@ -379,11 +318,30 @@ int lab_statistics(const uint8_t* rgb, int n, long P, int standardize, int want_
     return launch_status();
 }
 
+// the arguments every map shares; the entry points add their mode's
+LabMapArgs lab_map_args(const uint8_t* rgb, uint8_t* out, int n, long P, LabScratch* sc) {
+    LabMapArgs a{};
+    a.rgb = rgb; a.out = out; a.P = (int)P; a.parts = lab_parts(n, P); a.sc = sc; a.tt = lab_tabs_of(sc, n);
+    return a;
+}
+
 template <int MODE>
 int lab_map(const LabMapArgs& a, int n, hipStream_t s) {
-    if (MODE != 2) hipLaunchKernelGGL((k_lab_tables<MODE>), dim3((unsigned)n), dim3(256), 0, s, a);
+    if constexpr (MODE != 2) hipLaunchKernelGGL((k_lab_tables<MODE>), dim3((unsigned)n), dim3(256), 0, s, a);
     const dim3 grid((unsigned)((long)n * a.parts)), block(kLabWG);
     launch_aligned(aligned4(a.rgb, a.P) && aligned4(a.out, a.P), k_lab_map<MODE, true>, k_lab_map<MODE, false>, grid, block, 0, s, a);
+    return launch_status();
+}
+
+// DIR 0: sl_rgb_to_lab8, 1: sl_lab8_to_rgb
+template <int DIR>
+int lab_convert(const uint8_t* in, uint8_t* out, int n, int h, int w, void* stream) {
+    if (!in || !out || n <= 0 || h <= 0 || w <= 0 || (long)h * w > (1L << 30)) return SL_ERR_BADARG;
+    const long P = (long)h * w;
+    const int parts = parts_for(P);
+    const dim3 grid((unsigned)((long)n * parts)), block(kLabWG);
+    launch_aligned(aligned4(in, P) && aligned4(out, P), k_lab_convert<DIR, true>, k_lab_convert<DIR, false>, grid, block, 0, (hipStream_t)stream,
+                   in, out, (int)P, parts);
     return launch_status();
 }
 
@@ -392,23 +350,11 @@ int lab_map(const LabMapArgs& a, int n, hipStream_t s) {
 namespace sl { size_t lab_workspace_bytes(int n) { return lab_ws_bytes(n); } }      // for sl_workspace_bytes (macenko.hip)
 
 extern "C" int sl_rgb_to_lab8(const uint8_t* rgb, uint8_t* lab_out, int n, int h, int w, void* stream) {
-    if (!rgb || !lab_out || n <= 0 || h <= 0 || w <= 0 || (long)h * w > (1L << 30)) return SL_ERR_BADARG;
-    const long P = (long)h * w;
-    const int parts = parts_for(P);
-    const dim3 grid((unsigned)((long)n * parts)), block(kLabWG);
-    launch_aligned(aligned4(rgb, P) && aligned4(lab_out, P), k_lab_convert<0, true>, k_lab_convert<0, false>, grid, block, 0, (hipStream_t)stream,
-                   rgb, lab_out, (int)P, parts);
-    return launch_status();
+    return lab_convert<0>(rgb, lab_out, n, h, w, stream);
 }
 
 extern "C" int sl_lab8_to_rgb(const uint8_t* lab, uint8_t* rgb_out, int n, int h, int w, void* stream) {
-    if (!lab || !rgb_out || n <= 0 || h <= 0 || w <= 0 || (long)h * w > (1L << 30)) return SL_ERR_BADARG;
-    const long P = (long)h * w;
-    const int parts = parts_for(P);
-    const dim3 grid((unsigned)((long)n * parts)), block(kLabWG);
-    launch_aligned(aligned4(lab, P) && aligned4(rgb_out, P), k_lab_convert<1, true>, k_lab_convert<1, false>, grid, block, 0, (hipStream_t)stream,
-                   lab, rgb_out, (int)P, parts);
-    return launch_status();
+    return lab_convert<1>(lab, rgb_out, n, h, w, stream);
 }
 
 extern "C" int sl_lab_split(const uint8_t* rgb, int n, int h, int w, float* I1, float* I2, float* I3, void* stream) {
@@ -450,8 +396,8 @@ extern "C" int sl_standardize_brightness(const uint8_t* rgb, uint8_t* out, int n
     LabScratch* sc = (LabScratch*)workspace;
     rc = lab_statistics(rgb, n, P, 1, -1, 0.0, sc, s);
     if (rc) return rc;
-    LabMapArgs a{};
-    a.rgb = rgb; a.out = out; a.P = (int)P; a.parts = lab_parts(n, P); a.sc = sc; a.tt = lab_tabs_of(sc, n); a.p_out = p_out;
+    LabMapArgs a = lab_map_args(rgb, out, n, P, sc);
+    a.p_out = p_out;
     return lab_map<2>(a, n, s);
 }
 
@@ -479,8 +425,7 @@ extern "C" int sl_reinhard_transform(const uint8_t* rgb, uint8_t* out, int n, in
     rc = lab_statistics(rgb, n, P, 1, 1, luminosity_threshold, sc, s);
     if (rc) return rc;
     if (stats_out) hipLaunchKernelGGL(k_lab_stats, dim3((unsigned)n), dim3(64), 0, s, sc, 1, stats_out);
-    LabMapArgs a{};
-    a.rgb = rgb; a.out = out; a.P = (int)P; a.parts = lab_parts(n, P); a.sc = sc; a.tt = lab_tabs_of(sc, n);
+    LabMapArgs a = lab_map_args(rgb, out, n, P, sc);
     a.target_means = target_means; a.target_stds = target_stds;
     a.mask_background = mask_background ? 1 : 0; a.thr = luminosity_threshold;
     return lab_map<0>(a, n, s);
@@ -495,7 +440,7 @@ extern "C" int sl_luminosity_standardize(const uint8_t* rgb, uint8_t* out, int n
     LabScratch* sc = (LabScratch*)workspace;
     rc = lab_statistics(rgb, n, P, 0, 0, 0.8, sc, s);
     if (rc) return rc;
-    LabMapArgs a{};
-    a.rgb = rgb; a.out = out; a.P = (int)P; a.parts = lab_parts(n, P); a.sc = sc; a.tt = lab_tabs_of(sc, n); a.percentile = percentile; a.p_out = p_out;
+    LabMapArgs a = lab_map_args(rgb, out, n, P, sc);
+    a.percentile = percentile; a.p_out = p_out;
     return lab_map<1>(a, n, s);
 }

@@ -1,6 +1,8 @@
 // lab_device.hpp -- device helpers of the OpenCV 8-bit Lab family shared by lab.hip (per tile) and slide_lab.hip (per slide): the
 // conversion tables and functions restated from OpenCV's published color_lab.cpp (tables: gen_tables.py), the histogram scratch and
-// the numbers the reference derives from it (np.percentile, cv2.meanStdDev), numpy's clip-then-truncate.
+// the numbers the reference derives from it (np.percentile, cv2.meanStdDev), numpy's clip-then-truncate, and everything the reference
+// computes around the conversions: the byte-table formulas, the composed tables, the map of four pixels, the sweep loop.  The two
+// files keep their partitions of the pixels (tile x part; one flat span per workgroup), their kernels and their entry points.
 #pragma once
 #include "apply_kernels.hpp"
 
@@ -23,7 +25,7 @@ struct LabTabs {
     }
 };
 
-// the static tables a sweep needs, without the ones its per-tile tables (LabTileTabs) already contain
+// the static tables a sweep needs, without the ones its composed tables (LabMapTabs) already contain
 struct LabCbrt {              // RGB -> Lab8 behind a per-tile gamma table
     uint16_t cbrt[3072];
     __device__ __forceinline__ void fill() {
@@ -169,6 +171,126 @@ __device__ inline void mean_std_of_scratch(const LabScratch& sc, int channel, do
     mean = s1 / n;
     const double var = s2 / n - mean * mean;
     sd = sqrt(var > 0.0 ? var : 0.0);
+}
+
+// ---- the byte tables around the conversions: every per-pixel float expression of the reference has a uint8 argument, so each is
+// ---- evaluated once per byte value in binary64, in the reference's operation order, by a 256-thread workgroup (thread = byte) ------
+// The composed tables a map sweep looks up: per tile in the workspace (LabTileTabs, lab.hip), once per slide in the state
+// (state[SL_SLAB_TABLES ...], slide_lab.hip).  Written once by the two kernels between the sweeps, loaded by every workgroup.
+struct LabMapTabs {
+    uint32_t yf[256];         // L8 -> (y, f(y)) of the MAPPED L byte, packed
+    int ad[256], bd[256];     // a8 / b8 -> the mapped byte on abToXZ's scale
+    uint16_t g[256];          // byte -> gamma value, through the brightness table where the op standardises
+    uint8_t lut[256];         // the brightness table (identity when the op does not standardise)
+};
+
+// standardize_brightness (stain_utils.py:193-194): uint8(clip(v * 255.0 / p, 0, 255)); identity when the op does not standardise
+__device__ __forceinline__ uint32_t brightness_byte(int v, double p, int standardize) {
+    return standardize ? clip_trunc_u8((double)v * 255.0 / p) : (uint32_t)v;
+}
+// ReinhardStainNormalizer.transform (normalizer.py:81-83) in binary64: ((x - mean) * (tstd / std)) + tmean; merge_back
+// (stain_utils.py:168-171): * 2.55 resp. + 128.0, clip, truncate.  x is the binary32 value lab_split produced, promoted.  Every
+// operation rounds on its own, as numpy's do: contracted, (x - mean) * ratio + tmean becomes one v_fma_f64 with one rounding.
+__device__ __forceinline__ uint32_t reinhard_byte(int ch, int v, double mean, double sd, double tmean, double tstd) {
+#pragma clang fp contract(off)
+    const double ratio = tstd / sd;
+    const double x = ch == 0 ? (double)((float)v / 2.55f) : (double)((float)v - 128.0f);
+    const double nrm = ((x - mean) * ratio) + tmean;
+    return clip_trunc_u8(ch == 0 ? nrm * 2.55 : nrm + 128.0);
+}
+// LuminosityStandardizer (stain_utils.py:65): 255 * L_float / p
+__device__ __forceinline__ uint32_t luminosity_byte(int v, double p) { return clip_trunc_u8(255.0 * (double)v / p); }
+// a mapped Lab byte triple composed with the conversion tables the pixel path would look up next (lab8_to_rgb's first step)
+__device__ __forceinline__ void lab_compose(int L2, int A2, int B2, uint32_t& yf, int& ad, int& bd) {
+    yf = (uint32_t)d_lab_yf[2 * L2] | ((uint32_t)d_lab_yf[2 * L2 + 1] << 16);
+    ad = lab_adiv(A2);
+    bd = lab_bdiv(B2);
+}
+
+// After sweep A: the 90th percentile of the byte histogram (NaN when !standardize), the brightness table and the gamma values behind
+// it (what sweep B needs).  Returns the percentile to every thread.
+__device__ __forceinline__ double lab_begin_tables(LabMapTabs& tt, const unsigned long long* bytes, int standardize) {
+    __shared__ double s_p;
+    const int v = threadIdx.x;
+    if (v == 0) s_p = standardize ? percentile_of_hist(bytes, 90.0) : nan("");
+    __syncthreads();
+    const uint32_t lut = brightness_byte(v, s_p, standardize);
+    tt.lut[v] = (uint8_t)lut;
+    tt.g[v] = (uint16_t)d_gamma[lut];
+    return s_p;
+}
+// After sweep B: the map's tables from the statistics.  mode 0 Reinhard (ms = means L, a, b, stds L, a, b), 1 luminosity (p = the L
+// percentile; a and b stay).
+__device__ __forceinline__ void lab_finish_tables(LabMapTabs& tt, int mode, const double* ms, const double* tmeans, const double* tstds, double p) {
+    const int v = threadIdx.x;
+    int L2, A2 = v, B2 = v;
+    if (mode == 0) {
+        L2 = (int)reinhard_byte(0, v, ms[0], ms[3], tmeans[0], tstds[0]);
+        A2 = (int)reinhard_byte(1, v, ms[1], ms[4], tmeans[1], tstds[1]);
+        B2 = (int)reinhard_byte(2, v, ms[2], ms[5], tmeans[2], tstds[2]);
+    } else {
+        L2 = (int)luminosity_byte(v, p);
+    }
+    lab_compose(L2, A2, B2, tt.yf[v], tt.ad[v], tt.bd[v]);
+}
+
+// ---- the map: four pixels through the tables ----------------------------------------------------------------------------------
+// background of mask_background (normalizer.py:86-90): 254 + 0 on the L/2.55 scale -> clips to 255; a = b = 0 + 128
+struct LabBackground { uint32_t yf; int ad, bd; };
+__device__ __forceinline__ LabBackground lab_background() {
+    LabBackground bg;
+    lab_compose(255, 128, 128, bg.yf, bg.ad, bg.bd);
+    return bg;
+}
+// gamma (through the brightness table) -> Lab8 -> the tables -> background -> RGB, packed.  AB_TABLES: a and b are mapped (tables ad,
+// bd); otherwise they stay and go straight onto abToXZ's scale (three operations each).  The tables are the workgroup's LDS copies.
+template <bool AB_TABLES, class T>
+__device__ __forceinline__ Chunk lab_map_chunk(const T& t, const uint16_t* g, const uint32_t* yf_tab, const int* ad_tab, const int* bd_tab,
+                                               const Chunk& in, bool mask_bg, int lim, const LabBackground& bg) {
+    uint32_t ob[12];
+#pragma unroll
+    for (int px = 0; px < 4; ++px) {
+        int L, A, B;
+        gamma_to_lab8(t, g[chunk_byte(in, 3 * px)], g[chunk_byte(in, 3 * px + 1)], g[chunk_byte(in, 3 * px + 2)], L, A, B);
+        uint32_t yf = yf_tab[L];
+        int ad = AB_TABLES ? ad_tab[A] : lab_adiv(A), bd = AB_TABLES ? bd_tab[B] : lab_bdiv(B);
+        if (mask_bg) {
+            const bool is_bg = !(L < lim);
+            yf = is_bg ? bg.yf : yf; ad = is_bg ? bg.ad : ad; bd = is_bg ? bg.bd : bd;
+        }
+        yf_to_rgb(t, (int)(yf & 0xffffu), (int)(yf >> 16), ad, bd, ob[3 * px], ob[3 * px + 1], ob[3 * px + 2]);
+    }
+    return pack12(ob);
+}
+
+// ---- the sweeps ---------------------------------------------------------------------------------------------------------------
+// A run of 12-byte chunks `off` bytes into the batch (`src` points there), `nbytes` long: `nloc` chunks of which only the last can be
+// ragged (0 chunks: nothing to do).  slide_lab.hip cuts the shard into one run per workgroup; for lab.hip the run is the tile and a
+// workgroup takes the chunks of its part.
+struct ChunkSpan { const uint8_t* src; size_t off; size_t nbytes; int nloc; };
+// Chunks [c0, nloc) of a run, two per lane in flight: the next trip's are requested before this trip's work (clamped loads, never
+// predicated).  body(chunk, c) sees every chunk of the range once.  WG = the workgroup's size.  (The run goes in by reference, as
+// slide_lab.hip's loop took it: with src / nbytes / range as scalars the statistics sweeps compile to other, if equivalent, code.)
+template <bool ALIGNED, bool STREAM, int WG, class F>
+__device__ __forceinline__ void lab_sweep2(const ChunkSpan& s, int c0, F&& body) {
+    const int tid = threadIdx.x;
+    if (s.nloc <= c0) return;                                           // block-uniform
+    Chunk n0 = load_chunk_clamped<ALIGNED, STREAM>(s.src, s.nbytes, c0 + tid, s.nloc);
+    Chunk n1 = load_chunk_clamped<ALIGNED, STREAM>(s.src, s.nbytes, c0 + tid + WG, s.nloc);
+    for (int c = c0 + tid; c < s.nloc; c += 2 * WG) {
+        const Chunk i0 = n0, i1 = n1;
+        n0 = load_chunk_clamped<ALIGNED, STREAM>(s.src, s.nbytes, c + 2 * WG, s.nloc);
+        n1 = load_chunk_clamped<ALIGNED, STREAM>(s.src, s.nbytes, c + 3 * WG, s.nloc);
+        body(i0, c);
+        if (c + WG < s.nloc) body(i1, c + WG);
+    }
+}
+// the 12 bytes of chunk c counted into one LDS histogram copy (bytes past `nbytes` of a ragged last chunk are not)
+template <bool ALIGNED>
+__device__ __forceinline__ void count_chunk_bytes(uint32_t* h, const Chunk& in, int c, size_t nbytes) {
+#pragma unroll
+    for (int i = 0; i < 12; ++i)
+        if (ALIGNED || (size_t)c * 12 + i < nbytes) atomicAdd(&h[chunk_byte(in, i)], 1u);
 }
 
 }  // namespace sl

@@ -28,18 +28,12 @@ namespace {
 enum { kP90 = SL_SLAB_P90, kMeans = SL_SLAB_MEANS, kStds = SL_SLAB_STDS, kLpct = SL_SLAB_LPCT, kTissue = SL_SLAB_TISSUE, kNpx = SL_SLAB_NPX,
        kStatus = SL_SLAB_STATUS, kTables = SL_SLAB_TABLES };
 
-// the composed tables of the slide (state[SL_SLAB_TABLES ...]; what LabTileTabs is per tile)
-struct SlabTabs {
-    uint32_t yf[256];         // L8 -> (y, f(y)) of the MAPPED L byte, packed
-    int ad[256], bd[256];     // a8 / b8 -> the mapped byte on abToXZ's scale
-    uint16_t g[256];          // byte -> gamma value through the brightness table
-    uint8_t lut[256];         // the brightness table (identity when the chain does not standardise)
-};
-static_assert(kTables * 8 + sizeof(SlabTabs) <= SL_SLAB_STATE_DOUBLES * 8, "SlabTabs does not fit the state");
+// the composed tables of the slide fill state[SL_SLAB_TABLES ...] (what LabTileTabs holds per tile)
+static_assert(kTables * 8 + sizeof(LabMapTabs) == SL_SLAB_STATE_DOUBLES * 8, "LabMapTabs is the rest of the state");
 static_assert(SL_SLAB_SUMS_A == 256 && SL_SLAB_SUMS_B == 262, "256 counts; 256 counts + 4 sums + tissue pixels + pixels");
 
-__device__ __forceinline__ SlabTabs* tabs_of(double* st) { return reinterpret_cast<SlabTabs*>(st + kTables); }
-__device__ __forceinline__ const SlabTabs* tabs_of(const double* st) { return reinterpret_cast<const SlabTabs*>(st + kTables); }
+__device__ __forceinline__ LabMapTabs* tabs_of(double* st) { return reinterpret_cast<LabMapTabs*>(st + kTables); }
+__device__ __forceinline__ const LabMapTabs* tabs_of(const double* st) { return reinterpret_cast<const LabMapTabs*>(st + kTables); }
 
 constexpr int kSlabWG = 256;
 constexpr int kSlabMinTrips = 16;         // chunks per lane below which a shard is not cut further (a workgroup fills up to 17 KB of tables first)
@@ -59,32 +53,15 @@ SlabPlan slab_plan(int n, long P) {
     return p;
 }
 
-// this workgroup's span: where it starts, how many bytes and chunks it holds (0 chunks: nothing to do)
-struct SlabSpan { const uint8_t* src; size_t off; size_t nbytes; int nloc; };
-__device__ __forceinline__ SlabSpan span_of(const uint8_t* rgb, unsigned long long total_bytes, long long span) {
-    SlabSpan s;
+// this workgroup's span: where it starts, how many bytes and chunks it holds
+__device__ __forceinline__ ChunkSpan span_of(const uint8_t* rgb, unsigned long long total_bytes, long long span) {
+    ChunkSpan s;
     s.off = (size_t)blockIdx.x * (size_t)span * 12;
     s.src = rgb + s.off;
     const size_t left = s.off < total_bytes ? (size_t)total_bytes - s.off : 0;
     s.nbytes = left < (size_t)span * 12 ? left : (size_t)span * 12;
     s.nloc = (int)((s.nbytes + 11) / 12);
     return s;
-}
-
-// the chunks of a span, two per lane in flight (the next trip's are requested before this trip's work; clamped loads, never predicated)
-template <bool ALIGNED, bool STREAM, class F>
-__device__ __forceinline__ void slab_sweep(const SlabSpan& s, F&& body) {
-    const int tid = threadIdx.x;
-    if (s.nloc <= 0) return;                                            // block-uniform
-    Chunk n0 = load_chunk_clamped<ALIGNED, STREAM>(s.src, s.nbytes, tid, s.nloc);
-    Chunk n1 = load_chunk_clamped<ALIGNED, STREAM>(s.src, s.nbytes, tid + kSlabWG, s.nloc);
-    for (int c = tid; c < s.nloc; c += 2 * kSlabWG) {
-        const Chunk i0 = n0, i1 = n1;
-        n0 = load_chunk_clamped<ALIGNED, STREAM>(s.src, s.nbytes, c + 2 * kSlabWG, s.nloc);
-        n1 = load_chunk_clamped<ALIGNED, STREAM>(s.src, s.nbytes, c + 3 * kSlabWG, s.nloc);
-        body(i0, c);
-        if (c + kSlabWG < s.nloc) body(i1, c + kSlabWG);
-    }
 }
 
 // ---- sweep A: the byte counts of this rank's shard: partials[blockIdx.x][0 .. 255] ---------------------------------------------
@@ -95,13 +72,9 @@ __global__ __launch_bounds__(kSlabWG) void k_slab_bytes(const uint8_t* __restric
     for (int i = threadIdx.x; i < (kSlabWG / 64) * kSlabCopies * 256; i += kSlabWG) (&s_h[0][0][0])[i] = 0;
     __syncthreads();
     uint32_t* h = s_h[threadIdx.x >> 6][threadIdx.x & (kSlabCopies - 1)];
-    const SlabSpan s = span_of(rgb, total_bytes, span);
+    const ChunkSpan s = span_of(rgb, total_bytes, span);
     // (a span holds fewer than 2^32 bytes -- sl_slab_bytes checks it --, so the 32-bit counters cannot wrap)
-    slab_sweep<ALIGNED, false>(s, [&](const Chunk& in, int c) {
-#pragma unroll
-        for (int i = 0; i < 12; ++i)
-            if (ALIGNED || (size_t)c * 12 + i < s.nbytes) atomicAdd(&h[chunk_byte(in, i)], 1u);
-    });
+    lab_sweep2<ALIGNED, false, kSlabWG>(s, 0, [&](const Chunk& in, int c) { count_chunk_bytes<ALIGNED>(h, in, c, s.nbytes); });
     __syncthreads();
     const int v = threadIdx.x;
     unsigned long long t = 0;
@@ -126,11 +99,11 @@ __global__ __launch_bounds__(kSlabWG) void k_slab_lab(const uint8_t* __restrict_
     __syncthreads();
     uint32_t* h = s_h[tid >> 6][tid & (kSlabCopies - 1)];
     const int lim = l8_limit(thr);
-    const SlabSpan s = span_of(rgb, total_bytes, span);
+    const ChunkSpan s = span_of(rgb, total_bytes, span);
     const size_t npx = s.nbytes / 3;
     uint32_t n_tissue = 0, sa = 0, sb = 0;                           // a lane sees < 2^32 / (3 * 256) pixels of its span: the plain sums fit 32 bits
     unsigned long long saa = 0, sbb = 0;
-    slab_sweep<ALIGNED, false>(s, [&](const Chunk& in, int c) {
+    lab_sweep2<ALIGNED, false, kSlabWG>(s, 0, [&](const Chunk& in, int c) {
 #pragma unroll
         for (int px = 0; px < 4; ++px) {
             int L, A, B;
@@ -178,25 +151,16 @@ __global__ __launch_bounds__(kSlabReduceThreads) void k_slab_reduce(const unsign
 
 // ---- after the first all-reduce: p90 of the slide, its brightness table and the gamma values behind it ----------------------------
 __global__ __launch_bounds__(256) void k_slab_begin(double* __restrict__ st, const unsigned long long* __restrict__ sums_a, int standardize) {
-    __shared__ double s_p;
     const int tid = threadIdx.x;
-    if (tid == 0) s_p = standardize ? percentile_of_hist(sums_a, 90.0) : nan("");
-    __syncthreads();
-    const double p = s_p;
-    // stain_utils.py:193-194: uint8(clip(v * 255.0 / p, 0, 255)); identity when the chain does not standardise
-    const uint32_t lut = standardize ? clip_trunc_u8((double)tid * 255.0 / p) : (uint32_t)tid;
-    SlabTabs* tt = tabs_of(st);
-    tt->lut[tid] = (uint8_t)lut;
-    tt->g[tid] = (uint16_t)d_gamma[lut];
+    const double p = lab_begin_tables(*tabs_of(st), sums_a, standardize);
     if (tid < kTables) st[tid] = tid == kP90 ? p : ((tid >= kMeans && tid <= kLpct) ? nan("") : 0.0);      // (status SL_TILE_OK = 0)
 }
 
-// ---- after the second all-reduce: the slide's statistics and the composed tables of the map (k_lab_tables, once per slide) ---------
+// ---- after the second all-reduce: the slide's statistics and the composed tables of the map (what k_lab_tables does per tile) ---------
 __global__ __launch_bounds__(256) void k_slab_finish(double* __restrict__ st, const unsigned long long* __restrict__ sums_b, int mode,
                                                      const double* __restrict__ target_means, const double* __restrict__ target_stds,
                                                      double percentile, int mask_background) {
     __shared__ LabScratch s_sc;
-    __shared__ uint8_t s_ch[3][256];
     __shared__ double s_p;
     __shared__ double s_ms[6];
     const int tid = threadIdx.x;
@@ -212,25 +176,7 @@ __global__ __launch_bounds__(256) void k_slab_finish(double* __restrict__ st, co
         s_p = mode == 1 ? percentile_of_hist(s_sc.lab_l, percentile) : nan("");
     }
     __syncthreads();
-    if (mode == 0) {
-        // normalizer.py:81-83 in binary64: ((x - mean) * (tstd / std)) + tmean; merge_back (stain_utils.py:168-171): * 2.55 resp.
-        // + 128.0, clip, truncate.  x is the binary32 value lab_split produced, promoted.  Every operation rounds on its own, as numpy's do.
-#pragma clang fp contract(off)
-        for (int ch = 0; ch < 3; ++ch) {
-            const double ratio = target_stds[ch] / s_ms[3 + ch];
-            const double x = ch == 0 ? (double)((float)tid / 2.55f) : (double)((float)tid - 128.0f);
-            const double nrm = ((x - s_ms[ch]) * ratio) + target_means[ch];
-            s_ch[ch][tid] = (uint8_t)clip_trunc_u8(ch == 0 ? nrm * 2.55 : nrm + 128.0);
-        }
-    } else {
-        s_ch[0][tid] = (uint8_t)clip_trunc_u8(255.0 * (double)tid / s_p);          // stain_utils.py:65: 255 * L_float / p
-        s_ch[1][tid] = s_ch[2][tid] = (uint8_t)tid;                                // a and b stay
-    }
-    const int L2 = s_ch[0][tid], A2 = s_ch[1][tid], B2 = s_ch[2][tid];
-    SlabTabs* tt = tabs_of(st);
-    tt->yf[tid] = (uint32_t)d_lab_yf[2 * L2] | ((uint32_t)d_lab_yf[2 * L2 + 1] << 16);
-    tt->ad[tid] = lab_adiv(A2);
-    tt->bd[tid] = lab_bdiv(B2);
+    lab_finish_tables(*tabs_of(st), mode, s_ms, target_means, target_stds, s_p);
     if (tid < 6) st[kMeans + tid] = s_ms[tid];
     if (tid == 0) {
         const unsigned long long tissue = sums_b[260], npx = sums_b[261];
@@ -251,14 +197,14 @@ __global__ __launch_bounds__(kSlabWG) void k_slab_map(const uint8_t* __restrict_
     __shared__ uint32_t s_yf[256];
     __shared__ int s_ad[256], s_bd[256];
     const int tid = threadIdx.x;
-    const SlabSpan s = span_of(rgb, total_bytes, span);
+    const ChunkSpan s = span_of(rgb, total_bytes, span);
     uint8_t* dst = out + s.off;
     if (s.nloc <= 0) return;
     if ((int)st[kStatus] != SL_TILE_OK) {                              // unusable statistics: the tiles go through unchanged (k_apply's rule)
         for (int c = tid; c < s.nloc; c += kSlabWG) store_chunk<ALIGNED>(dst, s.nbytes, c, load_chunk<ALIGNED>(s.src, s.nbytes, c));
         return;
     }
-    const SlabTabs* tt = tabs_of(st);
+    const LabMapTabs* tt = tabs_of(st);
     s_t.fill();
     s_g[tid] = tt->g[tid];
     s_yf[tid] = tt->yf[tid];
@@ -266,24 +212,9 @@ __global__ __launch_bounds__(kSlabWG) void k_slab_map(const uint8_t* __restrict_
     s_bd[tid] = tt->bd[tid];
     __syncthreads();
     const int lim = l8_limit(thr);
-    // background (normalizer.py:86-90): 254 + 0 on the L/2.55 scale -> clips to 255; a = b = 0 + 128
-    const uint32_t yf_bg = (uint32_t)d_lab_yf[2 * 255] | ((uint32_t)d_lab_yf[2 * 255 + 1] << 16);
-    const int ad_bg = lab_adiv(128), bd_bg = lab_bdiv(128);
-    slab_sweep<ALIGNED, true>(s, [&](const Chunk& in, int c) {
-        uint32_t ob[12];
-#pragma unroll
-        for (int px = 0; px < 4; ++px) {
-            int L, A, B;
-            gamma_to_lab8(s_t, s_g[chunk_byte(in, 3 * px)], s_g[chunk_byte(in, 3 * px + 1)], s_g[chunk_byte(in, 3 * px + 2)], L, A, B);
-            uint32_t yf = s_yf[L];
-            int ad = s_ad[A], bd = s_bd[B];
-            if (mask_bg) {
-                const bool bg = !(L < lim);
-                yf = bg ? yf_bg : yf; ad = bg ? ad_bg : ad; bd = bg ? bd_bg : bd;
-            }
-            yf_to_rgb(s_t, (int)(yf & 0xffffu), (int)(yf >> 16), ad, bd, ob[3 * px], ob[3 * px + 1], ob[3 * px + 2]);
-        }
-        store_chunk<ALIGNED>(dst, s.nbytes, c, pack12(ob));
+    const LabBackground bg = lab_background();
+    lab_sweep2<ALIGNED, true, kSlabWG>(s, 0, [&](const Chunk& in, int c) {
+        store_chunk<ALIGNED>(dst, s.nbytes, c, lab_map_chunk<true>(s_t, s_g, s_yf, s_ad, s_bd, in, mask_bg, lim, bg));
     });
 }
 
@@ -308,6 +239,27 @@ void slab_reduce(const void* ws, int rows, int cols, int extra_col, unsigned lon
                        extra_col, extra, out);
 }
 
+// A statistics sweep of the shard and the reduce of its partial rows: sl_slab_bytes (cols SL_SLAB_SUMS_A) and sl_slab_lab (cols
+// SL_SLAB_SUMS_B, whose last column is the pixel count no row carries).  `args`: what the kernel takes between the span and the partials.
+template <class K, class... Args>
+int slab_sums(K k_aligned, K k_unaligned, const uint8_t* rgb, int n, int h, int w, void* workspace, size_t workspace_bytes, int cols, int extra_col,
+              unsigned long long* out, void* stream, Args... args) {
+    if (!out || !slab_shape_ok(n, h, w) || (n > 0 && !rgb)) return SL_ERR_BADARG;
+    const long P = (long)h * w;
+    if (const int rc = slab_ws_check(workspace, workspace_bytes, n, P)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    int rows = 0;
+    if (n > 0) {
+        const SlabPlan pl = slab_plan(n, P);
+        if (pl.span * 12 >= (1LL << 32)) return SL_ERR_BADARG;            // (a device with a handful of CUs and a 2^40-pixel shard)
+        rows = pl.rows;
+        launch_aligned(aligned4(rgb, (long)n * P), k_aligned, k_unaligned, dim3((unsigned)rows), dim3(kSlabWG), 0, s, rgb,
+                       (unsigned long long)n * (unsigned long long)P * 3ull, pl.span, args..., (unsigned long long*)workspace);
+    }
+    slab_reduce(workspace, rows, cols, extra_col, (unsigned long long)n * (unsigned long long)P, out, s);
+    return launch_status();
+}
+
 }  // namespace
 
 extern "C" size_t sl_slab_workspace_bytes(int n, int h, int w) {
@@ -317,20 +269,7 @@ extern "C" size_t sl_slab_workspace_bytes(int n, int h, int w) {
 
 extern "C" int sl_slab_bytes(const uint8_t* rgb, int n, int h, int w, void* workspace, size_t workspace_bytes, unsigned long long* sums_a_out,
                              void* stream) {
-    if (!sums_a_out || !slab_shape_ok(n, h, w) || (n > 0 && !rgb)) return SL_ERR_BADARG;
-    const long P = (long)h * w;
-    if (const int rc = slab_ws_check(workspace, workspace_bytes, n, P)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    int rows = 0;
-    if (n > 0) {
-        const SlabPlan pl = slab_plan(n, P);
-        if (pl.span * 12 >= (1LL << 32)) return SL_ERR_BADARG;            // (a device with a handful of CUs and a 2^40-pixel shard)
-        rows = pl.rows;
-        launch_aligned(aligned4(rgb, (long)n * P), k_slab_bytes<true>, k_slab_bytes<false>, dim3((unsigned)rows), dim3(kSlabWG), 0, s, rgb,
-                       (unsigned long long)n * (unsigned long long)P * 3ull, pl.span, (unsigned long long*)workspace);
-    }
-    slab_reduce(workspace, rows, SL_SLAB_SUMS_A, -1, 0ull, sums_a_out, s);
-    return launch_status();
+    return slab_sums(k_slab_bytes<true>, k_slab_bytes<false>, rgb, n, h, w, workspace, workspace_bytes, SL_SLAB_SUMS_A, -1, sums_a_out, stream);
 }
 
 extern "C" int sl_slab_begin(double* state, const unsigned long long* sums_a_reduced, int standardize, void* stream) {
@@ -341,20 +280,9 @@ extern "C" int sl_slab_begin(double* state, const unsigned long long* sums_a_red
 
 extern "C" int sl_slab_lab(const uint8_t* rgb, int n, int h, int w, const double* state, double luminosity_threshold, void* workspace,
                            size_t workspace_bytes, unsigned long long* sums_b_out, void* stream) {
-    if (!state || !sums_b_out || !slab_shape_ok(n, h, w) || (n > 0 && !rgb)) return SL_ERR_BADARG;
-    const long P = (long)h * w;
-    if (const int rc = slab_ws_check(workspace, workspace_bytes, n, P)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    int rows = 0;
-    if (n > 0) {
-        const SlabPlan pl = slab_plan(n, P);
-        if (pl.span * 12 >= (1LL << 32)) return SL_ERR_BADARG;
-        rows = pl.rows;
-        launch_aligned(aligned4(rgb, (long)n * P), k_slab_lab<true>, k_slab_lab<false>, dim3((unsigned)rows), dim3(kSlabWG), 0, s, rgb,
-                       (unsigned long long)n * (unsigned long long)P * 3ull, pl.span, luminosity_threshold, state, (unsigned long long*)workspace);
-    }
-    slab_reduce(workspace, rows, SL_SLAB_SUMS_B, SL_SLAB_SUMS_B - 1, (unsigned long long)n * (unsigned long long)P, sums_b_out, s);
-    return launch_status();
+    if (!state) return SL_ERR_BADARG;
+    return slab_sums(k_slab_lab<true>, k_slab_lab<false>, rgb, n, h, w, workspace, workspace_bytes, SL_SLAB_SUMS_B, SL_SLAB_SUMS_B - 1, sums_b_out,
+                     stream, luminosity_threshold, state);
 }
 
 extern "C" int sl_slab_finish(double* state, const unsigned long long* sums_b_reduced, int mode, const double* target_means,

@@ -99,6 +99,42 @@ def test_the_slides_statistics_were_used_not_the_tiles():
     assert torch.equal(one, per_tile[2:3])
 
 
+def _twin_tile(shape):
+    if shape == "61x67":        # tile 2 of the class-b slide, in place: it starts 24522 bytes into the batch (the unaligned kernels), 4087 pixels
+        return _dev(_slide("b"))[2:3]
+    if shape == "64x64":        # aligned, one workgroup on both sides
+        return _dev(_dark([so.synth_tile(64, 64, 64)], 0.7))
+    if shape == "191x193":      # 36863 pixels = 9216 chunks, the last one ragged: two parts per tile, three spans per slide
+        return _dev(_dark([so.synth_tile(191, 193, 191)], 0.7))
+    raise ValueError(shape)
+
+
+@pytest.mark.parametrize("shape", ["61x67", "64x64", "191x193"])
+def test_a_one_tile_slide_is_the_per_tile_family_on_another_partition(shape):
+    """The pooled chain and the per-tile family run the same device bodies (csrc/lab_device.hpp) over two cuts of the pixels: on a slide
+    of one tile they must agree to the byte, the integer statistics exactly, the means and standard deviations at this file's bars."""
+    from stainlib_amd import engine
+    from stainlib_amd.distributed import SlideNormalizer, slide_luminosity_standardize
+    dev = _twin_tile(shape)
+    nrm = _normalizer()
+    for name, kw in MASKS:
+        per_tile, st = nrm.transform_batch(dev, **kw)
+        sn = SlideNormalizer(nrm, group=False, mode="pooled")
+        out, m, s, status = sn.transform_shard(dev, **kw)
+        st = st[0].cpu().numpy()
+        print(f"{shape} {name}: {int((out != per_tile).sum())} bytes differ; p90 {sn.last_p90} / {st[0]}; tissue {sn.last_tissue} / {st[7]}; "
+              f"means {m.cpu().numpy()} / {st[1:4]}; stds {s.cpu().numpy()} / {st[4:7]}")
+        assert torch.equal(out, per_tile) and not status.any()
+        assert sn.last_p90 == st[0] and st[0] < 255 and sn.last_tissue == int(st[7])
+        np.testing.assert_allclose(m.cpu().numpy(), st[1:4], rtol=1e-13)
+        np.testing.assert_allclose(s.cpu().numpy(), st[4:7], rtol=1e-12)
+    for pct in (95, 80):
+        per_tile, p_tile = engine.luminosity_standardize(dev, pct)
+        out, p = slide_luminosity_standardize(dev, percentile=pct, group=False)
+        print(f"{shape} luminosity {pct}: {int((out != per_tile).sum())} bytes differ; p {p} / {float(p_tile[0])}")
+        assert torch.equal(out, per_tile) and p == float(p_tile[0])
+
+
 def _chain(dev_parts, tm, ts, mask_background=False, thr=0.8):
     """the chain with the sums of the parts added by hand (no process group): (state, [out per part])"""
     from stainlib_amd import engine
