@@ -157,20 +157,73 @@ __device__ __forceinline__ bool cube_worthwhile(const uint32_t* samp, int n_samp
     return share_pct <= kCubeMaxSharePct;
 }
 
-// exec-masked append of `value` for the lanes of m at LDS byte address buf + 4 n (n wave-uniform): RawSink::put_value's core
-__device__ __forceinline__ void lds_append_masked(uint32_t buf, uint32_t n, unsigned long long m, uint32_t value) {
-    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+// The cube test of one pixel p = r | g << 8 | b << 16 (a stray top byte reaches neither the cell address nor the bit index): true when
+// its cell is ambiguous.  bits_lds: LDS byte address of the 4 KB mask (wave-uniform).  The address is the two 5-bit fields shifted into
+// place behind the base, v_bfe_u32 + v_lshl_or_b32 each -- four instructions on inline constants and ONE scalar operand, where
+// `(p >> 12 & 0xF80) | (p >> 9 & 0x7C) | base` compiled to two shifts, two v_and and a v_or3; the bit test is two v_bfe_u32 and the
+// compare that makes the ballot.  (The address is bits_lds | cube_word_offset(p): the same value, built in another form.)
+__device__ __forceinline__ bool cube_ambiguous(uint32_t p, uint32_t bits_lds) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    uint32_t sbase;
-    asm("s_lshl2_add_u32 %0, %1, %2" : "=s"(sbase) : "s"((uint32_t)__builtin_amdgcn_readfirstlane((int)n)), "s"(buf) : "scc");
-    const uint32_t addr = sbase + 4u * rank;
-    unsigned long long saved;
-    asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, %1\n\tds_write_b32 %2, %3\n\ts_mov_b64 exec, %0"
-                 : "=&s"(saved) : "s"(m), "v"(addr), "v"(value) : "memory");
+    uint32_t x, a;
+    asm("v_lshl_or_b32 %0, %1, 2, %2" : "=v"(x) : "v"((p >> 11) & 31u), "s"(bits_lds));
+    asm("v_lshl_or_b32 %0, %1, 7, %2" : "=v"(a) : "v"((p >> 19) & 31u), "v"(x));
+    const uint32_t w = *(SL_LDS const uint32_t*)a;
 #else
-    (void)rank; (void)value; (void)buf; (void)n;
+    (void)bits_lds;
+    const uint32_t w = 0;
 #endif
+    return ((w >> cube_bit(p)) & 1u) != 0u;
 }
+
+// The per-wave ring of the pixels of ambiguous cells: kCubeRing entries in LDS, everything here wave-uniform (SGPRs).  The fill is kept
+// as the BYTE ADDRESS of the next free entry, so an append costs the scalar unit a popcount and one s_lshl2_add_u32, and the exec mask of
+// the sweep (no lane is ever switched off around the cube test: no predicated loads) is read ONCE per sweep: two pixel rows go in
+// with two exec moves, two masked ds_write and one restore.  The drain takes two full rows off the top whenever there are two.
+// (A ring of 127 + 4 x 64 entries would let a whole chunk go in behind one restore and one drain test, but 4 KB more per workgroup do
+// not fit beside the row table: sizeof(FusedShared<512>) is 81 424 of 81 920 B.)
+// PRECONDITION: put2 restores exec to what make() read, it does not save it.  Every put2 must run under exactly the exec of make():
+// never inside a divergent region, never under a narrower mask than the sweep's -- it would switch the other lanes back on.
+struct CubeRing {
+    uint32_t base;              // LDS byte address of entry 0
+    uint32_t at;                // LDS byte address of the next free entry
+    unsigned long long lanes;   // exec of the sweep
+    __device__ __forceinline__ static CubeRing make(uint32_t ring_lds) { return CubeRing{ring_lds, ring_lds, __builtin_amdgcn_read_exec()}; }
+    __device__ __forceinline__ static uint32_t rank(unsigned long long m) {
+        return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    }
+    // v0 for the lanes of m0, then v1 for the lanes of m1: at most 127 + 2 x 64 entries, kCubeRing holds them
+    __device__ __forceinline__ void put2(unsigned long long m0, uint32_t v0, unsigned long long m1, uint32_t v1) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        uint32_t at1, at2;
+        asm("s_lshl2_add_u32 %0, %1, %2" : "=s"(at1) : "s"((uint32_t)__popcll(m0)), "s"(at) : "scc");
+        asm("s_lshl2_add_u32 %0, %1, %2" : "=s"(at2) : "s"((uint32_t)__popcll(m1)), "s"(at1) : "scc");
+        const uint32_t a0 = at + 4u * rank(m0), a1 = at1 + 4u * rank(m1);
+        asm volatile("s_mov_b64 exec, %0\n\tds_write_b32 %1, %2\n\ts_mov_b64 exec, %3\n\tds_write_b32 %4, %5\n\ts_mov_b64 exec, %6"
+                     : : "s"(m0), "v"(a0), "v"(v0), "s"(m1), "v"(a1), "v"(v1), "s"(lanes) : "memory");
+        at = at2;
+#else
+        (void)m0; (void)v0; (void)m1; (void)v1;
+#endif
+    }
+    __device__ __forceinline__ bool two_rows() const { return at >= base + 512u; }
+    // the top two rows leave the ring: entry `lane` of each
+    __device__ __forceinline__ void pop2(int lane, uint32_t& q0, uint32_t& q1) {
+        at -= 512u;
+        read2(at, lane, q0, q1);
+    }
+    // the bottom two rows, whatever the fill (entries beyond it are stale ring contents, always valid pixels)
+    __device__ __forceinline__ void rest2(int lane, uint32_t& q0, uint32_t& q1) const { read2(base, lane, q0, q1); }
+    __device__ __forceinline__ uint32_t fill() const { return (at - base) >> 2; }
+    __device__ __forceinline__ static void read2(uint32_t from, int lane, uint32_t& q0, uint32_t& q1) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        const uint32_t a = from + 4u * (uint32_t)lane;
+        q0 = *(SL_LDS const uint32_t*)a;
+        q1 = *(SL_LDS const uint32_t*)(a + 256u);
+#else
+        q0 = q1 = from + (uint32_t)lane;
+#endif
+    }
+};
 
 // Where the exact test's candidates go: straight to the tile's lists (no second staging level: a drain flags ~50 pixels of 128 and
 // pays ONE allocation for them).  TWO lists: the angular candidates (tissue outside the plain cone) and the concentration candidates
@@ -206,7 +259,7 @@ struct RawDirect {
 
 // The merged selection sweep behind the cube mask.  bits_lds: LDS byte address of the 4 KB mask; ring_lds: LDS byte address of this
 // wave's kCubeRing staging entries (wave-uniform).  Pixels of ambiguous cells are appended to the ring; whenever it holds two full
-// rows (checked every second pixel row) they are re-tested exactly, two rows side by side, by the test of select_sweep<kStageMerged>
+// rows (checked every second pixel row: CubeRing) they are re-tested exactly, two rows side by side, by the test of select_sweep<kStageMerged>
 // (the variant with the per-pixel tissue test), and what that flags goes to the tile's two candidate lists (RawDirect).  c0 must be a multiple of 64.
 template <bool ALIGNED, int kTrip, bool STREAM, class TR>
 __device__ __forceinline__ void select_sweep_cube(const uint8_t* src, int P, int c0, int c1, int t, int nthreads, const TR& T, float ylimf,
@@ -216,7 +269,7 @@ __device__ __forceinline__ void select_sweep_cube(const uint8_t* src, int P, int
     const float nhi0m = in_vgpr(-(K.hi0 + kAngleMargin)), nlo1m = in_vgpr(-(K.lo1 - kAngleMargin));
     const int w0 = __builtin_amdgcn_readfirstlane(c0 + (t & ~63));
     auto fetch = [&](int cc) { return load_chunk_clamped<ALIGNED, STREAM>(src, nbytes, cc, c1); };
-    uint32_t rn = 0;                                             // ring fill, wave-uniform
+    CubeRing ring = CubeRing::make(ring_lds);
     struct G3 { float2 r, g, b; };
     auto gather = [&](uint32_t q) { return G3{T.gam_odf(T.addr(q, 0)), T.gam_odf(T.addr(q, 1)), T.gam_odf(T.addr(q, 2))}; };
     struct M2 { unsigned long long a, c; };                      // lane masks: angular candidate, concentration candidate
@@ -233,30 +286,14 @@ __device__ __forceinline__ void select_sweep_cube(const uint8_t* src, int P, int
         const bool g1 = fmaf(K.eps[0], sa, a1) >= K.thr[0], g2 = fmaf(K.eps[1], sa, a2) >= K.thr[1];
         return M2{__builtin_amdgcn_ballot_w64(tc) & ~__builtin_amdgcn_ballot_w64(pp), __builtin_amdgcn_ballot_w64(g1) | __builtin_amdgcn_ballot_w64(g2)};
     };
-    auto ring_read = [&](uint32_t i) -> uint32_t {
-#if defined(__HIP_DEVICE_COMPILE__)
-        return *(SL_LDS const uint32_t*)(ring_lds + 4u * i);
-#else
-        return i;
-#endif
-    };
     auto drain = [&]() {
-        while (rn >= 128u) {                                     // wave-uniform; two rows side by side: their LDS round trips overlap
-            rn -= 128u;
-            const uint32_t q0 = ring_read(rn + (uint32_t)lane), q1 = ring_read(rn + 64u + (uint32_t)lane);
+        while (ring.two_rows()) {                                // wave-uniform; two rows side by side: their LDS round trips overlap
+            uint32_t q0, q1;
+            ring.pop2(lane, q0, q1);
             const G3 e0 = gather(q0), e1 = gather(q1);
             const M2 f0 = flags(e0), f1 = flags(e1);
             out.put2(f0.a, f0.c, q0, f1.a, f1.c, q1, lane);
         }
-    };
-    auto pixel_mask = [&](uint32_t p) -> bool {
-#if defined(__HIP_DEVICE_COMPILE__)
-        // (bits_lds is 4 KB aligned: the base joins the address in the and-or that builds it)
-        const uint32_t w = *(SL_LDS const uint32_t*)(((p >> 12) & 0xF80u) | (((p >> 9) & 0x7Cu) | bits_lds));
-#else
-        const uint32_t w = 0;
-#endif
-        return ((w >> cube_bit(p)) & 1u) != 0u;
     };
     auto compute = [&](auto tail_tag, const Chunk& ch, int cc) {
         constexpr bool TAIL = decltype(tail_tag)::value;
@@ -265,18 +302,18 @@ __device__ __forceinline__ void select_sweep_cube(const uint8_t* src, int P, int
 #pragma unroll
         for (int px = 0; px < 4; ++px) {
             p[px] = chunk_pixel(ch, px);
-            amb[px] = pixel_mask(px == 0 ? ch.w0 : p[px]);        // (a stray top byte does not reach the cell address or the bit index)
+            amb[px] = cube_ambiguous(px == 0 ? ch.w0 : p[px], bits_lds);
         }
 #pragma unroll
-        for (int px = 0; px < 4; ++px) {
-            unsigned long long m = __builtin_amdgcn_ballot_w64(amb[px]);
-            if (TAIL) {
-                const bool inb = in_tile<ALIGNED>(cc, px, c1, P);
-                m &= __builtin_amdgcn_ballot_w64(inb);
+        for (int px = 0; px < 4; px += 2) {
+            unsigned long long m[2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                m[j] = __builtin_amdgcn_ballot_w64(amb[px + j]);
+                if (TAIL) m[j] &= __builtin_amdgcn_ballot_w64(in_tile<ALIGNED>(cc, px + j, c1, P));
             }
-            lds_append_masked(ring_lds, rn, m, p[px]);
-            rn += (uint32_t)__popcll(m);
-            if (px & 1) drain();                                 // at most 127 + 2 x 64 entries before it: kCubeRing holds them
+            ring.put2(m[0], p[px], m[1], p[px + 1]);
+            drain();
         }
     };
     // A deliberate variant of pipelined_sweep (sweep_pipeline.hpp, the canonical form of this loop): no table gather per chunk,
@@ -302,12 +339,13 @@ __device__ __forceinline__ void select_sweep_cube(const uint8_t* src, int P, int
     // what is left: fewer than 128 entries.  (Entries beyond the fill are stale ring contents, always valid pixels: read by every
     // lane -- no predicated load -- and masked out of the result.)
     {
-        const uint32_t q0 = ring_read((uint32_t)lane), q1 = ring_read(64u + (uint32_t)lane);
+        uint32_t q0, q1;
+        ring.rest2(lane, q0, q1);
+        const uint32_t rn = ring.fill();
         const G3 e0 = gather(q0 & 0xffffffu), e1 = gather(q1 & 0xffffffu);
         const unsigned long long l0 = __builtin_amdgcn_ballot_w64((uint32_t)lane < rn), l1 = __builtin_amdgcn_ballot_w64(64u + (uint32_t)lane < rn);
         const M2 f0 = flags(e0), f1 = flags(e1);
         out.put2(f0.a & l0, f0.c & l0, q0, f1.a & l1, f1.c & l1, q1, lane);
-        rn = 0;
     }
 }
 

@@ -990,7 +990,8 @@ __device__ __noinline__ void fused_sweep1c(FusedShared<NT>* shp, const uint8_t* 
     } else if (stream) ts_sweep<ALIGNED, kFusedTrip, true>(src, P, c0, c1, t, kFusedThreads, TB, ylimf, K, bits_lds, ring_lds, direct, mo, n_tissue);
     else ts_sweep<ALIGNED, kFusedTrip, false>(src, P, c0, c1, t, kFusedThreads, TB, ylimf, K, bits_lds, ring_lds, direct, mo, n_tissue);
     double v[10];
-    mo.to_array(v, n_tissue, lane);
+    mo.to_array(v, 0u, lane);
+    v[0] = (double)n_tissue;                                     // (ts_sweep counts per lane: the wave sum below is the same integer)
 #pragma unroll
     for (int i = 0; i < 10; ++i) v[i] = wave_sum(v[i]);
     if (lane == 0)

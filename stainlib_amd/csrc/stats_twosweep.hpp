@@ -283,6 +283,7 @@ __device__ __forceinline__ int ts_cube_share(const uint32_t* samp, int n_sample,
 // to every other schedule's) with the cube test of select_sweep_cube run on the trip's four chunks while the first table gather of the
 // trip is in flight.  Pixels of ambiguous cells go to the wave's ring in LDS and are re-tested exactly two rows at a time (the drain);
 // what the exact test flags goes to the tile's two candidate lists (RawDirect).  No sample bookkeeping: the sample exists already.
+// n_tissue comes back PER LANE: the tissue pixels this lane saw (the sum over the wave's lanes is the count the other sweeps keep).
 struct TsSweepConsts {      // wave-uniform (SGPRs): the exact test runs for the pixels of ambiguous cells only
     float gH[3], gL[3], n[3], k1;
     float W[2][3], kt[2], eps[2], zeta[2], thr[2];
@@ -304,19 +305,21 @@ __device__ __forceinline__ void ts_sweep(const uint8_t* src, int P, int c0, int 
         for (int px = 0; px < 4; ++px) {
             const float2 er = g.v[3 * px], eg = g.v[3 * px + 1], eb = g.v[3 * px + 2];
             const bool tc = is_tissue_f(er.x, eg.x, eb.x, ylimf);
-            if (!TAIL) {
-                n_tissue += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(tc));
-                if (tc) bm.add(er.y, eg.y, eb.y);
-            } else {
-                const bool inb = in_tile<ALIGNED>(cc, px, c1, P);
-                const unsigned long long m = __builtin_amdgcn_ballot_w64(tc) & __builtin_amdgcn_ballot_w64(inb);
-                n_tissue += (uint32_t)__popcll(m);
-                if (tc & inb) bm.add(er.y, eg.y, eb.y);
-            }
+            // (the tissue count is one carry-in add per pixel on the compare's mask, PER LANE -- the caller adds the lanes up -- in place of
+            //  a ballot's popcount and an add on the scalar unit the CU's two workgroups share.  It stays OUTSIDE the exec-masked region
+            //  of the sums: a tenth instruction in there makes the compiler put an s_cbranch_execz in front of every pixel's sums)
+            const bool ok = tc & (!TAIL || in_tile<ALIGNED>(cc, px, c1, P));
+#if defined(__HIP_DEVICE_COMPILE__)
+            unsigned long long carry;                            // (plain `n += ok` compiles to a v_cndmask and half a v_add3 per pixel)
+            asm("v_addc_co_u32 %0, %1, 0, %0, %2" : "+v"(n_tissue), "=s"(carry) : "s"(__builtin_amdgcn_ballot_w64(ok)));
+#else
+            n_tissue += ok ? 1u : 0u;
+#endif
+            if (ok) bm.add(er.y, eg.y, eb.y);
         }
     };
     // ---- the candidate side
-    uint32_t rn = 0;                                             // ring fill, wave-uniform
+    CubeRing ring = CubeRing::make(ring_lds);
     struct G3 { float2 r, g, b; };
     auto gather3 = [&](uint32_t q) { return G3{T.gam_odf(T.addr(q, 0)), T.gam_odf(T.addr(q, 1)), T.gam_odf(T.addr(q, 2))}; };
     struct M2 { unsigned long long a, c; };
@@ -332,29 +335,14 @@ __device__ __forceinline__ void ts_sweep(const uint8_t* src, int P, int c0, int 
         const bool g1 = fmaf(K.zeta[0], fabsf(z), fmaf(K.eps[0], sa, a1)) >= K.thr[0], g2 = fmaf(K.zeta[1], fabsf(z), fmaf(K.eps[1], sa, a2)) >= K.thr[1];
         return M2{__builtin_amdgcn_ballot_w64(tc) & ~__builtin_amdgcn_ballot_w64(pp), __builtin_amdgcn_ballot_w64(g1) | __builtin_amdgcn_ballot_w64(g2)};
     };
-    auto ring_read = [&](uint32_t i) -> uint32_t {
-#if defined(__HIP_DEVICE_COMPILE__)
-        return *(SL_LDS const uint32_t*)(ring_lds + 4u * i);
-#else
-        return i;
-#endif
-    };
     auto drain = [&]() {
-        while (rn >= 128u) {                                     // wave-uniform
-            rn -= 128u;
-            const uint32_t q0 = ring_read(rn + (uint32_t)lane), q1 = ring_read(rn + 64u + (uint32_t)lane);
+        while (ring.two_rows()) {                                // wave-uniform
+            uint32_t q0, q1;
+            ring.pop2(lane, q0, q1);
             const G3 e0 = gather3(q0), e1 = gather3(q1);
             const M2 f0 = flags(e0), f1 = flags(e1);
             out.put2(f0.a, f0.c, q0, f1.a, f1.c, q1, lane);
         }
-    };
-    auto pixel_mask = [&](uint32_t p) -> bool {
-#if defined(__HIP_DEVICE_COMPILE__)
-        const uint32_t w = *(SL_LDS const uint32_t*)(((p >> 12) & 0xF80u) | (((p >> 9) & 0x7Cu) | bits_lds));
-#else
-        const uint32_t w = 0;
-#endif
-        return ((w >> cube_bit(p)) & 1u) != 0u;
     };
     auto cube = [&](auto tail_tag, const Chunk& ch, int cc) {
         constexpr bool TAIL = decltype(tail_tag)::value;
@@ -363,18 +351,18 @@ __device__ __forceinline__ void ts_sweep(const uint8_t* src, int P, int c0, int 
 #pragma unroll
         for (int px = 0; px < 4; ++px) {
             p[px] = chunk_pixel(ch, px);
-            amb[px] = pixel_mask(px == 0 ? ch.w0 : p[px]);
+            amb[px] = cube_ambiguous(px == 0 ? ch.w0 : p[px], bits_lds);
         }
 #pragma unroll
-        for (int px = 0; px < 4; ++px) {
-            unsigned long long m = __builtin_amdgcn_ballot_w64(amb[px]);
-            if (TAIL) {
-                const bool inb = in_tile<ALIGNED>(cc, px, c1, P);
-                m &= __builtin_amdgcn_ballot_w64(inb);
+        for (int px = 0; px < 4; px += 2) {
+            unsigned long long m[2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                m[j] = __builtin_amdgcn_ballot_w64(amb[px + j]);
+                if (TAIL) m[j] &= __builtin_amdgcn_ballot_w64(in_tile<ALIGNED>(cc, px + j, c1, P));
             }
-            lds_append_masked(ring_lds, rn, m, p[px] & 0xffffffu);
-            rn += (uint32_t)__popcll(m);
-            if (px & 1) drain();
+            ring.put2(m[0], p[px] & 0xffffffu, m[1], p[px + 1] & 0xffffffu);
+            drain();
         }
     };
     // A deliberate variant of pipelined_sweep (sweep_pipeline.hpp, the canonical form of this loop): the cube test of the trip's
@@ -406,12 +394,13 @@ __device__ __forceinline__ void ts_sweep(const uint8_t* src, int P, int c0, int 
     for (; cb + (kTrip - 1) * nthreads + 64 <= lim; cb += nthreads * kTrip) trip(std::false_type{}, cb);
     if (cb < c1) trip(std::true_type{}, cb);
     {   // what is left in the ring: fewer than 128 entries (stale entries beyond the fill are valid pixels: read by every lane, masked out)
-        const uint32_t q0 = ring_read((uint32_t)lane), q1 = ring_read(64u + (uint32_t)lane);
+        uint32_t q0, q1;
+        ring.rest2(lane, q0, q1);
+        const uint32_t rn = ring.fill();
         const G3 e0 = gather3(q0 & 0xffffffu), e1 = gather3(q1 & 0xffffffu);
         const unsigned long long l0 = __builtin_amdgcn_ballot_w64((uint32_t)lane < rn), l1 = __builtin_amdgcn_ballot_w64(64u + (uint32_t)lane < rn);
         const M2 f0 = flags(e0), f1 = flags(e1);
         out.put2(f0.a & l0, f0.c & l0, q0, f1.a & l1, f1.c & l1, q1, lane);
-        rn = 0;
     }
 }
 
