@@ -667,6 +667,26 @@ SL_API int sl_normalize_sums(const uint8_t* rgb, int n, int h, int w, const doub
  * outside the SL_HED_* range or other than SL_HED_SKIMAGE_018.  out == rgb is not supported.  No workspace; capture-safe like the rest. */
 SL_API int sl_normalize_hed_view(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, const double* alpha_beta, int augment_background, const SlParams* params, const SlTensorFormat* fmt, const double* hed_sigma, const double* hed_bias, const int32_t* hed_applied, int skimage_mode, void* stream);
 
+/* ---- the Lab family in the one-pass loader (stainlib_amd/csrc/lab_view.hip; an extension: behind sl_reinhard_transform,
+ * sl_luminosity_standardize or sl_slab_map a training loader otherwise converts, crops, flips and turns a full-tile uint8 image, most of
+ * whose pixels went through the library's most expensive per-pixel arithmetic to be thrown away) ---------------------------------------
+ * sl_normalize_view's definition -- windows[t] = (y0, x0, d), d_mask, the clamp, the flip BEFORE the turn, (oh, ow), `out` as the
+ * n x oh x ow x 3 uint8 image (fmt == NULL) or the n x 3 x oh x ow tensor sl_to_tensor makes of it, bit for bit -- with full[t] the
+ * h x w x 3 uint8 image the existing call with the same arguments writes:
+ *     sl_reinhard_view      sl_reinhard_transform  (target_means, target_stds, mask_background, luminosity_threshold; stats_out as there)
+ *     sl_luminosity_view    sl_luminosity_standardize  (percentile; p_out as there)
+ *     sl_slab_view          sl_slab_map  (state, mode, mask_background, luminosity_threshold; with a status other than SL_TILE_OK the
+ *                           view of the SOURCE bytes, as sl_slab_map copies the tiles through)
+ * The statistics are those of the WHOLE tile (the whole slide): the per-tile calls run the unchanged statistics sweeps and table kernels
+ * of the existing calls in the same workspace (SL_OP_LAB_STATS), then ONE sweep that reads, maps and writes window pixels only.
+ * sl_slab_view: n == 0 is legal (SL_OK, nothing is launched; rgb, out and windows may then be NULL).
+ * SL_ERR_BADARG / SL_ERR_WORKSPACE before anything is enqueued: what the existing call refuses of rgb, out, n, h, w, the workspace, the
+ * state and the mode; NULL target_means / target_stds; what sl_normalize_view refuses of windows, oh, ow, d_mask, fmt and the number of
+ * (tile, patch) pairs; out == rgb.  Capture-safe like the rest (no allocation, no synchronisation, no memset). */
+SL_API int sl_reinhard_view(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, const double* target_means, const double* target_stds, int mask_background, double luminosity_threshold, double* stats_out, void* workspace, size_t workspace_bytes, const SlTensorFormat* fmt, void* stream);
+SL_API int sl_luminosity_view(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, double percentile, double* p_out, void* workspace, size_t workspace_bytes, const SlTensorFormat* fmt, void* stream);
+SL_API int sl_slab_view(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, const double* state, int mode, int mask_background, double luminosity_threshold, const SlTensorFormat* fmt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

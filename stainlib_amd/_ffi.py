@@ -181,6 +181,13 @@ _SIGNATURES = {
                                     _P, _P, _P]),
     "sl_normalize_hed_view": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, C.c_int,
                                         C.POINTER(SlParams), C.POINTER(SlTensorFormat), _P, _P, _P, C.c_int, _P]),
+    # the Lab family behind the view (rgb, out, n, h, w, oh, ow, windows, d_mask, <the existing call's arguments>, fmt, stream)
+    "sl_reinhard_view": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_double, _P, _P,
+                                   C.c_size_t, C.POINTER(SlTensorFormat), _P]),
+    "sl_luminosity_view": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_double, _P, _P, C.c_size_t,
+                                     C.POINTER(SlTensorFormat), _P]),
+    "sl_slab_view": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_double,
+                               C.POINTER(SlTensorFormat), _P]),
 }
 POOL_STATE_DOUBLES, POOL_M, POOL_MAXC, POOL_STATUS, POOL_MISS = 64, 0, 6, 8, 9
 POOL2_STATE_DOUBLES, POOL2_HIST_WORDS, POOL2_WHY = 256, 2 * 8192 + 8 * 32, 33

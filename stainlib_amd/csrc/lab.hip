@@ -12,8 +12,7 @@
 // uint8 argument, i.e. is a 256-entry table evaluated ONCE per tile in binary64 with the reference's operation order.
 // So a tile costs two histogram sweeps (3 B/px read each) and one map sweep (3 B/px read + 3 B/px written); no per-pixel
 // floating point at all.  Roofline: HBM; the LDS histogram atomics bound the two statistics sweeps in practice.
-#include "lab_device.hpp"
-#include "sl_host.hpp"
+#include "lab_host.hpp"
 
 namespace sl {
 
@@ -45,16 +44,7 @@ static __global__ __launch_bounds__(kLabWG) void k_byte_hist(const uint8_t* __re
     if (t) atomicAdd(&sc[tile].bytes[v], t);
 }
 
-// Per-tile composed tables (workspace, behind the LabScratch array): written ONCE per tile by k_lab_pre / k_lab_tables and loaded by every
-// workgroup of the sweeps that follow.  (Round 5: until then every workgroup of k_lab_hist / k_lab_map rebuilt them -- a serial
-// percentile over 256 global counters, three mean/std loops in binary64, five table passes -- before it touched a pixel: ~20 us of a
-// workgroup's ~450, which also kept the sweeps from being cut into workgroups small enough to fill the last round.)
-struct LabTileTabs : LabMapTabs {
-    double p;                 // the percentile the op reports (p90 of the bytes / the L percentile of MODE 1)
-    double pad_;
-};
-static_assert(sizeof(LabTileTabs) == sizeof(LabMapTabs) + 16, "the workspace sizes rest on it");
-
+// (the per-tile composed tables, LabTileTabs: lab_device.hpp)
 // after sweep A: the brightness table and the gamma values behind it (what sweep B needs)
 static __global__ __launch_bounds__(256) void k_lab_pre(const LabScratch* __restrict__ sc, int standardize, LabTileTabs* __restrict__ tt) {
     const int tile = blockIdx.x;
@@ -295,14 +285,6 @@ int lab_parts(int n, long P) {
 
 size_t lab_scratch_bytes(int n) { return (sizeof(LabScratch) * (size_t)n + 255) & ~(size_t)255; }
 size_t lab_ws_bytes(int n) { return lab_scratch_bytes(n) + ((sizeof(LabTileTabs) * (size_t)n + 255) & ~(size_t)255); }
-LabTileTabs* lab_tabs_of(void* ws, int n) { return (LabTileTabs*)((char*)ws + lab_scratch_bytes(n)); }
-
-int lab_check(const void* rgb, const void* out, int n, int h, int w, const void* ws, size_t ws_bytes) {
-    if (!rgb || !out || n <= 0 || h <= 0 || w <= 0) return SL_ERR_BADARG;
-    if ((long)h * w > (1L << 30)) return SL_ERR_BADARG;
-    if (!ws || ws_bytes < lab_ws_bytes(n) || ((uintptr_t)ws & 7u)) return SL_ERR_WORKSPACE;
-    return SL_OK;
-}
 
 // the two statistics sweeps shared by the entry points below (and k_lab_pre between them: the tile's brightness table)
 int lab_statistics(const uint8_t* rgb, int n, long P, int standardize, int want_ab, double thr, LabScratch* sc, hipStream_t s) {
@@ -325,9 +307,15 @@ LabMapArgs lab_map_args(const uint8_t* rgb, uint8_t* out, int n, long P, LabScra
     return a;
 }
 
+// the per-tile tables of the map (MODE 0, 1), behind the statistics
+template <int MODE>
+void lab_tables(const LabMapArgs& a, int n, hipStream_t s) {
+    hipLaunchKernelGGL((k_lab_tables<MODE>), dim3((unsigned)n), dim3(256), 0, s, a);
+}
+
 template <int MODE>
 int lab_map(const LabMapArgs& a, int n, hipStream_t s) {
-    if constexpr (MODE != 2) hipLaunchKernelGGL((k_lab_tables<MODE>), dim3((unsigned)n), dim3(256), 0, s, a);
+    if constexpr (MODE != 2) lab_tables<MODE>(a, n, s);
     const dim3 grid((unsigned)((long)n * a.parts)), block(kLabWG);
     launch_aligned(aligned4(a.rgb, a.P) && aligned4(a.out, a.P), k_lab_map<MODE, true>, k_lab_map<MODE, false>, grid, block, 0, s, a);
     return launch_status();
@@ -347,7 +335,41 @@ int lab_convert(const uint8_t* in, uint8_t* out, int n, int h, int w, void* stre
 
 }  // namespace
 
-namespace sl { size_t lab_workspace_bytes(int n) { return lab_ws_bytes(n); } }      // for sl_workspace_bytes (macenko.hip)
+namespace sl {
+
+size_t lab_workspace_bytes(int n) { return lab_ws_bytes(n); }      // for sl_workspace_bytes (macenko.hip)
+
+// ---- shared with lab_view.hip (lab_host.hpp) ---------------------------------------------------------------------------------------
+LabTileTabs* lab_tabs_of(void* ws, int n) { return (LabTileTabs*)((char*)ws + lab_scratch_bytes(n)); }
+
+int lab_check(const void* rgb, const void* out, int n, int h, int w, const void* ws, size_t ws_bytes) {
+    if (!rgb || !out || n <= 0 || h <= 0 || w <= 0) return SL_ERR_BADARG;
+    if ((long)h * w > (1L << 30)) return SL_ERR_BADARG;
+    if (!ws || ws_bytes < lab_ws_bytes(n) || ((uintptr_t)ws & 7u)) return SL_ERR_WORKSPACE;
+    return SL_OK;
+}
+
+int lab_reinhard_tables(const uint8_t* rgb, int n, long P, const double* target_means, const double* target_stds, double thr,
+                        double* stats_out, void* ws, hipStream_t s) {
+    LabScratch* sc = (LabScratch*)ws;
+    if (const int rc = lab_statistics(rgb, n, P, 1, 1, thr, sc, s)) return rc;
+    if (stats_out) hipLaunchKernelGGL(k_lab_stats, dim3((unsigned)n), dim3(64), 0, s, sc, 1, stats_out);
+    LabMapArgs a = lab_map_args(rgb, nullptr, n, P, sc);
+    a.target_means = target_means; a.target_stds = target_stds;
+    lab_tables<0>(a, n, s);
+    return launch_status();
+}
+
+int lab_luminosity_tables(const uint8_t* rgb, int n, long P, double percentile, void* ws, hipStream_t s) {
+    LabScratch* sc = (LabScratch*)ws;
+    if (const int rc = lab_statistics(rgb, n, P, 0, 0, 0.8, sc, s)) return rc;
+    LabMapArgs a = lab_map_args(rgb, nullptr, n, P, sc);
+    a.percentile = percentile;
+    lab_tables<1>(a, n, s);
+    return launch_status();
+}
+
+}  // namespace sl
 
 extern "C" int sl_rgb_to_lab8(const uint8_t* rgb, uint8_t* lab_out, int n, int h, int w, void* stream) {
     return lab_convert<0>(rgb, lab_out, n, h, w, stream);

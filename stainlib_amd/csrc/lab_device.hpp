@@ -3,6 +3,7 @@
 // the numbers the reference derives from it (np.percentile, cv2.meanStdDev), numpy's clip-then-truncate, and everything the reference
 // computes around the conversions: the byte-table formulas, the composed tables, the map of four pixels, the sweep loop.  The two
 // files keep their partitions of the pixels (tile x part; one flat span per workgroup), their kernels and their entry points.
+// lab_view_kernels.hpp puts the map of four pixels between the read side and the LDS stage of the view pass (tile x run of patches).
 #pragma once
 #include "apply_kernels.hpp"
 
@@ -150,6 +151,16 @@ __device__ __forceinline__ int l8_limit(double thr) {
     return lim;
 }
 
+// The same number by a 256-thread workgroup, one test per thread (thread = L8) instead of 256 per thread: the test is monotone in v, so
+// the limit is the count of values that pass.  l8_limit_begin before a barrier, l8_limit_end behind it; s_cnt: one int per wave.
+// (For a workgroup that maps 16 Ki pixels the serial loop -- 256 binary64 divisions per thread -- costs as much as its pixels.)
+__device__ __forceinline__ void l8_limit_begin(double thr, int* s_cnt) {
+    const int v = threadIdx.x;
+    const unsigned long long pass = __ballot((double)v / 255.0 < thr);
+    if ((v & 63) == 0) s_cnt[v >> 6] = __popcll(pass);
+}
+__device__ __forceinline__ int l8_limit_end(const int* s_cnt) { return s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3]; }
+
 // cv2.meanStdDev of a lab_split plane (stain_utils.py:153-157): sums in binary64, population variance clamped at 0.  One thread.
 // L: value(v) = binary32 v / 2.55f as lab_split makes it, from the histogram of L8.  a, b: value = byte - 128, so the two
 // sums follow exactly from the integer sums of the byte and its square (every term is an integer below 2^53).
@@ -183,6 +194,16 @@ struct LabMapTabs {
     uint16_t g[256];          // byte -> gamma value, through the brightness table where the op standardises
     uint8_t lut[256];         // the brightness table (identity when the op does not standardise)
 };
+
+// Per-tile composed tables (workspace, behind the LabScratch array): written ONCE per tile by k_lab_pre / k_lab_tables and loaded by every
+// workgroup of the sweeps that follow.  (Round 5: until then every workgroup of k_lab_hist / k_lab_map rebuilt them -- a serial
+// percentile over 256 global counters, three mean/std loops in binary64, five table passes -- before it touched a pixel: ~20 us of a
+// workgroup's ~450, which also kept the sweeps from being cut into workgroups small enough to fill the last round.)
+struct LabTileTabs : LabMapTabs {
+    double p;                 // the percentile the op reports (p90 of the bytes / the L percentile of MODE 1)
+    double pad_;
+};
+static_assert(sizeof(LabTileTabs) == sizeof(LabMapTabs) + 16, "the workspace sizes rest on it");
 
 // standardize_brightness (stain_utils.py:193-194): uint8(clip(v * 255.0 / p, 0, 255)); identity when the op does not standardise
 __device__ __forceinline__ uint32_t brightness_byte(int v, double p, int standardize) {

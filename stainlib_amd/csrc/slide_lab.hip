@@ -18,8 +18,7 @@
 // the span.  All tiles share ONE set of tables and ONE scratch, so the workgroups do not merge into it with global atomics (256
 // addresses under every workgroup of the chip): each writes one row of partial sums and k_slab_reduce adds the rows.  Integer sums:
 // run-to-run identical whatever the order.
-#include "lab_device.hpp"
-#include "sl_host.hpp"
+#include "lab_host.hpp"          // slab_shape_ok
 
 using namespace sl;
 
@@ -216,13 +215,6 @@ __global__ __launch_bounds__(kSlabWG) void k_slab_map(const uint8_t* __restrict_
     lab_sweep2<ALIGNED, true, kSlabWG>(s, 0, [&](const Chunk& in, int c) {
         store_chunk<ALIGNED>(dst, s.nbytes, c, lab_map_chunk<true>(s_t, s_g, s_yf, s_ad, s_bd, in, mask_bg, lim, bg));
     });
-}
-
-// n >= 0 tiles of h x w: the shape checks every entry point with a shard shares
-bool slab_shape_ok(int n, int h, int w) {
-    if (n < 0 || h <= 0 || w <= 0) return false;
-    const long P = (long)h * w;
-    return P <= (1L << 30) && (long)n * P <= (1L << 40);
 }
 
 size_t slab_ws_bytes(int n, long P) {

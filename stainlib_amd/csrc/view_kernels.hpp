@@ -7,7 +7,9 @@
 // Definition (include/stainlib_hip.h, sl_normalize_view): the result is "the same bits, elsewhere" -- the tensor value is defined on
 // the truncated byte and a dihedral transform is a permutation -- so the pixel arithmetic below is k_apply's / k_apply_jitter's
 // statement for statement (apply_consts, apply_px, apply_conc, the two casts, JitterK, is_tissue_f, cvt_chunk) on the same constants.
-// The kernel's body is view_body: k_view instantiates it as it stands, k_hed_view (hed_view_kernels.hpp) with the HED stage.
+// The kernel's body is view_body: k_view instantiates it as it stands, k_hed_view (hed_view_kernels.hpp) with the HED stage.  Its
+// geometry, read side, LDS stage and write side are callable pieces (ViewTile, ViewPatch, view_read, view_stage, view_write), which
+// k_lab_view (lab_view_kernels.hpp) puts around the Lab map.
 //
 // Shape: ONE workgroup = one tile and one patch of kViewB x kViewB OUTPUT pixels.  The dihedral code (block-uniform, read once, a
 // run-time value) decides which kViewB x kViewB block of the source window that is; the two sides meet in LDS:
@@ -105,6 +107,114 @@ __device__ __forceinline__ void store_view4(typename Elem<DT>::type* base, size_
     }
 }
 
+// ---- the pieces of a view pass: geometry, read side, LDS stage, write side.  view_body below is their sequence for one patch per
+// ---- workgroup; k_lab_view (lab_view_kernels.hpp) loops them over a run of patches behind one table fill ------------------------------
+// The view of one tile (block-uniform): the dihedral code as a transposition and two reversals, and the clamped window.
+struct ViewTile {
+    bool tr, ry, rx;
+    int wh, ww, y0, x0;
+    __device__ __forceinline__ ViewTile(const int32_t* windows, int tile, int d_mask, int h, int w, int oh, int ow) {
+        const int d = __builtin_amdgcn_readfirstlane(windows[3 * (size_t)tile + 2]) & d_mask;
+        const int k = d & 3;
+        tr = k & 1; ry = (k >> 1) & 1; rx = ((k >> 1) ^ k ^ (d >> 2)) & 1;
+        wh = tr ? ow : oh; ww = tr ? oh : ow;
+        y0 = max(0, min(__builtin_amdgcn_readfirstlane(windows[3 * (size_t)tile + 0]), h - wh));
+        x0 = max(0, min(__builtin_amdgcn_readfirstlane(windows[3 * (size_t)tile + 1]), w - ww));
+    }
+};
+// One patch of the tile's output (i0, j0; bh x bw pixels), the source block it comes from (ys, xs; nu rows of nv pixels) and the affine
+// map from output to LDS pixel: output pixel (il, jl) of the patch is LDS pixel a0 + il ai + jl aj.
+struct ViewPatch {
+    int i0, j0, bh, bw, nu, nv, ys, xs, a0, ai, aj;
+    __device__ __forceinline__ ViewPatch(const ViewTile& t, int patch, int npx, int oh, int ow) {
+        constexpr int B = kViewB, PITCH = kViewPitch;
+        const bool tr = t.tr, ry = t.ry, rx = t.rx;
+        i0 = (patch / npx) * B; j0 = (patch % npx) * B;                           // the patch, in output pixels
+        bh = min(B, oh - i0); bw = min(B, ow - j0);
+        const int u0 = tr ? j0 : i0;                                              // its rows and columns in the (flipped, turned) window
+        nu = tr ? bw : bh;
+        const int v0 = tr ? i0 : j0;
+        nv = tr ? bh : bw;
+        ys = t.y0 + (ry ? t.wh - u0 - nu : u0); xs = t.x0 + (rx ? t.ww - v0 - nv : v0);   // the source block: nu rows of nv pixels
+        const int su = ry ? -PITCH : PITCH, sv = rx ? -1 : 1;
+        a0 = (ry ? (nu - 1) * PITCH : 0) + (rx ? nv - 1 : 0);
+        ai = tr ? sv : su; aj = tr ? su : sv;
+    }
+};
+
+// ---- read side: the four chunks of this lane (lr = tid >> 4, lc = tid & 15), requested before any arithmetic
+__device__ __forceinline__ void view_read(const ViewPatch& g, const uint8_t* src, size_t nbytes, int w, int lr, int lc, Chunk (&in)[4]) {
+    const int cc = min(lc, (g.nv - 1) >> 2);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int r = min(16 * q + lr, g.nu - 1);
+        in[q] = load12(src, nbytes, 3 * ((size_t)(g.ys + r) * w + g.xs) + 12 * cc);
+    }
+}
+
+// the four packed pixels r | g << 8 | b << 16 of a chunk
+__device__ __forceinline__ void view_unpack(const Chunk& o, uint32_t (&px)[4]) {
+#pragma unroll
+    for (int p = 0; p < 4; ++p) px[p] = chunk_pixel(o, p) & 0xffffffu;
+}
+
+// ---- LDS stage: compute(chunk, px[4]) on each of the four chunks, the pixels of the source block into s_px (masked)
+template <class F>
+__device__ __forceinline__ void view_stage(const ViewPatch& g, uint32_t* s_px, int lr, int lc, const Chunk (&in)[4], F&& compute) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int r = 16 * q + lr;
+        uint32_t px[4];
+        compute(in[q], px);
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+            if (r < g.nu && 4 * lc + p < g.nv) s_px[r * kViewPitch + 4 * lc + p] = px[p];
+    }
+}
+
+// ---- write side: output rows, 4 adjacent pixels per lane (behind a barrier after the stage)
+template <int DT, int LAYOUT>
+__device__ __forceinline__ void view_write(const ViewPatch& g, const uint32_t* s_px, void* out, int tile, int oh, int ow, TensorK fmt,
+                                           int lr, int lc) {
+    constexpr bool TENSOR = DT != kDtU8;
+    constexpr int SDT = TENSOR ? DT : kDtF32;
+    typedef typename Elem<SDT>::type T;
+    const int i0 = g.i0, j0 = g.j0, bh = g.bh, bw = g.bw, a0 = g.a0, ai = g.ai, aj = g.aj;
+    const TensorK F = tensor_consts(fmt);
+    const size_t PO = (size_t)oh * ow;
+    const int jl = 4 * lc;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int il = 16 * q + lr;
+        const int row = a0 + min(il, bh - 1) * ai;
+        uint32_t px[4];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) px[p] = s_px[row + min(jl + p, bw - 1) * aj];
+        Chunk o;
+        o.w0 = px[0] | (px[1] << 24);
+        o.w1 = (px[1] >> 8) | (px[2] << 16);
+        o.w2 = (px[2] >> 16) | (px[3] << 8);
+        const int nvalid = min(4, bw - jl);
+        if (il < bh && nvalid > 0) {
+            const size_t pix = (size_t)(i0 + il) * ow + (j0 + jl);
+            if (TENSOR) {
+                float v[12];
+                cvt_chunk(o, F, v);
+                T* const base = (T*)out + (size_t)tile * 3 * PO;
+                store_view4<SDT, LAYOUT>(base, PO, pix, nvalid, v);
+            } else {
+                uint8_t* const p = (uint8_t*)out + ((size_t)tile * PO + pix) * 3;
+                if (nvalid == 4) {
+                    sl_u32x3u u; u.x = o.w0; u.y = o.w1; u.z = o.w2;
+                    *(SL_GLOBAL sl_u32x3u*)as_global(p) = u;
+                } else {
+                    for (int i = 0; i < 3 * nvalid; ++i) as_global(p)[i] = (uint8_t)chunk_byte(o, i);
+                }
+            }
+        }
+    }
+}
+
 // A further stage between the truncation to bytes and the LDS write, on the four packed pixels `stage` holds.  HED = 0: none -- the
 // primary template is empty and k_view's code is what it was without it (tools/isa_diff.py); HED = 1: the HED augmentation of
 // sl_normalize_hed_view (hed_view_kernels.hpp specialises it; its arguments arrive in HedViewArgs).
@@ -126,9 +236,6 @@ __device__ __forceinline__ void view_body(const uint8_t* rgb, void* out, int h, 
                                           const double* M_src, const double* maxC_src,
                                           const double* M_tgt, const double* maxC_tgt, const double* alpha_beta,
                                           double lam, float ylimf, TensorK fmt, const HedViewArgs* hv) {
-    constexpr bool TENSOR = DT != kDtU8;
-    constexpr int SDT = TENSOR ? DT : kDtF32;
-    typedef typename Elem<SDT>::type T;
     constexpr int B = kViewB, PITCH = kViewPitch;
     static_assert(kWG == 256 && B == 64, "16 lanes x 4 pixels per row, 16 rows per pass, 4 passes");
     __shared__ float2 s_tab[256];
@@ -143,49 +250,18 @@ __device__ __forceinline__ void view_body(const uint8_t* rgb, void* out, int h, 
     HedStage<HED> hed;
     hed.init(tid, tile, hv);
 
-    // the view of this tile (block-uniform) and the source block of this patch
-    const int d = __builtin_amdgcn_readfirstlane(windows[3 * (size_t)tile + 2]) & d_mask;
-    const int k = d & 3;
-    const bool tr = k & 1, ry = (k >> 1) & 1, rx = ((k >> 1) ^ k ^ (d >> 2)) & 1;
-    const int wh = tr ? ow : oh, ww = tr ? oh : ow;
-    const int y0 = max(0, min(__builtin_amdgcn_readfirstlane(windows[3 * (size_t)tile + 0]), h - wh));
-    const int x0 = max(0, min(__builtin_amdgcn_readfirstlane(windows[3 * (size_t)tile + 1]), w - ww));
-    const int i0 = (patch / npx) * B, j0 = (patch % npx) * B;                  // the patch, in output pixels
-    const int bh = min(B, oh - i0), bw = min(B, ow - j0);
-    const int u0 = tr ? j0 : i0, nu = tr ? bw : bh;                           // its rows and columns in the (flipped, turned) window
-    const int v0 = tr ? i0 : j0, nv = tr ? bh : bw;
-    const int ys = y0 + (ry ? wh - u0 - nu : u0), xs = x0 + (rx ? ww - v0 - nv : v0);   // the source block: nu rows of nv pixels
-    // output pixel (il, jl) of the patch is LDS pixel a0 + il ai + jl aj
-    const int su = ry ? -PITCH : PITCH, sv = rx ? -1 : 1;
-    const int a0 = (ry ? (nu - 1) * PITCH : 0) + (rx ? nv - 1 : 0);
-    const int ai = tr ? sv : su, aj = tr ? su : sv;
-
-    // ---- read side: the four chunks of this lane, requested before any arithmetic
+    // the view of this tile (block-uniform), the source block of this patch and the four chunks of this lane
+    const ViewTile vt(windows, tile, d_mask, h, w, oh, ow);
+    const ViewPatch g(vt, patch, npx, oh, ow);
     Chunk in[4];
-    {
-        const int cc = min(lc, (nv - 1) >> 2);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int r = min(16 * q + lr, nu - 1);
-            in[q] = load12(src, nbytes, 3 * ((size_t)(ys + r) * w + xs) + 12 * cc);
-        }
-    }
+    view_read(g, src, nbytes, w, lr, lc, in);
     auto stage = [&](auto compute) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int r = 16 * q + lr;
-            uint32_t px[4];
-            compute(in[q], px);
+        view_stage(g, s_px, lr, lc, in, [&](const Chunk& c, uint32_t (&px)[4]) {
+            compute(c, px);
             hed.apply(px);
-#pragma unroll
-            for (int p = 0; p < 4; ++p)
-                if (r < nu && 4 * lc + p < nv) s_px[r * PITCH + 4 * lc + p] = px[p];
-        }
+        });
     };
-    auto unpack = [](const Chunk& o, uint32_t (&px)[4]) {
-#pragma unroll
-        for (int p = 0; p < 4; ++p) px[p] = chunk_pixel(o, p) & 0xffffffu;
-    };
+    auto unpack = [](const Chunk& o, uint32_t (&px)[4]) { view_unpack(o, px); };
     auto raw = [&](const Chunk& c, uint32_t (&px)[4]) { unpack(c, px); };
 
     if (MODE == kViewRaw) {
@@ -256,40 +332,7 @@ __device__ __forceinline__ void view_body(const uint8_t* rgb, void* out, int h, 
     }
     __syncthreads();
 
-    // ---- write side: output rows, 4 adjacent pixels per lane
-    const TensorK F = tensor_consts(fmt);
-    const size_t PO = (size_t)oh * ow;
-    const int jl = 4 * lc;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int il = 16 * q + lr;
-        const int row = a0 + min(il, bh - 1) * ai;
-        uint32_t px[4];
-#pragma unroll
-        for (int p = 0; p < 4; ++p) px[p] = s_px[row + min(jl + p, bw - 1) * aj];
-        Chunk o;
-        o.w0 = px[0] | (px[1] << 24);
-        o.w1 = (px[1] >> 8) | (px[2] << 16);
-        o.w2 = (px[2] >> 16) | (px[3] << 8);
-        const int nvalid = min(4, bw - jl);
-        if (il < bh && nvalid > 0) {
-            const size_t pix = (size_t)(i0 + il) * ow + (j0 + jl);
-            if (TENSOR) {
-                float v[12];
-                cvt_chunk(o, F, v);
-                T* const base = (T*)out + (size_t)tile * 3 * PO;
-                store_view4<SDT, LAYOUT>(base, PO, pix, nvalid, v);
-            } else {
-                uint8_t* const p = (uint8_t*)out + ((size_t)tile * PO + pix) * 3;
-                if (nvalid == 4) {
-                    sl_u32x3u u; u.x = o.w0; u.y = o.w1; u.z = o.w2;
-                    *(SL_GLOBAL sl_u32x3u*)as_global(p) = u;
-                } else {
-                    for (int i = 0; i < 3 * nvalid; ++i) as_global(p)[i] = (uint8_t)chunk_byte(o, i);
-                }
-            }
-        }
-    }
+    view_write<DT, LAYOUT>(g, s_px, out, tile, oh, ow, fmt, lr, lc);
 }
 
 template <int DT, int LAYOUT, int MODE>

@@ -611,14 +611,24 @@ class PooledReinhardStatistics:
 
 
 def slide_luminosity_standardize(tiles_local: torch.Tensor, percentile=95, group=None, out: Optional[torch.Tensor] = None,
-                                 tensor_format=None):
+                                 tensor_format=None, view=None, windows=None):
     """LuminosityStandardizer.standardize (stain_utils.py:52-67) on the concatenation of every tile on every rank: (out, p), p the
     `percentile` of the slide's L8 as a float.  One sweep for the L8 histogram, one small all-reduce, the map.
     tensor_format: a stainlib_amd.TensorFormat; `out` is then the (n_local,3,H,W) tensor in that format (the map writes a uint8 scratch,
-    tensor_format.convert reads it)."""
+    tensor_format.convert reads it).
+    view: a stainlib_amd.TileView -- the map sweep writes per tile only the window windows[t] (default: view.draw(n_local, H, W), drawn
+    behind the statistics) of its result, flipped and turned, as (n_local,oh,ow,3) uint8 or the (n_local,3,oh,ow) tensor, without a
+    scratch (engine.slab_view); the call returns (out, p, windows).  windows without view is a ValueError."""
     from . import engine
+    with_view = engine.lab_view_check(view, windows, tiles_local)          # (before any collective: a refused call enqueues nothing)
+    if with_view:
+        engine._check_shard(tiles_local)
     stats = PooledReinhardStatistics(group)
     state = stats.enqueue_luminosity(tiles_local, percentile)
+    if with_view:
+        out, windows = engine.slab_view(tiles_local, windows, None, state, 1, fmt=tensor_format, out=out, view=view)
+        stats.finish(state)
+        return out, stats.last_percentile, windows
     if tensor_format is not None:
         out = tensor_format.convert(engine.slab_map(tiles_local, state, 1), out=out)
     else:
@@ -685,7 +695,7 @@ class SlideNormalizer:
         return state[_ffi.POOL_M:_ffi.POOL_M + 6].reshape(2, 3), state[_ffi.POOL_MAXC:_ffi.POOL_MAXC + 2]
 
     def transform_shard(self, tiles_local: torch.Tensor, out: Optional[torch.Tensor] = None, n_tiles_total: Optional[int] = None, *,
-                        mask_background=False, luminosity_threshold=0.8, tensor_format=None):
+                        mask_background=False, luminosity_threshold=0.8, tensor_format=None, view=None, windows=None):
         """tiles_local: this rank's (n_local,H,W,3) uint8 device tensor.  Returns (out, M_slide, maxC_slide, status_local).
         n_tiles_total (pooled mode, optional): the slide's tile count over all ranks; saves the one tiny all-reduce that otherwise
         agrees on the sample density.  On failure (TissueMaskException) `out` holds a copy of the input tiles.
@@ -694,11 +704,17 @@ class SlideNormalizer:
         extractive normalizers have no such arguments: a non-default value with one raises ValueError).
         tensor_format: a stainlib_amd.TensorFormat; `out` is then the (n_local,3,H,W) tensor in that format, bit for bit
         tensor_format.convert of the uint8 result: the apply pass of the extractive normalizers converts its bytes in registers, the
-        Reinhard map writes a uint8 scratch that the converter reads.  Not with graph=True (ValueError)."""
+        Reinhard map writes a uint8 scratch that the converter reads.  Not with graph=True (ValueError).
+        view, windows (a Reinhard normalizer only; ValueError otherwise): a stainlib_amd.TileView -- the pooled map sweep writes per tile
+        only the window windows[t] (default: view.draw(n_local, H, W), drawn behind the statistics) of its result, flipped and turned,
+        as (n_local,oh,ow,3) uint8 or the (n_local,3,oh,ow) tensor, without a scratch (engine.slab_view); `windows` is appended to the
+        returned tuple.  On failure `out` then holds the view of the input tiles."""
         if tensor_format is not None and self.graph:
             raise ValueError("tensor_format is not supported with graph=True")
+        if (view is not None or windows is not None) and not self._reinhard:
+            raise ValueError("view / windows apply to a Reinhard normalizer only (the extractive normalizers' views: transform_batch)")
         if self._reinhard:
-            return self._transform_reinhard(tiles_local, out, mask_background, luminosity_threshold, tensor_format)
+            return self._transform_reinhard(tiles_local, out, mask_background, luminosity_threshold, tensor_format, view, windows)
         if mask_background or luminosity_threshold != 0.8:
             raise ValueError("mask_background / luminosity_threshold apply to a Reinhard normalizer only")
         if self.mode == "median":
@@ -804,10 +820,14 @@ class SlideNormalizer:
             out = through()                    # an empty shard: the empty tensor in the format
         return out, M_s, maxC_s, torch.zeros((n,), dtype=torch.int32, device=dev)
 
-    def _transform_reinhard(self, tiles_local: torch.Tensor, out: Optional[torch.Tensor], mask_background, luminosity_threshold, fmt=None):
+    def _transform_reinhard(self, tiles_local: torch.Tensor, out: Optional[torch.Tensor], mask_background, luminosity_threshold, fmt=None,
+                            view=None, windows=None):
         """Pooled mode with a Reinhard normalizer.  Device-driven: the statistics AND the map are enqueued before the one read-back; with
         an unusable status (an empty tissue mask under mask_background, an empty slide) the map copies the tiles through."""
         from . import engine, _ffi
+        with_view = engine.lab_view_check(view, windows, tiles_local)      # (before any collective: a refused call enqueues nothing)
+        if with_view:
+            engine._check_shard(tiles_local)
         stats = PooledReinhardStatistics(self.group)
         tm, ts = self.normalizer._targets()
         key = (str(tiles_local.device), tuple(tm), tuple(ts))         # the six target doubles on the device, uploaded once per fit (cf. _target_on)
@@ -816,7 +836,10 @@ class SlideNormalizer:
                                       torch.tensor(ts, dtype=torch.float64, device=tiles_local.device))
         _, tm, ts = self._reinhard_targets
         state = stats.enqueue(tiles_local, tm, ts, mask_background, luminosity_threshold)
-        if fmt is not None:                    # the map into a uint8 scratch, then the converter
+        if with_view:                          # the map, the view and the conversion in one sweep
+            out, windows = engine.slab_view(tiles_local, windows, None, state, 0, mask_background=mask_background,
+                                            luminosity_threshold=luminosity_threshold, fmt=fmt, out=out, view=view)
+        elif fmt is not None:                  # the map into a uint8 scratch, then the converter
             out = fmt.convert(engine.slab_map(tiles_local, state, 0, mask_background, luminosity_threshold), out=out)
         else:
             out = engine.slab_map(tiles_local, state, 0, mask_background, luminosity_threshold, out=out)
@@ -827,4 +850,5 @@ class SlideNormalizer:
         finally:
             self.last_p90 = stats.last_p90
             self.last_tissue, self.last_pixels = stats.last_tissue, stats.last_pixels
-        return out, means, stds, torch.zeros((tiles_local.shape[0],), dtype=torch.int32, device=tiles_local.device)
+        return (out, means, stds, torch.zeros((tiles_local.shape[0],), dtype=torch.int32, device=tiles_local.device)) + (
+            (windows,) if with_view else ())

@@ -868,6 +868,113 @@ def luminosity_standardize(rgb, percentile=95, out=None, ws=None):
     return out, p
 
 
+# ---- the Lab family behind the view (sl_reinhard_view, sl_luminosity_view, sl_slab_view; see include/stainlib_hip.h) ------------------
+def _lab_view_prepare(rgb, windows, size, d_mask, fmt, out, view=None, before_device=None):
+    """_view_prepare for a Lab map: its checks in its order (size, windows, format, before_device(n), then _check_tiles and out;
+    ValueError) -> (n, h, w, oh, ow, d_mask, windows on the device, SlTensorFormat or None, out, windows as given or drawn).
+    view: a TileView (a batch method's view=) -- size and d_mask are its own (_view_call), and windows=None means view.draw(n, h, w)
+    from the global numpy stream, drawn behind every check: a refused call draws nothing, and nothing goes to the device before it."""
+    from .tensor_format import TensorFormat
+    from .tile_view import check_size
+    if view is not None:
+        size, d_mask, _ = _view_call(view, windows, rgb, draw=False)
+    if not (isinstance(rgb, torch.Tensor) and rgb.dim() == 4 and rgb.shape[-1] == 3):
+        raise ValueError("expected a contiguous CUDA uint8 tensor of shape (N, H, W, 3)")
+    n, h, w = (int(v) for v in rgb.shape[:3])
+    oh, ow = check_size(size, h, w, d_mask)
+    win = _view_windows(windows, n, h, w, oh, ow, d_mask) if (windows is not None or view is None) else None
+    if fmt is not None and not isinstance(fmt, TensorFormat):
+        raise ValueError("fmt must be a stainlib_amd.TensorFormat or None (the uint8 image)")
+    if before_device is not None:
+        before_device(n)
+    _check_tiles(rgb)
+    dev = rgb.device
+    if isinstance(win, torch.Tensor) and win.device != dev:
+        raise ValueError(f"windows must be on {dev}")
+    f, out = _image_out(out, rgb, n, oh, ow, fmt, "view")
+    if win is None:
+        windows = win = view.draw(n, h, w)
+    if not isinstance(win, torch.Tensor):
+        win = torch.from_numpy(win).to(dev)
+    return n, h, w, oh, ow, int(d_mask), win, f, out, windows
+
+
+def _three(x, what):
+    """three float64 on the host (ValueError), or the device tensor as it is"""
+    if isinstance(x, torch.Tensor) and x.is_cuda:
+        if x.numel() != 3:
+            raise ValueError(f"{what} must hold 3 values (L, a, b)")
+        return x
+    import numpy as np
+    try:
+        v = np.asarray(x.numpy() if isinstance(x, torch.Tensor) else x, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(f"{what} must hold 3 values (L, a, b)") from None
+    if v.shape != (3,):
+        raise ValueError(f"{what} must hold 3 values (L, a, b)")
+    return v
+
+
+def reinhard_view(rgb, windows, size, target_means, target_stds, d_mask=7, mask_background=False, luminosity_threshold=0.8, fmt=None,
+                  out=None, ws=None, view=None):
+    """reinhard_transform with normalize_view's crop, flip and quarter turn per tile in its map sweep (sl_reinhard_view): the unchanged
+    statistics of the WHOLE tiles, then ONE sweep that reads, maps and writes window pixels only -- bit for bit the view of
+    reinhard_transform's image (fmt: its fmt.convert).  windows, size, d_mask, fmt, out: normalize_view's; view: a TileView in place of
+    size and d_mask, whose draw gives the windows when windows is None.  -> (out, stats (N, 8), windows)."""
+    tm_ts = []
+    n, h, w, oh, ow, d_mask, win, f, out, windows = _lab_view_prepare(
+        rgb, windows, size, d_mask, fmt, out, view,
+        lambda n: tm_ts.extend((_three(target_means, "target_means"), _three(target_stds, "target_stds"))))
+    dev = rgb.device
+    tm, ts = _f64(tm_ts[0], (3,), dev), _f64(tm_ts[1], (3,), dev)
+    st = torch.empty((n, 8), dtype=torch.float64, device=dev)
+    wsb = _scratch(ws, _ffi.OP_LAB_STATS, n, h, w, dev)
+    _call("sl_reinhard_view", _ptr(rgb), _ptr(out), n, h, w, oh, ow, _ptr(win), int(d_mask), _ptr(tm), _ptr(ts), 1 if mask_background else 0,
+          float(luminosity_threshold), _ptr(st), _ptr(wsb), wsb.numel(), _byref(f))
+    return out, st, windows
+
+
+def luminosity_view(rgb, windows, size, percentile=95, d_mask=7, fmt=None, out=None, ws=None, view=None):
+    """luminosity_standardize with the view in its map sweep (sl_luminosity_view; see reinhard_view) -> (out, p (N,) f64, windows)."""
+    def pct_ok(n):
+        try:
+            float(percentile)
+        except (TypeError, ValueError):
+            raise ValueError("percentile must be a number") from None
+    n, h, w, oh, ow, d_mask, win, f, out, windows = _lab_view_prepare(rgb, windows, size, d_mask, fmt, out, view, pct_ok)
+    p = torch.empty((n,), dtype=torch.float64, device=rgb.device)
+    wsb = _scratch(ws, _ffi.OP_LAB_STATS, n, h, w, rgb.device)
+    _call("sl_luminosity_view", _ptr(rgb), _ptr(out), n, h, w, oh, ow, _ptr(win), int(d_mask), float(percentile), _ptr(p), _ptr(wsb),
+          wsb.numel(), _byref(f))
+    return out, p, windows
+
+
+def slab_view(rgb, windows, size, state, mode, d_mask=7, mask_background=False, luminosity_threshold=0.8, fmt=None, out=None, view=None):
+    """slab_map with the view in its sweep (sl_slab_view): per tile the window of the image slab_map writes under the slide's tables (a
+    non-OK status: of the tile's own bytes), as the uint8 image or the tensor.  An empty shard gives the empty output.
+    -> (out, windows)."""
+    def state_ok(n):
+        if mode not in (0, 1):
+            raise ValueError("mode must be 0 (Reinhard) or 1 (luminosity)")
+        if not (isinstance(state, torch.Tensor) and state.dtype == torch.float64 and state.numel() == _ffi.SLAB_STATE_DOUBLES
+                and state.is_contiguous()):
+            raise ValueError(f"state must be the ({_ffi.SLAB_STATE_DOUBLES},) float64 tensor of slab_begin / slab_finish")
+    n, h, w, oh, ow, d_mask, win, f, out, windows = _lab_view_prepare(rgb, windows, size, d_mask, fmt, out, view, state_ok)
+    if n:
+        _call("sl_slab_view", _ptr(rgb), _ptr(out), n, h, w, oh, ow, _ptr(win), int(d_mask), _ptr(state), int(mode),
+              1 if mask_background else 0, float(luminosity_threshold), _byref(f))
+    return out, windows
+
+
+def lab_view_check(view, windows, tiles):
+    """The view= / windows= pair of a Lab batch method, checked without a device and without a draw (ValueError: windows= without
+    view=, and what _view_call refuses) -> whether there is a view."""
+    if view is None and windows is None:
+        return False
+    _view_call(view, windows, tiles, draw=False)
+    return True
+
+
 # ---- pooled slide-level mode: per-process reductions (combined over ranks in stainlib_amd.distributed) -------------
 def tile_moments(rgb, params=None, ws=None):
     """(n, 10) float64 per tile: tissue count, sum od[3], sum od od^T [xx, xy, xz, yy, yz, zz]  (sl_tile_moments)."""

@@ -311,12 +311,20 @@ class ReinhardStainNormalizer(object):
             raise TissueMaskException("Empty tissue mask computed")       # stain_utils.py:46-47 via normalizer.py:86
         return out[0].cpu().numpy()
 
-    def transform_batch(self, tiles, mask_background=False, luminosity_threshold=0.8, out=None, ws=None, tensor_format=None):
+    def transform_batch(self, tiles, mask_background=False, luminosity_threshold=0.8, out=None, ws=None, tensor_format=None, view=None,
+                        windows=None):
         """Batched extension: (N,H,W,3) uint8 device tensor -> (out, stats (N,8): p90, means, stds, tissue pixels).
         ``tensor_format``: a ``stainlib_amd.TensorFormat``; `out` is then the (N,3,H,W) tensor in that format (the map writes a uint8
-        scratch, ``tensor_format.convert`` reads it)."""
+        scratch, ``tensor_format.convert`` reads it).
+        ``view``: a ``stainlib_amd.TileView`` -- the unchanged statistics of the WHOLE tiles, then ONE map sweep that writes per tile only
+        the window ``windows[t]`` (default: ``view.draw(N, H, W)``) of that result, flipped and turned, as (N,oh,ow,3) uint8 or, with a
+        ``tensor_format``, the (N,3,oh,ow) tensor -- no uint8 scratch (engine.reinhard_view); the call returns (out, stats, windows).
+        ``TileView(None, flip=False, rot90=False)`` is the fused full-tile tensor.  ``windows`` without ``view`` is a ValueError."""
         from .. import engine
         tm, ts = self._targets()
+        if engine.lab_view_check(view, windows, tiles):
+            return engine.reinhard_view(tiles, windows, None, tm, ts, mask_background=mask_background,
+                                        luminosity_threshold=luminosity_threshold, fmt=tensor_format, out=out, ws=ws, view=view)
         if tensor_format is None:
             return engine.reinhard_transform(tiles, tm, ts, mask_background, luminosity_threshold, out=out, ws=ws)
         u8, st = engine.reinhard_transform(tiles, tm, ts, mask_background, luminosity_threshold, ws=ws)

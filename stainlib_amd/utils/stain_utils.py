@@ -87,6 +87,23 @@ class LuminosityStandardizer(object):
         out, _ = engine.luminosity_standardize(_to_device(I), percentile)
         return out[0].cpu().numpy()
 
+    @staticmethod
+    def standardize_batch(tiles, percentile=95, out=None, ws=None, tensor_format=None, view=None, windows=None):
+        """Batched extension: (N,H,W,3) uint8 device tensor -> (out, p (N,) float64: every tile's `percentile` of L8).
+        ``tensor_format``: a ``stainlib_amd.TensorFormat``; `out` is then the (N,3,H,W) tensor in that format (the map writes a uint8
+        scratch, ``tensor_format.convert`` reads it).
+        ``view``: a ``stainlib_amd.TileView`` -- the unchanged statistics of the WHOLE tiles, then ONE map sweep that writes per tile only
+        the window ``windows[t]`` (default: ``view.draw(N, H, W)``) of that result, flipped and turned, as (N,oh,ow,3) uint8 or the
+        (N,3,oh,ow) tensor -- no uint8 scratch (engine.luminosity_view); the call returns (out, p, windows).  ``windows`` without
+        ``view`` is a ValueError."""
+        from .. import engine
+        if engine.lab_view_check(view, windows, tiles):
+            return engine.luminosity_view(tiles, windows, None, percentile, fmt=tensor_format, out=out, ws=ws, view=view)
+        if tensor_format is None:
+            return engine.luminosity_standardize(tiles, percentile, out=out, ws=ws)
+        u8, p = engine.luminosity_standardize(tiles, percentile, ws=ws)
+        return tensor_format.convert(u8, out=out), p
+
 
 def get_concentrations(I, stain_matrix, regularizer=0.01):
     """stain_utils.py:69-78 -> (P, 2) float64 (binary32 values from the device)."""
