@@ -42,7 +42,9 @@ extern "C" {
 
 /* return codes */
 #define SL_OK 0
-#define SL_ERR_BADARG (-1)    /* null pointer, n/h/w <= 0, unknown op/mode */
+#define SL_ERR_BADARG (-1)    /* null pointer, n/h/w <= 0, unknown op/mode; on every per-tile entry point also h w > 2^30 and a batch
+                                 whose (tile, part) grid does not fit 31 bits: n * ceil(h w / 32768) > 2^31 - 1 (the views: n times
+                                 the 64 x 64 patches of an output) */
 #define SL_ERR_WORKSPACE (-2) /* workspace missing or smaller than sl_workspace_bytes() */
 #define SL_ERR_NODEVICE (-3)  /* no HIP device / wrong architecture */
 #define SL_ERR_HIP_BASE (-1000) /* HIP runtime error e is returned as SL_ERR_HIP_BASE - e */
@@ -405,7 +407,11 @@ SL_API int sl_pool_resolve(double* state, int keyset, const unsigned long long* 
  * state[SL_POOL2_WHY] != 0 says the sample gave no usable estimate (the sweep then returns at once and the chain ends in a miss).
  * `workspace` (sl_pool2_workspace_bytes, 256-byte aligned) carries the sample list, the candidate list (up to 1/8 of the pixels) and
  * the per-workgroup partial sums from sl_pool2_sample to the last sl_pool2_hist.  Every step consumes all-reduced data only: the ranks
- * reach the same state without a broadcast.  Reference: macenko_stain_extractor.py:18-44, normalizer.py:36,45-47 on the concatenation. */
+ * reach the same state without a broadcast.  Reference: macenko_stain_extractor.py:18-44, normalizer.py:36,45-47 on the concatenation.
+ * Limits: h w <= 2^30 and n h w <= 2^40 pixels, AND both lists must count their blocks in 32 bits -- the sample list holds about
+ * n h w / (256 * 2^sample_log2) blocks, so the densest samples are not accepted for the largest shards (2^40 pixels need
+ * sample_log2 >= 1 or so; the Python layer's own choice for that size is 9).  Where they do not fit, sl_pool2_workspace_bytes returns 0 and every
+ * sl_pool2_* entry point that takes the shape returns SL_ERR_BADARG before anything is launched. */
 #define SL_POOL2_STATE_DOUBLES 256
 #define SL_POOL2_TAIL_SLOTS 32
 #define SL_POOL2_GRID_BINS 8192

@@ -228,7 +228,7 @@ extern "C" int sl_hed_augment(const uint8_t* rgb, uint8_t* out, int n, int h, in
     if (!rgb || !out || !sigma || !bias || n <= 0 || h <= 0 || w <= 0) return SL_ERR_BADARG;
     if (skimage_mode < SL_HED_SKIMAGE_018 || skimage_mode > SL_HED_EXPERIMENTAL_LOG10) return SL_ERR_BADARG;
     const long P = (long)h * w;
-    if (P > (1L << 30)) return SL_ERR_BADARG;
+    if (P > (1L << 30) || !grid_fits(n, parts_for(P))) return SL_ERR_BADARG;
     if (!workspace || workspace_bytes < sizeof(unsigned long long) * (size_t)n || ((uintptr_t)workspace & 7u))
         return SL_ERR_WORKSPACE;
     HedConst hc;
@@ -257,7 +257,7 @@ extern "C" int sl_hed_augment_f64(const double* rgb, double* out, int n, int h, 
     if (!rgb || !out || !sigma || !bias || n <= 0 || h <= 0 || w <= 0) return SL_ERR_BADARG;
     if (skimage_mode < SL_HED_SKIMAGE_018 || skimage_mode > SL_HED_EXPERIMENTAL_LOG10) return SL_ERR_BADARG;
     const long P = (long)h * w;
-    if (P > (1L << 30)) return SL_ERR_BADARG;
+    if (P > (1L << 30) || !grid_fits(n, parts_for(P))) return SL_ERR_BADARG;
     if (!workspace || workspace_bytes < sizeof(double) * (size_t)n || ((uintptr_t)workspace & 7u)) return SL_ERR_WORKSPACE;
     HedConst hc;
     hed_matrices(hc.R, hc.H);

@@ -324,7 +324,7 @@ int lab_map(const LabMapArgs& a, int n, hipStream_t s) {
 // DIR 0: sl_rgb_to_lab8, 1: sl_lab8_to_rgb
 template <int DIR>
 int lab_convert(const uint8_t* in, uint8_t* out, int n, int h, int w, void* stream) {
-    if (!in || !out || n <= 0 || h <= 0 || w <= 0 || (long)h * w > (1L << 30)) return SL_ERR_BADARG;
+    if (const int rc = check_shape(in, out, n, h, w)) return rc;
     const long P = (long)h * w;
     const int parts = parts_for(P);
     const dim3 grid((unsigned)((long)n * parts)), block(kLabWG);
@@ -344,7 +344,7 @@ LabTileTabs* lab_tabs_of(void* ws, int n) { return (LabTileTabs*)((char*)ws + la
 
 int lab_check(const void* rgb, const void* out, int n, int h, int w, const void* ws, size_t ws_bytes) {
     if (!rgb || !out || n <= 0 || h <= 0 || w <= 0) return SL_ERR_BADARG;
-    if ((long)h * w > (1L << 30)) return SL_ERR_BADARG;
+    if ((long)h * w > (1L << 30) || !grid_fits(n, lab_parts(n, (long)h * w))) return SL_ERR_BADARG;
     if (!ws || ws_bytes < lab_ws_bytes(n) || ((uintptr_t)ws & 7u)) return SL_ERR_WORKSPACE;
     return SL_OK;
 }

@@ -47,10 +47,24 @@ int zero_async(void* p, size_t bytes, hipStream_t s);
 // workspace of the Lab family (lab.hip)
 size_t lab_workspace_bytes(int n_tiles);
 
-// The shape checks every per-tile entry point starts with: the input, a positive batch and tile, at most 2^30 pixels per tile.
+// The launchers that give every (tile, part) a workgroup of its own hand n * parts to dim3 as an unsigned: a batch whose product
+// does not fit a signed 32-bit grid is refused where the shape is checked (the view routes check n * npatch the same way:
+// view_geometry of route_host.hpp), never truncated.
+inline bool grid_fits(int n, long parts) { return (long)n * parts <= 0x7fffffffL; }
+
+// Workgroups a tile of P pixels is split into for the streaming sweeps: ~32 Ki pixels each,
+// at least 1, so that a batch of >=32 tiles launches >>256 workgroups.
+inline int parts_for(long P) {
+    long p = (P + 32767) / 32768;
+    return (int)(p < 1 ? 1 : p);
+}
+
+// The shape checks every per-tile entry point starts with: the input, a positive batch and tile, at most 2^30 pixels per tile, and
+// a (tile, part) grid that fits (grid_fits).
 inline int check_shape(const void* rgb, int n, int h, int w) {
     if (!rgb || n <= 0 || h <= 0 || w <= 0) return SL_ERR_BADARG;
     if ((long)h * w > (1L << 30)) return SL_ERR_BADARG;
+    if (!grid_fits(n, parts_for((long)h * w))) return SL_ERR_BADARG;
     return SL_OK;
 }
 inline int check_shape(const void* rgb, const void* out, int n, int h, int w) { return out ? check_shape(rgb, n, h, w) : SL_ERR_BADARG; }
@@ -91,13 +105,6 @@ template <class K, class... Args>
 inline void launch_aligned(bool aligned, K k_aligned, K k_unaligned, dim3 grid, dim3 block, unsigned lds, hipStream_t s, Args... args) {
     if (aligned) hipLaunchKernelGGL(k_aligned, grid, block, lds, s, args...);
     else hipLaunchKernelGGL(k_unaligned, grid, block, lds, s, args...);
-}
-
-// Workgroups a tile of P pixels is split into for the streaming sweeps: ~32 Ki pixels each,
-// at least 1, so that a batch of >=32 tiles launches >>256 workgroups.
-inline int parts_for(long P) {
-    long p = (P + 32767) / 32768;
-    return (int)(p < 1 ? 1 : p);
 }
 
 // The geometry of the launchers that give every (tile, part) a workgroup of its own.  `threads` is always kWG: a parameter only

@@ -91,6 +91,7 @@ struct P2Layout {
     uint32_t c_priv;         // candidate list: blocks each wave of the sweep owns before it turns to the shared pool
     uint32_t s_cap, c_cap;
     int hist_wgs;            // workgroups of a grid-mode list pass (its partial histograms live in the workspace)
+    bool fits;               // s_cap and c_cap hold their block counts (32 bits): p2_check refuses a shard whose lists do not
     size_t hdr, partials, hpart, tpart, local, s_counts, s_entries, c_counts, c_entries, total;
 };
 
@@ -107,6 +108,7 @@ P2Layout p2_layout(int n, int h, int w, int slog) {
     const long m_max = (((span + 15) >> 4) >> slog) + 2;
     L.bpi = (int)((m_max + 3) / 4);
     L.s_cap = (uint32_t)((long)L.n_items * L.bpi);
+    L.fits = (long)L.n_items * L.bpi <= 0xffffffffL;
     const long total_px = (long)n * P;
     long cand = total_px / 8;
     const long small = total_px < (1L << 22) ? total_px : (1L << 22);
@@ -115,6 +117,7 @@ P2Layout p2_layout(int n, int h, int w, int slog) {
     long blocks = (cand >> kP2CandBlkLog2) + 2 * waves + 16;
     L.c_priv = (uint32_t)(blocks / (2 * waves));                  // half of the capacity in private runs (>= 1 block per wave)
     L.c_cap = (uint32_t)blocks;
+    L.fits = L.fits && blocks <= 0xffffffffL;
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     L.hdr = 0;
     L.partials = 256;
@@ -1101,6 +1104,7 @@ int p2_check(const uint8_t* rgb, int n, int h, int w, const SlParams* params, in
     if (!params_ok(params)) return SL_ERR_BADARG;
     p = params_or_defaults(params);
     L = p2_layout(n, h, w, slog);
+    if (!L.fits) return SL_ERR_BADARG;              // (a sample density too high for a shard this size: block indices are 32 bits)
     if (!ws || ws_bytes < L.total || ((uintptr_t)ws & 255u)) return SL_ERR_WORKSPACE;
     return SL_OK;
 }
@@ -1109,7 +1113,8 @@ int p2_check(const uint8_t* rgb, int n, int h, int w, const SlParams* params, in
 
 extern "C" size_t sl_pool2_workspace_bytes(int n, int h, int w, int sample_log2) {
     if (n <= 0 || h <= 0 || w <= 0 || sample_log2 < 0 || sample_log2 > 12 || (long)h * w > (1L << 30) || (long)n * h * w > (1L << 40)) return 0;
-    return p2_layout(n, h, w, sample_log2).total;
+    const P2Layout L = p2_layout(n, h, w, sample_log2);
+    return L.fits ? L.total : 0;
 }
 
 extern "C" int sl_pool2_sample(const uint8_t* rgb, int n, int h, int w, const SlParams* params, int sample_log2, void* workspace,

@@ -10,6 +10,63 @@ from oracle import stain_oracle as so
 from stainlib_amd import distributed as sd
 
 
+def _lerp(a, b, t):
+    """numpy's _lerp (lib/function_base.py), restated here: the reference of the stand-ins takes nothing from the library under test"""
+    d = b - a
+    return b - d * (1.0 - t) if t >= 0.5 else a + d * t
+
+
+def _replicated_position(count, R, q):
+    """numpy.percentile's (method='linear') position among count * R values: (k, g) with the result lerp(v[k], v[k + 1], g)"""
+    n = float(count) * float(R)
+    qq = q / 100.0
+    vi = min(max(n * qq + (1.0 + qq * (1.0 - 1.0 - 1.0)) - 1.0, 0.0), n - 1.0)          # numpy's _compute_virtual_index, alpha = beta = 1
+    k = int(math.floor(vi))
+    return k, vi - k
+
+
+def replicated_percentile(x, R, q):
+    """np.percentile(np.repeat(x, R), q) without the repeat: a population in which every element of x occurs R times.  Position
+    pos = (R m - 1) q / 100 of the sorted population is element floor(pos) // R of sorted x; interpolate to its successor."""
+    xs = np.sort(np.asarray(x, dtype=np.float64).ravel())
+    k, g = _replicated_position(len(xs), R, q)
+    lo, hi = xs[k // R], xs[min(k + 1, len(xs) * R - 1) // R]
+    return float(_lerp(lo, hi, g))
+
+
+def replicated_percentile_hist(hist, R, q):
+    """replicated_percentile for a byte population given by its 256 counts (np.bincount(x, minlength=256))"""
+    cum = np.cumsum(np.asarray(hist, dtype=np.int64)) * int(R)
+    k, g = _replicated_position(int(cum[-1]) // int(R), R, q)
+    lo, hi = (int(np.searchsorted(cum, p, side="right")) for p in (k, min(k + 1, int(cum[-1]) - 1)))
+    return float(_lerp(float(lo), float(hi), g))
+
+
+def replicated_macenko(block_tiles, R, luminosity_threshold=0.8, angular_percentile=99, details=None):
+    """The oracle's Macenko recipe (so.macenko_stain_matrix, then the 99th percentile of so.get_concentrations) for a slide of R
+    repeats of the tiles in block_tiles -> (M (2, 3), maxC (2,)), from the block alone: mean and covariance of the population are the
+    block's (np.cov's divisor changes the scale only, which the eigenvectors do not see), the percentile calls become
+    replicated_percentile."""
+    px = np.concatenate([np.asarray(t).reshape(-1, 3) for t in block_tiles]).reshape(1, -1, 3)
+    mask = so.tissue_mask(px, luminosity_threshold).reshape(-1)
+    OD = so.rgb_to_od(px).reshape(-1, 3)[mask]
+    _, V = np.linalg.eigh(np.cov(OD, rowvar=False))
+    V = V[:, [2, 1]]
+    for i in range(2):
+        if V[0, i] < 0:
+            V[:, i] *= -1
+    That = OD @ V
+    phi = np.arctan2(That[:, 1], That[:, 0])
+    lo, hi = replicated_percentile(phi, R, 100 - angular_percentile), replicated_percentile(phi, R, angular_percentile)
+    v1, v2 = V @ np.array([np.cos(lo), np.sin(lo)]), V @ np.array([np.cos(hi), np.sin(hi)])
+    M = so.normalize_rows(np.array([v1, v2]) if v1[0] > v2[0] else np.array([v2, v1]))
+    C = so.get_concentrations(px, M)
+    maxC = np.array([replicated_percentile(C[:, j], R, 99) for j in range(2)])
+    if details is not None:
+        details.update(n_tissue=int(mask.sum()) * R, n_pixels=px.shape[1] * R)
+    return M, maxC
+
+
 def f2ord(a):
     """binary32 -> the unsigned integer with the same order (in uint64)"""
     u = np.asarray(a, np.float32).view(np.uint32)

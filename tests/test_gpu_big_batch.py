@@ -1,0 +1,692 @@
+"""-m gpu: every per-tile entry point on batches whose byte offsets pass 2^31 and 2^32 (tests/big_batch.py: K = 4 distinct tiles
+repeated, 5464 tiles of 512 x 512 and 5444 tiles of 509 x 517).
+
+Each test makes one call on the whole batch and checks it three ways, on the device:
+  periodic   tile i + K holds the bytes (and the side results) of tile i, over the whole batch, by one torch.equal (assert_periodic)
+  anchor     the first K tiles against the oracle, under the bar the project already states for that entry point (u8_parity,
+             M_ATOL / MAXC_RTOL, V_ATOL, bit identity for the Lab family and for the tensor conversion of an anchored uint8 image)
+  guard      where the entry point takes out=, the output sits between sentinel margins that must survive the call
+The only host-to-device copy is the K-tile base; only K (8 for the views) tiles and the per-tile scalars come back.  The K-periodic
+input of a shape (4.3 GB) is made once and shared by the tests of this file; each test states what it allocates beyond it, the
+gate (need_memory) counts that and every shared batch resident beside it against the 40 GB a test may hold -- the full-tile float32
+views drop the other shape's batch first and their own before the comparison -- and every test ends with release().  Order: the entry points that only read the batch first, then the writers."""
+import types
+
+import numpy as np
+import pytest
+import torch
+
+import stainlib_amd
+from oracle import stain_oracle as so
+from tests.big_batch import (K, SHAPES, assert_periodic, base_tiles, bits, guarded, need_memory, period8_windows, periodic_batch, periodic_rows,
+                             release)
+from tests.gpu_util import oracle_fit_tile, u8_parity
+from tests.test_gpu_jitter import M_TGT, MAXC_TGT, MEAN, STD
+from tests.test_gpu_macenko import M_ATOL, MAXC_RTOL
+
+pytestmark = pytest.mark.gpu
+
+BOTH = ["aligned", "odd"]
+MARGIN = 4096                                   # sentinel bytes on either side of a guarded output
+_S = {}                                         # per shape: the batch and what the tests share about its K tiles
+AB = np.array([[1.1, 0.05, 0.9, -0.1], [0.85, -0.15, 1.15, 0.1], [1.0, 0.0, 1.0, 0.0], [1.2, 0.2, 0.8, -0.2]])
+GRAY_AB = np.array([[0.9, 0.05], [1.2, -0.2], [1.0, 0.0], [0.8, 0.1]])
+HED_SIGMA = np.array([[0.03, -0.02, 0.01], [-0.04, 0.02, 0.03], [0.02, 0.04, -0.03], [0.01, 0.01, 0.01]])
+HED_BIAS = np.array([[0.01, -0.02, 0.02], [0.02, 0.01, -0.01], [-0.02, 0.02, 0.01], [0.01, -0.01, 0.02]])
+
+
+def _fmt(dtype, channels_last):
+    return stainlib_amd.TensorFormat(dtype=dtype, channels_last=channels_last, mean=MEAN, std=STD)
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _drop_the_batches():
+    yield
+    _S.clear()
+    release()
+
+
+def _forget(S):
+    """drop a shape's shared batch (the next test that wants it makes it again: no host-to-device copy but the K tiles)"""
+    _S.pop(S.name, None)
+    S.dev = S.M = S.mc = S.ab = None
+    S.memo.clear()
+    release()
+
+
+def _state(name, own_bytes=0, alone=False):
+    """the shared state of a shape; own_bytes: what the calling test allocates beyond the shared input; alone: the other shape's batch
+    is dropped first.  The memory gate counts everything resident while the test runs: its own allocations AND the shared batches."""
+    from stainlib_amd import engine
+    h, w, n = SHAPES[name]
+    B = n * h * w * 3
+    if alone:
+        for other in [S for k, S in list(_S.items()) if k != name]:
+            _forget(other)
+    need_memory(own_bytes + sum(S.B for k, S in _S.items() if k != name) + B + (1 << 28), resident=sum(S.B for S in _S.values()))
+    if name not in _S:
+        base_np = base_tiles(h, w)
+        base = torch.from_numpy(base_np).cuda()                                  # the only host-to-device copy of tiles
+        S = types.SimpleNamespace(name=name, h=h, w=w, n=n, B=B, base_np=base_np, base=base, dev=periodic_batch(base, n), memo={})
+        assert S.dev.data_ptr() % 16 == 0 and S.dev.numel() == B > 1 << 32
+        M, mc, st = engine.macenko_fit(base)
+        assert st.cpu().tolist()[:3] == [0, 0, 0] and int(st[3]) != 0 and bool(torch.isnan(M[3]).all())       # the all-white tile: no fit
+        S.M4, S.mc4 = M, mc
+        S.M, S.mc = periodic_rows(M, n), periodic_rows(mc, n)                    # tile 3 of every block: NaN, the pass-through
+        S.ab = periodic_rows(torch.from_numpy(AB).cuda(), n)
+        _S[name] = S
+    return _S[name]
+
+
+def _tissue(I):
+    """the oracle's tissue mask without its exception for an empty one (stain_utils.py:41-43)"""
+    return so.lab_l8(I) / 255.0 < 0.8
+
+
+def _memo(S, key, fn):
+    if key not in S.memo:
+        S.memo[key] = fn()
+    return S.memo[key]
+
+
+def _oracle_fits(S):
+    return _memo(S, "fits", lambda: [oracle_fit_tile(I) for I in S.base_np[:3]])
+
+
+def _oracle_apply(S):
+    """the oracle's normalizer.py:46-50 on the K base tiles under the DEVICE's own statistics (isolates the pass); the failed fit: the tile"""
+    def make():
+        M, mc = S.M4.cpu().numpy(), S.mc4.cpu().numpy()
+        out = [so.truncate_u8((255 * np.exp(-(so.get_concentrations(I, M[i]) * (MAXC_TGT / mc[i])) @ M_TGT)).reshape(I.shape))
+               for i, I in enumerate(S.base_np[:3])]
+        return out + [S.base_np[3]]
+    return _memo(S, "apply", make)
+
+
+def _anchor_u8(S, got, want, label):
+    """the first K tiles of a uint8 image against the oracle's, u8_parity; the all-white tile exactly"""
+    got = got[:K].cpu().numpy()
+    for i in range(K):
+        u8_parity(got[i], want[i], label=f"{label} {S.name} tile {i}", src=S.base_np[i])
+
+
+def _guard_image(S, fmt, call, oh=None, ow=None, label=""):
+    """call(out) with out the guarded (n, oh, ow) image (uint8 without fmt) -> (out, what call returned); the margins checked"""
+    oh, ow = (S.h, S.w) if oh is None else (oh, ow)
+    g = guarded(S.n * oh * ow * 3, fmt.dtype if fmt is not None else torch.uint8, margin=MARGIN)
+    out = g.image(S.n, oh, ow, fmt)
+    res = call(out)
+    g.check(f"{label} {S.name}")
+    return out, res
+
+
+def _check_fit(S, M, mc, st, atol, rtol, fits, label):
+    assert_periodic((M, mc, st), label=f"{label} {S.name}")
+    M, mc, st = M[:K].cpu().numpy(), mc[:K].cpu().numpy(), st[:K].cpu().tolist()
+    assert st[:3] == [0, 0, 0] and st[3] != 0, st
+    for i in range(3):
+        print(f"{label} {S.name} tile {i}: |dM| {np.abs(M[i] - fits[i][0]).max():.1e} maxC rel {np.abs(mc[i] / fits[i][1] - 1).max():.1e}")
+        np.testing.assert_allclose(M[i], fits[i][0], rtol=0, atol=atol)
+        np.testing.assert_allclose(mc[i], fits[i][1], rtol=rtol)
+
+
+# =============================================== readers ====================================================================================
+@pytest.mark.parametrize("name", BOTH)
+def test_tissue_mask_counts(name):
+    from stainlib_amd import engine
+    S = _state(name, 1 << 20)
+    _, counts = engine.tissue_mask(S.dev, want_mask=False)
+    assert_periodic(counts, label="tissue counts")
+    assert counts[:K].cpu().tolist() == [int(_tissue(I).sum()) for I in S.base_np] and int(counts[3]) == 0
+    release()
+
+
+def test_tissue_mask_with_the_mask():
+    from stainlib_amd import engine
+    S = _state("odd", S_bytes("odd") // 3 * 2)
+    mask, counts = engine.tissue_mask(S.dev)
+    assert_periodic((mask, counts), label="tissue mask")
+    assert np.array_equal(mask[:K].cpu().numpy().astype(bool), np.stack([_tissue(I) for I in S.base_np]))
+    _last_block_is(mask, engine.tissue_mask(S.base)[0], "tissue mask")
+    assert torch.equal(mask.view(S.n, -1).sum(dim=1), counts)
+    del mask
+    release()
+
+
+def _last_block_is(out, small, label):
+    """For outputs the engine allocates itself (torch.empty: no sentinel, so a region the kernel never wrote could hold stale bytes of an
+    earlier identical run and still be periodic): the LAST K tiles, past both lines, against the same call on the K-tile base, on the
+    device.  Every batch is a whole number of K-tile blocks."""
+    if isinstance(out, (tuple, list)):
+        for o, s_ in zip(out, small):
+            _last_block_is(o, s_, label)
+        return
+    assert out.shape[0] % K == 0 and torch.equal(bits(out[-K:]), bits(small)), f"{label}: the last {K} tiles are not the K-tile call's"
+
+
+def S_bytes(name):
+    h, w, n = SHAPES[name]
+    return n * h * w * 3
+
+
+@pytest.mark.parametrize("name", BOTH)
+def test_tile_moments(name):
+    from stainlib_amd import engine
+    from tests.standin_math import eig2, tissue
+    S = _state(name, 1 << 24)
+    mom = engine.tile_moments(S.dev)
+    assert_periodic(mom, label="tile_moments")
+    got = mom[:K].cpu().numpy()
+    # the bars test_gpu_sweep_edges.py states for this entry point: every tissue pixel counted once, nothing for a tile without any
+    # (the split of a tile into parts depends on the batch size, so the sums of a K-tile call need not have the same last bits)
+    assert [int(c) for c in got[:, 0]] == [int(tissue(I).sum()) for I in S.base_np] and not got[3].any()
+    M_o = _oracle_fits(S)
+    for i in range(3):                                                           # and they ARE the tile's moments: their plane is the oracle's
+        V = eig2(got[i])
+        assert np.abs(V.T @ np.cross(M_o[i][0][0], M_o[i][0][1])).max() <= M_ATOL
+    release()
+
+
+@pytest.mark.parametrize("sched", [1, 2])
+@pytest.mark.parametrize("name", BOTH)
+def test_macenko_fit(name, sched):
+    from stainlib_amd import engine
+    p = engine.make_params(schedule=sched)
+    S = _state(name, engine._ws_need(stainlib_amd._ffi.OP_MACENKO_FIT, SHAPES[name][2], *SHAPES[name][:2], p) + (1 << 24))
+    M, mc, st = engine.macenko_fit(S.dev, params=p)
+    _check_fit(S, M, mc, st, M_ATOL, MAXC_RTOL, _oracle_fits(S), f"macenko_fit schedule {sched}")
+    release()
+
+
+def _vahadane_fits(S):
+    def make():
+        fits = []
+        for I in S.base_np[:3]:
+            M = so.vahadane_stain_matrix(I, max_sweeps=600, tol=1e-12)
+            fits.append((M, np.percentile(so.get_concentrations(I, M), 99, axis=0)))
+        return fits
+    return _memo(S, "vfits", make)
+
+
+def test_vahadane_fit():
+    from stainlib_amd import engine
+    from tests.test_gpu_vahadane import V_ATOL
+    S = _state("aligned", engine._ws_need(stainlib_amd._ffi.OP_VAHADANE_FIT, *_nhw("aligned")) + (1 << 24))
+    M, mc, st, sweeps = engine.vahadane_fit(S.dev)
+    assert_periodic(sweeps, label="vahadane sweeps")
+    _check_fit(S, M, mc, st, V_ATOL, 1e-4, _vahadane_fits(S), "vahadane_fit")   # (1e-4: the maxC bar of test_gpu_vahadane.py)
+    release()
+
+
+def _nhw(name):
+    h, w, n = SHAPES[name]
+    return n, h, w
+
+
+@pytest.mark.parametrize("name", BOTH)
+def test_reinhard_stats(name):
+    from stainlib_amd import engine
+    S = _state(name, 1 << 26)
+    st = engine.reinhard_stats(S.dev)
+    assert_periodic(st, label="reinhard_stats")
+    got = st[:K].cpu().numpy()
+    for i, I in enumerate(S.base_np):
+        Is = so.standardize_brightness(I)
+        assert got[i, 0] == np.percentile(I, 90) and got[i, 7] == int(_tissue(Is).sum())
+        if i < 3:
+            means, stds = so.get_mean_std(Is)
+            np.testing.assert_allclose(got[i, 1:4], np.ravel(means), rtol=1e-13)                  # (the bars of test_gpu_lab.py)
+            np.testing.assert_allclose(got[i, 4:7], np.ravel(stds), rtol=1e-12)
+    release()
+
+
+@pytest.mark.parametrize("name", BOTH)
+def test_normalize_sums(name):
+    from stainlib_amd import engine
+    S = _state(name, S_bytes(name) // 1000)
+    want = _memo(S, "apply4", lambda: engine.normalize_apply(S.base, S.M4, S.mc4, M_TGT, MAXC_TGT))
+    for kw, full in ((dict(), S.base), (dict(M_src=S.M, maxC_src=S.mc, M_tgt=M_TGT, maxC_tgt=MAXC_TGT), want)):
+        sums, applied = engine.normalize_sums(S.dev, **kw)
+        assert_periodic((sums, applied), label="normalize_sums")
+        assert sums[:K].cpu().tolist() == full.to(torch.int64).sum(dim=(1, 2, 3)).cpu().tolist()
+        assert applied[:K].cpu().tolist()[3] == 0                                # the all-white tile is outside the cutoff
+    release()
+
+
+# =============================================== writers ====================================================================================
+@pytest.mark.parametrize("name", BOTH)
+def test_normalize_apply(name):
+    from stainlib_amd import engine
+    S = _state(name, S_bytes(name) * 2)
+    out, _ = _guard_image(S, None, lambda o: engine.normalize_apply(S.dev, S.M, S.mc, M_TGT, MAXC_TGT, out=o), label="normalize_apply")
+    assert_periodic(out, label="normalize_apply")
+    _anchor_u8(S, out, _oracle_apply(S), "normalize_apply")
+    assert torch.equal(out[3], S.base[3])                                        # the pass-through copy
+    del out
+    release()
+
+
+@pytest.mark.parametrize("dtype,cl", [(torch.float32, False), (torch.float16, True)])
+@pytest.mark.parametrize("name", BOTH)
+def test_normalize_apply_tensor(name, dtype, cl):
+    from stainlib_amd import engine
+    fmt = _fmt(dtype, cl)
+    esize = 4 if dtype == torch.float32 else 2
+    S = _state(name, S_bytes(name) * (esize + 1))
+    out, _ = _guard_image(S, fmt, lambda o: engine.normalize_apply_tensor(S.dev, S.M, S.mc, M_TGT, MAXC_TGT, fmt, out=o), label="apply_tensor")
+    assert out.numel() > 1 << 32
+    assert_periodic(out, label=f"normalize_apply_tensor {fmt}")
+    u8 = _memo(S, "apply4", lambda: engine.normalize_apply(S.base, S.M4, S.mc4, M_TGT, MAXC_TGT))
+    _anchor_u8(S, u8, _oracle_apply(S), "normalize_apply (K tiles)")
+    assert torch.equal(bits(out[:K]), bits(fmt.convert(u8)))                     # the tensor conversion: bit identity
+    del out
+    release()
+
+
+@pytest.mark.parametrize("name", BOTH)
+def test_to_tensor_bfloat16(name):
+    from stainlib_amd import engine
+    fmt = _fmt(torch.bfloat16, False)
+    S = _state(name, S_bytes(name) * 3)
+    out, _ = _guard_image(S, fmt, lambda o: engine.to_tensor(S.dev, fmt, out=o), label="to_tensor")
+    assert_periodic(out, label="to_tensor")
+    # the definition (include/stainlib_hip.h): fma(b, 1 / (255 std), -mean / std) in binary32, rounded to nearest even -- with torch
+    sc = torch.tensor([1.0 / (255.0 * s) for s in STD], dtype=torch.float32, device="cuda").view(1, 3, 1, 1)
+    sh = torch.tensor([-m / s for m, s in zip(MEAN, STD)], dtype=torch.float32, device="cuda").view(1, 3, 1, 1)
+    want = torch.addcmul(sh.double(), S.base.permute(0, 3, 1, 2).double(), sc.double()).float().to(torch.bfloat16)
+    assert torch.equal(bits(out[:K].contiguous()), bits(want.contiguous()))
+    del out
+    release()
+
+
+@pytest.mark.parametrize("sched", [1, 2])
+@pytest.mark.parametrize("name", BOTH)
+def test_macenko_transform(name, sched):
+    from stainlib_amd import _ffi, engine
+    p = engine.make_params(schedule=sched)
+    # (the workspace stays far below 2^31 bytes on either schedule -- the fused one keeps candidate buffers per workgroup, the per-phase
+    # one per tile of a 2 GiB group -- so what passes the lines here is the batch: schedule 1 walks it in three groups whose first tiles
+    # sit 2 GiB and 4 GiB into it)
+    ws_bytes = int(_ffi.lib().sl_workspace_bytes_for(_ffi.OP_MACENKO_TRANSFORM, *_nhw(name), p))
+    print(f"macenko_transform schedule {sched} {name}: workspace {ws_bytes} bytes")
+    assert 0 < ws_bytes < 1 << 31
+    S = _state(name, S_bytes(name) * 2 + ws_bytes)
+    (out, (_, M, mc, st)) = _guard_image(S, None, lambda o: engine.macenko_transform(S.dev, M_TGT, MAXC_TGT, params=p, out=o),
+                                         label=f"macenko_transform {sched}")
+    assert_periodic(out, label=f"macenko_transform schedule {sched}")
+    _check_fit(S, M, mc, st, M_ATOL, MAXC_RTOL, _oracle_fits(S), f"macenko_transform schedule {sched}")
+    nz = _memo(S, "onz", lambda: _oracle_normalizer("macenko"))
+    want = _memo(S, "mtrans", lambda: [nz.transform(I) for I in S.base_np[:3]] + [S.base_np[3]])
+    _anchor_u8(S, out, want, f"macenko_transform schedule {sched}")
+    del out
+    release()
+
+
+def _oracle_normalizer(method):
+    nz = so.ExtractiveStainNormalizer(method)
+    nz.stain_matrix_target, nz.maxC_target = M_TGT, MAXC_TGT.reshape(1, 2)
+    return nz
+
+
+def test_vahadane_transform():
+    from stainlib_amd import _ffi, engine
+    from tests.test_gpu_vahadane import V_ATOL
+    ws_bytes = int(_ffi.lib().sl_workspace_bytes_for(_ffi.OP_VAHADANE_TRANSFORM, *_nhw("aligned"), None))
+    S = _state("aligned", S_bytes("aligned") * 2 + ws_bytes)
+    (out, (_, M, mc, st)) = _guard_image(S, None, lambda o: engine.vahadane_transform(S.dev, M_TGT, MAXC_TGT, out=o), label="vahadane_transform")
+    assert_periodic(out, label="vahadane_transform")
+    fits = _vahadane_fits(S)
+    _check_fit(S, M, mc, st, V_ATOL, 1e-4, fits, "vahadane_transform")
+    want = [so.truncate_u8((255 * np.exp(-(so.get_concentrations(I, fits[i][0]) * (MAXC_TGT / fits[i][1])) @ M_TGT)).reshape(I.shape))
+            for i, I in enumerate(S.base_np[:3])] + [S.base_np[3]]
+    _anchor_u8(S, out, want, "vahadane_transform")
+    del out
+    release()
+
+
+def _oracle_jitter(S, bg, own):
+    """test_gpu_jitter.py's oracle recipe on the K base tiles (the device's statistics); own: under the tile's own matrix, no target"""
+    M, mc = S.M4.cpu().numpy(), S.mc4.cpu().numpy()
+    out = []
+    for i, I in enumerate(S.base_np[:3]):
+        a = so.StainAugmentor("macenko", augment_background=bg)
+        a.image_shape, a.stain_matrix = I.shape, (M[i] if own else M_TGT)
+        a.source_concentrations = so.get_concentrations(I, M[i]) * (1.0 if own else MAXC_TGT / mc[i])
+        a.tissue_mask = so.tissue_mask(I).ravel()
+        out.append(a.pop_with([AB[i, 0], AB[i, 2]], [AB[i, 1], AB[i, 3]]))
+    return out + [S.base_np[3]]
+
+
+@pytest.mark.parametrize("name", BOTH)
+def test_normalize_jitter_uint8(name):
+    from stainlib_amd import engine
+    S = _state(name, S_bytes(name) * 2)
+    out, _ = _guard_image(S, None, lambda o: engine.normalize_jitter(S.dev, S.M, S.mc, M_TGT, MAXC_TGT, S.ab, out=o), label="jitter")
+    assert_periodic(out, label="normalize_jitter")
+    _anchor_u8(S, out, _oracle_jitter(S, False, False), "normalize_jitter")
+    del out
+    release()
+
+
+@pytest.mark.parametrize("name", BOTH)
+def test_normalize_jitter_float32_nhwc_with_background(name):
+    from stainlib_amd import engine
+    fmt = _fmt(torch.float32, True)
+    S = _state(name, S_bytes(name) * 5)
+    out, _ = _guard_image(S, fmt, lambda o: engine.normalize_jitter(S.dev, S.M, S.mc, M_TGT, MAXC_TGT, S.ab, augment_background=True, fmt=fmt,
+                                                                   out=o), label="jitter f32")
+    assert_periodic(out, label="normalize_jitter float32 NHWC")
+    u8 = engine.normalize_jitter(S.base, S.M4, S.mc4, M_TGT, MAXC_TGT, AB, augment_background=True)
+    _anchor_u8(S, u8, _oracle_jitter(S, True, False), "normalize_jitter bg (K tiles)")
+    assert torch.equal(bits(out[:K]), bits(fmt.convert(u8)))
+    del out
+    release()
+
+
+@pytest.mark.parametrize("name", BOTH)
+def test_stain_augment(name):
+    from stainlib_amd import engine
+    S = _state(name, S_bytes(name) * 2)
+    out, _ = _guard_image(S, None, lambda o: engine.stain_augment(S.dev, S.M, S.ab, out=o), label="stain_augment")
+    assert_periodic(out, label="stain_augment")
+    got, want = out[:3].cpu().numpy(), _oracle_jitter(S, False, True)
+    for i in range(3):                                                           # (the all-white tile has no stain matrix to augment under)
+        u8_parity(got[i], want[i], label=f"stain_augment {name} tile {i}", src=S.base_np[i])
+    del out
+    release()
+
+
+@pytest.mark.parametrize("name", BOTH)
+def test_grayscale_augment(name):
+    from stainlib_amd import engine
+    S = _state(name, S_bytes(name) * 2)
+    ab = periodic_rows(torch.from_numpy(GRAY_AB).cuda(), S.n)
+    out, _ = _guard_image(S, None, lambda o: engine.grayscale_augment(S.dev, ab, out=o), label="grayscale")
+    assert_periodic(out, label="grayscale_augment")
+    want = []
+    for i, I in enumerate(S.base_np):
+        o = so.GrayscaleAugmentor()
+        o.image = I                                                              # (fit() refuses the all-white tile; pop_with needs the image only)
+        want.append(o.pop_with(*GRAY_AB[i]))
+    _anchor_u8(S, out, want, "grayscale_augment")
+    del out
+    release()
+
+
+@pytest.mark.parametrize("want,dtype", [(("norm", "h", "e", "conc"), torch.float32), (("conc",), torch.float16)])
+@pytest.mark.parametrize("name", BOTH)
+def test_stain_separate(name, want, dtype):
+    from stainlib_amd import engine
+    from stainlib_amd.engine import Separated
+    esize = 4 if dtype == torch.float32 else 2
+    S = _state(name, S_bytes(name) * (len(want) - 1) + S_bytes(name) // 3 * 2 * esize + (1 << 24))
+    P = S.h * S.w
+    gs = {k: guarded(S.n * P * (2 if k == "conc" else 3), dtype if k == "conc" else torch.uint8, margin=MARGIN) for k in want}
+    bufs = Separated(*[(gs[k].body.view(S.n, 2, S.h, S.w) if k == "conc" else gs[k].body.view(S.n, S.h, S.w, 3)) if k in want else None
+                       for k in Separated._fields])
+    got = engine.stain_separate(S.dev, S.M, S.mc, M_TGT, MAXC_TGT, want=want, conc_dtype=dtype, out=bufs)
+    for k in want:
+        gs[k].check(f"stain_separate {k} {name}")
+        assert_periodic(getattr(got, k), label=f"stain_separate {k}")
+    M, mc = S.M4.cpu().numpy(), S.mc4.cpu().numpy()
+    # the float32 planes are held to the oracle (the bar of test_gpu_separate.py); a half type is those planes rounded to nearest even,
+    # bit for bit (test_half_types_round_the_float32_planes): the float32 planes of the K-tile base, anchored here, converted by torch
+    c32 = got.conc[:K].cpu() if dtype == torch.float32 else engine.stain_separate(S.base, S.M4, S.mc4, M_TGT, MAXC_TGT, want=("conc",)).conc.cpu()
+    if dtype != torch.float32:
+        assert torch.equal(bits(got.conc[:3].cpu()), bits(c32[:3].to(dtype))), f"stain_separate {name}: {dtype} is not the rounded float32 plane"
+    for i, I in enumerate(S.base_np[:3]):
+        ratio = MAXC_TGT / mc[i]
+        Cn = so.get_concentrations(I, M[i]) * ratio
+        conc = c32[i].numpy().reshape(2, -1).astype(np.float64)
+        for k in range(2):
+            err = float(np.abs(conc[k] - Cn[:, k]).max())
+            bound = 5e-6 * max(1.0, ratio[k])
+            print(f"stain_separate {name} {dtype} tile {i} float32 conc[{k}]: max abs error {err:.2e} (bound {bound:.2e})")
+            assert err <= bound
+        if "norm" in want:
+            u8_parity(got.norm[i].cpu().numpy(), _oracle_apply(S)[i], label=f"separate norm tile {i}", src=I)
+            for k, img in enumerate((got.h, got.e)):
+                u8_parity(img[i].cpu().numpy(), so.truncate_u8((255 * np.exp(-Cn[:, k, None] * M_TGT[k])).reshape(I.shape)),
+                          label=f"separate stain {k} tile {i}", src=I)
+    if "norm" in want:
+        assert torch.equal(got.norm[3], S.base[3])
+    del got, bufs, gs
+    release()
+
+
+@pytest.mark.parametrize("name", BOTH)
+def test_hed_augment(name):
+    from stainlib_amd import engine
+    S = _state(name, S_bytes(name) * 2)
+    sig, bia = (periodic_rows(torch.from_numpy(x).cuda(), S.n) for x in (HED_SIGMA, HED_BIAS))
+    out, (_, applied) = _guard_image(S, None, lambda o: engine.hed_augment(S.dev, sig, bia, out=o), label="hed_augment")
+    assert_periodic((out, applied), label="hed_augment")
+    assert applied[:K].cpu().tolist() == [1, 1, 1, 0] and int(applied[3::K].sum()) == 0          # the all-white class: never applied
+    _anchor_u8(S, out, [so.hed_transform(I, HED_SIGMA[i], HED_BIAS[i]) for i, I in enumerate(S.base_np)], "hed_augment")
+    assert torch.equal(out[3], S.base[3])
+    del out
+    release()
+
+
+# ---- the Lab family: bit identity with the oracle ------------------------------------------------------------------------------------------
+def _reinhard():
+    nz = so.ReinhardStainNormalizer()
+    nz.fit(so.synth_tile(80, 80, 1001, so.M_TRUE_TGT))
+    return nz, np.ravel(nz.target_means).astype(np.float64), np.ravel(nz.target_stds).astype(np.float64)
+
+
+@pytest.mark.parametrize("mask", [False, True])
+@pytest.mark.parametrize("name", BOTH)
+def test_reinhard_transform(name, mask):
+    from stainlib_amd import engine
+    S = _state(name, S_bytes(name) * 2)
+    nz, tm, ts = _reinhard()
+    out, (_, st) = _guard_image(S, None, lambda o: engine.reinhard_transform(S.dev, tm, ts, mask_background=mask, out=o), label="reinhard")
+    assert_periodic((out, st), label=f"reinhard_transform mask={mask}")
+    got = out[:K].cpu().numpy()
+    for i, I in enumerate(S.base_np[:3]):
+        assert np.array_equal(got[i], nz.transform(I, mask_background=mask)), f"{name} mask={mask} tile {i}"
+    assert int(st[3, 7]) == 0                                                    # the all-white tile: no tissue pixel, reported
+    del out
+    release()
+
+
+@pytest.mark.parametrize("name", BOTH)
+def test_luminosity_standardize_and_standardize_brightness(name):
+    from stainlib_amd import engine
+    S = _state(name, S_bytes(name) * 2)
+    out, (_, p) = _guard_image(S, None, lambda o: engine.luminosity_standardize(S.dev, out=o), label="luminosity")
+    assert_periodic((out, p), label="luminosity_standardize")
+    assert np.array_equal(out[:K].cpu().numpy(), np.stack([so.luminosity_standardize(I) for I in S.base_np]))
+    del out
+    release()
+    out, (_, p) = _guard_image(S, None, lambda o: engine.standardize_brightness(S.dev, out=o), label="brightness")
+    assert_periodic((out, p), label="standardize_brightness")
+    assert np.array_equal(out[:K].cpu().numpy(), np.stack([so.standardize_brightness(I) for I in S.base_np]))
+    assert p[:K].cpu().tolist() == [float(np.percentile(I, 90)) for I in S.base_np]
+    del out
+    release()
+
+
+@pytest.mark.parametrize("name", BOTH)
+def test_lab_conversions(name):
+    from stainlib_amd import engine
+    S = _state(name, S_bytes(name) * 3)
+    lab = engine.rgb_to_lab8(S.dev)
+    assert_periodic(lab, label="rgb_to_lab8")
+    assert np.array_equal(lab[:K].cpu().numpy(), np.stack([so.rgb2lab_u8(I) for I in S.base_np]))
+    _last_block_is(lab, engine.rgb_to_lab8(S.base), "rgb_to_lab8")
+    back = engine.lab8_to_rgb(lab)
+    assert_periodic(back, label="lab8_to_rgb")
+    _last_block_is(back, engine.lab8_to_rgb(lab[:K].contiguous()), "lab8_to_rgb")
+    assert np.array_equal(back[:K].cpu().numpy(), np.stack([so.lab2rgb_u8(so.rgb2lab_u8(I)) for I in S.base_np]))
+    del lab, back
+    release()
+
+
+@pytest.mark.parametrize("name", BOTH)
+def test_lab_split_then_merge(name):
+    from stainlib_amd import engine
+    S = _state(name, S_bytes(name) * 6)                                          # three float32 planes (4 B/px each), the merged image, a mask
+    planes = engine.lab_split(S.dev)
+    assert_periodic(planes, label="lab_split")
+    for i, I in enumerate(S.base_np):
+        for got, want in zip(planes, so.lab_split(I)):
+            assert np.array_equal(got[i].cpu().numpy().view(np.int32), want.view(np.int32)), f"lab_split tile {i}"
+    _last_block_is(planes, engine.lab_split(S.base), "lab_split")
+    out = engine.lab_merge(*planes)
+    assert_periodic(out, label="lab_merge")
+    _last_block_is(out, engine.lab_merge(*(p[:K].contiguous() for p in planes)), "lab_merge")
+    assert np.array_equal(out[:K].cpu().numpy(), np.stack([so.merge_back(*so.lab_split(I)) for I in S.base_np]))
+    del planes, out
+    release()
+
+
+# =============================================== the view routes ============================================================================
+def _route(S, route):
+    """(keyword arguments of the view call on the batch, the existing full-tile entry point on the K-tile base as uint8)"""
+    from stainlib_amd import engine
+    if route == "raw":
+        return dict(), S.base
+    return dict(M_src=S.M, maxC_src=S.mc, M_tgt=M_TGT, maxC_tgt=MAXC_TGT), \
+        _memo(S, "apply4", lambda: engine.normalize_apply(S.base, S.M4, S.mc4, M_TGT, MAXC_TGT))
+
+
+def _small_view_check(S, out, full4, win, label):
+    """a view of 64 x 64 windows with period 8 over the tiles: periodic, and the first 8 tiles the definition on the 4-tile base"""
+    from tests.test_gpu_view import _ref
+    assert_periodic(out, period=8, label=label)
+    idx = torch.arange(8) % K
+    want = _ref(full4.cpu()[idx], win[:8], 64, 64, 7)
+    assert torch.equal(bits(out[:8].cpu().contiguous()), bits(want)), label
+
+
+@pytest.mark.parametrize("route", ["apply", "raw"])
+@pytest.mark.parametrize("name", BOTH)
+def test_normalize_view_small_windows(name, route):
+    from stainlib_amd import engine
+    S = _state(name, 1 << 28)
+    kw, full4 = _route(S, route)
+    win = period8_windows(S.n, S.h, S.w, 64, 64)
+    dwin = torch.from_numpy(win).cuda()
+    out, _ = _guard_image(S, None, lambda o: engine.normalize_view(S.dev, dwin, (64, 64), 7, out=o, **kw), 64, 64, label=f"view {route}")
+    _small_view_check(S, out, full4, win, f"normalize_view {route} {name}")
+    del out
+    release()
+
+
+def _full_tile_state(name):
+    """the full-tile float32 views: two 17 GB tensors beside the batch while the calls run, then -- the batch dropped (_same_bits_alone)
+    -- beside the mask of their comparison: 9 x 4.3 GB either way, with nothing else resident"""
+    return _state(name, S_bytes(name) * 8, alone=True)
+
+
+def _same_bits_alone(S, out, want, label):
+    """one torch.equal over the whole batch, once the input is gone (its 4.3 GB make room for the comparison's mask)"""
+    _forget(S)
+    assert out.numel() > 1 << 32 and torch.equal(bits(out), bits(want)), label
+
+
+@pytest.mark.parametrize("route", ["apply", "raw"])
+@pytest.mark.parametrize("name", BOTH)
+def test_normalize_view_full_tile_float32_is_the_tensor_entry_point(name, route):
+    from stainlib_amd import engine
+    fmt = _fmt(torch.float32, False)
+    S = _full_tile_state(name)
+    kw, _ = _route(S, route)
+    want = engine.to_tensor(S.dev, fmt) if route == "raw" else engine.normalize_apply_tensor(S.dev, S.M, S.mc, M_TGT, MAXC_TGT, fmt)
+    dwin = torch.zeros((S.n, 3), dtype=torch.int32, device="cuda")
+    out, _ = _guard_image(S, fmt, lambda o: engine.normalize_view(S.dev, dwin, None, 0, fmt=fmt, out=o, **kw), label=f"view {route} f32")
+    _same_bits_alone(S, out, want, f"normalize_view {route} {name}: not the tensor entry point's bits")
+    del out, want
+    release()
+
+
+def _hed_args(S):
+    from stainlib_amd import engine
+    sig, bia = (periodic_rows(torch.from_numpy(x).cuda(), S.n) for x in (HED_SIGMA, HED_BIAS))
+    kw, full4 = _route(S, "apply")
+    _, applied = engine.normalize_sums(S.dev, **kw)
+    assert_periodic(applied, label="hed applied")
+    assert applied[:K].cpu().tolist() == [1, 1, 1, 0]
+    return sig, bia, applied, kw, full4
+
+
+@pytest.mark.parametrize("name", BOTH)
+def test_normalize_hed_view_small_windows(name):
+    from stainlib_amd import engine
+    S = _state(name, 1 << 28)
+    sig, bia, applied, kw, full4 = _hed_args(S)
+    chain4, _ = engine.hed_augment(full4, HED_SIGMA, HED_BIAS)                    # (its cutoff leaves the all-white tile as it is)
+    win = period8_windows(S.n, S.h, S.w, 64, 64)
+    dwin = torch.from_numpy(win).cuda()
+    out, _ = _guard_image(S, None, lambda o: engine.normalize_hed_view(S.dev, dwin, (64, 64), 7, sig, bia, applied, out=o, **kw), 64, 64,
+                          label="hed view")
+    _small_view_check(S, out, chain4, win, f"normalize_hed_view {name}")
+    del out
+    release()
+
+
+@pytest.mark.parametrize("name", BOTH)
+def test_normalize_hed_view_full_tile_float32_is_the_chain(name):
+    from stainlib_amd import engine
+    fmt = _fmt(torch.float32, False)
+    S = _full_tile_state(name)
+    sig, bia, applied, kw, _ = _hed_args(S)
+    img, _ = engine.hed_augment(engine.normalize_apply(S.dev, S.M, S.mc, M_TGT, MAXC_TGT), sig, bia)
+    want = engine.to_tensor(img, fmt)
+    del img
+    release()
+    dwin = torch.zeros((S.n, 3), dtype=torch.int32, device="cuda")
+    out, _ = _guard_image(S, fmt, lambda o: engine.normalize_hed_view(S.dev, dwin, None, 0, sig, bia, applied, fmt=fmt, out=o, **kw),
+                          label="hed view f32")
+    _same_bits_alone(S, out, want, f"normalize_hed_view {name}: not the chain's bits")
+    del out, want
+    release()
+
+
+LAB_VIEWS = [("reinhard", dict(mask_background=True)), ("luminosity", {})]
+
+
+def _lab_calls(kind, kw):
+    from stainlib_amd import engine
+    _, tm, ts = _reinhard()
+    if kind == "reinhard":
+        return (lambda dev, **k: engine.reinhard_transform(dev, tm, ts, **kw, **k),
+                lambda dev, win, size, d_mask, **k: engine.reinhard_view(dev, win, size, tm, ts, d_mask, **kw, **k))
+    return (lambda dev, **k: engine.luminosity_standardize(dev, **k),
+            lambda dev, win, size, d_mask, **k: engine.luminosity_view(dev, win, size, d_mask=d_mask, **k))
+
+
+@pytest.mark.parametrize("kind,kw", LAB_VIEWS, ids=["reinhard", "luminosity"])
+@pytest.mark.parametrize("name", BOTH)
+def test_lab_view_small_windows(name, kind, kw):
+    S = _state(name, 1 << 28)
+    full, view = _lab_calls(kind, kw)
+    full4, extra4 = full(S.base)
+    win = period8_windows(S.n, S.h, S.w, 64, 64)
+    dwin = torch.from_numpy(win).cuda()
+    out, (_, extra, _) = _guard_image(S, None, lambda o: view(S.dev, dwin, (64, 64), 7, out=o), 64, 64, label=f"{kind} view")
+    _small_view_check(S, out, full4, win, f"{kind}_view {name}")
+    assert_periodic(extra, label=f"{kind}_view statistics")
+    assert torch.equal(bits(extra[:K]), bits(extra4))
+    del out
+    release()
+
+
+@pytest.mark.parametrize("kind,kw", LAB_VIEWS, ids=["reinhard", "luminosity"])
+@pytest.mark.parametrize("name", BOTH)
+def test_lab_view_full_tile_float32_is_convert_of_the_transform(name, kind, kw):
+    fmt = _fmt(torch.float32, False)
+    S = _full_tile_state(name)
+    full, view = _lab_calls(kind, kw)
+    u8, _ = full(S.dev)
+    from stainlib_amd import engine
+    want = engine.to_tensor(u8, fmt)
+    del u8
+    release()
+    dwin = torch.zeros((S.n, 3), dtype=torch.int32, device="cuda")
+    out, _ = _guard_image(S, fmt, lambda o: view(S.dev, dwin, None, 0, fmt=fmt, out=o), label=f"{kind} view f32")
+    _same_bits_alone(S, out, want, f"{kind}_view {name}: not the bits of the transform's tensor")
+    del out, want
+    release()

@@ -13,6 +13,8 @@ import torch
 
 import stainlib_amd
 from oracle import stain_oracle as so
+from tests import big_batch
+from tests.big_batch import guarded
 from tests.test_gpu_jitter import SENTINEL, _dev_tiles, _formats, _same_bits
 from tests.test_gpu_view import _ref, _windows
 
@@ -42,24 +44,12 @@ def _tiles(n, h, w, seed0=40):
 def _guarded(call, n, oh, ow, fmt, out_off=0):
     """call(out) -> whatever it returns, `out` a view 16 bytes + out_off elements into a buffer of SENTINEL with 16 more bytes behind
     it; everything outside the body must still hold SENTINEL afterwards.  -> (out on the CPU, the call's result)"""
-    dtype = fmt.dtype if fmt is not None else torch.uint8
-    esize = torch.empty((), dtype=dtype).element_size()
-    start, numel = 16 // esize + out_off, n * oh * ow * 3
-    buf = torch.full((start + numel + 16 // esize,), SENTINEL, dtype=dtype, device="cuda")
-    assert buf.data_ptr() % 16 == 0
-    body = buf[start:start + numel]
-    if fmt is None:
-        out = body.view(n, oh, ow, 3)
-    elif fmt.channels_last:
-        out = body.view(n, oh, ow, 3).permute(0, 3, 1, 2)
-    else:
-        out = body.view(n, 3, oh, ow)
+    g = guarded(n * oh * ow * 3, fmt.dtype if fmt is not None else torch.uint8, out_off)       # (shared: tests/big_batch.py)
+    assert SENTINEL == big_batch.SENTINEL
+    out = g.image(n, oh, ow, fmt)
     res = call(out)
     assert res[0] is out
-    torch.cuda.synchronize()
-    got = buf.cpu()
-    outside = torch.cat([got[:start], got[start + numel:]])
-    assert bool((outside == SENTINEL).all()), f"{n} x {oh} x {ow} fmt={fmt} out+{out_off}: written outside the output"
+    g.check(f"{n} x {oh} x {ow} fmt={fmt} out+{out_off}")
     return out.cpu(), res
 
 
