@@ -245,11 +245,58 @@ __device__ __forceinline__ Chunk pack_trunc_general(const float (&t)[12]) {
     return o;
 }
 
+// The trip loop of apply_sweep: lane chunk `cb`, then every `nthreads`-th chunk up to c1, N chunks per trip.
+// (A second loop shape beside pipelined_sweep of sweep_pipeline.hpp: per-lane loop control, no tail instantiation, the store
+// predicated on cc < c1 inside `compute`.  The callers keep their own gather: sweep_pipeline.hpp includes this header.)
+// Two register sets X and Y of N chunks each, and the loop body is two trips: X is the current set in the first and Y in the
+// second, so a loaded chunk is never copied from one set to the other (a copy needs the data: the rotation `cur = nx` made the
+// back-edge wait for every outstanding load AND store of the wave, once per trip).  A chunk's registers are dead once its 12
+// table gathers are issued -- one chunk ahead of its arithmetic, the sched_barrier-fenced stages -- and right there they are
+// refilled with the chunk of the trip two ahead: 2N loads per lane in flight, each consumed almost two trips after its issue, and
+// no wait inside the loop is a full drain (tools/isa_loops.py prints the smallest vmcnt of a loop).  `fetch` clamps
+// (load_chunk_clamped: lanes and trips past the end re-read the last chunk, no predicated load), so an odd number of trips simply
+// runs its second half-iteration clamped and masked; there is one copy of the body per set, none per parity.
+template <int N, class FETCH, class GATHER, class COMPUTE>
+__device__ __forceinline__ void lookahead_sweep(int cb, int c1, int nthreads, const FETCH& fetch, const GATHER& gather,
+                                                const COMPUTE& compute) {
+    Chunk X[N], Y[N];
+    // (issued in the order the loop consumes them, a fence behind each so that the scheduler cannot turn them round: the compiler's
+    //  wait for a chunk is the smaller of what the prologue and the back-edge leave behind it, and a predicated store counts for
+    //  nothing -- vmcnt(2N - 1) at the loop's head, vmcnt(2N) at the other steps: the first store of an iteration is unconditional)
+#pragma unroll
+    for (int k = 0; k < N; ++k) { X[k] = fetch(cb + k * nthreads); __builtin_amdgcn_sched_barrier(0); }
+#pragma unroll
+    for (int k = 0; k < N; ++k) { Y[k] = fetch(cb + (N + k) * nthreads); __builtin_amdgcn_sched_barrier(0); }
+    decltype(gather(X[0])) g[2];
+    g[0] = gather(X[0]);
+    X[0] = fetch(cb + 2 * N * nthreads);
+    auto trip = [&](Chunk (&cur)[N], Chunk (&oth)[N], int c) {      // on entry g[0] holds cur[0]'s gathers and cur[0] the trip after next
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            if (k + 1 < N) {
+                g[(k + 1) & 1] = gather(cur[k + 1]);
+                cur[k + 1] = fetch(c + (2 * N + k + 1) * nthreads);
+            } else {
+                g[0] = gather(oth[0]);
+                oth[0] = fetch(c + 3 * N * nthreads);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            compute(g[k & 1], c + k * nthreads);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+    static_assert(N % 2 == 0, "g[0] must hold the first chunk of a trip");
+    for (int c = cb; c < c1; c += 2 * N * nthreads) {
+        trip(X, Y, c);
+        trip(Y, X, c + N * nthreads);
+    }
+}
+
 // The apply sweep over chunks [c0, c1) of one tile with `nthreads` cooperating threads, table values from the
-// row table.  Two chunks per trip; the next trip's chunks are in flight during the current one and the 12 table
-// gathers of a chunk are issued one chunk ahead of its arithmetic.
-// (A second loop shape beside pipelined_sweep of sweep_pipeline.hpp, shared with augment_sweep: per-lane loop control, no
-// tail instantiation, the store predicated on cc < c1.  Both keep their own gather: sweep_pipeline.hpp includes this header.)
+// row table.  Four chunks per trip on lookahead_sweep: the next two trips' chunks are in flight during the current one and the
+// 12 table gathers of a chunk are issued one chunk ahead of its arithmetic.  (The general lasso, !FAST -- no real stain matrix --
+// takes two chunks per trip: with four its loop needs 86 registers and fused_apply saves seven callee-saved ones in a 32-byte frame
+// once per tile; so, and with the fast / stream dispatch in this order, fused_apply<*, aligned> has no frame at all.)
 template <bool ALIGNED, bool FAST, class TR, bool STREAM = false>
 __device__ __forceinline__ void apply_sweep(const uint8_t* src, uint8_t* dst, int P, int c0, int c1, int t, int nthreads,
                                             const TR& T, const ApplyK& K) {
@@ -273,27 +320,12 @@ __device__ __forceinline__ void apply_sweep(const uint8_t* src, uint8_t* dst, in
         const Chunk o = FAST ? pack_trunc_fast(tv) : pack_trunc_general(tv);
         if (cc < c1) store_chunk<ALIGNED, STREAM>(dst, nbytes, cc, o);
     };
-    constexpr int N = 4;                                       // chunks per lane and trip; the next trip is in flight
-    Chunk cur[N], nx[N];
-#pragma unroll
-    for (int k = 0; k < N; ++k) { cur[k] = fetch(c0 + t + k * nthreads); nx[k] = fetch(c0 + t + (N + k) * nthreads); }
-    G g[2];
-    g[0] = gather(cur[0]);
-    for (int c = c0 + t; c < c1; c += N * nthreads) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-            if (k + 1 < N) {
-                g[(k + 1) & 1] = gather(cur[k + 1]);
-            } else {
-#pragma unroll
-                for (int j = 0; j < N; ++j) { cur[j] = nx[j]; nx[j] = fetch(c + (2 * N + j) * nthreads); }
-                g[0] = gather(cur[0]);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            compute(g[k & 1], c + k * nthreads);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
+    // (an empty statement that differs between the instantiations and hands out the lane's first chunk: without it hipcc hoists the
+    //  prologue's loads and their addresses, identical in all four, above the stream / fast dispatch of fused_apply -- dropping the
+    //  non-temporal hint -- and copies them into each loop's registers)
+    int cb = c0 + t;
+    asm volatile("" : "+v"(cb) : "n"((int)STREAM * 2 + (int)FAST));
+    lookahead_sweep<FAST ? 4 : 2>(cb, c1, nthreads, fetch, gather, compute);      // chunks per lane and trip; two trips in flight
 }
 
 constexpr int kU = 4;       // chunks in flight per lane per trip (plain sweeps: 4 x 12 B loads issued back to back)
@@ -301,7 +333,7 @@ constexpr int kU = 4;       // chunks in flight per lane per trip (plain sweeps:
 // StainAugmentor.pop: own stain matrix both ways, affine on the concentrations of tissue pixels
 // (augmenter.py:435-443), clip (augmenter.py:447).  Persistent 512-thread workgroups over (tile, part) items with the
 // row table in layout B: one conflict-free ds_read_b64 {gamma, od32} per byte, gathers issued one chunk ahead of the
-// arithmetic, the next trip's chunks in flight (the structure of apply_sweep).
+// arithmetic, the next trip's chunks in flight (the structure apply_sweep had before lookahead_sweep).
 struct AugmentK {
     LassoK L;            // VGPR-resident, weights scaled by 2^-k (see ApplyK)
     float q[2][3];       // -log2(e) * M[i][c] * 2^k
@@ -348,6 +380,9 @@ __device__ __forceinline__ void augment_sweep(const uint8_t* src, uint8_t* dst, 
         const Chunk o = pack_trunc_fast(tv);        // values are >= 0; > 255 saturates = np.clip(.., 0, 255)
         if (cc < c1) store_chunk<ALIGNED, true>(dst, nbytes, cc, o);
     };
+    // (The loop apply_sweep had before lookahead_sweep, kept: on lookahead_sweep<2> k_stain_augment grows from 101 / 116 to 115 / 128
+    //  registers (aligned / unaligned) and this sweep is not on a measured path.  Its back-edge copies nx into cur and so waits for
+    //  every outstanding load and store once per trip; see lookahead_sweep for the form without the copy.)
     constexpr int N = 2;                                       // chunks per lane and trip; the next trip is in flight
     Chunk cur[N], nx[N];
 #pragma unroll

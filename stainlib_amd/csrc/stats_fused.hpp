@@ -355,11 +355,11 @@ __device__ __noinline__ void fused_apply(FusedShared<NT>* shp, const uint8_t* sr
     int t, c0, c1;
     fused_geometry<NT>(nch, tid, t, c0, c1);
     if (c0 >= c1) return;                                        // (a half without pixels: wave-uniform)
-    if (stream) {
-        if (K.fast) apply_sweep<ALIGNED, true, TabReaderB, true>(src, dst, P, c0, c1, t, kFusedThreads, TB, K);
-        else apply_sweep<ALIGNED, false, TabReaderB, true>(src, dst, P, c0, c1, t, kFusedThreads, TB, K);
+    if (K.fast) {
+        if (stream) apply_sweep<ALIGNED, true, TabReaderB, true>(src, dst, P, c0, c1, t, kFusedThreads, TB, K);
+        else apply_sweep<ALIGNED, true, TabReaderB, false>(src, dst, P, c0, c1, t, kFusedThreads, TB, K);
     } else {
-        if (K.fast) apply_sweep<ALIGNED, true, TabReaderB, false>(src, dst, P, c0, c1, t, kFusedThreads, TB, K);
+        if (stream) apply_sweep<ALIGNED, false, TabReaderB, true>(src, dst, P, c0, c1, t, kFusedThreads, TB, K);
         else apply_sweep<ALIGNED, false, TabReaderB, false>(src, dst, P, c0, c1, t, kFusedThreads, TB, K);
     }
 }
@@ -1195,6 +1195,7 @@ template <int METHOD, bool TRANSFORM, bool ALIGNED, int NT>
 static __global__ __launch_bounds__(NT, 4) void k_fused(FusedArgs a) {
     __shared__ FusedShared<NT> sh;
     fused_lds_origin(sh);
+    __builtin_amdgcn_s_setprio(1);                        // every phase above the apply sweep's priority 0: see the call of fused_apply
     [[maybe_unused]] const int tid = threadIdx.x;      // (the development macros; the glue below reads lane_id())
     const TabReaderB TB = TabReaderB::make(sh.tab);       // the 8-byte {gamma, od32} rows serve every sweep
     const int nch = (a.P + 3) >> 2;
@@ -1215,7 +1216,8 @@ static __global__ __launch_bounds__(NT, 4) void k_fused(FusedArgs a) {
 
     // (Two workgroups live on a CU and the instruction arbiter serves the OLDER one's waves first: the first-launched workgroup of every CU
     //  runs its sweeps ~20 % faster than its partner and the launch ends when the slow half does.  s_setprio schemes -- finish steps on
-    //  top, sweeps alternating or by age -- were measured in rounds 1, 4 and 5 and changed nothing: the tail is bound by bytes)
+    //  top, sweeps alternating or by age -- were measured in rounds 1, 4 and 5 and changed nothing: the tail is bound by bytes, DESIGN 9.
+    //  The one priority the kernel does set, the apply sweep below every other phase, belongs to that sweep's stall-free loop: see its call.)
     // Tiles: the first by position, the later rounds from the launch's counter -- a workgroup whose tiles were quick (empty, background)
     // takes more of them (a batch of 2 048 tiles 512^2, every fourth one white: 2.15 -> 1.88 ms); a tile's results do not depend on who
     // computes them.  The counter is asked before the apply sweep, whose length hides the answer's way back; sh.next_tile is read after
@@ -1409,7 +1411,13 @@ static __global__ __launch_bounds__(NT, 4) void k_fused(FusedArgs a) {
                         if (c + k * NT < nch) store_chunk<ALIGNED>(dst, nbytes, c + k * NT, ch[k]);
                 }
             } else {
+                // The apply sweep issues behind the partner workgroup's phases (s_setprio: the kernel runs at 1, this sweep at 0).  Its loop
+                // no longer stalls once per trip (lookahead_sweep), so at equal priority workgroup A's apply -- which ends 350 us before the
+                // launch does -- took the issue slots of B's merged sweep, the critical path: B's sweep 630 -> 700 us, the launch no shorter.
+                // Behind B's sweep it fills B's latency-bound finish instead.  (profiles/apply_lookahead.txt; B's own apply runs alone.)
+                __builtin_amdgcn_s_setprio(0);
                 fused_apply<NT, ALIGNED>(&sh, src, dst, a.P, a.M_tgt, a.maxC_tgt, a.lam, stream ? 1 : 0);
+                __builtin_amdgcn_s_setprio(1);
             }
         }
         __syncthreads();     // sh.* is reused by the next tile

@@ -2,10 +2,14 @@
     python tools/isa_loops.py FILE.s SYMBOL_SUBSTRING [min_lines=40]
 A loop is the span from a local label to the last backward branch to it.  For every loop of at least min_lines instruction lines it
 prints the VALU (v_*), SALU (s_* without waits, nops and branches), branch, wait, LDS (ds_*) and memory (global_/flat_/scratch_/buffer_)
-instruction counts of the span WITHOUT its inner loops (an inner loop -- the drain of the cube sweeps -- runs a data-dependent number
-of times), the inner loops' own counts indented below it, and the function's register and scratch figures."""
+instruction counts, the number of `v_mov_b32` among the VALU (a register rotation on the back-edge shows up here) and the smallest
+`vmcnt` any `s_waitcnt` of the span waits for (0: the loop drains its loads and stores; `-`: it waits for none) of the span WITHOUT
+its inner loops (an inner loop -- the drain of the cube sweeps -- runs a data-dependent number of times), the inner loops' own
+counts indented below it, and the function's register and scratch figures."""
 import re
 import sys
+
+VMCNT = re.compile(r"vmcnt\((\d+)\)")
 
 
 def body_of(path, sym):
@@ -68,12 +72,20 @@ def main():
     print(f"{name}: " + " ".join(f"{k} {v}" for k, v in foot.items()))
 
     def count(a, b, holes):
-        c = dict(valu=0, salu=0, branch=0, wait=0, lds=0, mem=0, other=0)
+        c = dict(valu=0, salu=0, branch=0, wait=0, lds=0, mem=0, other=0, mov=0, vmcnt=None)
         for i in range(a, b + 1):
             if L[i].endswith(":") or any(x <= i <= y for x, y in holes):
                 continue
-            c[classify(L[i].split()[0])] += 1
+            op = L[i].split()[0]
+            c[classify(op)] += 1
+            c["mov"] += op.startswith("v_mov_b32")                  # register rotation shows up here (counted within VALU too)
+            m = VMCNT.search(L[i]) if op.startswith("s_waitcnt") else None
+            if m:                                                  # the smallest count waited for: 0 = the loop drains its loads and stores
+                c["vmcnt"] = int(m.group(1)) if c["vmcnt"] is None else min(c["vmcnt"], int(m.group(1)))
         return c
+
+    def rot(c):
+        return f"v_mov_b32 {c['mov']} min vmcnt {'-' if c['vmcnt'] is None else c['vmcnt']}"
 
     for a, b in spans:
         if any(x < a and b < y for x, y in spans):
@@ -82,13 +94,13 @@ def main():
         if b - a + 1 < min_lines:
             continue
         c = count(a, b, inner)
-        print(f"  loop at line {a}..{b}: VALU {c['valu']} SALU {c['salu']} branch {c['branch']} wait {c['wait']} LDS {c['lds']} mem {c['mem']} other {c['other']}"
+        print(f"  loop at line {a}..{b}: VALU {c['valu']} SALU {c['salu']} branch {c['branch']} wait {c['wait']} LDS {c['lds']} mem {c['mem']} other {c['other']} {rot(c)}"
               f"  (VALU + SALU {c['valu'] + c['salu']}, with branches {c['valu'] + c['salu'] + c['branch']}, {len(inner)} inner loops left out)")
         for x, y in inner:
             if any(p < x and y < q for p, q in inner):
                 continue
             ci = count(x, y, [])
-            print(f"      inner {x}..{y}: VALU {ci['valu']} SALU {ci['salu']} branch {ci['branch']} wait {ci['wait']} LDS {ci['lds']} mem {ci['mem']}")
+            print(f"      inner {x}..{y}: VALU {ci['valu']} SALU {ci['salu']} branch {ci['branch']} wait {ci['wait']} LDS {ci['lds']} mem {ci['mem']} {rot(ci)}")
         # the short path of one trip: every wave-uniform forward skip inside the loop (s_cbranch_scc*: the drain test) is taken,
         # exec-dependent skips fall through, forward s_branch is followed
         p = dict(valu=0, salu=0, branch=0, wait=0, lds=0, mem=0, other=0)
