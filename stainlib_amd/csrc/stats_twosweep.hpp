@@ -296,7 +296,7 @@ __device__ __forceinline__ void ts_sweep(const uint8_t* src, int P, int c0, int 
     const int lane = t & 63;
     const int w0 = __builtin_amdgcn_readfirstlane(c0 + (t & ~63));
     using G = GatherGamOd;
-    auto fetch = [&](int cc) { return load_chunk_clamped<ALIGNED, STREAM>(src, nbytes, cc, c1); };
+    auto fetch = [&](int cc) { return load_chunk<ALIGNED, STREAM>(src, nbytes, cc); };      // (the driver clamps cc into [.., c1))
     auto gather = [&](const Chunk& ch) { return gather_gam_od(T, ch); };
     BurstMoments bm;
     auto compute = [&](auto tail_tag, const G& g, int cc) {
@@ -365,34 +365,18 @@ __device__ __forceinline__ void ts_sweep(const uint8_t* src, int P, int c0, int 
             drain();
         }
     };
-    // A deliberate variant of pipelined_sweep (sweep_pipeline.hpp, the canonical form of this loop): the cube test of the trip's
-    // chunks runs behind the trip's first gather, so the look-ahead buffers live inside the trip.
-    Chunk cur[kTrip], nx[kTrip];
-#pragma unroll
-    for (int k = 0; k < kTrip; ++k) { cur[k] = fetch(w0 + lane + k * nthreads); nx[k] = fetch(w0 + lane + (kTrip + k) * nthreads); }
-    auto trip = [&](auto tail_tag, int cb) {
-        G g[2];
-        g[0] = gather(cur[0]);
-#pragma unroll
-        for (int k = 0; k < kTrip; ++k) cube(tail_tag, cur[k], cb + k * nthreads + lane);
-#pragma unroll
-        for (int k = 0; k < kTrip; ++k) {
-            if (k + 1 < kTrip) {
-                g[(k + 1) & 1] = gather(cur[k + 1]);
-            } else {
-#pragma unroll
-                for (int j = 0; j < kTrip; ++j) { cur[j] = nx[j]; nx[j] = fetch(cb + lane + (2 * kTrip + j) * nthreads); }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            compute(tail_tag, g[k & 1], cb + k * nthreads + lane);
-            __builtin_amdgcn_sched_barrier(0);
-        }
+    // (the totals are pinned where a trip ends: the loop body is two trips, and left alone the compiler sinks the first trip's nine
+    //  binary64 additions behind the second trip -- the same sums in the same order, but the first trip's burst stays live that long)
+    auto end_trip = [&]() {
         bm.flush(mo);
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(mo.sx), "+v"(mo.sy), "+v"(mo.sz), "+v"(mo.sxx), "+v"(mo.sxy), "+v"(mo.sxz), "+v"(mo.syy), "+v"(mo.syz), "+v"(mo.szz));
+#endif
     };
-    const int lim = ALIGNED ? c1 : min(c1, P >> 2);
-    int cb = w0;
-    for (; cb + (kTrip - 1) * nthreads + 64 <= lim; cb += nthreads * kTrip) trip(std::false_type{}, cb);
-    if (cb < c1) trip(std::true_type{}, cb);
+    // On lookahead_wave_sweep (sweep_lookahead.hpp), a deliberate variant of pipelined_sweep (sweep_pipeline.hpp, the canonical form of
+    // this loop): the cube test of the trip's chunks runs behind the trip's first gather, and the chunks of the next TWO trips are in
+    // flight in two register sets that are never copied into each other.
+    lookahead_wave_sweep<kTrip>(w0, lane, c1, ALIGNED ? c1 : min(c1, P >> 2), nthreads, fetch, gather, cube, compute, end_trip);
     {   // what is left in the ring: fewer than 128 entries (stale entries beyond the fill are valid pixels: read by every lane, masked out)
         uint32_t q0, q1;
         ring.rest2(lane, q0, q1);

@@ -3,6 +3,7 @@
 // trip, the twelve table gathers of a chunk).
 #pragma once
 #include "apply_kernels.hpp"
+#include "sweep_lookahead.hpp"
 #include <type_traits>
 
 namespace sl {
