@@ -123,9 +123,16 @@ typedef struct SlParams {
                                     entry point that takes an SlParams (SL_ERR_BADARG on a mismatch) -- a caller built against another
                                     version of this struct is refused instead of being read past its end */
     uint32_t reserved0;
-    double luminosity_threshold; /* 0.8  (binary64 like the Python float the reference compares with) */
-    double angular_percentile;   /* 99   */
-    double lasso_lambda;        /* 0.01 */
+    double luminosity_threshold; /* 0.8  (binary64 like the Python float the reference compares with).  ANY value: the tissue test is
+                                    L8 / 255.0 < threshold as the reference writes it -- at 0 and below, and for NaN, no pixel is tissue
+                                    (every tile SL_TILE_EMPTY_MASK); above 1 every pixel is, saturated white included */
+    double angular_percentile;   /* 99.  [0, 100]; outside it, or NaN: SL_ERR_BADARG (np.percentile raises there).  The pair the reference
+                                    takes is (100 - p, p) and it orders the two stain vectors afterwards, so p and 100 - p give the same
+                                    matrix: the kernels run with max(p, 100 - p).  50 makes the two vectors one: SL_TILE_DEGENERATE_COV */
+    double lasso_lambda;        /* 0.01.  >= 0; negative or NaN: SL_ERR_BADARG -- from every entry point that takes an SlParams and from those
+                                   that take lasso_lambda as a bare double (sl_normalize_apply, sl_normalize_apply_tensor, sl_concentrations,
+                                   sl_stain_separate).  0 is plain non-negative least squares; a penalty above every pixel's projection
+                                   zeroes all concentrations: SL_TILE_ZERO_MAXC */
     double dl_lambda;           /* 0.1  (Vahadane) */
     int32_t dl_max_sweeps;      /* 200  (Vahadane; the reference is wall-clock budgeted) */
     int32_t schedule;           /* 0 = automatic; 1 = one launch per phase; 2 = persistent fused kernel (two 512-thread workgroups per CU);

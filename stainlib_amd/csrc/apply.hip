@@ -8,7 +8,7 @@ extern "C" int sl_normalize_apply(const uint8_t* rgb, uint8_t* out, int n, int h
                                   const double* maxC_src, const double* M_tgt, const double* maxC_tgt,
                                   double lasso_lambda, float* prequant, void* stream) {
     if (const int rc = check_shape(rgb, out, n, h, w)) return rc;
-    if (!M_src || !maxC_src || !M_tgt || !maxC_tgt) return SL_ERR_BADARG;
+    if (!M_src || !maxC_src || !M_tgt || !maxC_tgt || !lambda_ok(lasso_lambda)) return SL_ERR_BADARG;
     const TileLaunch L(n, h, w, kWG);
     const bool al = aligned4(rgb, L.P) && aligned4(out, L.P);
     launch_aligned(al, prequant ? k_apply<true, true> : k_apply<true, false>, prequant ? k_apply<false, true> : k_apply<false, false>, L.grid,
@@ -47,7 +47,7 @@ extern "C" int sl_grayscale_augment(const uint8_t* rgb, uint8_t* out, int n, int
 extern "C" int sl_concentrations(const uint8_t* rgb, int n, int h, int w, const double* M, double lasso_lambda,
                                  float* C_out, void* stream) {
     if (const int rc = check_shape(rgb, C_out, n, h, w)) return rc;
-    if (!M) return SL_ERR_BADARG;
+    if (!M || !lambda_ok(lasso_lambda)) return SL_ERR_BADARG;
     const TileLaunch L(n, h, w, kWG);
     hipLaunchKernelGGL(k_concentrations, L.grid, L.block, 0, (hipStream_t)stream, rgb, (int)L.P, L.parts, M, lasso_lambda, C_out);
     return launch_status();

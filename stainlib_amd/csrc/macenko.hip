@@ -137,7 +137,7 @@ StatsArgs stats_args(const uint8_t* rgb, int g0, int m, long P, const SlParams& 
     a.n_sample = L.n_sample;
     a.ylimf = tissue_ylimf(p);
     a.lam = p.lasso_lambda;
-    a.pct = p.angular_percentile;
+    a.pct = folded_percentile(p.angular_percentile);
     a.partials = (double*)(ws + L.off_partials);
     a.sample = (uint32_t*)(ws + L.off_sample);
     a.cap_raw = L.cap_raw;
@@ -238,7 +238,7 @@ int run_fused(int method, const uint8_t* rgb, uint8_t* out, int n, long P, const
     a.n_sample = L.n_sample;
     a.ylimf = tissue_ylimf(p);
     a.lam = p.lasso_lambda;
-    a.pct = p.angular_percentile;
+    a.pct = folded_percentile(p.angular_percentile);
     a.M_tgt = M_tgt;
     a.maxC_tgt = maxC_tgt;
     a.cap_raw = L.cap_raw;

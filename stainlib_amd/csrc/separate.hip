@@ -37,7 +37,7 @@ extern "C" int sl_stain_separate(const uint8_t* rgb, int n, int h, int w, const 
                                  const double* M_tgt, const double* maxC_tgt, double lasso_lambda, const SlSeparateOut* outs,
                                  void* stream) {
     if (const int rc = check_shape(rgb, n, h, w)) return rc;
-    if (!outs || !M_src || !maxC_src) return SL_ERR_BADARG;
+    if (!outs || !M_src || !maxC_src || !lambda_ok(lasso_lambda)) return SL_ERR_BADARG;
     if ((M_tgt == nullptr) != (maxC_tgt == nullptr)) return SL_ERR_BADARG;       // both: a target; neither: every tile's own matrix
     const TileLaunch L(n, h, w, kWG);
     const long P = L.P;

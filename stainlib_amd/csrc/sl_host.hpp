@@ -19,7 +19,19 @@ inline int launch_status() { return hip_err(hipGetLastError()); }
 
 // An SlParams handed over by the caller: NULL (defaults) or a struct of THIS header's size (SlParams.struct_size, set by sl_default_params).
 // (and with its enumerated fields inside their ranges: an unknown two_sweep used to run as "automatic" without a word)
-inline bool params_ok(const SlParams* p) { return !p || (p->struct_size == (uint32_t)sizeof(SlParams) && p->two_sweep >= 0 && p->two_sweep <= 4); }
+// (... and its numbers inside the ranges numpy and the lasso accept: np.percentile raises outside [0, 100], a negative penalty has no
+//  minimiser; NaN fails every comparison.  luminosity_threshold is unrestricted: every value, NaN included, has a meaning in the reference)
+inline bool lambda_ok(double lasso_lambda) { return lasso_lambda >= 0.0; }
+inline bool percentile_ok(double pct) { return pct >= 0.0 && pct <= 100.0; }
+inline bool params_ok(const SlParams* p) {
+    return !p || (p->struct_size == (uint32_t)sizeof(SlParams) && p->two_sweep >= 0 && p->two_sweep <= 4 && percentile_ok(p->angular_percentile) &&
+                  lambda_ok(p->lasso_lambda));
+}
+
+// The angular percentile the selection kernels run with.  The reference takes the pair (100 - pct, pct) and orders the two stain vectors
+// afterwards (macenko_stain_extractor.py:33-43), so pct and 100 - pct give the same matrix; the kernels are built for the upper one --
+// bracket 0 below bracket 1, the plain pixels between them.
+inline double folded_percentile(double pct) { return pct < 100.0 - pct ? 100.0 - pct : pct; }
 
 // The SlParams a call runs with, once params_ok has accepted them: the caller's, or the defaults for NULL.
 inline SlParams params_or_defaults(const SlParams* params) {

@@ -725,7 +725,8 @@ extern "C" int sl_slide_key_next_above(const uint8_t* rgb, int n, int h, int w, 
 extern "C" int sl_pool_begin(const double* moments11, const SlParams* params, double* state, void* stream) {
     if (!moments11 || !state) return SL_ERR_BADARG;
     if (!params_ok(params)) return SL_ERR_BADARG;
-    hipLaunchKernelGGL(k_pool_begin, dim3(1), dim3(64), 0, (hipStream_t)stream, moments11, state, params_or_defaults(params).angular_percentile);
+    hipLaunchKernelGGL(k_pool_begin, dim3(1), dim3(64), 0, (hipStream_t)stream, moments11, state,
+                       folded_percentile(params_or_defaults(params).angular_percentile));
     return launch_status();
 }
 

@@ -1143,7 +1143,7 @@ extern "C" int sl_pool2_begin(const double* moments16_reduced, const SlParams* p
     if (!moments16_reduced || !state || sample_log2 < 0 || sample_log2 > 12) return SL_ERR_BADARG;
     if (!params_ok(params)) return SL_ERR_BADARG;
     const SlParams p = params_or_defaults(params);
-    hipLaunchKernelGGL(k_p2_begin, dim3(1), dim3(64), 0, (hipStream_t)stream, moments16_reduced, state, p.angular_percentile, p.lasso_lambda,
+    hipLaunchKernelGGL(k_p2_begin, dim3(1), dim3(64), 0, (hipStream_t)stream, moments16_reduced, state, folded_percentile(p.angular_percentile), p.lasso_lambda,
                        sample_log2);
     return launch_status();
 }

@@ -28,7 +28,7 @@ extern "C" int sl_normalize_apply_tensor(const uint8_t* rgb, void* out, int n, i
                                          const double* M_tgt, const double* maxC_tgt, double lasso_lambda, const SlTensorFormat* fmt,
                                          void* stream) {
     if (const int rc = check_shape(rgb, out, n, h, w)) return rc;
-    if (!M_src || !maxC_src || !M_tgt || !maxC_tgt) return SL_ERR_BADARG;
+    if (!M_src || !maxC_src || !M_tgt || !maxC_tgt || !lambda_ok(lasso_lambda)) return SL_ERR_BADARG;
     if (!format_ok(fmt)) return SL_ERR_BADARG;
     const TileLaunch L(n, h, w, kWG);
     const TensorK k = tensor_k(*fmt);

@@ -280,8 +280,9 @@ class _PooledStatistics:
     """What the pooled statistics of both methods share: the process group and the normalizer's parameters."""
 
     def __init__(self, group=None, luminosity_threshold=0.8, angular_percentile=99.0, lasso_lambda=0.01):
+        from .utils.stain_utils import check_percentile
         self.group = group
-        self.thr, self.pct, self.lam = luminosity_threshold, angular_percentile, lasso_lambda
+        self.thr, self.pct, self.lam = luminosity_threshold, check_percentile(angular_percentile), lasso_lambda
         self.last_path = []          # how each stage of the last call settled ("merged", "window" or "radix")
         self.sample_log2 = None      # None: the sample density follows the slide's pixel count (sample_log2_for); 0...12: one 64-pixel sub-row in 2^s
                                      # (tests and experiments; the same on every rank -- the RESULT does not depend on it, only which route settles it)
@@ -382,13 +383,14 @@ class PooledSlideStatistics(_PooledStatistics):
 
     def finish(self, state: torch.Tensor):
         """The one read-back of the device-driven path: (M, maxC) as numpy, or None when a window missed (the caller then runs the
-        host-driven rounds).  Raises like the reference on an empty tissue mask."""
+        host-driven rounds).  Raises like the reference on an empty tissue mask, and like MacenkoStainExtractor.get_stain_matrix on a
+        degenerate slide (fewer than two tissue pixels, or two parallel stain vectors -- an angular percentile of 50 makes them so:
+        the host-driven rounds have no such check and would divide by the singular Gram matrix)."""
         from . import _ffi
-        from .utils.excepts import TissueMaskException
+        from .utils.stain_utils import raise_for_status
         s = state.cpu().numpy()
         status, miss = int(s[_ffi.POOL_STATUS]), int(s[_ffi.POOL_MISS])
-        if status == _ffi.TILE_EMPTY_MASK:
-            raise TissueMaskException("Empty tissue mask computed")
+        raise_for_status(status)
         self.last_miss = miss
         if len(s) > _ffi.POOL2_WHY:
             self.last_why = int(s[_ffi.POOL2_WHY])
@@ -455,7 +457,8 @@ class PooledSlideStatistics(_PooledStatistics):
                 return math.atan2(p, 1.0 - abs(p))
             pp = 2.0 - p if p > 0 else -2.0 - p
             return math.atan2(pp, -(1.0 - abs(pp)))
-        (k_lo, g_lo), (k_hi, g_hi) = percentile_position(T, 100.0 - self.pct), percentile_position(T, self.pct)
+        pct = max(self.pct, 100.0 - self.pct)       # (100 - pct, pct) is the same pair either way; the window sweeps want target 0 below target 1
+        (k_lo, g_lo), (k_hi, g_hi) = percentile_position(T, 100.0 - pct), percentile_position(T, pct)
         (xa0, xb0), (xa1, xb1) = key_rank_pairs(tiles_local, _ffi.KEYSET_ANGLE, Vf.reshape(6), (k_lo, k_hi), (T, T),
                                                 window_sample_log2(n_pixels), params, self.group, self.last_path)
         phis = [np_lerp(angle_of_pseudo(xa0), angle_of_pseudo(xb0), g_lo), np_lerp(angle_of_pseudo(xa1), angle_of_pseudo(xb1), g_hi)]

@@ -3,7 +3,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ..utils.stain_utils import ABCStainExtractor, _UINT8_MSG, _to_device, is_uint8_image, raise_for_status
+from ..utils.stain_utils import ABCStainExtractor, _UINT8_MSG, _to_device, check_percentile, is_uint8_image, raise_for_status
 
 
 class MacenkoStainExtractor(ABCStainExtractor):
@@ -17,7 +17,7 @@ class MacenkoStainExtractor(ABCStainExtractor):
         assert is_uint8_image(I), _UINT8_MSG
         from .. import engine
         p = engine.make_params(luminosity_threshold=float(luminosity_threshold),
-                               angular_percentile=float(angular_percentile))
+                               angular_percentile=check_percentile(angular_percentile))
         M, _, status = engine.macenko_fit(_to_device(I), params=p)
         raise_for_status(int(status[0]))
         return M[0].cpu().numpy()
@@ -27,6 +27,6 @@ class MacenkoStainExtractor(ABCStainExtractor):
         """Batched extension: (N,H,W,3) uint8 device tensor -> ((N,2,3) float64, (N,) int32 status) tensors."""
         from .. import engine
         p = engine.make_params(luminosity_threshold=float(luminosity_threshold),
-                               angular_percentile=float(angular_percentile))
+                               angular_percentile=check_percentile(angular_percentile))
         M, _, status = engine.macenko_fit(tiles, params=p)
         return M, status

@@ -33,6 +33,15 @@ def _to_device(I: np.ndarray):
     return torch.from_numpy(np.ascontiguousarray(I)[None]).cuda()
 
 
+def check_percentile(pct) -> float:
+    """An angular percentile as a float, refused the way np.percentile refuses it (macenko_stain_extractor.py:33-34 hands it to numpy,
+    which raises for values outside [0, 100] and for NaN) -- before the library's own SL_ERR_BADARG."""
+    pct = float(pct)
+    if not 0.0 <= pct <= 100.0:
+        raise ValueError("Percentiles must be in the range [0, 100]")
+    return pct
+
+
 def raise_for_status(status: int) -> None:
     """Per-tile status of the engine -> what the reference does for a single image."""
     from .. import _ffi

@@ -87,6 +87,41 @@ int main(void) {
             EXPECT(sl_pool_begin(d6, &q, d6, 0), SL_ERR_BADARG);
         }
     }
+    /* SlParams' numbers: what numpy or the lasso refuse is refused here -- a percentile outside [0, 100] or NaN (np.percentile raises), a
+     * negative or NaN penalty -- by every entry point that takes the struct, and by those that take lasso_lambda as a bare double;
+     * the ends of the ranges are accepted (the workspace check comes next), luminosity_threshold is unrestricted */
+    {
+        const double bad_pct[] = {-1.0, 100.5, (double)NAN}, bad_lam[] = {-0.01, (double)NAN};
+        for (unsigned i = 0; i < 5; ++i) {
+            SlParams q = p;
+            if (i < 3) q.angular_percentile = bad_pct[i]; else q.lasso_lambda = bad_lam[i - 3];
+            EXPECT(sl_macenko_fit(rgb, n, h, w, &q, d6, d2, st, ws, need, 0), SL_ERR_BADARG);
+            EXPECT(sl_macenko_transform(rgb, out, n, h, w, &q, d6, d2, 0, 0, 0, ws, need, 0), SL_ERR_BADARG);
+            EXPECT(sl_vahadane_fit(rgb, n, h, w, &q, d6, d2, st, st, ws, needv, 0), SL_ERR_BADARG);
+            EXPECT(sl_stain_augment(rgb, out, n, h, w, d6, d6, 0, &q, 0), SL_ERR_BADARG);
+            EXPECT(sl_tile_moments(rgb, n, h, w, &q, d6, ws, sl_workspace_bytes(SL_OP_TILE_MOMENTS, n, h, w), 0), SL_ERR_BADARG);
+            EXPECT(sl_pool_begin(d6, &q, d6, 0), SL_ERR_BADARG);
+            EXPECT(sl_pool2_begin(d6, &q, 0, d6, 0), SL_ERR_BADARG);
+            EXPECT(sl_workspace_bytes_for(SL_OP_MACENKO_TRANSFORM, n, h, w, &q), 0);
+        }
+        for (unsigned i = 0; i < 2; ++i) {
+            SlSeparateOut so;
+            sl_default_separate_out(&so);
+            so.norm = out;
+            EXPECT(sl_normalize_apply(rgb, out, n, h, w, d6, d2, d6, d2, bad_lam[i], 0, 0), SL_ERR_BADARG);
+            EXPECT(sl_concentrations(rgb, n, h, w, d6, bad_lam[i], f, 0), SL_ERR_BADARG);
+            EXPECT(sl_stain_separate(rgb, n, h, w, d6, d2, d6, d2, bad_lam[i], &so, 0), SL_ERR_BADARG);
+        }
+        const double ok_pct[] = {0.0, 50.0, 100.0};
+        for (unsigned i = 0; i < 3; ++i) {
+            SlParams q = p;
+            q.angular_percentile = ok_pct[i];
+            q.lasso_lambda = 0.0;
+            q.luminosity_threshold = i == 0 ? (double)NAN : (i == 1 ? -1.0 : 2.0);
+            EXPECT(sl_macenko_fit(rgb, n, h, w, &q, d6, d2, st, 0, need, 0), SL_ERR_WORKSPACE);
+            EXPECT(sl_workspace_bytes_for(SL_OP_MACENKO_TRANSFORM, n, h, w, &q) > 0, 1);
+        }
+    }
     /* single-pass operators */
     EXPECT(sl_normalize_apply(0, out, n, h, w, d6, d2, d6, d2, 0.01, 0, 0), SL_ERR_BADARG);
     EXPECT(sl_normalize_apply(rgb, 0, n, h, w, d6, d2, d6, d2, 0.01, 0, 0), SL_ERR_BADARG);
