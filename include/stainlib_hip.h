@@ -700,6 +700,33 @@ SL_API int sl_reinhard_view(const uint8_t* rgb, void* out, int n, int h, int w, 
 SL_API int sl_luminosity_view(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, double percentile, double* p_out, void* workspace, size_t workspace_bytes, const SlTensorFormat* fmt, void* stream);
 SL_API int sl_slab_view(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, const double* state, int mode, int mask_background, double luminosity_threshold, const SlTensorFormat* fmt, void* stream);
 
+/* ---- magnification change in the one-pass loader: a 2x / 4x box shrink inside the view (view.hip, hed_view.hip, lab_view.hip; an extension:
+ * slides are tiled at 40x and most networks train at 20x or 10x, so a loader otherwise runs avg_pool2d(2) or (4) behind the call, on the
+ * widest data type, over a full-resolution tensor of which three quarters or fifteen sixteenths are averaged away) ------------------------
+ * Each call is its parent -- sl_normalize_view, sl_normalize_hed_view, sl_reinhard_view, sl_luminosity_view, sl_slab_view -- with
+ * `int shrink` = s in {1, 2, 4} after d_mask; the parent is the call with s = 1, by forwarding.  (oh, ow) stays the size of the OUTPUT:
+ *     (wh, ww) = (oh, ow) for an even number of quarter turns, (ow, oh) for an odd one: the window in BOXES of s x s source pixels
+ *     y0' = clamp(y0, 0, h - s wh),  x0' = clamp(x0, 0, w - s ww), clamped on the device; any pixel, not only a multiple of s
+ * With full[t] the h x w x 3 uint8 image the parent defines -- at SOURCE resolution: normalised, jittered, HED-transformed, Lab-mapped per
+ * source pixel, the statistics (fits, cutoff sums, Lab and pooled statistics) those of the whole tile at source resolution -- per channel
+ *     S[i, j] = sum of full[t][y0' + s i + a, x0' + s j + b] over a, b in 0 .. s-1          (an integer, at most 16 x 255 = 4080)
+ *     b[i, j] = (S[i, j] + s s / 2) >> (2 log2 s)                                           (the mean, round half up; a uint8)
+ *     view[t] = rot90(flip_w_if(f, b), k)                                                   (the parent's dihedral rule)
+ * The boxes start at the window's corner and the window is a whole number of them, so shrinking commutes with the flip and the turn.  The
+ * tensor is defined on b as it is on a byte everywhere else: fma(float32(b), 1 / (255 std), -mean / std), rounded to fmt->dtype.  A tile
+ * whose fit failed, and every tile of a pooled slide whose status is not SL_TILE_OK: the shrunk view of its own bytes.  Averaging happens
+ * AFTER normalisation, in byte space; "shrink first, normalise a quarter of the pixels" is another image and not offered.  Neither are
+ * other factors, arbitrary or per-tile ratios, bilinear or antialiased filters.
+ * Every source pixel of the window is read and computed (s s times the output's); only the output is written.
+ * SL_ERR_BADARG (SL_ERR_WORKSPACE) before anything is launched: what the parent refuses, with s oh, s ow in place of oh, ow in its tests
+ * against h and w (s oh > h, s ow > w; d_mask & 1 with s ow > h or s oh > w); shrink other than 1, 2, 4; more than 2^31 - 1 (tile, patch)
+ * pairs, a patch being 64 / s output pixels square.  out == rgb is not supported.  Capture-safe like the parents. */
+SL_API int sl_normalize_view_shrink(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, int shrink, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, const double* alpha_beta, int augment_background, const SlParams* params, const SlTensorFormat* fmt, void* stream);
+SL_API int sl_normalize_hed_view_shrink(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, int shrink, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, const double* alpha_beta, int augment_background, const SlParams* params, const SlTensorFormat* fmt, const double* hed_sigma, const double* hed_bias, const int32_t* hed_applied, int skimage_mode, void* stream);
+SL_API int sl_reinhard_view_shrink(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, int shrink, const double* target_means, const double* target_stds, int mask_background, double luminosity_threshold, double* stats_out, void* workspace, size_t workspace_bytes, const SlTensorFormat* fmt, void* stream);
+SL_API int sl_luminosity_view_shrink(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, int shrink, double percentile, double* p_out, void* workspace, size_t workspace_bytes, const SlTensorFormat* fmt, void* stream);
+SL_API int sl_slab_view_shrink(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, int shrink, const double* state, int mode, int mask_background, double luminosity_threshold, const SlTensorFormat* fmt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

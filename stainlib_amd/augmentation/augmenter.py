@@ -131,7 +131,7 @@ class HedColorAugmenter(ColorAugmenterBase):
             n = int(tiles.shape[0])
             sigmas = [self._sigmas] * n if sigmas is None else sigmas
             biases = [self._biases] * n if biases is None else biases
-            engine._hed_call(self, sigmas, biases, tiles)
+            engine._hed_call(self, sigmas, biases, tiles, view)
             engine._check_tiles(tiles)
             x, windows, draw = engine.hed_stage(tiles, self, sigmas, biases, view, windows, {}, fmt=tensor_format, out=out)
             return x, draw.applied, windows
@@ -268,7 +268,7 @@ class StainAugmentor(object):
         engine._jitter_args(None, None, alpha_beta if alpha_beta is not None else np.empty((0, 4)), None, tensor_format, None)
         if view is not None or windows is not None:
             engine._view_call(view, windows, tiles, draw=False)
-        with_hed = engine._hed_call(hed, hed_sigmas, hed_biases, tiles)
+        with_hed = engine._hed_call(hed, hed_sigmas, hed_biases, tiles, view)
         n, h, w = engine._check_tiles(tiles)
         fit = (engine.macenko_fit if self._method == "macenko" else engine.vahadane_fit)(tiles)[:3]
         if alpha_beta is None:

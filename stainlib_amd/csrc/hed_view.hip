@@ -1,5 +1,5 @@
 // hed_view.hip -- C-ABI launchers of HED augmentation behind the apply pass: the byte sums of the image a route would write, and the
-// view pass with the HED stage (kernels: hed_view_kernels.hpp).  A translation unit of its own: view.hip compiles as before.
+// view pass with the HED stage and the view's box shrink (kernels: hed_view_kernels.hpp).  A translation unit of its own: view.hip compiles as before.
 #include "hed_view_kernels.hpp"
 #include "route_host.hpp"
 
@@ -32,14 +32,14 @@ extern "C" int sl_normalize_sums(const uint8_t* rgb, int n, int h, int w, const 
     return launch_status();
 }
 
-extern "C" int sl_normalize_hed_view(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask,
-                                     const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt,
-                                     const double* alpha_beta, int augment_background, const SlParams* params, const SlTensorFormat* fmt,
-                                     const double* hed_sigma, const double* hed_bias, const int32_t* hed_applied, int skimage_mode,
-                                     void* stream) {
+extern "C" int sl_normalize_hed_view_shrink(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows,
+                                            int d_mask, int shrink, const double* M_src, const double* maxC_src, const double* M_tgt,
+                                            const double* maxC_tgt, const double* alpha_beta, int augment_background,
+                                            const SlParams* params, const SlTensorFormat* fmt, const double* hed_sigma,
+                                            const double* hed_bias, const int32_t* hed_applied, int skimage_mode, void* stream) {
     if (const int rc = check_shape(rgb, out, n, h, w)) return rc;
     long npx = 0, npatch = 0;
-    if (const int rc = view_geometry(n, h, w, oh, ow, windows, d_mask, npx, npatch)) return rc;
+    if (const int rc = view_geometry(n, h, w, oh, ow, windows, d_mask, shrink, npx, npatch)) return rc;
     int mode = 0;
     if (const int rc = route_of(M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, augment_background, mode)) return rc;
     if (!params_ok(params)) return SL_ERR_BADARG;
@@ -56,9 +56,18 @@ extern "C" int sl_normalize_hed_view(const uint8_t* rgb, void* out, int n, int h
     with_format_or_u8(fmt, false, false, [&](auto dt, auto lay, auto, auto) {     // (no ALIGNED / WIDE variants: see view_kernels.hpp)
         with_mode(mode, [&](auto m) {
             hipLaunchKernelGGL((k_hed_view<decltype(dt)::value, decltype(lay)::value, decltype(m)::value>), dim3((unsigned)(n * npatch)),
-                               dim3(kWG), 0, s, rgb, out, h, w, oh, ow, (int)npx, (int)npatch, windows, d_mask, M_src, maxC_src, M_tgt, maxC_tgt,
-                               alpha_beta, p.lasso_lambda, ylimf, fmt ? tensor_k(*fmt) : TensorK{}, hv);
+                               dim3(kWG), 0, s, rgb, out, h, w, oh, ow, (int)npx, (int)npatch, windows, d_mask, shrink, M_src, maxC_src, M_tgt,
+                               maxC_tgt, alpha_beta, p.lasso_lambda, ylimf, fmt ? tensor_k(*fmt) : TensorK{}, hv);
         });
     });
     return launch_status();
+}
+
+extern "C" int sl_normalize_hed_view(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask,
+                                     const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt,
+                                     const double* alpha_beta, int augment_background, const SlParams* params, const SlTensorFormat* fmt,
+                                     const double* hed_sigma, const double* hed_bias, const int32_t* hed_applied, int skimage_mode,
+                                     void* stream) {
+    return sl_normalize_hed_view_shrink(rgb, out, n, h, w, oh, ow, windows, d_mask, 1, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta,
+                                        augment_background, params, fmt, hed_sigma, hed_bias, hed_applied, skimage_mode, stream);
 }

@@ -4,7 +4,8 @@
 //   k_sums        the read-only half: the exact byte sum of the image an apply-pass route WOULD write (HedColorAugmenter's cutoff test
 //                 needs the mean of its whole input before any pixel is transformed) -- 3 B/px read, one 64-bit atomic per workgroup
 //   k_sums_applied  k_hed_fixup's decision on those sums
-//   k_hed_view    k_view (view_kernels.hpp: view_body) with HedStage<1> between the truncation to bytes and the LDS write
+//   k_hed_view    k_view (view_kernels.hpp: view_body) with HedStage<1> between the truncation to bytes and the LDS write; the box
+//                 shrink of sl_normalize_hed_view_shrink is view_body's (the stage runs per SOURCE pixel, the write side averages)
 //
 // Definition (include/stainlib_hip.h, sl_normalize_sums / sl_normalize_hed_view): with full[t] the image sl_normalize_view defines by its
 // pointer pattern, sums[t] = the sum of the 3 h w bytes of full[t], and the view is taken of hed_applied[t] ? HED(full[t]) : full[t] with
@@ -76,11 +77,11 @@ struct HedStage<1> {
 
 template <int DT, int LAYOUT, int MODE>
 static __global__ __launch_bounds__(kWG) void k_hed_view(const uint8_t* __restrict__ rgb, void* __restrict__ out, int h, int w, int oh, int ow,
-                                                         int npx, int npatch, const int32_t* __restrict__ windows, int d_mask,
+                                                         int npx, int npatch, const int32_t* __restrict__ windows, int d_mask, int shrink,
                                                          const double* __restrict__ M_src, const double* __restrict__ maxC_src,
                                                          const double* M_tgt, const double* maxC_tgt, const double* __restrict__ alpha_beta,
                                                          double lam, float ylimf, TensorK fmt, HedViewArgs hv) {
-    view_body<DT, LAYOUT, MODE, 1>(rgb, out, h, w, oh, ow, npx, npatch, windows, d_mask, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, lam,
+    view_body<DT, LAYOUT, MODE, 1>(rgb, out, h, w, oh, ow, npx, npatch, windows, d_mask, shrink, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, lam,
                                    ylimf, fmt, &hv);
 }
 

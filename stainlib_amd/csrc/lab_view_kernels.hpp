@@ -17,6 +17,9 @@
 // Tables: (tabs, stride_bytes) -- per-tile calls pass the workspace's LabTileTabs array and sizeof(LabTileTabs), pooled calls the slide's
 // one LabMapTabs in the state and 0.  status (pooled; may be NULL): anything but SL_TILE_OK and every window comes from its source bytes,
 // as k_slab_map copies the tiles through.
+//
+// shrink (sl_reinhard_view_shrink and its siblings; block-uniform, 1 / 2 / 4): view_kernels.hpp's box shrink through the shared pieces --
+// a patch is 64 / shrink output pixels square, its source block still at most 64 x 64, and view_write averages; nothing of it is restated.
 #pragma once
 #include "../../include/stainlib_hip.h"        // SL_TILE_OK
 #include "lab_device.hpp"
@@ -32,7 +35,7 @@ constexpr int kLabViewRun = 4;                   // patches per workgroup and ta
 template <int DT, int LAYOUT, bool AB_TABLES>
 static __global__ __launch_bounds__(kWG) void k_lab_view(const uint8_t* __restrict__ rgb, void* __restrict__ out, int h, int w, int oh, int ow,
                                                          int npx, int npatch, int nrun, const int32_t* __restrict__ windows, int d_mask,
-                                                         const LabMapTabs* __restrict__ tabs, size_t stride_bytes,
+                                                         int shrink, const LabMapTabs* __restrict__ tabs, size_t stride_bytes,
                                                          const double* __restrict__ status, int mask_background, double thr,
                                                          double* __restrict__ p_out, TensorK fmt) {
     static_assert(kWG == 256 && kViewB == 64, "16 lanes x 4 pixels per row, 16 rows per pass, 4 passes; one table entry per thread");
@@ -61,8 +64,9 @@ static __global__ __launch_bounds__(kWG) void k_lab_view(const uint8_t* __restri
     const LabBackground bg = lab_background();
     const bool mask_bg = mask_background != 0;
 
-    const ViewTile vt(windows, tile, d_mask, h, w, oh, ow);
-    ViewPatch g(vt, p0, npx, oh, ow);
+    const int s = __builtin_amdgcn_readfirstlane(shrink);
+    const ViewTile vt(windows, tile, d_mask, h, w, oh, ow, s);
+    ViewPatch g(vt, p0, npx, oh, ow, s);
     Chunk in[4];
     view_read(g, src, nbytes, w, lr, lc, in);
     __syncthreads();                                                      // the tables
@@ -77,11 +81,11 @@ static __global__ __launch_bounds__(kWG) void k_lab_view(const uint8_t* __restri
         }
         const ViewPatch cur = g;
         if (p + 1 < p1) {                                                 // the next patch's loads, in flight across this one's write side
-            g = ViewPatch(vt, p + 1, npx, oh, ow);
+            g = ViewPatch(vt, p + 1, npx, oh, ow, s);
             view_read(g, src, nbytes, w, lr, lc, in);
         }
         __syncthreads();
-        view_write<DT, LAYOUT>(cur, s_px, out, tile, oh, ow, fmt, lr, lc);
+        view_write<DT, LAYOUT>(cur, s_px, out, tile, oh, ow, fmt, lr, lc, s);
         __syncthreads();                                                  // s_px is the next patch's
     }
 }

@@ -31,14 +31,16 @@ inline void with_mode(int mode, F&& f) {
     else f(std::integral_constant<int, kViewJitAll>{});
 }
 
-// The geometry of a view of n tiles of h x w (check_shape has accepted them): SL_OK and the patches per output row and per tile, or
-// SL_ERR_BADARG.
-inline int view_geometry(int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, long& npx, long& npatch) {
-    if (!windows || oh < 1 || ow < 1 || oh > h || ow > w) return SL_ERR_BADARG;
+// The geometry of a view of n tiles of h x w (check_shape has accepted them) under the shrink s: SL_OK and the patches (kViewB / s output
+// pixels square) per output row and per tile, or SL_ERR_BADARG.  The window is s times the output.
+inline int view_geometry(int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, int s, long& npx, long& npatch) {
+    if (s != 1 && s != 2 && s != 4) return SL_ERR_BADARG;
+    if (!windows || oh < 1 || ow < 1 || (long)s * oh > h || (long)s * ow > w) return SL_ERR_BADARG;
     if (d_mask < 0 || d_mask > 7) return SL_ERR_BADARG;
-    if ((d_mask & 1) && (ow > h || oh > w)) return SL_ERR_BADARG;               // the transposed window must fit too
-    npx = (ow + kViewB - 1) / kViewB;
-    npatch = npx * ((oh + kViewB - 1) / kViewB);
+    if ((d_mask & 1) && ((long)s * ow > h || (long)s * oh > w)) return SL_ERR_BADARG;   // the transposed window must fit too
+    const int B = kViewB / s;
+    npx = (ow + B - 1) / B;
+    npatch = npx * ((oh + B - 1) / B);
     if ((long)n * npatch > 0x7fffffffL) return SL_ERR_BADARG;                    // one workgroup per (tile, patch)
     return SL_OK;
 }

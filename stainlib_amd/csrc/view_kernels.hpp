@@ -29,6 +29,21 @@
 // stride is 4 pitches = 4 banks, the same picture: 2-way, where an even pitch would make it 16-way.  Chosen: pitch 65 with this plain
 // 4-pixels-per-lane assignment; the remaining 2-way conflict on 8 of the ~20 LDS instructions of a chunk could be rotated away
 // (instruction s takes pixel (s + rot) & 3, rot per lane) at 16 selects per chunk -- not done, the pass is not LDS bound.
+//
+// Box shrink (sl_normalize_view_shrink): with s = 2 or 4 an output pixel is the rounded mean of an s x s box of `full`.  The
+// 64 x 64 SOURCE block, the read side and the LDS stage stay as they are; one patch becomes 64 / s OUTPUT pixels square, ViewPatch maps it
+// to its s nu x s nv source block with the affine map at strides s ai, s aj, and the write side gathers s s LDS dwords per output pixel
+// (view_box: the packed dword as two words of 16-bit lanes, sums <= 4080, no carry), rounds, repacks and goes on through cvt_chunk and the
+// stores as before.  Lanes: 4 adjacent output pixels each, 16 / s per output row: 256 busy lanes at s = 2, 64 (the first wave) at s = 4.
+// Where s lives: a block-uniform RUN-TIME kernel argument for the geometry (a few scalar multiplies), and a compile-time S for the write
+// side alone, picked by one scalar branch (view_write).  A template parameter of the kernels would triple the 32 + 32 + 16 instantiations
+// of k_view, k_hed_view and k_lab_view -- each a copy of the per-source-pixel arithmetic, which does not depend on s -- and their build
+// time; this way a code object grows by two write sides.  S = 1 is the write side as it was, statement for statement.
+// Banks of the strided reads (pitch 65: bank (r + x) % 32; a 32-lane half of an instruction reads one (a, b) of the box of one p):
+//   s = 2  8 lanes per output row, 4 rows per half: the lane strides are 8 and 2 banks (row-wise: 8 columns, 2 rows; column-wise the
+//          other way round, 8 pitches = 8 banks) -> lanes c and c + 4 of a row share a bank, the rows fall between: 2-way, as at s = 1.
+//   s = 4  4 lanes per output row, 8 rows per half: strides 16 and 4 banks -> bank 4 ((r + 4 c) % 8): 32 lanes on 8 banks, 4-way.  One
+//          wave issues 64 such reads per patch, behind 4096 source pixels of arithmetic: left as it is.
 #pragma once
 #include "jitter_kernels.hpp"        // JitterK, the {gamma, od32} table; tensor_kernels.hpp and apply_pass.hpp through it
 
@@ -109,35 +124,39 @@ __device__ __forceinline__ void store_view4(typename Elem<DT>::type* base, size_
 
 // ---- the pieces of a view pass: geometry, read side, LDS stage, write side.  view_body below is their sequence for one patch per
 // ---- workgroup; k_lab_view (lab_view_kernels.hpp) loops them over a run of patches behind one table fill ------------------------------
-// The view of one tile (block-uniform): the dihedral code as a transposition and two reversals, and the clamped window.
+// The view of one tile (block-uniform): the dihedral code as a transposition and two reversals, and the clamped window.  s: the shrink
+// (1, 2 or 4; block-uniform, a kernel argument) -- the window is wh x ww BOXES of s x s source pixels at the pixel (y0, x0).
 struct ViewTile {
     bool tr, ry, rx;
     int wh, ww, y0, x0;
-    __device__ __forceinline__ ViewTile(const int32_t* windows, int tile, int d_mask, int h, int w, int oh, int ow) {
+    __device__ __forceinline__ ViewTile(const int32_t* windows, int tile, int d_mask, int h, int w, int oh, int ow, int s) {
         const int d = __builtin_amdgcn_readfirstlane(windows[3 * (size_t)tile + 2]) & d_mask;
         const int k = d & 3;
         tr = k & 1; ry = (k >> 1) & 1; rx = ((k >> 1) ^ k ^ (d >> 2)) & 1;
-        wh = tr ? ow : oh; ww = tr ? oh : ow;
-        y0 = max(0, min(__builtin_amdgcn_readfirstlane(windows[3 * (size_t)tile + 0]), h - wh));
-        x0 = max(0, min(__builtin_amdgcn_readfirstlane(windows[3 * (size_t)tile + 1]), w - ww));
+        wh = tr ? ow : oh; ww = tr ? oh : ow;                                     // the window, in boxes of s x s source pixels
+        y0 = max(0, min(__builtin_amdgcn_readfirstlane(windows[3 * (size_t)tile + 0]), h - s * wh));
+        x0 = max(0, min(__builtin_amdgcn_readfirstlane(windows[3 * (size_t)tile + 1]), w - s * ww));
     }
 };
-// One patch of the tile's output (i0, j0; bh x bw pixels), the source block it comes from (ys, xs; nu rows of nv pixels) and the affine
-// map from output to LDS pixel: output pixel (il, jl) of the patch is LDS pixel a0 + il ai + jl aj.
+// One patch of the tile's output (i0, j0; bh x bw pixels, at most kViewB / s square), the source block it comes from (ys, xs; nu rows of
+// nv pixels, s times the patch) and the affine map from output to LDS pixel: the s x s box of output pixel (il, jl) of the patch has its
+// first pixel (lowest row and column) at LDS pixel a0 + il ai + jl aj -- at s = 1 the pixel itself.
 struct ViewPatch {
     int i0, j0, bh, bw, nu, nv, ys, xs, a0, ai, aj;
-    __device__ __forceinline__ ViewPatch(const ViewTile& t, int patch, int npx, int oh, int ow) {
-        constexpr int B = kViewB, PITCH = kViewPitch;
+    __device__ __forceinline__ ViewPatch(const ViewTile& t, int patch, int npx, int oh, int ow, int s) {
+        constexpr int PITCH = kViewPitch;
+        const int B = kViewB >> (s >> 1);                                         // kViewB / s for s = 1, 2, 4, without a division
         const bool tr = t.tr, ry = t.ry, rx = t.rx;
         i0 = (patch / npx) * B; j0 = (patch % npx) * B;                           // the patch, in output pixels
         bh = min(B, oh - i0); bw = min(B, ow - j0);
         const int u0 = tr ? j0 : i0;                                              // its rows and columns in the (flipped, turned) window
-        nu = tr ? bw : bh;
+        const int nub = tr ? bw : bh;                                             // (in boxes)
         const int v0 = tr ? i0 : j0;
-        nv = tr ? bh : bw;
-        ys = t.y0 + (ry ? t.wh - u0 - nu : u0); xs = t.x0 + (rx ? t.ww - v0 - nv : v0);   // the source block: nu rows of nv pixels
-        const int su = ry ? -PITCH : PITCH, sv = rx ? -1 : 1;
-        a0 = (ry ? (nu - 1) * PITCH : 0) + (rx ? nv - 1 : 0);
+        const int nvb = tr ? bh : bw;
+        nu = s * nub; nv = s * nvb;
+        ys = t.y0 + s * (ry ? t.wh - u0 - nub : u0); xs = t.x0 + s * (rx ? t.ww - v0 - nvb : v0);   // the source block: nu rows of nv pixels
+        const int su = ry ? -s * PITCH : s * PITCH, sv = rx ? -s : s;
+        a0 = (ry ? (nu - s) * PITCH : 0) + (rx ? nv - s : 0);
         ai = tr ? sv : su; aj = tr ? su : sv;
     }
 };
@@ -172,24 +191,55 @@ __device__ __forceinline__ void view_stage(const ViewPatch& g, uint32_t* s_px, i
     }
 }
 
-// ---- write side: output rows, 4 adjacent pixels per lane (behind a barrier after the stage)
-template <int DT, int LAYOUT>
-__device__ __forceinline__ void view_write(const ViewPatch& g, const uint32_t* s_px, void* out, int tile, int oh, int ow, TensorK fmt,
-                                           int lr, int lc) {
+// The rounded mean of the S x S box of packed pixels whose first pixel is s_px[at] (S = 2, 4): the packed dword as two words of 16-bit
+// lanes -- r and b in px & 0xff00ff, g in (px >> 8) & 0xff --, whose sums (at most 16 x 255 = 4080, + S S / 2) cannot carry into the next
+// lane; (sum + S S / 2) >> 2 log2 S is round half up, and the bits the shift moves across a lane's edge are masked off.
+template <int S>
+__device__ __forceinline__ uint32_t view_box(const uint32_t* s_px, int at) {
+    static_assert(S == 2 || S == 4, "a 2 x 2 or 4 x 4 box");
+    constexpr int SH = S == 2 ? 2 : 4;                       // log2 of the pixels of a box
+    constexpr uint32_t HALF = (uint32_t)(S * S / 2);
+    uint32_t rb = HALF | (HALF << 16), gg = HALF;
+#pragma unroll
+    for (int a = 0; a < S; ++a)
+#pragma unroll
+        for (int b = 0; b < S; ++b) {
+            const uint32_t px = s_px[at + a * kViewPitch + b];
+            rb += px & 0x00ff00ffu;
+            gg += (px >> 8) & 0xffu;
+        }
+    return ((rb >> SH) & 0x00ff00ffu) | ((gg >> SH) << 8);
+}
+
+// ---- write side: output rows, 4 adjacent pixels per lane (behind a barrier after the stage).  S: the shrink, a compile-time value HERE
+// ---- only (view_write below picks it by the block-uniform run-time one); S = 1 is the write side as it was, statement for statement.
+// Lanes: 16 / S per output row (the patch is 64 / S pixels wide), so 16 S rows per pass -- 4 passes at S = 1, ONE at S = 2 (32 rows, every
+// lane busy) and at S = 4 (16 rows: the first wave only; accepted, the pass is bound by the arithmetic in front of the stage).
+template <int DT, int LAYOUT, int S>
+__device__ __forceinline__ void view_write_s(const ViewPatch& g, const uint32_t* s_px, void* out, int tile, int oh, int ow, TensorK fmt,
+                                             int lr16, int lc16) {
     constexpr bool TENSOR = DT != kDtU8;
     constexpr int SDT = TENSOR ? DT : kDtF32;
+    constexpr int LPR = 16 / S, NPASS = S == 1 ? 4 : 1;      // lanes per output row, passes
     typedef typename Elem<SDT>::type T;
     const int i0 = g.i0, j0 = g.j0, bh = g.bh, bw = g.bw, a0 = g.a0, ai = g.ai, aj = g.aj;
     const TensorK F = tensor_consts(fmt);
     const size_t PO = (size_t)oh * ow;
+    const int lr = S == 1 ? lr16 : (16 * lr16 + lc16) / LPR, lc = S == 1 ? lc16 : lc16 % LPR;
     const int jl = 4 * lc;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
+    for (int q = 0; q < NPASS; ++q) {
         const int il = 16 * q + lr;
         const int row = a0 + min(il, bh - 1) * ai;
         uint32_t px[4];
+        if constexpr (S == 1) {
 #pragma unroll
-        for (int p = 0; p < 4; ++p) px[p] = s_px[row + min(jl + p, bw - 1) * aj];
+            for (int p = 0; p < 4; ++p) px[p] = s_px[row + min(jl + p, bw - 1) * aj];
+        } else {
+            if (il >= bh || jl >= bw) continue;              // (whole waves at S = 4; nothing below has a barrier)
+#pragma unroll
+            for (int p = 0; p < 4; ++p) px[p] = view_box<S>(s_px, row + min(jl + p, bw - 1) * aj);
+        }
         Chunk o;
         o.w0 = px[0] | (px[1] << 24);
         o.w1 = (px[1] >> 8) | (px[2] << 16);
@@ -215,6 +265,15 @@ __device__ __forceinline__ void view_write(const ViewPatch& g, const uint32_t* s
     }
 }
 
+// the write side of a patch under the run-time shrink s (block-uniform: one scalar branch)
+template <int DT, int LAYOUT>
+__device__ __forceinline__ void view_write(const ViewPatch& g, const uint32_t* s_px, void* out, int tile, int oh, int ow, TensorK fmt,
+                                           int lr, int lc, int s) {
+    if (s == 1) view_write_s<DT, LAYOUT, 1>(g, s_px, out, tile, oh, ow, fmt, lr, lc);
+    else if (s == 2) view_write_s<DT, LAYOUT, 2>(g, s_px, out, tile, oh, ow, fmt, lr, lc);
+    else view_write_s<DT, LAYOUT, 4>(g, s_px, out, tile, oh, ow, fmt, lr, lc);
+}
+
 // A further stage between the truncation to bytes and the LDS write, on the four packed pixels `stage` holds.  HED = 0: none -- the
 // primary template is empty and k_view's code is what it was without it (tools/isa_diff.py); HED = 1: the HED augmentation of
 // sl_normalize_hed_view (hed_view_kernels.hpp specialises it; its arguments arrive in HedViewArgs).
@@ -232,7 +291,7 @@ struct HedStage {
 // DT: kDtU8 or a tensor type; LAYOUT: tensor only; MODE: kView*; HED: the stage above.  npx: patches per output row, npatch: per tile.
 template <int DT, int LAYOUT, int MODE, int HED>
 __device__ __forceinline__ void view_body(const uint8_t* rgb, void* out, int h, int w, int oh, int ow,
-                                          int npx, int npatch, const int32_t* windows, int d_mask,
+                                          int npx, int npatch, const int32_t* windows, int d_mask, int shrink,
                                           const double* M_src, const double* maxC_src,
                                           const double* M_tgt, const double* maxC_tgt, const double* alpha_beta,
                                           double lam, float ylimf, TensorK fmt, const HedViewArgs* hv) {
@@ -251,8 +310,9 @@ __device__ __forceinline__ void view_body(const uint8_t* rgb, void* out, int h, 
     hed.init(tid, tile, hv);
 
     // the view of this tile (block-uniform), the source block of this patch and the four chunks of this lane
-    const ViewTile vt(windows, tile, d_mask, h, w, oh, ow);
-    const ViewPatch g(vt, patch, npx, oh, ow);
+    const int s = __builtin_amdgcn_readfirstlane(shrink);
+    const ViewTile vt(windows, tile, d_mask, h, w, oh, ow, s);
+    const ViewPatch g(vt, patch, npx, oh, ow, s);
     Chunk in[4];
     view_read(g, src, nbytes, w, lr, lc, in);
     auto stage = [&](auto compute) {
@@ -332,16 +392,16 @@ __device__ __forceinline__ void view_body(const uint8_t* rgb, void* out, int h, 
     }
     __syncthreads();
 
-    view_write<DT, LAYOUT>(g, s_px, out, tile, oh, ow, fmt, lr, lc);
+    view_write<DT, LAYOUT>(g, s_px, out, tile, oh, ow, fmt, lr, lc, s);
 }
 
 template <int DT, int LAYOUT, int MODE>
 static __global__ __launch_bounds__(kWG) void k_view(const uint8_t* __restrict__ rgb, void* __restrict__ out, int h, int w, int oh, int ow,
-                                                     int npx, int npatch, const int32_t* __restrict__ windows, int d_mask,
+                                                     int npx, int npatch, const int32_t* __restrict__ windows, int d_mask, int shrink,
                                                      const double* __restrict__ M_src, const double* __restrict__ maxC_src,
                                                      const double* M_tgt, const double* maxC_tgt, const double* __restrict__ alpha_beta,
                                                      double lam, float ylimf, TensorK fmt) {
-    view_body<DT, LAYOUT, MODE, 0>(rgb, out, h, w, oh, ow, npx, npatch, windows, d_mask, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, lam,
+    view_body<DT, LAYOUT, MODE, 0>(rgb, out, h, w, oh, ow, npx, npatch, windows, d_mask, shrink, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, lam,
                                    ylimf, fmt, nullptr);
 }
 

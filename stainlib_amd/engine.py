@@ -369,9 +369,19 @@ def normalize_jitter(rgb, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, augment_
 
 # ---- crop / flip / rot90 in the apply pass (sl_normalize_view; see include/stainlib_hip.h and stainlib_amd/tile_view.py) -------------------
 
-def _view_windows(windows, n, h, w, oh, ow, d_mask):
+def _call_view(name, shrink, head, *tail):
+    """The C call of a view pass: `name` as it is at shrink = 1, else its `_shrink` export, which takes shrink behind d_mask (the last
+    of head)."""
+    if shrink == 1:
+        _call(name, *head, *tail)
+    else:
+        _call(name + "_shrink", *head, int(shrink), *tail)
+
+
+def _view_windows(windows, n, h, w, oh, ow, d_mask, shrink=1):
     """The (n, 3) int32 windows of a normalize_view call (no device needed).  numpy / CPU windows are range-checked here (ValueError) and
-    come back as numpy; device windows are taken as they are -- the kernel masks the code and clamps the corner, nothing is read back."""
+    come back as numpy; device windows are taken as they are -- the kernel masks the code and clamps the corner, nothing is read back.
+    shrink: the window is shrink times the (oh, ow) output (TileView(shrink=))."""
     import numpy as np
     if windows is None:
         raise ValueError("windows must hold (y0, x0, d) per tile: an (N, 3) int32 array (TileView.draw)")
@@ -393,7 +403,7 @@ def _view_windows(windows, n, h, w, oh, ow, d_mask):
     if bad.any():
         raise ValueError(f"windows: tile {int(np.argmax(bad))} has the code {int(d[np.argmax(bad)])}, outside d_mask = {d_mask}")
     odd = (d & 1) != 0
-    wh, ww = np.where(odd, ow, oh), np.where(odd, oh, ow)
+    wh, ww = int(shrink) * np.where(odd, ow, oh), int(shrink) * np.where(odd, oh, ow)
     bad = (win[:, 0] < 0) | (win[:, 0] > h - wh) | (win[:, 1] < 0) | (win[:, 1] > w - ww)
     if bad.any():
         t = int(np.argmax(bad))
@@ -402,7 +412,7 @@ def _view_windows(windows, n, h, w, oh, ow, d_mask):
     return np.ascontiguousarray(win.astype(np.int32))
 
 
-def _view_prepare(rgb, windows, size, d_mask, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, params, fmt, out, before_device=None):
+def _view_prepare(rgb, windows, size, d_mask, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, params, fmt, out, before_device=None, shrink=1):
     """The checks of normalize_view (ValueError, in its order, nothing on the device before they pass; before_device(n): a caller's own
     checks at the end of them) and its arguments on the device -> (n, h, w, oh, ow, windows, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta,
     SlTensorFormat or None, out)."""
@@ -411,8 +421,8 @@ def _view_prepare(rgb, windows, size, d_mask, M_src, maxC_src, M_tgt, maxC_tgt, 
     if not (isinstance(rgb, torch.Tensor) and rgb.dim() == 4 and rgb.shape[-1] == 3):
         raise ValueError("expected a contiguous CUDA uint8 tensor of shape (N, H, W, 3)")
     n, h, w = (int(v) for v in rgb.shape[:3])
-    oh, ow = check_size(size, h, w, d_mask)
-    win = _view_windows(windows, n, h, w, oh, ow, d_mask)
+    oh, ow = check_size(size, h, w, d_mask, shrink)
+    win = _view_windows(windows, n, h, w, oh, ow, d_mask, shrink)
     _route_check(M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, params, n)
     if fmt is not None and not isinstance(fmt, TensorFormat):
         raise ValueError("fmt must be a stainlib_amd.TensorFormat or None (the uint8 image)")
@@ -429,7 +439,7 @@ def _view_prepare(rgb, windows, size, d_mask, M_src, maxC_src, M_tgt, maxC_tgt, 
 
 
 def normalize_view(rgb, windows, size, d_mask=7, M_src=None, maxC_src=None, M_tgt=None, maxC_tgt=None, alpha_beta=None,
-                   augment_background=False, params=None, fmt=None, out=None):
+                   augment_background=False, params=None, fmt=None, out=None, shrink=1):
     """A crop, flip and quarter turn per tile INSIDE the apply pass (sl_normalize_view): per tile the window windows[t] = (y0, x0, d) of
     the image that normalize_jitter (alpha_beta given), normalize_apply (M_src given) or nothing (M_src=None: the tiles' own bytes)
     writes, flipped along the width when d & 4 and then turned d & 3 quarter turns counter-clockwise -- torch.rot90(torch.flip(
@@ -438,11 +448,14 @@ def normalize_view(rgb, windows, size, d_mask=7, M_src=None, maxC_src=None, M_tg
     d_mask: the bits of d that count (7: everything; 6: no quarter turns -- the size need not fit transposed).
     windows: (N, 3) int32 (TileView.draw).  numpy or CPU tensor: range-checked, ValueError.  Device tensor: taken as it is, the kernel
     clamps every window into the tile; nothing is synchronised.
-    fmt: a stainlib_amd.TensorFormat -> the (N,3,oh,ow) tensor, else (N,oh,ow,3) uint8.  The statistics are the WHOLE tile's."""
+    fmt: a stainlib_amd.TensorFormat -> the (N,3,oh,ow) tensor, else (N,oh,ow,3) uint8.  The statistics are the WHOLE tile's.
+    shrink: 1, 2 or 4 (sl_normalize_view_shrink) -- the window is shrink times (oh, ow) and every output pixel the rounded mean of a
+    shrink x shrink box of `full`, per channel (sum + shrink^2 / 2) >> (2 log2 shrink), boxes counted from the window's corner; the
+    flip and the turn as before (they commute with it).  size=None is then (h // shrink, w // shrink)."""
     n, h, w, oh, ow, win, M_src, maxC_src, M_tgt, maxC_tgt, ab, f, out = _view_prepare(
-        rgb, windows, size, d_mask, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, params, fmt, out)
-    _call("sl_normalize_view", _ptr(rgb), _ptr(out), n, h, w, oh, ow, _ptr(win), int(d_mask), _ptr(M_src), _ptr(maxC_src), _ptr(M_tgt),
-          _ptr(maxC_tgt), _ptr(ab), 1 if augment_background else 0, _byref(params), _byref(f))
+        rgb, windows, size, d_mask, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, params, fmt, out, shrink=shrink)
+    _call_view("sl_normalize_view", shrink, (_ptr(rgb), _ptr(out), n, h, w, oh, ow, _ptr(win), int(d_mask)), _ptr(M_src), _ptr(maxC_src),
+               _ptr(M_tgt), _ptr(maxC_tgt), _ptr(ab), 1 if augment_background else 0, _byref(params), _byref(f))
     return out
 
 
@@ -506,22 +519,24 @@ def _hed_rows(x, what):
 
 
 def normalize_hed_view(rgb, windows, size, d_mask, hed_sigma, hed_bias, hed_applied, skimage_mode=0, M_src=None, maxC_src=None, M_tgt=None,
-                       maxC_tgt=None, alpha_beta=None, augment_background=False, params=None, fmt=None, out=None):
+                       maxC_tgt=None, alpha_beta=None, augment_background=False, params=None, fmt=None, out=None, shrink=1):
     """normalize_view of hed_applied[t] ? HED(full[t]) : full[t] in ONE pass (sl_normalize_hed_view): `full` is normalize_view's (the
     route arguments are the same), HED(.) is hed_augment with the tile's hed_sigma / hed_bias ((N, 3) each), skimage_mode and a cutoff that
     never fails -- bit for bit hed_augment then normalize_view of the result, without a pixel outside the window being touched.
     hed_applied: (N,) int32, the decision per tile (normalize_sums gives it).
-    skimage_mode 0 ("0.18", the pinned one) runs in the kernel; the other three go through that chain (same bits, two more passes)."""
+    skimage_mode 0 ("0.18", the pinned one) runs in the kernel; the other three go through that chain (same bits, two more passes).
+    shrink: normalize_view's, on that image (sl_normalize_hed_view_shrink); skimage_mode 0 only -- the chain does not know it."""
     def hed_checks(n):
         for x, what in ((hed_sigma, "hed_sigma"), (hed_bias, "hed_bias")):
             if _hed_rows(x, what) != n:
                 raise ValueError(f"{what} must have one row per tile ({n})")
         if skimage_mode not in (_ffi.HED_SKIMAGE_018, _ffi.HED_SKIMAGE_019, _ffi.HED_SKIMAGE_017, _ffi.HED_EXPERIMENTAL_LOG10):
             raise ValueError("skimage_mode must be one of the HED_* modes (0..3)")
+        _hed_shrink_ok(skimage_mode, shrink)
         if hed_applied is None:
             raise ValueError("hed_applied must hold the decision per tile: (N,) int32 (normalize_sums)")
     n, h, w, oh, ow, win, M_src, maxC_src, M_tgt, maxC_tgt, ab, f, out = _view_prepare(
-        rgb, windows, size, d_mask, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, params, fmt, out, before_device=hed_checks)
+        rgb, windows, size, d_mask, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, params, fmt, out, before_device=hed_checks, shrink=shrink)
     dev = rgb.device
     sigma = _f64(hed_sigma, (n, 3), dev)
     bias = _f64(hed_bias, (n, 3), dev)
@@ -531,15 +546,24 @@ def normalize_hed_view(rgb, windows, size, d_mask, hed_sigma, hed_bias, hed_appl
         aug, _ = hed_augment(full, sigma, bias, cutoff=(-float("inf"), float("inf")), skimage_mode=skimage_mode)
         img = torch.where((applied != 0).view(n, 1, 1, 1), aug, full)
         return normalize_view(img, win, size, d_mask, fmt=fmt, out=out)
-    _call("sl_normalize_hed_view", _ptr(rgb), _ptr(out), n, h, w, oh, ow, _ptr(win), int(d_mask), _ptr(M_src), _ptr(maxC_src), _ptr(M_tgt),
-          _ptr(maxC_tgt), _ptr(ab), 1 if augment_background else 0, _byref(params), _byref(f), _ptr(sigma), _ptr(bias), _ptr(applied),
-          int(skimage_mode))
+    _call_view("sl_normalize_hed_view", shrink, (_ptr(rgb), _ptr(out), n, h, w, oh, ow, _ptr(win), int(d_mask)), _ptr(M_src), _ptr(maxC_src),
+               _ptr(M_tgt), _ptr(maxC_tgt), _ptr(ab), 1 if augment_background else 0, _byref(params), _byref(f), _ptr(sigma), _ptr(bias),
+               _ptr(applied), int(skimage_mode))
     return out
 
 
-def _hed_call(hed, hed_sigmas, hed_biases, tiles):
+def _hed_shrink_ok(skimage_mode, shrink):
+    """ValueError for a HED skimage_mode that goes through the chain (every one but HED_SKIMAGE_018) under a view with a shrink: the
+    chain does not know it."""
+    if shrink != 1 and skimage_mode != _ffi.HED_SKIMAGE_018:
+        names = {_ffi.HED_SKIMAGE_019: "0.19", _ffi.HED_SKIMAGE_017: "0.17", _ffi.HED_EXPERIMENTAL_LOG10: "experimental_log10"}
+        raise ValueError(f"skimage_mode {names.get(skimage_mode, skimage_mode)!r} ({skimage_mode}) goes through the hed_augment chain, which has "
+                         f"no shrink: a view with shrink={shrink} needs skimage_mode '0.18' (0)")
+
+
+def _hed_call(hed, hed_sigmas, hed_biases, tiles, view=None):
     """The hed= / hed_sigmas= / hed_biases= arguments of a batch method, checked without a device (ValueError).  True when the call has a
-    HED stage."""
+    HED stage.  view: the call's view= (checked elsewhere) -- its shrink must be one the HED mode knows (_hed_shrink_ok)."""
     from .augmentation.augmenter import HedColorAugmenter
     if hed is None:
         if hed_sigmas is not None or hed_biases is not None:
@@ -555,6 +579,7 @@ def _hed_call(hed, hed_sigmas, hed_biases, tiles):
     for x, what in ((hed_sigmas, "hed_sigmas"), (hed_biases, "hed_biases")):
         if x is not None and _hed_rows(x, what) != n:
             raise ValueError(f"{what} must have one row per tile ({n})")
+    _hed_shrink_ok(hed._skimage_mode, getattr(view, "shrink", 1))
     return True
 
 
@@ -604,18 +629,19 @@ def hed_stage(tiles, hed, hed_sigmas, hed_biases, view, windows, route, fmt=None
     if hed_sigmas is None:
         hed_sigmas, hed_biases = hed.randomize_batch(n)
     if view is not None:
-        size, d_mask, windows = _view_call(view, windows, tiles)
+        size, d_mask, windows, shrink = _view_call(view, windows, tiles)
         win = windows
     else:
-        size, d_mask, windows, win = None, 0, None, np.zeros((n, 3), dtype=np.int32)
+        size, d_mask, windows, win, shrink = None, 0, None, np.zeros((n, 3), dtype=np.int32), 1
     applied = hed_decide(tiles, hed._cutoff_range, **route)
-    x = normalize_hed_view(tiles, win, size, d_mask, hed_sigmas, hed_biases, applied, hed._skimage_mode, fmt=fmt, out=out, **route)
+    x = normalize_hed_view(tiles, win, size, d_mask, hed_sigmas, hed_biases, applied, hed._skimage_mode, fmt=fmt, out=out, shrink=shrink,
+                           **route)
     return x, windows, HedDraw(hed_sigmas, hed_biases, applied)
 
 
 def _view_call(view, windows, tiles, draw=True):
-    """(size, d_mask, windows) of the view= / windows= pair of a batch method, checked without a device (ValueError): the windows as
-    given, or drawn (TileView.draw; draw=False: left None for a later call)."""
+    """(size, d_mask, windows, shrink) of the view= / windows= pair of a batch method, checked without a device (ValueError): the windows
+    as given, or drawn (TileView.draw; draw=False: left None for a later call)."""
     from .tile_view import TileView
     if not isinstance(view, TileView):
         raise ValueError("view must be a stainlib_amd.TileView" + (" (windows= goes with view=)" if view is None else ""))
@@ -624,10 +650,10 @@ def _view_call(view, windows, tiles, draw=True):
     n, h, w = (int(v) for v in tiles.shape[:3])
     oh, ow = view.out_size(h, w)
     if windows is not None:
-        _view_windows(windows, n, h, w, oh, ow, view.d_mask)
+        _view_windows(windows, n, h, w, oh, ow, view.d_mask, view.shrink)
     elif draw:
         windows = view.draw(n, h, w)
-    return view.size, view.d_mask, windows
+    return view.size, view.d_mask, windows, view.shrink
 
 
 def route_stage(tiles, fit, route, fmt=None, out=None, view=None, windows=None, hed=None):
@@ -642,8 +668,8 @@ def route_stage(tiles, fit, route, fmt=None, out=None, view=None, windows=None, 
         x, windows, draw = hed_stage(tiles, *hed, view, windows, route, fmt=fmt, out=out)
         return (x, M, maxC, status) + ((windows,) if view is not None else ()) + (draw,)
     if view is not None:
-        size, d_mask, windows = _view_call(view, windows, tiles)
-        return normalize_view(tiles, windows, size, d_mask, fmt=fmt, out=out, **route), M, maxC, status, windows
+        size, d_mask, windows, shrink = _view_call(view, windows, tiles)
+        return normalize_view(tiles, windows, size, d_mask, fmt=fmt, out=out, shrink=shrink, **route), M, maxC, status, windows
     return normalize_jitter(tiles, fmt=fmt, out=out, **route), M, maxC, status
 
 
@@ -869,20 +895,20 @@ def luminosity_standardize(rgb, percentile=95, out=None, ws=None):
 
 
 # ---- the Lab family behind the view (sl_reinhard_view, sl_luminosity_view, sl_slab_view; see include/stainlib_hip.h) ------------------
-def _lab_view_prepare(rgb, windows, size, d_mask, fmt, out, view=None, before_device=None):
+def _lab_view_prepare(rgb, windows, size, d_mask, fmt, out, view=None, before_device=None, shrink=1):
     """_view_prepare for a Lab map: its checks in its order (size, windows, format, before_device(n), then _check_tiles and out;
-    ValueError) -> (n, h, w, oh, ow, d_mask, windows on the device, SlTensorFormat or None, out, windows as given or drawn).
-    view: a TileView (a batch method's view=) -- size and d_mask are its own (_view_call), and windows=None means view.draw(n, h, w)
+    ValueError) -> (n, h, w, oh, ow, d_mask, windows on the device, SlTensorFormat or None, out, windows as given or drawn, shrink).
+    view: a TileView (a batch method's view=) -- size, d_mask and shrink are its own (_view_call), and windows=None means view.draw(n, h, w)
     from the global numpy stream, drawn behind every check: a refused call draws nothing, and nothing goes to the device before it."""
     from .tensor_format import TensorFormat
     from .tile_view import check_size
     if view is not None:
-        size, d_mask, _ = _view_call(view, windows, rgb, draw=False)
+        size, d_mask, _, shrink = _view_call(view, windows, rgb, draw=False)
     if not (isinstance(rgb, torch.Tensor) and rgb.dim() == 4 and rgb.shape[-1] == 3):
         raise ValueError("expected a contiguous CUDA uint8 tensor of shape (N, H, W, 3)")
     n, h, w = (int(v) for v in rgb.shape[:3])
-    oh, ow = check_size(size, h, w, d_mask)
-    win = _view_windows(windows, n, h, w, oh, ow, d_mask) if (windows is not None or view is None) else None
+    oh, ow = check_size(size, h, w, d_mask, shrink)
+    win = _view_windows(windows, n, h, w, oh, ow, d_mask, shrink) if (windows is not None or view is None) else None
     if fmt is not None and not isinstance(fmt, TensorFormat):
         raise ValueError("fmt must be a stainlib_amd.TensorFormat or None (the uint8 image)")
     if before_device is not None:
@@ -896,7 +922,7 @@ def _lab_view_prepare(rgb, windows, size, d_mask, fmt, out, view=None, before_de
         windows = win = view.draw(n, h, w)
     if not isinstance(win, torch.Tensor):
         win = torch.from_numpy(win).to(dev)
-    return n, h, w, oh, ow, int(d_mask), win, f, out, windows
+    return n, h, w, oh, ow, int(d_mask), win, f, out, windows, int(shrink)
 
 
 def _three(x, what):
@@ -916,40 +942,42 @@ def _three(x, what):
 
 
 def reinhard_view(rgb, windows, size, target_means, target_stds, d_mask=7, mask_background=False, luminosity_threshold=0.8, fmt=None,
-                  out=None, ws=None, view=None):
+                  out=None, ws=None, view=None, shrink=1):
     """reinhard_transform with normalize_view's crop, flip and quarter turn per tile in its map sweep (sl_reinhard_view): the unchanged
     statistics of the WHOLE tiles, then ONE sweep that reads, maps and writes window pixels only -- bit for bit the view of
     reinhard_transform's image (fmt: its fmt.convert).  windows, size, d_mask, fmt, out: normalize_view's; view: a TileView in place of
-    size and d_mask, whose draw gives the windows when windows is None.  -> (out, stats (N, 8), windows)."""
+    size, d_mask and shrink, whose draw gives the windows when windows is None; shrink: normalize_view's (sl_reinhard_view_shrink).
+    -> (out, stats (N, 8), windows)."""
     tm_ts = []
-    n, h, w, oh, ow, d_mask, win, f, out, windows = _lab_view_prepare(
+    n, h, w, oh, ow, d_mask, win, f, out, windows, shrink = _lab_view_prepare(
         rgb, windows, size, d_mask, fmt, out, view,
-        lambda n: tm_ts.extend((_three(target_means, "target_means"), _three(target_stds, "target_stds"))))
+        lambda n: tm_ts.extend((_three(target_means, "target_means"), _three(target_stds, "target_stds"))), shrink)
     dev = rgb.device
     tm, ts = _f64(tm_ts[0], (3,), dev), _f64(tm_ts[1], (3,), dev)
     st = torch.empty((n, 8), dtype=torch.float64, device=dev)
     wsb = _scratch(ws, _ffi.OP_LAB_STATS, n, h, w, dev)
-    _call("sl_reinhard_view", _ptr(rgb), _ptr(out), n, h, w, oh, ow, _ptr(win), int(d_mask), _ptr(tm), _ptr(ts), 1 if mask_background else 0,
-          float(luminosity_threshold), _ptr(st), _ptr(wsb), wsb.numel(), _byref(f))
+    _call_view("sl_reinhard_view", shrink, (_ptr(rgb), _ptr(out), n, h, w, oh, ow, _ptr(win), int(d_mask)), _ptr(tm), _ptr(ts),
+               1 if mask_background else 0, float(luminosity_threshold), _ptr(st), _ptr(wsb), wsb.numel(), _byref(f))
     return out, st, windows
 
 
-def luminosity_view(rgb, windows, size, percentile=95, d_mask=7, fmt=None, out=None, ws=None, view=None):
+def luminosity_view(rgb, windows, size, percentile=95, d_mask=7, fmt=None, out=None, ws=None, view=None, shrink=1):
     """luminosity_standardize with the view in its map sweep (sl_luminosity_view; see reinhard_view) -> (out, p (N,) f64, windows)."""
     def pct_ok(n):
         try:
             float(percentile)
         except (TypeError, ValueError):
             raise ValueError("percentile must be a number") from None
-    n, h, w, oh, ow, d_mask, win, f, out, windows = _lab_view_prepare(rgb, windows, size, d_mask, fmt, out, view, pct_ok)
+    n, h, w, oh, ow, d_mask, win, f, out, windows, shrink = _lab_view_prepare(rgb, windows, size, d_mask, fmt, out, view, pct_ok, shrink)
     p = torch.empty((n,), dtype=torch.float64, device=rgb.device)
     wsb = _scratch(ws, _ffi.OP_LAB_STATS, n, h, w, rgb.device)
-    _call("sl_luminosity_view", _ptr(rgb), _ptr(out), n, h, w, oh, ow, _ptr(win), int(d_mask), float(percentile), _ptr(p), _ptr(wsb),
-          wsb.numel(), _byref(f))
+    _call_view("sl_luminosity_view", shrink, (_ptr(rgb), _ptr(out), n, h, w, oh, ow, _ptr(win), int(d_mask)), float(percentile), _ptr(p),
+               _ptr(wsb), wsb.numel(), _byref(f))
     return out, p, windows
 
 
-def slab_view(rgb, windows, size, state, mode, d_mask=7, mask_background=False, luminosity_threshold=0.8, fmt=None, out=None, view=None):
+def slab_view(rgb, windows, size, state, mode, d_mask=7, mask_background=False, luminosity_threshold=0.8, fmt=None, out=None, view=None,
+              shrink=1):
     """slab_map with the view in its sweep (sl_slab_view): per tile the window of the image slab_map writes under the slide's tables (a
     non-OK status: of the tile's own bytes), as the uint8 image or the tensor.  An empty shard gives the empty output.
     -> (out, windows)."""
@@ -959,10 +987,10 @@ def slab_view(rgb, windows, size, state, mode, d_mask=7, mask_background=False, 
         if not (isinstance(state, torch.Tensor) and state.dtype == torch.float64 and state.numel() == _ffi.SLAB_STATE_DOUBLES
                 and state.is_contiguous()):
             raise ValueError(f"state must be the ({_ffi.SLAB_STATE_DOUBLES},) float64 tensor of slab_begin / slab_finish")
-    n, h, w, oh, ow, d_mask, win, f, out, windows = _lab_view_prepare(rgb, windows, size, d_mask, fmt, out, view, state_ok)
+    n, h, w, oh, ow, d_mask, win, f, out, windows, shrink = _lab_view_prepare(rgb, windows, size, d_mask, fmt, out, view, state_ok, shrink)
     if n:
-        _call("sl_slab_view", _ptr(rgb), _ptr(out), n, h, w, oh, ow, _ptr(win), int(d_mask), _ptr(state), int(mode),
-              1 if mask_background else 0, float(luminosity_threshold), _byref(f))
+        _call_view("sl_slab_view", shrink, (_ptr(rgb), _ptr(out), n, h, w, oh, ow, _ptr(win), int(d_mask)), _ptr(state), int(mode),
+                   1 if mask_background else 0, float(luminosity_threshold), _byref(f))
     return out, windows
 
 

@@ -176,7 +176,7 @@ class ExtractiveStainNormalizer(object):
         default ``hed.randomize_batch(N)``, drawn BEFORE the windows.  Works with or without ``view`` / ``tensor_format``; the call then
         returns one more element at the end, ``engine.HedDraw(sigmas, biases, applied)``."""
         from .. import engine
-        with_hed = engine._hed_call(hed, hed_sigmas, hed_biases, tiles)
+        with_hed = engine._hed_call(hed, hed_sigmas, hed_biases, tiles, view)
         if with_hed or view is not None or windows is not None:
             return self._route_batch(tiles, True, {}, out, ws, tensor_format, view, windows, (hed, hed_sigmas, hed_biases) if with_hed else None)
         if tensor_format is None:
@@ -229,7 +229,7 @@ class ExtractiveStainNormalizer(object):
         engine._jitter_args(None, None, alpha_beta, None, tensor_format, out)
         if normalize and not hasattr(self, "stain_matrix_target"):
             raise ValueError("augment_batch(normalize=True) needs a fitted target: call fit() first, or pass normalize=False")
-        with_hed = engine._hed_call(hed, hed_sigmas, hed_biases, tiles)
+        with_hed = engine._hed_call(hed, hed_sigmas, hed_biases, tiles, view)
         return self._route_batch(tiles, normalize, dict(alpha_beta=alpha_beta, augment_background=augment_background), out, ws,
                                  tensor_format, view, windows, (hed, hed_sigmas, hed_biases) if with_hed else None)
 
