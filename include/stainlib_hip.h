@@ -727,6 +727,37 @@ SL_API int sl_reinhard_view_shrink(const uint8_t* rgb, void* out, int n, int h, 
 SL_API int sl_luminosity_view_shrink(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, int shrink, double percentile, double* p_out, void* workspace, size_t workspace_bytes, const SlTensorFormat* fmt, void* stream);
 SL_API int sl_slab_view_shrink(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, int shrink, const double* state, int mode, int mask_background, double luminosity_threshold, const SlTensorFormat* fmt, void* stream);
 
+/* ---- random-resized crop in the one-pass loader: a per-tile window of any size, area-resampled to the output inside the view (view.hip,
+ * hed_view.hip, view_resize_kernels.hpp; an extension: RandomResizedCrop(224, scale=(0.08, 1)) is the one augmentation every training
+ * recipe otherwise runs behind the call -- on the full-tile tensor, in a per-tile loop, because the windows differ in size) -----------
+ * Each call is its parent -- sl_normalize_view, sl_normalize_hed_view -- with `int max_wh, int max_ww` after d_mask and windows of
+ * n x 5 int32 on the device: windows[t] = (y0, x0, d, wh, ww), a window of wh rows and ww columns in the TILE's orientation at (y0, x0).
+ * (oh, ow) stays the size of the OUTPUT, one for the call.  On the device, per tile:
+ *     d' = d & d_mask;  (nu, nv) = (oh, ow) for an even number of quarter turns, (ow, oh) for an odd one
+ *     wh' = clamp(wh, 1, min(max_wh, 16 nu)),  ww' = clamp(ww, 1, min(max_ww, 16 nv))
+ *     y0' = clamp(y0, 0, h - wh'),  x0' = clamp(x0, 0, w - ww')
+ * With full[t] the h x w x 3 uint8 image the parent defines (at SOURCE resolution; every statistic the whole tile's) and
+ * win = full[t][y0' : y0' + wh', x0' : x0' + ww'], the window is resampled to nu x nv by exact pixel-area averaging (OpenCV's INTER_AREA
+ * for shrinking, in integers).  Along an axis of nw window pixels and no outputs, in coordinates scaled by no, source pixel k covers
+ * [k no, (k + 1) no), output i covers [i nw, (i + 1) nw) and c(i, k) is the length of their overlap: an integer, every row of c sums to
+ * nw, every column to no.  Per channel
+ *     S[i, j] = sum_k sum_l cy(i, k) cx(j, l) win[k, l]                                    (an integer, at most 255 wh' ww')
+ *     b[i, j] = (2 S[i, j] + D) / (2 D),  D = wh' ww', integer division                     (the mean, round half up; a uint8)
+ *     view[t] = rot90(flip_w_if(f, b), k)                                                   (the parent's dihedral rule)
+ * wh' = nu and ww' = nv: the window itself (the parent's result).  wh' = s nu and ww' = s nv: the s x s box mean of the _shrink calls.
+ * The resample commutes with the flip and the turn.  wh' < nu (upscaling) is the same formula: piecewise constant with blended edges where
+ * an output straddles two source pixels -- not bilinear.  The tensor is defined on b as on a byte everywhere else.  A tile whose fit
+ * failed: the resampled view of its own bytes.  Bilinear, bicubic or antialiased-triangle filters are other definitions and not offered.
+ * (max_wh, max_ww): an upper bound of the window sides of this call; the launch is sized from it (the windows are never read back), and
+ * a window beyond it is clamped to it.  Limits: wh ww <= 2^22 (2 S + D < 2^31), wh <= 16 nu and ww <= 16 nv (at most 17 source pixels
+ * per output and axis).
+ * SL_ERR_BADARG before anything is launched: what the parent refuses of rgb, out, n, h, w, d_mask, the statistics pattern, params, fmt
+ * (and the HED arguments); a NULL windows; oh < 1 or ow < 1; max_wh outside [1, h] or max_ww outside [1, w]; max_wh max_ww > 2^22;
+ * max(oh, ow) max(max_wh, max_ww) > 2^30; more (tile, patch) pairs than 2^31 - 1.  Unlike the parents, (oh, ow) need not fit in the
+ * tile.  out == rgb is not supported.  Capture-safe like the parents. */
+SL_API int sl_normalize_view_resize(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, int max_wh, int max_ww, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, const double* alpha_beta, int augment_background, const SlParams* params, const SlTensorFormat* fmt, void* stream);
+SL_API int sl_normalize_hed_view_resize(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, int max_wh, int max_ww, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, const double* alpha_beta, int augment_background, const SlParams* params, const SlTensorFormat* fmt, const double* hed_sigma, const double* hed_bias, const int32_t* hed_applied, int skimage_mode, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

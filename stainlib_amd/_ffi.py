@@ -193,6 +193,10 @@ _SIGNATURES = {
 for _name in ("sl_normalize_view", "sl_normalize_hed_view", "sl_reinhard_view", "sl_luminosity_view", "sl_slab_view"):
     _res, _args = _SIGNATURES[_name]
     _SIGNATURES[_name + "_shrink"] = (_res, _args[:9] + [C.c_int] + _args[9:])
+# the resizing views (windows: n x 5 int32): each parent's parameters with `int max_wh, int max_ww` behind d_mask
+for _name in ("sl_normalize_view", "sl_normalize_hed_view"):
+    _res, _args = _SIGNATURES[_name]
+    _SIGNATURES[_name + "_resize"] = (_res, _args[:9] + [C.c_int, C.c_int] + _args[9:])
 del _name, _res, _args
 POOL_STATE_DOUBLES, POOL_M, POOL_MAXC, POOL_STATUS, POOL_MISS = 64, 0, 6, 8, 9
 POOL2_STATE_DOUBLES, POOL2_HIST_WORDS, POOL2_WHY = 256, 2 * 8192 + 8 * 32, 33

@@ -1,6 +1,8 @@
 // hed_view.hip -- C-ABI launchers of HED augmentation behind the apply pass: the byte sums of the image a route would write, and the
-// view pass with the HED stage and the view's box shrink (kernels: hed_view_kernels.hpp).  A translation unit of its own: view.hip compiles as before.
+// view pass with the HED stage and the view's box shrink (kernels: hed_view_kernels.hpp), and the resizing view with the HED stage
+// (kernel: view_resize_kernels.hpp).  A translation unit of its own: view.hip compiles as before.
 #include "hed_view_kernels.hpp"
+#include "view_resize_kernels.hpp"  // (behind HedStage<1>)
 #include "route_host.hpp"
 
 using namespace sl;
@@ -70,4 +72,35 @@ extern "C" int sl_normalize_hed_view(const uint8_t* rgb, void* out, int n, int h
                                      void* stream) {
     return sl_normalize_hed_view_shrink(rgb, out, n, h, w, oh, ow, windows, d_mask, 1, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta,
                                         augment_background, params, fmt, hed_sigma, hed_bias, hed_applied, skimage_mode, stream);
+}
+
+extern "C" int sl_normalize_hed_view_resize(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows,
+                                            int d_mask, int max_wh, int max_ww, const double* M_src, const double* maxC_src,
+                                            const double* M_tgt, const double* maxC_tgt, const double* alpha_beta, int augment_background,
+                                            const SlParams* params, const SlTensorFormat* fmt, const double* hed_sigma,
+                                            const double* hed_bias, const int32_t* hed_applied, int skimage_mode, void* stream) {
+    if (const int rc = check_shape(rgb, out, n, h, w)) return rc;
+    long npatch = 0;
+    if (const int rc = view_resize_geometry(n, h, w, oh, ow, windows, d_mask, max_wh, max_ww, npatch)) return rc;
+    int mode = 0;
+    if (const int rc = route_of(M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, augment_background, mode)) return rc;
+    if (!params_ok(params)) return SL_ERR_BADARG;
+    if (fmt && !format_ok(fmt)) return SL_ERR_BADARG;
+    if (!hed_sigma || !hed_bias || !hed_applied) return SL_ERR_BADARG;
+    if (skimage_mode != SL_HED_SKIMAGE_018) return SL_ERR_BADARG;               // the pinned semantics only (see the header)
+    const SlParams p = params_or_defaults(params);
+    const float ylimf = tissue_ylimf(p);
+    HedViewArgs hv;
+    hv.sigma = hed_sigma; hv.bias = hed_bias; hv.applied = hed_applied;
+    hed_matrices(hv.R, hv.H);                                                    // sl_hed_augment's
+    hipStream_t s = (hipStream_t)stream;
+    with_format_or_u8(fmt, false, false, [&](auto dt, auto lay, auto, auto) {
+        with_mode(mode, [&](auto m) {
+            hipLaunchKernelGGL((k_hed_view_resize<decltype(dt)::value, decltype(lay)::value, decltype(m)::value>),
+                               dim3((unsigned)(n * npatch)), dim3(kWG), 0, s, rgb, out, h, w, oh, ow, (int)npatch, windows, d_mask, max_wh,
+                               max_ww, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, p.lasso_lambda, ylimf, fmt ? tensor_k(*fmt) : TensorK{},
+                               hv);
+        });
+    });
+    return launch_status();
 }

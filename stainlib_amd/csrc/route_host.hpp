@@ -2,7 +2,7 @@
 // The *route* is the pointer pattern (M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, augment_background) by which a call names the
 // image it would write: the tiles' own bytes, sl_normalize_apply's, the jitter under a target or the jitter under the tile's own matrix.
 #pragma once
-#include "view_kernels.hpp"        // kView*, kViewB
+#include "view_resize_kernels.hpp" // kView*, kViewB (view_kernels.hpp through it), resize_patch_edge
 #include "tensor_host.hpp"
 
 namespace sl {
@@ -41,6 +41,25 @@ inline int view_geometry(int n, int h, int w, int oh, int ow, const int32_t* win
     const int B = kViewB / s;
     npx = (ow + B - 1) / B;
     npatch = npx * ((oh + B - 1) / B);
+    if ((long)n * npatch > 0x7fffffffL) return SL_ERR_BADARG;                    // one workgroup per (tile, patch)
+    return SL_OK;
+}
+
+// The geometry of a resizing view (view_resize_kernels.hpp) of n tiles of h x w whose windows are at most max_wh x max_ww: SL_OK and the
+// upper bound of the patches of a tile -- those of the largest window the kernel lets through, in either orientation d_mask allows --
+// or SL_ERR_BADARG.  The window sides themselves may live on the device and are clamped there.
+inline int view_resize_geometry(int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, int max_wh, int max_ww, long& npatch) {
+    if (!windows || oh < 1 || ow < 1) return SL_ERR_BADARG;
+    if (d_mask < 0 || d_mask > 7) return SL_ERR_BADARG;
+    if (max_wh < 1 || max_wh > h || max_ww < 1 || max_ww > w) return SL_ERR_BADARG;
+    if ((long)max_wh * max_ww > kResizeMaxArea) return SL_ERR_BADARG;
+    if ((long)(oh > ow ? oh : ow) * (max_wh > max_ww ? max_wh : max_ww) > kResizeMaxProduct) return SL_ERR_BADARG;
+    auto patches = [&](int nu, int nv) {
+        const int bu = resize_patch_edge(nu, resize_side_max(nu, max_wh)), bv = resize_patch_edge(nv, resize_side_max(nv, max_ww));
+        return (long)((nu + bu - 1) / bu) * ((nv + bv - 1) / bv);
+    };
+    npatch = patches(oh, ow);
+    if (d_mask & 1) npatch = std::max(npatch, patches(ow, oh));
     if ((long)n * npatch > 0x7fffffffL) return SL_ERR_BADARG;                    // one workgroup per (tile, patch)
     return SL_OK;
 }

@@ -143,6 +143,7 @@ struct ViewTile {
 // first pixel (lowest row and column) at LDS pixel a0 + il ai + jl aj -- at s = 1 the pixel itself.
 struct ViewPatch {
     int i0, j0, bh, bw, nu, nv, ys, xs, a0, ai, aj;
+    ViewPatch() = default;                                                        // (filled in by resize_patch, view_resize_kernels.hpp)
     __device__ __forceinline__ ViewPatch(const ViewTile& t, int patch, int npx, int oh, int ow, int s) {
         constexpr int PITCH = kViewPitch;
         const int B = kViewB >> (s >> 1);                                         // kViewB / s for s = 1, 2, 4, without a division

@@ -1,0 +1,331 @@
+// view_resize_kernels.hpp -- the random-resized crop of a training loader inside the view pass: per tile a window of ANY size, resampled
+// to the call's one output size by exact pixel-area averaging, then flipped and turned.
+//
+//   k_view_resize      k_view (view_kernels.hpp) with a per-tile window side and the area-resampling write side
+//   k_hed_view_resize  the same with the HED stage (HedStage<1>, hed_view_kernels.hpp) in front of LDS
+//
+// Definition (include/stainlib_hip.h, sl_normalize_view_resize): windows[t] = (y0, x0, d, wh, ww); with (nu, nv) = (oh, ow) for an even
+// number of quarter turns and (ow, oh) for an odd one, along an axis of nw window pixels and no outputs the coordinates are scaled by no:
+// source pixel k covers [k no, (k + 1) no), output i covers [i nw, (i + 1) nw), c(i, k) = the length of their overlap (an integer; a row
+// of c sums to nw, a column to no).  Per channel S[i, j] = sum_k sum_l cy(i, k) cx(j, l) window[k, l], b = (2 S + D) / (2 D) with
+// D = wh ww (round half up), result = rot90(flip(b) if d & 4 else b, d & 3).  The resample commutes with the flip and the turn, so the
+// kernel resamples in OUTPUT orientation: each output axis is one window axis, forwards or backwards.
+//
+// What is shared with k_view: load12 / view_read (the read side), view_stage / view_unpack (the LDS stage, one packed dword per SOURCE
+// pixel, pitch 65), the apply / jitter / HED arithmetic per source pixel (view_body's, statement for statement), cvt_chunk and
+// store_view4.  What is new: the geometry (ResizeTile, resize_patch) and the write side (resize_write).
+//
+// Shape: ONE workgroup = one tile and one patch of at most 64 x 64 OUTPUT pixels whose source pixels fit the 64 x 64 LDS block.  Along an
+// axis the patch edge is resize_patch_edge(no, nw) = min(64, 63 no / nw) outputs: b outputs starting anywhere touch at most
+// ceil(b nw / no) + 1 <= 64 source pixels.  The edge is per tile and block-uniform.  The windows may live on the device, so the grid is
+// sized on the host from the upper bound (max_wh, max_ww) of the window sides (view_resize_geometry, route_host.hpp): the edge does not
+// grow with nw, so a tile has at most the bound's patches, and a workgroup past its tile's own count returns before it loads a pixel.
+//   taps        threads 0..127 divide once each: for the patch's <= 64 output rows and <= 64 output columns the first source pixel an
+//               output overlaps (relative to the LDS block) and how many (1..17), packed into s_tap.  No lane divides by nu or nv again.
+//   write side  output rows, 4 adjacent output pixels per lane; 16, 8, 4, 2 or 1 lanes per row -- the power of two that covers the patch's
+//               width -- and 256 / that many rows per pass (16 and 16 as at S = 1 for a patch wider than 32).  Per output pixel two
+//               nested loops over its taps; the weights come from the tap's scaled coordinate (min - max of four edges, no table), the
+//               three channel sums are 32-bit (S <= 255 D < 2^30 for D <= 2^22; weight products < 2^24: v_mad_u32_u24).
+//   division    by 2 D, block-uniform: q0 = trunc(float(2 S + D) * (1 / float(2 D))) is within one of the quotient (2 D <= 2^23 is exact
+//               in binary32, three roundings of 2^-24 relative on a value below 256), and one remainder test each way makes it exact for
+//               every residue.
+// LDS banking of the tap reads (pitch 65: bank (r + x) % 32): at step (ta, tb) of pixel p a lane reads row k0(i) + ta, column
+// l0(j) + tb, so lanes of one output row are ~4 ww / nv columns apart and rows ~wh / nu apart -- the picture of the shrink's strided
+// reads at that ratio under the same lanes per row: 2-way at ratios 1 and 2, 4-way at ratio 4 (lane strides of 16 and 4 banks), in between the
+// strides are not constant and the lanes spread further.  The loop issues ~12 VALU instructions per LDS read, so the read is not what it waits for.
+// Lanes: a patch of b x b outputs has b ceil(b / 4) lane-passes of work -- four passes of all lanes at ratio <= 1, one pass of 248 lanes at
+// ratio 2 (b = 31), 60 lanes of one pass at ratio 4 (b = 15); the per-source-pixel arithmetic in front of LDS stays on all 256 lanes
+// (DESIGN 4.17 for what that costs).
+#pragma once
+#include "view_kernels.hpp"
+
+namespace sl {
+
+constexpr int kResizeMaxRatio = 16;              // wh <= 16 nu, ww <= 16 nv: at most 17 taps per axis
+constexpr int kResizeMaxArea = 1 << 22;          // wh ww: 2 S + D < 2^31
+constexpr long kResizeMaxProduct = 1L << 30;     // an output side times a window side: the scaled coordinates are 32-bit
+
+// outputs per patch along an axis of `no` outputs from `nw` window pixels (nw <= 16 no): min(64, 63 no / nw), at least 3; does not grow with nw
+__host__ __device__ inline int resize_patch_edge(int no, int nw) {
+    if (no > nw) return 63L * no >= 64L * nw ? 64 : 63;
+    return 63 * no / nw;
+}
+// the largest window side along an axis of `no` outputs under the call's bound
+__host__ __device__ inline int resize_side_max(int no, int bound) { return (int)(16L * no < (long)bound ? 16L * no : (long)bound); }
+
+// The view of one tile (block-uniform): the code as in ViewTile, the clamped window and the patch edges along the window's two axes.
+struct ResizeTile {
+    bool tr, ry, rx;
+    int nu, nv, wh, ww, y0, x0, bu, bv;
+    __device__ __forceinline__ ResizeTile(const int32_t* windows, int tile, int d_mask, int h, int w, int oh, int ow, int max_wh, int max_ww) {
+        const int32_t* const wv = windows + 5 * (size_t)tile;
+        const int d = __builtin_amdgcn_readfirstlane(wv[2]) & d_mask;
+        const int k = d & 3;
+        tr = k & 1; ry = (k >> 1) & 1; rx = ((k >> 1) ^ k ^ (d >> 2)) & 1;
+        nu = tr ? ow : oh; nv = tr ? oh : ow;                                     // the outputs along the window's rows and columns
+        wh = max(1, min(__builtin_amdgcn_readfirstlane(wv[3]), resize_side_max(nu, max_wh)));
+        ww = max(1, min(__builtin_amdgcn_readfirstlane(wv[4]), resize_side_max(nv, max_ww)));
+        y0 = max(0, min(__builtin_amdgcn_readfirstlane(wv[0]), h - wh));
+        x0 = max(0, min(__builtin_amdgcn_readfirstlane(wv[1]), w - ww));
+        bu = resize_patch_edge(nu, wh); bv = resize_patch_edge(nv, ww);
+    }
+};
+
+// One OUTPUT axis of a patch (block-uniform): o0 + t, t = 0 .. nb - 1, are its outputs; the axis has `no` outputs from `nw` window pixels,
+// runs backwards through the window when rev, and its source pixels start at window pixel `lo` (= LDS pixel 0 of that axis), `stride`
+// dwords apart in LDS.
+struct ResizeAxis {
+    int o0, nb, no, nw, lo, stride;
+    bool rev;
+    // the output's index along the window axis
+    __device__ __forceinline__ int at(int t) const { return rev ? no - 1 - (o0 + t) : o0 + t; }
+};
+
+// Patch `patch` of the tile: false when the tile has fewer patches.  g: i0, j0, bh, bw and the source block ys, xs, nu x nv for view_read
+// and view_stage; ai, aj: the patch's row and column axis.
+__device__ __forceinline__ bool resize_patch(const ResizeTile& t, int patch, int oh, int ow, ViewPatch& g, ResizeAxis& ai, ResizeAxis& aj) {
+    const int bi = t.tr ? t.bv : t.bu, bj = t.tr ? t.bu : t.bv;                  // the patch edge along output rows and columns
+    const int npi = (oh + bi - 1) / bi, npj = (ow + bj - 1) / bj;
+    if (patch >= npi * npj) return false;
+    g.i0 = (patch / npj) * bi; g.j0 = (patch % npj) * bj;
+    g.bh = min(bi, oh - g.i0); g.bw = min(bj, ow - g.j0);
+    ai.o0 = g.i0; ai.nb = g.bh; ai.no = oh; ai.nw = t.tr ? t.ww : t.wh; ai.rev = t.tr ? t.rx : t.ry; ai.stride = t.tr ? 1 : kViewPitch;
+    aj.o0 = g.j0; aj.nb = g.bw; aj.no = ow; aj.nw = t.tr ? t.wh : t.ww; aj.rev = t.tr ? t.ry : t.rx; aj.stride = t.tr ? kViewPitch : 1;
+    int n[2];
+    ResizeAxis* const ax[2] = {&ai, &aj};
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        ResizeAxis& a = *ax[e];
+        const uint32_t first = (uint32_t)(a.rev ? a.no - a.o0 - a.nb : a.o0);    // the patch's outputs along the window axis: first .. first + nb - 1
+        a.lo = (int)(first * (uint32_t)a.nw / (uint32_t)a.no);
+        n[e] = (int)(((first + (uint32_t)a.nb) * (uint32_t)a.nw + (uint32_t)a.no - 1u) / (uint32_t)a.no) - a.lo;   // <= 64 (resize_patch_edge)
+    }
+    g.ys = t.y0 + (t.tr ? aj.lo : ai.lo); g.nu = min(t.tr ? n[1] : n[0], kViewB);     // (the min: the LDS block, whatever the arithmetic above)
+    g.xs = t.x0 + (t.tr ? ai.lo : aj.lo); g.nv = min(t.tr ? n[0] : n[1], kViewB);
+    g.a0 = 0; g.ai = ai.stride; g.aj = aj.stride;
+    return true;
+}
+
+// ---- taps: for output t of each patch axis the first LDS pixel it overlaps | the number it overlaps << 8 (threads 0 .. 2 kViewB - 1)
+__device__ __forceinline__ void resize_taps(const ResizeAxis& ai, const ResizeAxis& aj, uint32_t* s_tap, int tid) {
+    if (tid >= 2 * kViewB) return;
+    const ResizeAxis& a = tid < kViewB ? ai : aj;
+    const int t = tid & (kViewB - 1);
+    if (t >= a.nb) return;
+    const uint32_t o = (uint32_t)a.at(t), nw = (uint32_t)a.nw, no = (uint32_t)a.no;
+    const uint32_t k0 = o * nw / no, k1 = ((o + 1u) * nw + no - 1u) / no;
+    s_tap[tid] = (k0 - (uint32_t)a.lo) | ((k1 - k0) << 8);
+}
+
+// (2 S + D) / (2 D) for S <= 255 D, D <= 2^22: rden = 1 / float(2 D) (block-uniform)
+__device__ __forceinline__ uint32_t resize_round(uint32_t S, uint32_t D, float rden) {
+    const uint32_t num = 2u * S + D, den = 2u * D;
+    uint32_t q = (uint32_t)((float)num * rden);
+    const int r = (int)(num - q * den);
+    q = r < 0 ? q - 1u : (r >= (int)den ? q + 1u : q);
+    return q;
+}
+
+// ---- write side: output rows, 4 adjacent pixels per lane (behind a barrier after the stage and resize_taps).  Lanes per output row: the
+// ---- power of two that covers the patch's width, 1 .. 16 (block-uniform), so that a narrow patch spreads its rows over all the lanes.
+template <int DT, int LAYOUT>
+__device__ __forceinline__ void resize_write(const ViewPatch& g, const ResizeAxis& ai, const ResizeAxis& aj, const uint32_t* s_px,
+                                             const uint32_t* s_tap, void* out, int tile, int oh, int ow, TensorK fmt, int tid) {
+    constexpr bool TENSOR = DT != kDtU8;
+    constexpr int SDT = TENSOR ? DT : kDtF32;
+    typedef typename Elem<SDT>::type T;
+    const int i0 = g.i0, j0 = g.j0, bh = g.bh, bw = g.bw;
+    const TensorK F = tensor_consts(fmt);
+    const size_t PO = (size_t)oh * ow;
+    const uint32_t D = (uint32_t)ai.nw * (uint32_t)aj.nw;
+    const float rden = 1.0f / (float)(2u * D);
+    const int n4 = (bw + 3) >> 2;                            // chunks of 4 pixels per output row, 1 .. 16
+    const int lg = n4 <= 1 ? 0 : 32 - __builtin_clz((unsigned)(n4 - 1));       // log2 of the lanes per row: 0 .. 4
+    const int lr = tid >> lg, lc = tid & ((1 << lg) - 1), rows = kWG >> lg;     // rows per pass: 16 .. 256
+    const int jl = 4 * lc;
+    if (jl >= bw) return;                                    // (nothing below has a barrier)
+    for (int il = lr; il < bh; il += rows) {
+        // the row axis of this lane: its taps, the output's interval [elo, ehi) and the first tap's start, all scaled by no
+        const uint32_t ta = s_tap[il];
+        const int na = (int)(ta >> 8), ka = (int)(ta & 0xffu);
+        const int elo_a = ai.at(il) * ai.nw, ehi_a = elo_a + ai.nw, c0_a = (ai.lo + ka) * ai.no;
+        uint32_t px[4];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const int jj = min(jl + p, bw - 1);
+            const uint32_t tb = s_tap[kViewB + jj];
+            const int nb = (int)(tb >> 8), kb = (int)(tb & 0xffu);
+            const int elo_b = aj.at(jj) * aj.nw, ehi_b = elo_b + aj.nw, c0_b = (aj.lo + kb) * aj.no;
+            uint32_t S0 = 0, S1 = 0, S2 = 0;
+            int ca = c0_a, ra = ka * ai.stride;
+            for (int a = 0; a < na; ++a, ca += ai.no, ra += ai.stride) {
+                const uint32_t wa = (uint32_t)(min(ca + ai.no, ehi_a) - max(ca, elo_a));
+                int cb = c0_b, rb = ra + kb * aj.stride;
+                for (int b = 0; b < nb; ++b, cb += aj.no, rb += aj.stride) {
+                    const uint32_t wb = (uint32_t)(min(cb + aj.no, ehi_b) - max(cb, elo_b));
+                    const uint32_t wgt = __umul24(wa, wb);   // <= D <= 2^22
+                    const uint32_t v = s_px[rb];
+                    S0 += __umul24(wgt, v & 0xffu);
+                    S1 += __umul24(wgt, (v >> 8) & 0xffu);
+                    S2 += __umul24(wgt, v >> 16);
+                }
+            }
+            px[p] = resize_round(S0, D, rden) | (resize_round(S1, D, rden) << 8) | (resize_round(S2, D, rden) << 16);
+        }
+        Chunk o;
+        o.w0 = px[0] | (px[1] << 24);
+        o.w1 = (px[1] >> 8) | (px[2] << 16);
+        o.w2 = (px[2] >> 16) | (px[3] << 8);
+        const int nvalid = min(4, bw - jl);
+        const size_t pix = (size_t)(i0 + il) * ow + (j0 + jl);
+        if (TENSOR) {
+            float v[12];
+            cvt_chunk(o, F, v);
+            T* const base = (T*)out + (size_t)tile * 3 * PO;
+            store_view4<SDT, LAYOUT>(base, PO, pix, nvalid, v);
+        } else {
+            uint8_t* const p = (uint8_t*)out + ((size_t)tile * PO + pix) * 3;
+            if (nvalid == 4) {
+                sl_u32x3u u; u.x = o.w0; u.y = o.w1; u.z = o.w2;
+                *(SL_GLOBAL sl_u32x3u*)as_global(p) = u;
+            } else {
+                for (int i = 0; i < 3 * nvalid; ++i) as_global(p)[i] = (uint8_t)chunk_byte(o, i);
+            }
+        }
+    }
+}
+
+// view_body with the geometry and the write side above; everything between view_read and the barrier is view_body's, statement for
+// statement.  npatch: the host's upper bound of the patches of a tile.
+template <int DT, int LAYOUT, int MODE, int HED>
+__device__ __forceinline__ void view_resize_body(const uint8_t* rgb, void* out, int h, int w, int oh, int ow, int npatch,
+                                                 const int32_t* windows, int d_mask, int max_wh, int max_ww,
+                                                 const double* M_src, const double* maxC_src,
+                                                 const double* M_tgt, const double* maxC_tgt, const double* alpha_beta,
+                                                 double lam, float ylimf, TensorK fmt, const HedViewArgs* hv) {
+    constexpr int B = kViewB, PITCH = kViewPitch;
+    static_assert(kWG == 256 && B == 64, "16 lanes x 4 pixels per row, 16 rows per pass, 4 passes");
+    __shared__ float2 s_tab[256];
+    __shared__ uint32_t s_px[B * PITCH];
+    __shared__ uint32_t s_tap[2 * B];
+    const int tid = threadIdx.x;
+    const int lr = tid >> 4, lc = tid & 15;
+    const int tile = blockIdx.x / npatch, patch = blockIdx.x % npatch;
+    const int P = h * w;
+    const size_t nbytes = (size_t)P * 3;
+    const uint8_t* const src = rgb + (size_t)tile * nbytes;
+
+    // the view of this tile (block-uniform), the source block of this patch -- or none: the grid is sized for the largest window
+    const ResizeTile vt(windows, tile, d_mask, h, w, oh, ow, max_wh, max_ww);
+    ViewPatch g;
+    ResizeAxis ai, aj;
+    if (!resize_patch(vt, patch, oh, ow, g, ai, aj)) return;
+    if (MODE != kViewRaw) fill_gam_od_lut(s_tab);
+    HedStage<HED> hed;
+    hed.init(tid, tile, hv);
+    Chunk in[4];
+    view_read(g, src, nbytes, w, lr, lc, in);
+    resize_taps(ai, aj, s_tap, tid);
+    auto stage = [&](auto compute) {
+        view_stage(g, s_px, lr, lc, in, [&](const Chunk& c, uint32_t (&px)[4]) {
+            compute(c, px);
+            hed.apply(px);
+        });
+    };
+    auto unpack = [](const Chunk& o, uint32_t (&px)[4]) { view_unpack(o, px); };
+    auto raw = [&](const Chunk& c, uint32_t (&px)[4]) { unpack(c, px); };
+
+    if (MODE == kViewRaw) {
+        if (HED != 0) __syncthreads();                              // the stage's table
+        stage(raw);
+    } else {
+        const ApplyTile<1> A(blockIdx.x, npatch, P, rgb, M_src, maxC_src, M_tgt, maxC_tgt, lam);
+        const ApplyK& K = A.K;
+        JitterK J;
+        if (MODE != kViewApply) {                                   // k_apply_jitter's constants
+            const double sc = 1.0 / A.unit;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                J.al[i] = in_vgpr(uni((float)alpha_beta[4 * (size_t)A.tile + 2 * i]));
+                J.be[i] = in_vgpr(uni((float)(alpha_beta[4 * (size_t)A.tile + 2 * i + 1] / (A.mct[i] / A.mcs[i]) * sc)));
+            }
+            J.ylimf = in_vgpr(ylimf);
+        }
+        __syncthreads();                                            // the table
+        if (SL_FIT_FAILED(A)) {                                     // the view of the source bytes
+            stage(raw);
+        } else if (MODE == kViewApply) {                            // k_apply: K.fast picks the lasso form and the cast
+            auto sweep = [&](auto fast_tag) {
+                constexpr bool FAST = decltype(fast_tag)::value;
+                stage([&](const Chunk& c, uint32_t (&px)[4]) {
+                    float t[12];
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) {
+                        const float x = s_tab[chunk_byte(c, 3 * p + 0)].y, y = s_tab[chunk_byte(c, 3 * p + 1)].y,
+                                    z = s_tab[chunk_byte(c, 3 * p + 2)].y;
+                        float v[3];
+                        apply_px<FAST>(K, x, y, z, v);
+                        t[3 * p] = v[0]; t[3 * p + 1] = v[1]; t[3 * p + 2] = v[2];
+                    }
+                    unpack(FAST ? pack_trunc_fast(t) : pack_trunc_general(t), px);
+                });
+            };
+            if (K.fast) sweep(std::true_type{}); else sweep(std::false_type{});
+        } else {                                                    // k_apply_jitter: g12 picks the lasso form, the cast saturates
+            auto sweep = [&](auto fast_tag) {
+                constexpr bool FAST = decltype(fast_tag)::value;
+                stage([&](const Chunk& c, uint32_t (&px)[4]) {
+                    float t[12];
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) {
+                        const float2 er = s_tab[chunk_byte(c, 3 * p + 0)];      // x = gamma, y = od32
+                        const float2 eg = s_tab[chunk_byte(c, 3 * p + 1)];
+                        const float2 eb = s_tab[chunk_byte(c, 3 * p + 2)];
+                        float c1, c2;
+                        apply_conc<FAST>(K, er.y, eg.y, eb.y, c1, c2);
+                        if (MODE == kViewJitAll) {
+                            c1 = fmaf(c1, J.al[0], J.be[0]);
+                            c2 = fmaf(c2, J.al[1], J.be[1]);
+                        } else {
+                            const bool tissue = is_tissue_f(er.x, eg.x, eb.x, J.ylimf);
+                            c1 = tissue ? fmaf(c1, J.al[0], J.be[0]) : c1;
+                            c2 = tissue ? fmaf(c2, J.al[1], J.be[1]) : c2;
+                        }
+#pragma unroll
+                        for (int ch = 0; ch < 3; ++ch)
+                            t[3 * p + ch] = 255.0f * __builtin_amdgcn_exp2f(fmaf(c1, K.q[0][ch], c2 * K.q[1][ch]));
+                    }
+                    unpack(pack_trunc_fast(t), px);
+                });
+            };
+            if (K.L.g12 >= 0.0f) sweep(std::true_type{}); else sweep(std::false_type{});
+        }
+    }
+    __syncthreads();
+
+    resize_write<DT, LAYOUT>(g, ai, aj, s_px, s_tap, out, tile, oh, ow, fmt, tid);
+}
+
+template <int DT, int LAYOUT, int MODE>
+static __global__ __launch_bounds__(kWG) void k_view_resize(const uint8_t* __restrict__ rgb, void* __restrict__ out, int h, int w, int oh,
+                                                            int ow, int npatch, const int32_t* __restrict__ windows, int d_mask, int max_wh,
+                                                            int max_ww, const double* __restrict__ M_src,
+                                                            const double* __restrict__ maxC_src, const double* M_tgt, const double* maxC_tgt,
+                                                            const double* __restrict__ alpha_beta, double lam, float ylimf, TensorK fmt) {
+    view_resize_body<DT, LAYOUT, MODE, 0>(rgb, out, h, w, oh, ow, npatch, windows, d_mask, max_wh, max_ww, M_src, maxC_src, M_tgt, maxC_tgt,
+                                          alpha_beta, lam, ylimf, fmt, nullptr);
+}
+
+// (instantiated where HedStage<1> is: hed_view_resize.hip includes hed_view_kernels.hpp first)
+template <int DT, int LAYOUT, int MODE>
+static __global__ __launch_bounds__(kWG) void k_hed_view_resize(const uint8_t* __restrict__ rgb, void* __restrict__ out, int h, int w,
+                                                                int oh, int ow, int npatch, const int32_t* __restrict__ windows, int d_mask,
+                                                                int max_wh, int max_ww, const double* __restrict__ M_src,
+                                                                const double* __restrict__ maxC_src, const double* M_tgt,
+                                                                const double* maxC_tgt, const double* __restrict__ alpha_beta, double lam,
+                                                                float ylimf, TensorK fmt, HedViewArgs hv) {
+    view_resize_body<DT, LAYOUT, MODE, 1>(rgb, out, h, w, oh, ow, npatch, windows, d_mask, max_wh, max_ww, M_src, maxC_src, M_tgt, maxC_tgt,
+                                          alpha_beta, lam, ylimf, fmt, &hv);
+}
+
+}  // namespace sl

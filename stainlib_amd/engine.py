@@ -369,20 +369,86 @@ def normalize_jitter(rgb, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, augment_
 
 # ---- crop / flip / rot90 in the apply pass (sl_normalize_view; see include/stainlib_hip.h and stainlib_amd/tile_view.py) -------------------
 
-def _call_view(name, shrink, head, *tail):
+def _call_view(name, shrink, head, *tail, resize=None):
     """The C call of a view pass: `name` as it is at shrink = 1, else its `_shrink` export, which takes shrink behind d_mask (the last
-    of head)."""
-    if shrink == 1:
+    of head); with resize = (max_wh, max_ww) its `_resize` export, which takes those two there."""
+    if resize is not None:
+        _call(name + "_resize", *head, int(resize[0]), int(resize[1]), *tail)
+    elif shrink == 1:
         _call(name, *head, *tail)
     else:
         _call(name + "_shrink", *head, int(shrink), *tail)
 
 
-def _view_windows(windows, n, h, w, oh, ow, d_mask, shrink=1):
+def _check_resize(resize, h, w, shrink=1):
+    """resize= of normalize_view / normalize_hed_view as (max_wh, max_ww) ints, or ValueError: the bound of the window sides of the call."""
+    from .tile_view import RESIZE_MAX_AREA
+    import numpy as np
+    try:
+        mh, mw = resize
+        if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in (mh, mw)):
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError(f"resize must be None or (max_wh, max_ww) ints, the largest window sides of the call, not {resize!r}") from None
+    if shrink != 1:
+        raise ValueError(f"resize= (windows of their own sizes) does not go with shrink={shrink}")
+    if not (1 <= mh <= h and 1 <= mw <= w):
+        raise ValueError(f"resize = ({mh}, {mw}) must lie within 1 x 1 and the {h} x {w} tile")
+    if int(mh) * int(mw) > RESIZE_MAX_AREA:
+        raise ValueError(f"resize = ({mh}, {mw}): a window may hold at most 2^22 pixels")
+    return int(mh), int(mw)
+
+
+def _resize_windows(windows, n, h, w, oh, ow, d_mask, resize):
+    """_view_windows for a resizing view: the (n, 5) int32 windows (y0, x0, d, wh, ww).  numpy / CPU windows are range-checked here
+    (ValueError); device windows are taken as they are -- the kernel masks the code and clamps the sides and the corner."""
+    import numpy as np
+    from .tile_view import RESIZE_MAX_AREA, RESIZE_MAX_RATIO
+    what = "windows of a resizing view must hold (y0, x0, d, wh, ww) per tile"
+    if windows is None:
+        raise ValueError(f"{what}: an (N, 5) int32 array (TileView(scale=).draw)")
+    if isinstance(windows, torch.Tensor) and windows.is_cuda:
+        if not (windows.dtype == torch.int32 and tuple(windows.shape) == (n, 5) and windows.is_contiguous()):
+            raise ValueError(f"device windows of a resizing view must be a contiguous int32 tensor of shape ({n}, 5)")
+        return windows
+    try:
+        win = windows.numpy() if isinstance(windows, torch.Tensor) else np.asarray(windows)
+        if win.dtype.kind not in "iu":
+            raise TypeError
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(f"{what}: an (N, 5) integer array") from None
+    if win.shape != (n, 5):
+        raise ValueError(f"{what}: an ({n}, 5) array, not one of shape {win.shape}")
+    win = win.astype(np.int64)
+    d, wh, ww = win[:, 2], win[:, 3], win[:, 4]
+    bad = (d < 0) | (d > 7) | ((d & ~int(d_mask)) != 0)
+    if bad.any():
+        raise ValueError(f"windows: tile {int(np.argmax(bad))} has the code {int(d[np.argmax(bad)])}, outside d_mask = {d_mask}")
+    odd = (d & 1) != 0
+    nu, nv = np.where(odd, ow, oh), np.where(odd, oh, ow)
+    hi_h = np.minimum(min(int(resize[0]), h), RESIZE_MAX_RATIO * nu.astype(np.int64))
+    hi_w = np.minimum(min(int(resize[1]), w), RESIZE_MAX_RATIO * nv.astype(np.int64))
+    bad = (wh < 1) | (wh > hi_h) | (ww < 1) | (ww > hi_w) | (wh * ww > RESIZE_MAX_AREA)
+    if bad.any():
+        t = int(np.argmax(bad))
+        raise ValueError(f"windows: tile {t} has a {int(wh[t])} x {int(ww[t])} window, outside 1 x 1 .. {int(hi_h[t])} x {int(hi_w[t])} "
+                         f"(resize = {tuple(resize)}, at most 16 times its {int(nu[t])} x {int(nv[t])} output and 2^22 pixels)")
+    bad = (win[:, 0] < 0) | (win[:, 0] > h - wh) | (win[:, 1] < 0) | (win[:, 1] > w - ww)
+    if bad.any():
+        t = int(np.argmax(bad))
+        raise ValueError(f"windows: tile {t} has its {int(wh[t])} x {int(ww[t])} window at ({int(win[t, 0])}, {int(win[t, 1])}), "
+                         f"outside the {h} x {w} tile")
+    return np.ascontiguousarray(win.astype(np.int32))
+
+
+def _view_windows(windows, n, h, w, oh, ow, d_mask, shrink=1, resize=None):
     """The (n, 3) int32 windows of a normalize_view call (no device needed).  numpy / CPU windows are range-checked here (ValueError) and
     come back as numpy; device windows are taken as they are -- the kernel masks the code and clamps the corner, nothing is read back.
-    shrink: the window is shrink times the (oh, ow) output (TileView(shrink=))."""
+    shrink: the window is shrink times the (oh, ow) output (TileView(shrink=)).  resize: (max_wh, max_ww) -- the (n, 5) windows of a
+    resizing view (_resize_windows)."""
     import numpy as np
+    if resize is not None:
+        return _resize_windows(windows, n, h, w, oh, ow, d_mask, resize)
     if windows is None:
         raise ValueError("windows must hold (y0, x0, d) per tile: an (N, 3) int32 array (TileView.draw)")
     if isinstance(windows, torch.Tensor) and windows.is_cuda:
@@ -412,17 +478,22 @@ def _view_windows(windows, n, h, w, oh, ow, d_mask, shrink=1):
     return np.ascontiguousarray(win.astype(np.int32))
 
 
-def _view_prepare(rgb, windows, size, d_mask, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, params, fmt, out, before_device=None, shrink=1):
+def _view_prepare(rgb, windows, size, d_mask, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, params, fmt, out, before_device=None, shrink=1,
+                  resize=None):
     """The checks of normalize_view (ValueError, in its order, nothing on the device before they pass; before_device(n): a caller's own
     checks at the end of them) and its arguments on the device -> (n, h, w, oh, ow, windows, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta,
     SlTensorFormat or None, out)."""
     from .tensor_format import TensorFormat
-    from .tile_view import check_size
+    from .tile_view import check_resize_size, check_size
     if not (isinstance(rgb, torch.Tensor) and rgb.dim() == 4 and rgb.shape[-1] == 3):
         raise ValueError("expected a contiguous CUDA uint8 tensor of shape (N, H, W, 3)")
     n, h, w = (int(v) for v in rgb.shape[:3])
-    oh, ow = check_size(size, h, w, d_mask, shrink)
-    win = _view_windows(windows, n, h, w, oh, ow, d_mask, shrink)
+    if resize is not None:                                   # a resizing view: any output size, windows of their own sizes
+        resize = _check_resize(resize, h, w, shrink)
+        oh, ow = check_resize_size(size, h, w, d_mask)
+    else:
+        oh, ow = check_size(size, h, w, d_mask, shrink)
+    win = _view_windows(windows, n, h, w, oh, ow, d_mask, shrink, resize)
     _route_check(M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, params, n)
     if fmt is not None and not isinstance(fmt, TensorFormat):
         raise ValueError("fmt must be a stainlib_amd.TensorFormat or None (the uint8 image)")
@@ -439,7 +510,7 @@ def _view_prepare(rgb, windows, size, d_mask, M_src, maxC_src, M_tgt, maxC_tgt, 
 
 
 def normalize_view(rgb, windows, size, d_mask=7, M_src=None, maxC_src=None, M_tgt=None, maxC_tgt=None, alpha_beta=None,
-                   augment_background=False, params=None, fmt=None, out=None, shrink=1):
+                   augment_background=False, params=None, fmt=None, out=None, shrink=1, resize=None):
     """A crop, flip and quarter turn per tile INSIDE the apply pass (sl_normalize_view): per tile the window windows[t] = (y0, x0, d) of
     the image that normalize_jitter (alpha_beta given), normalize_apply (M_src given) or nothing (M_src=None: the tiles' own bytes)
     writes, flipped along the width when d & 4 and then turned d & 3 quarter turns counter-clockwise -- torch.rot90(torch.flip(
@@ -451,11 +522,18 @@ def normalize_view(rgb, windows, size, d_mask=7, M_src=None, maxC_src=None, M_tg
     fmt: a stainlib_amd.TensorFormat -> the (N,3,oh,ow) tensor, else (N,oh,ow,3) uint8.  The statistics are the WHOLE tile's.
     shrink: 1, 2 or 4 (sl_normalize_view_shrink) -- the window is shrink times (oh, ow) and every output pixel the rounded mean of a
     shrink x shrink box of `full`, per channel (sum + shrink^2 / 2) >> (2 log2 shrink), boxes counted from the window's corner; the
-    flip and the turn as before (they commute with it).  size=None is then (h // shrink, w // shrink)."""
+    flip and the turn as before (they commute with it).  size=None is then (h // shrink, w // shrink).
+    resize: (max_wh, max_ww) -- a random-resized crop (sl_normalize_view_resize): windows is (N, 5) int32, (y0, x0, d, wh, ww) per tile
+    (TileView(scale=).draw), a window of wh x ww pixels in the tile's orientation, resampled to the output size by exact pixel-area
+    averaging in integers (stainlib_amd.tile_view.area_resample: the definition), then flipped and turned.  (max_wh, max_ww) is an
+    upper bound of the window sides, within the tile and at most 2^22 pixels together: the launch is sized from it.  A window side is
+    at most 16 times the output side it maps to; host windows beyond a limit are a ValueError, device windows are clamped.  (oh, ow)
+    need not fit in the tile (size=None: the tile's own size); a window smaller than the output comes out piecewise constant with
+    blended edges, not bilinear."""
     n, h, w, oh, ow, win, M_src, maxC_src, M_tgt, maxC_tgt, ab, f, out = _view_prepare(
-        rgb, windows, size, d_mask, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, params, fmt, out, shrink=shrink)
+        rgb, windows, size, d_mask, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, params, fmt, out, shrink=shrink, resize=resize)
     _call_view("sl_normalize_view", shrink, (_ptr(rgb), _ptr(out), n, h, w, oh, ow, _ptr(win), int(d_mask)), _ptr(M_src), _ptr(maxC_src),
-               _ptr(M_tgt), _ptr(maxC_tgt), _ptr(ab), 1 if augment_background else 0, _byref(params), _byref(f))
+               _ptr(M_tgt), _ptr(maxC_tgt), _ptr(ab), 1 if augment_background else 0, _byref(params), _byref(f), resize=resize)
     return out
 
 
@@ -519,24 +597,26 @@ def _hed_rows(x, what):
 
 
 def normalize_hed_view(rgb, windows, size, d_mask, hed_sigma, hed_bias, hed_applied, skimage_mode=0, M_src=None, maxC_src=None, M_tgt=None,
-                       maxC_tgt=None, alpha_beta=None, augment_background=False, params=None, fmt=None, out=None, shrink=1):
+                       maxC_tgt=None, alpha_beta=None, augment_background=False, params=None, fmt=None, out=None, shrink=1, resize=None):
     """normalize_view of hed_applied[t] ? HED(full[t]) : full[t] in ONE pass (sl_normalize_hed_view): `full` is normalize_view's (the
     route arguments are the same), HED(.) is hed_augment with the tile's hed_sigma / hed_bias ((N, 3) each), skimage_mode and a cutoff that
     never fails -- bit for bit hed_augment then normalize_view of the result, without a pixel outside the window being touched.
     hed_applied: (N,) int32, the decision per tile (normalize_sums gives it).
     skimage_mode 0 ("0.18", the pinned one) runs in the kernel; the other three go through that chain (same bits, two more passes).
-    shrink: normalize_view's, on that image (sl_normalize_hed_view_shrink); skimage_mode 0 only -- the chain does not know it."""
+    shrink: normalize_view's, on that image (sl_normalize_hed_view_shrink); skimage_mode 0 only -- the chain does not know it.
+    resize: normalize_view's, on that image (sl_normalize_hed_view_resize), with (N, 5) windows; skimage_mode 0 only."""
     def hed_checks(n):
         for x, what in ((hed_sigma, "hed_sigma"), (hed_bias, "hed_bias")):
             if _hed_rows(x, what) != n:
                 raise ValueError(f"{what} must have one row per tile ({n})")
         if skimage_mode not in (_ffi.HED_SKIMAGE_018, _ffi.HED_SKIMAGE_019, _ffi.HED_SKIMAGE_017, _ffi.HED_EXPERIMENTAL_LOG10):
             raise ValueError("skimage_mode must be one of the HED_* modes (0..3)")
-        _hed_shrink_ok(skimage_mode, shrink)
+        _hed_shrink_ok(skimage_mode, shrink, resize)
         if hed_applied is None:
             raise ValueError("hed_applied must hold the decision per tile: (N,) int32 (normalize_sums)")
     n, h, w, oh, ow, win, M_src, maxC_src, M_tgt, maxC_tgt, ab, f, out = _view_prepare(
-        rgb, windows, size, d_mask, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, params, fmt, out, before_device=hed_checks, shrink=shrink)
+        rgb, windows, size, d_mask, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, params, fmt, out, before_device=hed_checks, shrink=shrink,
+        resize=resize)
     dev = rgb.device
     sigma = _f64(hed_sigma, (n, 3), dev)
     bias = _f64(hed_bias, (n, 3), dev)
@@ -548,15 +628,18 @@ def normalize_hed_view(rgb, windows, size, d_mask, hed_sigma, hed_bias, hed_appl
         return normalize_view(img, win, size, d_mask, fmt=fmt, out=out)
     _call_view("sl_normalize_hed_view", shrink, (_ptr(rgb), _ptr(out), n, h, w, oh, ow, _ptr(win), int(d_mask)), _ptr(M_src), _ptr(maxC_src),
                _ptr(M_tgt), _ptr(maxC_tgt), _ptr(ab), 1 if augment_background else 0, _byref(params), _byref(f), _ptr(sigma), _ptr(bias),
-               _ptr(applied), int(skimage_mode))
+               _ptr(applied), int(skimage_mode), resize=resize)
     return out
 
 
-def _hed_shrink_ok(skimage_mode, shrink):
-    """ValueError for a HED skimage_mode that goes through the chain (every one but HED_SKIMAGE_018) under a view with a shrink: the
-    chain does not know it."""
+def _hed_shrink_ok(skimage_mode, shrink, resize=None):
+    """ValueError for a HED skimage_mode that goes through the chain (every one but HED_SKIMAGE_018) under a view with a shrink or a
+    resizing view (resize: anything but None): the chain does not know either."""
+    names = {_ffi.HED_SKIMAGE_019: "0.19", _ffi.HED_SKIMAGE_017: "0.17", _ffi.HED_EXPERIMENTAL_LOG10: "experimental_log10"}
+    if resize is not None and skimage_mode != _ffi.HED_SKIMAGE_018:
+        raise ValueError(f"skimage_mode {names.get(skimage_mode, skimage_mode)!r} ({skimage_mode}) goes through the hed_augment chain, which does "
+                         "not resample: a resizing view (TileView(scale=), resize=) needs skimage_mode '0.18' (0)")
     if shrink != 1 and skimage_mode != _ffi.HED_SKIMAGE_018:
-        names = {_ffi.HED_SKIMAGE_019: "0.19", _ffi.HED_SKIMAGE_017: "0.17", _ffi.HED_EXPERIMENTAL_LOG10: "experimental_log10"}
         raise ValueError(f"skimage_mode {names.get(skimage_mode, skimage_mode)!r} ({skimage_mode}) goes through the hed_augment chain, which has "
                          f"no shrink: a view with shrink={shrink} needs skimage_mode '0.18' (0)")
 
@@ -579,7 +662,7 @@ def _hed_call(hed, hed_sigmas, hed_biases, tiles, view=None):
     for x, what in ((hed_sigmas, "hed_sigmas"), (hed_biases, "hed_biases")):
         if x is not None and _hed_rows(x, what) != n:
             raise ValueError(f"{what} must have one row per tile ({n})")
-    _hed_shrink_ok(hed._skimage_mode, getattr(view, "shrink", 1))
+    _hed_shrink_ok(hed._skimage_mode, getattr(view, "shrink", 1), getattr(view, "scale", None))
     return True
 
 
@@ -635,7 +718,7 @@ def hed_stage(tiles, hed, hed_sigmas, hed_biases, view, windows, route, fmt=None
         size, d_mask, windows, win, shrink = None, 0, None, np.zeros((n, 3), dtype=np.int32), 1
     applied = hed_decide(tiles, hed._cutoff_range, **route)
     x = normalize_hed_view(tiles, win, size, d_mask, hed_sigmas, hed_biases, applied, hed._skimage_mode, fmt=fmt, out=out, shrink=shrink,
-                           **route)
+                           resize=_view_resize(view, win, tiles), **route)
     return x, windows, HedDraw(hed_sigmas, hed_biases, applied)
 
 
@@ -650,10 +733,29 @@ def _view_call(view, windows, tiles, draw=True):
     n, h, w = (int(v) for v in tiles.shape[:3])
     oh, ow = view.out_size(h, w)
     if windows is not None:
-        _view_windows(windows, n, h, w, oh, ow, view.d_mask, view.shrink)
+        _view_windows(windows, n, h, w, oh, ow, view.d_mask, view.shrink, _view_resize(view, windows, tiles))
     elif draw:
         windows = view.draw(n, h, w)
     return view.size, view.d_mask, windows, view.shrink
+
+
+def _view_resize(view, windows, tiles):
+    """resize= of the normalize_view call behind a batch method's view= (no device needed): None unless the view resizes
+    (TileView(scale=)); else the bound of the window sides -- of host windows their own largest sides, of device windows (never read
+    back) or none yet the largest the view can draw (TileView.window_bound)."""
+    import numpy as np
+    if view is None or not view.resizing:
+        return None
+    h, w = (int(v) for v in tiles.shape[1:3])
+    if windows is None or (isinstance(windows, torch.Tensor) and windows.is_cuda):
+        return view.window_bound(h, w)
+    try:
+        win = windows.numpy() if isinstance(windows, torch.Tensor) else np.asarray(windows)
+        if win.dtype.kind not in "iu" or win.ndim != 2 or win.shape[1] != 5 or win.shape[0] == 0:
+            raise TypeError
+    except (TypeError, ValueError, RuntimeError):
+        return view.window_bound(h, w)                       # (_resize_windows says what is wrong with them)
+    return max(1, min(h, int(win[:, 3].max()))), max(1, min(w, int(win[:, 4].max())))
 
 
 def route_stage(tiles, fit, route, fmt=None, out=None, view=None, windows=None, hed=None):
@@ -669,7 +771,8 @@ def route_stage(tiles, fit, route, fmt=None, out=None, view=None, windows=None, 
         return (x, M, maxC, status) + ((windows,) if view is not None else ()) + (draw,)
     if view is not None:
         size, d_mask, windows, shrink = _view_call(view, windows, tiles)
-        return normalize_view(tiles, windows, size, d_mask, fmt=fmt, out=out, shrink=shrink, **route), M, maxC, status, windows
+        return normalize_view(tiles, windows, size, d_mask, fmt=fmt, out=out, shrink=shrink, resize=_view_resize(view, windows, tiles),
+                              **route), M, maxC, status, windows
     return normalize_jitter(tiles, fmt=fmt, out=out, **route), M, maxC, status
 
 
@@ -902,6 +1005,7 @@ def _lab_view_prepare(rgb, windows, size, d_mask, fmt, out, view=None, before_de
     from the global numpy stream, drawn behind every check: a refused call draws nothing, and nothing goes to the device before it."""
     from .tensor_format import TensorFormat
     from .tile_view import check_size
+    _lab_no_resize(view)
     if view is not None:
         size, d_mask, _, shrink = _view_call(view, windows, rgb, draw=False)
     if not (isinstance(rgb, torch.Tensor) and rgb.dim() == 4 and rgb.shape[-1] == 3):
@@ -994,9 +1098,17 @@ def slab_view(rgb, windows, size, state, mode, d_mask=7, mask_background=False, 
     return out, windows
 
 
+def _lab_no_resize(view):
+    """ValueError for a resizing view (TileView(scale=)) in a Lab-family call: their fused pass has no resampling write side."""
+    if getattr(view, "resizing", False):
+        raise ValueError(f"a resizing view ({view!r}) is not supported by the Lab-family calls (Reinhard, luminosity, pooled or per "
+                         "tile): take their full-tile result through TensorFormat.convert(view=), which resamples")
+
+
 def lab_view_check(view, windows, tiles):
     """The view= / windows= pair of a Lab batch method, checked without a device and without a draw (ValueError: windows= without
     view=, and what _view_call refuses) -> whether there is a view."""
+    _lab_no_resize(view)
     if view is None and windows is None:
         return False
     _view_call(view, windows, tiles, draw=False)

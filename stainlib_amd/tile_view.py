@@ -9,12 +9,22 @@ the whole batch, so a code with odd k takes an (ow, oh) window.
 shrink = s in {1, 2, 4} is a change of magnification in the same pass (sl_normalize_view_shrink): the window is s times the output in
 both directions, and every output pixel is the rounded mean of an s x s box of the image at source resolution -- per channel
 (sum + s s / 2) >> (2 log2 s) of the uint8 bytes, boxes counted from the window's corner (any pixel, not only a multiple of s).
+
+scale = (lo, hi) makes the view a random-resized crop (sl_normalize_view_resize): a view of one tile is then (y0, x0, d, wh, ww), a
+window of wh rows and ww columns in the TILE's orientation, of random area and aspect ratio, resampled to the output size by exact
+pixel-area averaging in integers -- OpenCV's INTER_AREA for shrinking.  Along an axis of nw window pixels and no outputs, in coordinates
+scaled by no, source pixel k covers [k no, (k + 1) no), output i covers [i nw, (i + 1) nw) and c(i, k) is the length of their overlap;
+per channel b = (2 S + D) // (2 D) with S = sum cy(i, k) cx(j, l) window[k, l] and D = wh ww.  A window smaller than the output comes
+out piecewise constant with blended edges (the same formula), not bilinear.  area_resample below is that definition in numpy.
 """
 from __future__ import annotations
 
 import numpy as np
 
 SHRINKS = (1, 2, 4)
+RESIZE_MAX_RATIO = 16            # a window side is at most 16 times the output side it is resampled to (17 source pixels per output)
+RESIZE_MAX_AREA = 1 << 22        # wh ww: the weighted sums stay below 2^31
+RESIZE_MAX_PRODUCT = 1 << 30     # an output side times a window side: the scaled coordinates are 32-bit
 
 
 def _size2(size):
@@ -61,17 +71,74 @@ def check_size(size, h, w, d_mask, shrink=1):
     return oh, ow
 
 
+def _range2(x, what, upper=None):
+    try:
+        lo, hi = (float(v) for v in x)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be a pair (lo, hi), not {x!r}") from None
+    if not (0.0 < lo <= hi and np.isfinite(hi)) or (upper is not None and hi > upper):
+        raise ValueError(f"{what} must be a pair (lo, hi) with 0 < lo <= hi" + (f" <= {upper:g}" if upper is not None else "") + f", not {x!r}")
+    return lo, hi
+
+
+def check_resize_size(size, h, w, d_mask):
+    """(oh, ow) of a resizing view of size `size` (None: the tile's own (h, w)) out of (h, w) tiles: any size at least 1 x 1 -- the
+    window is resampled to it --, or ValueError beyond the 32-bit limit of the scaled coordinates."""
+    if not (isinstance(d_mask, (int, np.integer)) and not isinstance(d_mask, bool) and 0 <= d_mask <= 7):
+        raise ValueError(f"d_mask must be an int in 0..7, not {d_mask!r}")
+    oh, ow = (int(h), int(w)) if size is None else _size2(size)
+    if max(oh, ow) * max(int(h), int(w)) > RESIZE_MAX_PRODUCT:
+        raise ValueError(f"a {oh} x {ow} resizing view of a {h} x {w} tile is too large: the larger output side times the larger tile "
+                         f"side must not exceed 2^30")
+    return oh, ow
+
+
+def resize_side_max(no, side):
+    """the largest window side along an axis of `no` outputs in a tile side `side`"""
+    return min(int(side), RESIZE_MAX_RATIO * int(no))
+
+
+def overlap_matrix(nw, no):
+    """c of the definition: (no, nw) int64, c[i, k] = the overlap of [i nw, (i + 1) nw) and [k no, (k + 1) no)"""
+    i = np.arange(no, dtype=np.int64)[:, None]
+    k = np.arange(nw, dtype=np.int64)[None, :]
+    return np.maximum(0, np.minimum((i + 1) * nw, (k + 1) * no) - np.maximum(i * nw, k * no))
+
+
+def area_resample(window, nu, nv):
+    """The definition of the resizing view in numpy: the (wh, ww, C) uint8 `window` resampled to (nu, nv, C) uint8 by exact pixel-area
+    averaging, round half up -- per channel (2 S + D) // (2 D), S = cy @ window @ cx.T, D = wh ww."""
+    window = np.asarray(window)
+    wh, ww = window.shape[:2]
+    cy, cx = overlap_matrix(wh, nu), overlap_matrix(ww, nv)
+    S = np.einsum("ik,klc,jl->ijc", cy, window.astype(np.int64), cx)
+    D = wh * ww
+    return ((2 * S + D) // (2 * D)).astype(np.uint8)
+
+
 class TileView(object):
     """size: None (the full tile), an int or (oh, ow) -- the size of the OUTPUT.  flip: draw flips.  rot90: draw quarter turns (the
     view must then fit transposed as well).  Half turns are drawn whenever flips are: a flip along the height is a flip along the
     width and a half turn.  shrink: 1, 2 or 4 -- the window is shrink times the output, averaged down in boxes (see the module);
-    size=None is then (h // shrink, w // shrink)."""
+    size=None is then (h // shrink, w // shrink).
+    scale: None, or (lo, hi) with 0 < lo <= hi <= 1 -- the view is a random-resized crop: per tile a window of a random share of the
+    tile's area in [lo, hi] and a random aspect ratio ww / wh in ratio = (lo, hi), log-uniform, resampled to the output size by exact
+    area averaging (see the module).  Not with a shrink.  size=None is then the tile's own size."""
 
-    def __init__(self, size=None, flip=True, rot90=True, shrink=1):
+    def __init__(self, size=None, flip=True, rot90=True, shrink=1, scale=None, ratio=(3.0 / 4.0, 4.0 / 3.0)):
         self.size = None if size is None else _size2(size)
         self.flip = bool(flip)
         self.rot90 = bool(rot90)
         self.shrink = check_shrink(shrink)
+        self.scale = None if scale is None else _range2(scale, "scale", 1.0)
+        self.ratio = _range2(ratio, "ratio")
+        if self.scale is not None and self.shrink != 1:
+            raise ValueError(f"scale= (a resizing view) does not go with shrink={self.shrink}: the window's size is drawn per tile")
+
+    @property
+    def resizing(self):
+        """whether the view draws (y0, x0, d, wh, ww) and resamples (scale=)"""
+        return self.scale is not None
 
     @property
     def d_mask(self):
@@ -83,16 +150,31 @@ class TileView(object):
         return [c for c in range(8) if c & ~self.d_mask == 0]
 
     def out_size(self, h, w):
+        if self.resizing:
+            return check_resize_size(self.size, h, w, self.d_mask)
         return check_size(self.size, h, w, self.d_mask, self.shrink)
+
+    def window_bound(self, h, w):
+        """(max_wh, max_ww) of a resizing view of (h, w) tiles: the largest window sides a draw can give, in any orientation -- what
+        a call with windows on the device sizes its launch from.  The tile's sides, at most 16 times the larger output side they can
+        map to, and for a tile of more than 2^22 pixels both scaled down together (by sqrt(2^22 / (h w)), rounded down) until their
+        product is at most 2^22: a call takes ONE bound for all its windows, so no two of them may be tall and wide beyond it."""
+        oh, ow = self.out_size(h, w)
+        big = max(oh, ow) if self.d_mask & 1 else None
+        mh, mw = resize_side_max(big or oh, h), resize_side_max(big or ow, w)
+        return _reduce_area(mh, mw)
 
     def draw(self, n, h, w):
         """(n, 3) int32: y0, x0, d per tile, from the GLOBAL numpy stream (the convention of StainJitter.draw).  Per tile, in order:
         d = the np.random.randint(len(codes))-th code; y0 = np.random.randint(0, h - s wh + 1); x0 = np.random.randint(0, w - s ww + 1),
-        (wh, ww) the output size as that code's window sees it and s the shrink."""
+        (wh, ww) the output size as that code's window sees it and s the shrink.  A resizing view (scale=) returns (n, 5) int32,
+        y0, x0, d, wh, ww per tile: five draws per tile, in the order _draw_resize documents."""
         n = int(n)
         if n < 0:
             raise ValueError("n must be >= 0")
         oh, ow = self.out_size(h, w)
+        if self.resizing:
+            return self._draw_resize(n, int(h), int(w), oh, ow)
         s = self.shrink
         codes = self.codes
         win = np.empty((n, 3), dtype=np.int32)
@@ -104,5 +186,38 @@ class TileView(object):
             win[t, 2] = d
         return win
 
+    def _draw_resize(self, n, h, w, oh, ow):
+        """(n, 5) int32: y0, x0, d, wh, ww per tile, from the GLOBAL numpy stream.  Per tile, in order: d as in draw;
+        a = np.random.uniform(*scale); r = exp(np.random.uniform(log ratio[0], log ratio[1]));
+        wh = clip(floor(sqrt(a h w / r) + 0.5), 1, min(h, 16 nu, bh)), ww = clip(floor(sqrt(a h w r) + 0.5), 1, min(w, 16 nv, bw)) with
+        (nu, nv) the output size as that code's window sees it and (bh, bw) = window_bound(h, w), which keeps wh ww <= 2^22 (it is
+        (h, w) itself up to 2048 x 2048); y0 = np.random.randint(0, h - wh + 1); x0 = np.random.randint(0, w - ww + 1).  Five draws per tile, always: a
+        window that does not fit is CLAMPED, not redrawn -- this is not torchvision's rejection loop (ten tries, then a centre crop),
+        whose number of draws varies."""
+        codes = self.codes
+        lr0, lr1 = np.log(self.ratio[0]), np.log(self.ratio[1])
+        bh, bw = self.window_bound(h, w)
+        win = np.empty((n, 5), dtype=np.int32)
+        for t in range(n):
+            d = codes[np.random.randint(len(codes))]
+            nu, nv = (ow, oh) if d & 1 else (oh, ow)
+            a = np.random.uniform(self.scale[0], self.scale[1])
+            r = np.exp(np.random.uniform(lr0, lr1))
+            wh = int(np.clip(np.floor(np.sqrt(a * h * w / r) + 0.5), 1, resize_side_max(nu, min(h, bh))))
+            ww = int(np.clip(np.floor(np.sqrt(a * h * w * r) + 0.5), 1, resize_side_max(nv, min(w, bw))))
+            win[t] = (np.random.randint(0, h - wh + 1), np.random.randint(0, w - ww + 1), d, wh, ww)
+        return win
+
     def __repr__(self):
-        return f"TileView(size={self.size}, flip={self.flip}, rot90={self.rot90}" + (f", shrink={self.shrink})" if self.shrink != 1 else ")")
+        tail = f", shrink={self.shrink}" if self.shrink != 1 else ""
+        if self.resizing:
+            tail += f", scale={self.scale}, ratio={self.ratio}"
+        return f"TileView(size={self.size}, flip={self.flip}, rot90={self.rot90}{tail})"
+
+
+def _reduce_area(wh, ww):
+    """(wh, ww) as they are, or both scaled by sqrt(2^22 / (wh ww)) and rounded down (at least 1), until wh ww <= 2^22"""
+    while wh * ww > RESIZE_MAX_AREA:
+        f = np.sqrt(RESIZE_MAX_AREA / float(wh * ww))
+        wh, ww = max(1, int(wh * f)), max(1, int(ww * f))           # (f < 1: a side above 1 gets smaller, so this ends)
+    return int(wh), int(ww)
