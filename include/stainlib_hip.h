@@ -758,6 +758,33 @@ SL_API int sl_slab_view_shrink(const uint8_t* rgb, void* out, int n, int h, int 
 SL_API int sl_normalize_view_resize(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, int max_wh, int max_ww, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, const double* alpha_beta, int augment_background, const SlParams* params, const SlTensorFormat* fmt, void* stream);
 SL_API int sl_normalize_hed_view_resize(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, int max_wh, int max_ww, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, const double* alpha_beta, int augment_background, const SlParams* params, const SlTensorFormat* fmt, const double* hed_sigma, const double* hed_bias, const int32_t* hed_applied, int skimage_mode, void* stream);
 
+/* ---- stain separation in the view pass (stainlib_amd/csrc/separate_view.hip; an extension: segmentation and nuclei-detection training
+ * consumes the haematoxylin image, the eosin image and the concentration planes -- cropped, flipped, turned and often at half the
+ * magnification; behind sl_stain_separate a loader re-reads up to 9 B/px of images and 8 B/px of planes of the FULL tile to do so) -----
+ * "The same bits, elsewhere".  Let full = what sl_stain_separate writes for the same rgb, statistics, target (or none), lasso_lambda and
+ * outs->conc_dtype: full.norm, full.stain[0], full.stain[1] (h x w x 3 uint8 per tile) and full.conc (2 x h x w per tile).  With
+ * sl_normalize_view_shrink's view -- windows[t] = (y0, x0, d), d_mask, (oh, ow) the size of the OUTPUT, shrink = s, the clamp on the
+ * device, the flip BEFORE the turn --:
+ *     an image X, s = 1    rot90(flip_w_if(f, full.X[t][y0' : y0' + wh, x0' : x0' + ww]), k)
+ *     an image X, s = 2, 4 the box shrink of sl_normalize_view_shrink on those bytes: (S + s s / 2) >> (2 log2 s) of every s x s box,
+ *                          boxes counted from the window's corner, then the flip and the turn
+ *     conc, s = 1 only     the same slice, flip and turn of each of the two h x w planes of full.conc[t]: a permutation of elements of
+ *                          conc_dtype, bit for bit.  (A mean of floats is another definition and not offered.)
+ * A tile whose fit failed (NaN M_src, maxC_src <= 0): norm = the view of its source bytes, both stain images 255 in every byte,
+ * conc +0 -- sl_stain_separate's rule under the view.  Without a target (M_tgt == NULL and maxC_tgt == NULL): as there.
+ *   outs  SlSeparateOut as for sl_stain_separate (same struct, same size), NULL = not wanted.  fmt == NULL: each image is
+ *         n x oh x ow x 3 uint8.  Otherwise its three image pointers are read as pointers to elements of fmt->dtype, and each image is
+ *         the n x 3 x oh x ow tensor sl_to_tensor makes of the uint8 view, bit for bit, in fmt->layout.  conc: n x 2 x oh x ow
+ *         elements of conc_dtype, planar, H plane first; fmt does not apply to it.
+ * Only window pixels are read (3 B), solved (ONE lasso solve per source pixel) and written.
+ * SL_ERR_BADARG before anything is launched: what sl_stain_separate refuses (a NULL rgb / M_src / maxC_src / outs; a one-sided target;
+ * n, h or w <= 0 or h w > 2^30; a negative or NaN lasso_lambda; a struct_size mismatch; an unknown conc_dtype; no output requested; two
+ * outputs at one address or an output at rgb; conc not aligned to its element size); what sl_normalize_view_shrink refuses of windows,
+ * oh, ow, d_mask, shrink and the number of (tile, patch) pairs; shrink != 1 with a non-NULL conc; a format sl_to_tensor refuses; an
+ * image pointer not aligned to its element size.  No workspace; capture-safe like the rest (no allocation, no synchronisation, no
+ * memset). */
+SL_API int sl_stain_separate_view(const uint8_t* rgb, int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, int shrink, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, double lasso_lambda, const SlSeparateOut* outs, const SlTensorFormat* fmt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -198,6 +198,9 @@ for _name in ("sl_normalize_view", "sl_normalize_hed_view"):
     _res, _args = _SIGNATURES[_name]
     _SIGNATURES[_name + "_resize"] = (_res, _args[:9] + [C.c_int, C.c_int] + _args[9:])
 del _name, _res, _args
+# stain separation in the view pass (rgb, n, h, w, oh, ow, windows, d_mask, shrink, <sl_stain_separate's statistics, lambda and outs>, fmt, stream)
+_SIGNATURES["sl_stain_separate_view"] = (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P,
+                                                   C.c_double, C.POINTER(SlSeparateOut), C.POINTER(SlTensorFormat), _P])
 POOL_STATE_DOUBLES, POOL_M, POOL_MAXC, POOL_STATUS, POOL_MISS = 64, 0, 6, 8, 9
 POOL2_STATE_DOUBLES, POOL2_HIST_WORDS, POOL2_WHY = 256, 2 * 8192 + 8 * 32, 33
 SDICT_STATE_DOUBLES, SDICT_SUMS, SDICT_M, SDICT_STATUS, SDICT_SWEEPS, SDICT_ROUNDS, SDICT_MODE, SDICT_D, SDICT_NPX = 64, 32, 0, 6, 7, 8, 9, 10, 16

@@ -244,8 +244,9 @@ def _separate_want(want, conc_dtype):
     return want
 
 
-def _separate_out_fields(out, want, conc_dtype):
-    """What can be said about `out` without the tiles (no device needed): its form, and per field presence and dtype."""
+def _separate_out_fields(out, want, conc_dtype, image_dtype=torch.uint8):
+    """What can be said about `out` without the tiles (no device needed): its form, and per field presence and dtype (image_dtype: of the
+    three images -- uint8, or the format's under stain_separate_view(fmt=))."""
     if out is None:
         return
     if not (isinstance(out, tuple) and len(out) == 4):
@@ -255,7 +256,7 @@ def _separate_out_fields(out, want, conc_dtype):
             continue
         if name not in want:
             raise ValueError(f"out.{name} is given but {name!r} is not in want")
-        dtype = conc_dtype if name == "conc" else torch.uint8
+        dtype = conc_dtype if name == "conc" else image_dtype
         if not (isinstance(t, torch.Tensor) and t.dtype == dtype):
             raise ValueError(f"out.{name} must be a {dtype} tensor")
 
@@ -535,6 +536,94 @@ def normalize_view(rgb, windows, size, d_mask=7, M_src=None, maxC_src=None, M_tg
     _call_view("sl_normalize_view", shrink, (_ptr(rgb), _ptr(out), n, h, w, oh, ow, _ptr(win), int(d_mask)), _ptr(M_src), _ptr(maxC_src),
                _ptr(M_tgt), _ptr(maxC_tgt), _ptr(ab), 1 if augment_background else 0, _byref(params), _byref(f), resize=resize)
     return out
+
+
+# ---- stain separation in the view pass (sl_stain_separate_view; see include/stainlib_hip.h) ---------------------------------------------
+
+def _separate_view_args(want, conc_dtype, fmt, out, shrink, M_tgt, maxC_tgt):
+    """What can be said about a stain_separate_view call behind its size and windows and without the tiles (no device needed) -> want."""
+    from .tensor_format import TensorFormat
+    if (M_tgt is None) != (maxC_tgt is None):
+        raise ValueError("M_tgt and maxC_tgt go together: both, or neither (no target)")
+    want = _separate_want(want, conc_dtype)
+    if shrink != 1 and "conc" in want:
+        raise ValueError(f"shrink={shrink} does not go with 'conc' in want: a shrunk concentration plane would be a mean of floats, "
+                         "another definition; ask for the images alone, or take conc at shrink=1")
+    if fmt is not None and not isinstance(fmt, TensorFormat):
+        raise ValueError("fmt must be a stainlib_amd.TensorFormat or None (the uint8 images)")
+    _separate_out_fields(out, want, conc_dtype, fmt.dtype if fmt is not None else torch.uint8)
+    return want
+
+
+def stain_separate_view(rgb, windows, size, M_src, maxC_src, M_tgt=None, maxC_tgt=None, d_mask=7, lasso_lambda=0.01,
+                        want=("norm", "h", "e", "conc"), conc_dtype=torch.float32, fmt=None, out=None, shrink=1):
+    """stain_separate under normalize_view's crop, flip and quarter turn per tile, in ONE pass (sl_stain_separate_view) -> Separated:
+    per tile the window windows[t] = (y0, x0, d) of what stain_separate writes, flipped along the width when d & 4 and then turned d & 3
+    quarter turns -- bit for bit the torch slice / flip / rot90 of the full-tile result, without the pixels outside the window: one read
+    and one lasso solve per source pixel of the window.
+    size, d_mask, windows: normalize_view's (numpy / CPU windows are range-checked, device windows are clamped by the kernel; nothing
+    is synchronised).  M_tgt=None (and maxC_tgt=None): no target, as in stain_separate.
+    fmt: a stainlib_amd.TensorFormat -> norm, h and e are (N,3,oh,ow) tensors, bit for bit fmt.convert of the uint8 views; None ->
+    (N,oh,ow,3) uint8.  conc is (N,2,oh,ow) planes of conc_dtype either way.
+    shrink: 1, 2 or 4 -- the images box-shrunk as in normalize_view (the window is shrink times (oh, ow)); not with 'conc' in want.
+    out: a Separated of caller buffers in the view's shapes (None where the library allocates).
+    A tile whose fit failed (NaN M_src, maxC_src <= 0): norm = the view of the tile, h = e = white, conc = 0."""
+    from .tile_view import check_size
+    if not (isinstance(rgb, torch.Tensor) and rgb.dim() == 4 and rgb.shape[-1] == 3):
+        raise ValueError("expected a contiguous CUDA uint8 tensor of shape (N, H, W, 3)")
+    n, h, w = (int(v) for v in rgb.shape[:3])
+    oh, ow = check_size(size, h, w, d_mask, shrink)
+    win = _view_windows(windows, n, h, w, oh, ow, d_mask, shrink)
+    if M_src is None or maxC_src is None:
+        raise ValueError("M_src and maxC_src are needed: the per-tile fit (macenko_fit / vahadane_fit)")
+    want = _separate_view_args(want, conc_dtype, fmt, out, shrink, M_tgt, maxC_tgt)
+    _check_tiles(rgb)
+    dev = rgb.device
+    if not isinstance(win, torch.Tensor):
+        win = torch.from_numpy(win).to(dev)
+    if win.device != dev:
+        raise ValueError(f"windows must be on {dev}")
+    f, res = None, []
+    for k, name in enumerate(Separated._fields):
+        t = out[k] if out is not None else None
+        if name not in want:
+            res.append(None)
+        elif name != "conc":
+            f, t = _image_out(t, rgb, n, oh, ow, fmt, "view")
+            res.append(t)
+        elif t is None:
+            res.append(torch.empty((n, 2, oh, ow), dtype=conc_dtype, device=dev))
+        elif not (t.device == dev and tuple(t.shape) == (n, 2, oh, ow) and t.is_contiguous()):
+            raise ValueError(f"out.conc must be a contiguous {conc_dtype} tensor of shape {(n, 2, oh, ow)} on {dev}")
+        else:
+            res.append(t)
+    if fmt is not None and f is None:                                # (conc alone: the format is still checked by the C side)
+        f = _tensor_format(fmt)[0]
+    res = Separated(*res)
+    M_src, maxC_src, M_tgt, maxC_tgt, _ = _route_upload(n, dev, M_src, maxC_src, M_tgt, maxC_tgt)
+    o = _ffi.default_separate_out()
+    o.conc_dtype = _TENSOR_DTYPES[conc_dtype]
+    o.norm, o.stain[0], o.stain[1], o.conc = (t.data_ptr() if t is not None else None for t in res)
+    _call("sl_stain_separate_view", _ptr(rgb), n, h, w, oh, ow, _ptr(win), int(d_mask), int(shrink), _ptr(M_src), _ptr(maxC_src),
+          _ptr(M_tgt), _ptr(maxC_tgt), float(lasso_lambda), C.byref(o), _byref(f))
+    return res
+
+
+def separate_view_check(view, windows, tensor_format, want, conc_dtype, tiles):
+    """The view= / windows= / tensor_format= arguments of separate_batch, checked without a device and without a draw (ValueError) ->
+    whether the call goes through stain_separate_view."""
+    if view is None:
+        if windows is not None:
+            raise ValueError("view must be a stainlib_amd.TileView (windows= goes with view=)")
+        if tensor_format is not None:
+            raise ValueError("tensor_format= goes with view=: the fused full-tile tensor is view=TileView(None, flip=False, rot90=False)")
+        return False
+    if getattr(view, "resizing", False):
+        raise ValueError(f"a resizing view ({view!r}) is not supported by separate_batch: take the full-tile images through "
+                         "TensorFormat.convert(view=), which resamples")
+    _, _, _, shrink = _view_call(view, windows, tiles, draw=False)
+    _separate_view_args(want, conc_dtype, tensor_format, None, shrink, None, None)
+    return True
 
 
 # ---- HED augmentation behind the apply pass (sl_normalize_sums, sl_normalize_hed_view; see include/stainlib_hip.h) ------------------------

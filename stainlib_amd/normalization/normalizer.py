@@ -194,20 +194,36 @@ class ExtractiveStainNormalizer(object):
         return x, M, maxC, status
 
     # -- stain separation (an extension: torchstain's normalize(..., stains=True), the concentration maps of staintools) ----
-    def separate_batch(self, tiles, want=("norm", "h", "e", "conc"), conc_dtype=None, normalize=True, ws=None):
+    def separate_batch(self, tiles, want=("norm", "h", "e", "conc"), conc_dtype=None, normalize=True, ws=None, tensor_format=None, view=None,
+                       windows=None):
         """(N,H,W,3) uint8 device tensor -> (Separated, M_src, maxC_src, status): the per-tile fit, then ONE pass that writes what
         ``want`` names -- norm (transform_batch's image), h / e (the haematoxylin-only / eosin-only image, (N,H,W,3) uint8) and conc
         (the normalised concentrations, (N,2,H,W) planes of ``conc_dtype``: float32 by default, float16 or bfloat16).
         ``normalize=False``: no target (no fit() needed) -- every tile under its own stain matrix, conc = the raw concentrations.
-        A tile whose status is non-zero: norm = the tile, h = e = white, conc = 0."""
+        A tile whose status is non-zero: norm = the tile, h = e = white, conc = 0.
+        ``view``: a ``stainlib_amd.TileView`` -- the unchanged fit of the WHOLE tiles, then ONE pass that writes per tile only the window
+        ``windows[t]`` (default: ``view.draw(N, H, W)``, drawn behind every check) of each wanted output, flipped and turned
+        (engine.stain_separate_view): bit for bit the torch slice / flip / rot90 of the call without a view, the images (N,oh,ow,3) and
+        conc (N,2,oh,ow); the call then returns (Separated, M_src, maxC_src, status, windows).  ``TileView(shrink=2 or 4)`` box-shrinks
+        the images as in transform_batch and does not go with 'conc' in ``want``; a resizing view (``TileView(scale=)``) is refused.
+        ``tensor_format``: a ``stainlib_amd.TensorFormat`` (with ``view`` only; ``TileView(None, flip=False, rot90=False)`` is the
+        fused full-tile tensor) -- norm, h and e are then (N,3,oh,ow) tensors, bit for bit ``tensor_format.convert`` of the uint8 views."""
         import torch
         from .. import engine
         conc_dtype = torch.float32 if conc_dtype is None else conc_dtype
         want = engine._separate_want(want, conc_dtype)
+        with_view = engine.separate_view_check(view, windows, tensor_format, want, conc_dtype, tiles)
         if normalize and not hasattr(self, "stain_matrix_target"):
             raise ValueError("separate_batch(normalize=True) needs a fitted target: call fit() first, or pass normalize=False")
+        if with_view:
+            engine._check_tiles(tiles)
         M, maxC, status = self._fit_tiles(tiles, ws=ws)
         M_t, c_t = self._target_on(tiles.device) if normalize else (None, None)
+        if with_view:
+            size, d_mask, windows, shrink = engine._view_call(view, windows, tiles)          # (the draw, behind every check)
+            sep = engine.stain_separate_view(tiles, windows, size, M, maxC, M_t, c_t, d_mask=d_mask, want=want, conc_dtype=conc_dtype,
+                                             fmt=tensor_format, shrink=shrink)
+            return sep, M, maxC, status, windows
         sep = engine.stain_separate(tiles, M, maxC, M_t, c_t, want=want, conc_dtype=conc_dtype)
         return sep, M, maxC, status
 
