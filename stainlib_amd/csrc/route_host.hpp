@@ -75,4 +75,36 @@ inline void with_format_or_u8(const SlTensorFormat* fmt, bool aligned, bool wide
     else f(u8, lay, std::false_type{}, std::false_type{});
 }
 
+// ---- the four route views (sl_normalize_view_shrink / _view_resize, sl_normalize_hed_view_shrink / _hed_view_resize) -------------------
+struct RouteView { int mode; SlParams p; float ylimf; };      // what the common checks hand on: kView*, the parameters, tissue_ylimf
+
+// The common checks, in the order the entry points have always made them -- a call that is wrong in two ways keeps its return code --:
+// check_shape, the geometry (a callable returning view_geometry's or view_resize_geometry's code), route_of, params_ok, format_ok.
+template <class Geometry>
+inline int route_view_checks(const uint8_t* rgb, const void* out, int n, int h, int w, Geometry&& geometry, const double* M_src,
+                             const double* maxC_src, const double* M_tgt, const double* maxC_tgt, const double* alpha_beta,
+                             int augment_background, const SlParams* params, const SlTensorFormat* fmt, RouteView& v) {
+    if (const int rc = check_shape(rgb, out, n, h, w)) return rc;
+    if (const int rc = geometry()) return rc;
+    if (const int rc = route_of(M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, augment_background, v.mode)) return rc;
+    if (!params_ok(params)) return SL_ERR_BADARG;
+    if (fmt && !format_ok(fmt)) return SL_ERR_BADARG;
+    v.p = params_or_defaults(params);
+    v.ylimf = tissue_ylimf(v.p);
+    return SL_OK;
+}
+
+// A kernel family k<DT, LAYOUT, MODE> as a value (a function template cannot be a template argument, a generic lambda can be passed),
+// and its launch on nblocks workgroups of kWG threads with args (no ALIGNED / WIDE variants: view_kernels.hpp)
+#define SL_VIEW_FAMILY(k) [](auto dt, auto lay, auto m) { return k<decltype(dt)::value, decltype(lay)::value, decltype(m)::value>; }
+template <class Family, class... Args>
+inline int launch_route_view(Family family, const SlTensorFormat* fmt, int mode, long nblocks, void* stream, Args... args) {
+    with_format_or_u8(fmt, false, false, [&](auto dt, auto lay, auto, auto) {
+        with_mode(mode, [&](auto m) {
+            hipLaunchKernelGGL(family(dt, lay, m), dim3((unsigned)nblocks), dim3(kWG), 0, (hipStream_t)stream, args...);
+        });
+    });
+    return launch_status();
+}
+
 }  // namespace sl

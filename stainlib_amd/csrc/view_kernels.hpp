@@ -126,13 +126,17 @@ __device__ __forceinline__ void store_view4(typename Elem<DT>::type* base, size_
 // ---- workgroup; k_lab_view (lab_view_kernels.hpp) loops them over a run of patches behind one table fill ------------------------------
 // The view of one tile (block-uniform): the dihedral code as a transposition and two reversals, and the clamped window.  s: the shrink
 // (1, 2 or 4; block-uniform, a kernel argument) -- the window is wh x ww BOXES of s x s source pixels at the pixel (y0, x0).
-struct ViewTile {
+struct Dihedral {                                                                 // the ONE decode of a (masked) code: ViewTile, ResizeTile
     bool tr, ry, rx;
-    int wh, ww, y0, x0;
-    __device__ __forceinline__ ViewTile(const int32_t* windows, int tile, int d_mask, int h, int w, int oh, int ow, int s) {
-        const int d = __builtin_amdgcn_readfirstlane(windows[3 * (size_t)tile + 2]) & d_mask;
+    __device__ __forceinline__ explicit Dihedral(int d) {
         const int k = d & 3;
         tr = k & 1; ry = (k >> 1) & 1; rx = ((k >> 1) ^ k ^ (d >> 2)) & 1;
+    }
+};
+struct ViewTile : Dihedral {
+    int wh, ww, y0, x0;
+    __device__ __forceinline__ ViewTile(const int32_t* windows, int tile, int d_mask, int h, int w, int oh, int ow, int s)
+        : Dihedral(__builtin_amdgcn_readfirstlane(windows[3 * (size_t)tile + 2]) & d_mask) {
         wh = tr ? ow : oh; ww = tr ? oh : ow;                                     // the window, in boxes of s x s source pixels
         y0 = max(0, min(__builtin_amdgcn_readfirstlane(windows[3 * (size_t)tile + 0]), h - s * wh));
         x0 = max(0, min(__builtin_amdgcn_readfirstlane(windows[3 * (size_t)tile + 1]), w - s * ww));

@@ -53,15 +53,12 @@ __host__ __device__ inline int resize_patch_edge(int no, int nw) {
 // the largest window side along an axis of `no` outputs under the call's bound
 __host__ __device__ inline int resize_side_max(int no, int bound) { return (int)(16L * no < (long)bound ? 16L * no : (long)bound); }
 
-// The view of one tile (block-uniform): the code as in ViewTile, the clamped window and the patch edges along the window's two axes.
-struct ResizeTile {
-    bool tr, ry, rx;
+// The view of one tile (block-uniform): the code (Dihedral, view_kernels.hpp), the clamped window and the patch edges along the window's two axes.
+struct ResizeTile : Dihedral {
     int nu, nv, wh, ww, y0, x0, bu, bv;
-    __device__ __forceinline__ ResizeTile(const int32_t* windows, int tile, int d_mask, int h, int w, int oh, int ow, int max_wh, int max_ww) {
+    __device__ __forceinline__ ResizeTile(const int32_t* windows, int tile, int d_mask, int h, int w, int oh, int ow, int max_wh, int max_ww)
+        : Dihedral(__builtin_amdgcn_readfirstlane(windows[5 * (size_t)tile + 2]) & d_mask) {
         const int32_t* const wv = windows + 5 * (size_t)tile;
-        const int d = __builtin_amdgcn_readfirstlane(wv[2]) & d_mask;
-        const int k = d & 3;
-        tr = k & 1; ry = (k >> 1) & 1; rx = ((k >> 1) ^ k ^ (d >> 2)) & 1;
         nu = tr ? ow : oh; nv = tr ? oh : ow;                                     // the outputs along the window's rows and columns
         wh = max(1, min(__builtin_amdgcn_readfirstlane(wv[3]), resize_side_max(nu, max_wh)));
         ww = max(1, min(__builtin_amdgcn_readfirstlane(wv[4]), resize_side_max(nv, max_ww)));

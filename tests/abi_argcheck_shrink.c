@@ -84,6 +84,8 @@ int main(void) {
     EXPECT(sl_normalize_hed_view_shrink(rgb, out, n, h, w, 8, 8, win, 7, 2, 0, 0, 0, 0, 0, 0, 0, 0, 0, sg, ap, SL_HED_SKIMAGE_018, 0), SL_ERR_BADARG);
     EXPECT(sl_normalize_hed_view_shrink(rgb, out, n, h, w, 8, 8, win, 7, 2, 0, 0, 0, 0, 0, 0, 0, 0, sg, sg, 0, SL_HED_SKIMAGE_018, 0), SL_ERR_BADARG);
     EXPECT(sl_normalize_hed_view_shrink(rgb, out, n, h, w, 8, 8, win, 7, 4, 0, 0, 0, 0, 0, 0, 0, 0, sg, sg, ap, SL_HED_SKIMAGE_019, 0), SL_ERR_BADARG);
+    EXPECT(sl_normalize_hed_view_shrink(rgb, out, n, h, w, 8, 8, win, 7, 4, 0, 0, 0, 0, 0, 0, 0, 0, sg, sg, ap, SL_HED_EXPERIMENTAL_LOG10 + 1, 0), SL_ERR_BADARG);
+    EXPECT(sl_normalize_hed_view_shrink(rgb, out, n, h, w, 8, 8, win, 7, 2, 0, 0, 0, 0, 0, 0, 0, 0, sg, sg, ap, -1, 0), SL_ERR_BADARG);
     EXPECT(sl_reinhard_view_shrink(rgb, out, n, h, w, 8, 8, win, 7, 2, 0, d6, 1, 0.8, st, ws, wsb, 0, 0), SL_ERR_BADARG);       /* no target means */
     EXPECT(sl_reinhard_view_shrink(rgb, out, n, h, w, 8, 8, win, 7, 2, d6, d6, 1, 0.8, st, 0, wsb, 0, 0), SL_ERR_WORKSPACE);
     EXPECT(sl_luminosity_view_shrink(rgb, out, n, h, w, 8, 8, win, 7, 4, 95.0, st, ws, wsb - 1, &f, 0), SL_ERR_WORKSPACE);
