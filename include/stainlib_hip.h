@@ -785,6 +785,33 @@ SL_API int sl_normalize_hed_view_resize(const uint8_t* rgb, void* out, int n, in
  * memset). */
 SL_API int sl_stain_separate_view(const uint8_t* rgb, int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, int shrink, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, double lasso_lambda, const SlSeparateOut* outs, const SlTensorFormat* fmt, void* stream);
 
+/* ---- companion planes through the windows of a view (stainlib_amd/csrc/planes_view.hip; an extension: segmentation and nuclei-detection
+ * training carries per-pixel companions of every tile -- class map, instance map, loss mask, tissue mask, distance map -- which have to
+ * go through the window, the flip, the turn and the change of magnification of their image) -------------------------------------------
+ * planes: n x c x h x w elements of elem_bytes bytes (1, 2, 4 or 8; any type, only bits are moved), contiguous; out: n x c x oh x ow of
+ * the same.  windows: the ones the image call took -- max_wh == max_ww == 0: n x 3 int32 (y0, x0, d) of sl_normalize_view_shrink under
+ * shrink = s in {1, 2, 4}; both above 0: n x 5 int32 (y0, x0, d, wh, ww) of sl_normalize_view_resize under that bound (shrink = 1).  d is
+ * masked with d_mask and the window is clamped on the device by those calls' own rules, so a companion sees the window its image saw.
+ * Per tile t and plane ch, with k = d & 3, f = d & 4, (nu, nv) = (ow, oh) for odd k, else (oh, ow), and the source window
+ * win = planes[t, ch][y0' : y0' + s nu, x0' : x0' + s nv] (a resizing view: [y0' : y0' + wh', x0' : x0' + ww']):
+ *     SL_PLANES_NEAREST   R[i, j] = win[ky(i), kx(j)], a bit copy; along an axis of nw window pixels and no outputs
+ *                         k(i) = ((2 i + 1) nw) / (2 no), the pixel under the output's centre (i itself for the plain view, s i + s / 2
+ *                         under a shrink); the product stays below 2^31 under the resizing view's limits
+ *     SL_PLANES_AREA      elem_bytes = 1 only: the images' own definition on one channel -- (S + s s / 2) >> (2 log2 s) of every s x s box,
+ *                         or the exact area average (2 S + D) / (2 D) of sl_normalize_view_resize
+ *     out[t, ch] = rot90(flip_w_if(f, R), k)
+ * The order matters: the centre sample does NOT commute with a reversal when nw / no is even (nw = 10, no = 5: 1 3 5 7 9 against
+ * 0 2 4 6 8 after the reversal); R is sampled in the TILE's orientation.  Without a shrink or a resize both modes are the same permutation.
+ * SL_ERR_BADARG before anything is launched: a NULL planes, out or windows; n, c, h, w, oh or ow <= 0; h w > 2^30; elem_bytes not 1, 2, 4
+ * or 8; planes or out not aligned to elem_bytes; an unknown mode; SL_PLANES_AREA with elem_bytes != 1; exactly one of the two bounds
+ * zero, or a negative bound; what sl_normalize_view_shrink / sl_normalize_view_resize refuse of h, w, oh, ow, d_mask, shrink and the
+ * bounds; more (plane, patch) pairs than 2^31 - 1.  n c h w elem_bytes may pass 2^32: all byte offsets are size_t.  out == planes is
+ * not supported.  No workspace; capture-safe like the rest. */
+#define SL_PLANES_NEAREST 0
+#define SL_PLANES_AREA    1
+SL_API int sl_view_planes(const void* planes, void* out, int n, int c, int h, int w, int elem_bytes, int oh, int ow,
+                          const int32_t* windows, int d_mask, int shrink, int max_wh, int max_ww, int mode, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

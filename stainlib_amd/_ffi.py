@@ -201,6 +201,10 @@ del _name, _res, _args
 # stain separation in the view pass (rgb, n, h, w, oh, ow, windows, d_mask, shrink, <sl_stain_separate's statistics, lambda and outs>, fmt, stream)
 _SIGNATURES["sl_stain_separate_view"] = (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P,
                                                    C.c_double, C.POINTER(SlSeparateOut), C.POINTER(SlTensorFormat), _P])
+# companion planes through the windows of a view (planes, out, n, c, h, w, elem_bytes, oh, ow, windows, d_mask, shrink, max_wh, max_ww, mode, stream)
+_SIGNATURES["sl_view_planes"] = (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int,
+                                           C.c_int, C.c_int, _P])
+PLANES_NEAREST, PLANES_AREA = range(2)
 POOL_STATE_DOUBLES, POOL_M, POOL_MAXC, POOL_STATUS, POOL_MISS = 64, 0, 6, 8, 9
 POOL2_STATE_DOUBLES, POOL2_HIST_WORDS, POOL2_WHY = 256, 2 * 8192 + 8 * 32, 33
 SDICT_STATE_DOUBLES, SDICT_SUMS, SDICT_M, SDICT_STATUS, SDICT_SWEEPS, SDICT_ROUNDS, SDICT_MODE, SDICT_D, SDICT_NPX = 64, 32, 0, 6, 7, 8, 9, 10, 16

@@ -46,11 +46,10 @@
 //          wave issues 64 such reads per patch, behind 4096 source pixels of arithmetic: left as it is.
 #pragma once
 #include "jitter_kernels.hpp"        // JitterK, the {gamma, od32} table; tensor_kernels.hpp and apply_pass.hpp through it
+#include "view_geometry.hpp"         // kViewB, kViewPitch, Dihedral, ViewTile, ViewPatch
 
 namespace sl {
 
-constexpr int kViewB = 64;                       // patch edge in pixels
-constexpr int kViewPitch = kViewB + 1;           // LDS row pitch in dwords (odd: see above)
 constexpr int kViewRaw = 0, kViewApply = 1, kViewJitTissue = 2, kViewJitAll = 3;     // which pass `full` is
 
 typedef uint32_t sl_u32x2u __attribute__((ext_vector_type(2), aligned(1)));
@@ -124,47 +123,7 @@ __device__ __forceinline__ void store_view4(typename Elem<DT>::type* base, size_
 
 // ---- the pieces of a view pass: geometry, read side, LDS stage, write side.  view_body below is their sequence for one patch per
 // ---- workgroup; k_lab_view (lab_view_kernels.hpp) loops them over a run of patches behind one table fill ------------------------------
-// The view of one tile (block-uniform): the dihedral code as a transposition and two reversals, and the clamped window.  s: the shrink
-// (1, 2 or 4; block-uniform, a kernel argument) -- the window is wh x ww BOXES of s x s source pixels at the pixel (y0, x0).
-struct Dihedral {                                                                 // the ONE decode of a (masked) code: ViewTile, ResizeTile
-    bool tr, ry, rx;
-    __device__ __forceinline__ explicit Dihedral(int d) {
-        const int k = d & 3;
-        tr = k & 1; ry = (k >> 1) & 1; rx = ((k >> 1) ^ k ^ (d >> 2)) & 1;
-    }
-};
-struct ViewTile : Dihedral {
-    int wh, ww, y0, x0;
-    __device__ __forceinline__ ViewTile(const int32_t* windows, int tile, int d_mask, int h, int w, int oh, int ow, int s)
-        : Dihedral(__builtin_amdgcn_readfirstlane(windows[3 * (size_t)tile + 2]) & d_mask) {
-        wh = tr ? ow : oh; ww = tr ? oh : ow;                                     // the window, in boxes of s x s source pixels
-        y0 = max(0, min(__builtin_amdgcn_readfirstlane(windows[3 * (size_t)tile + 0]), h - s * wh));
-        x0 = max(0, min(__builtin_amdgcn_readfirstlane(windows[3 * (size_t)tile + 1]), w - s * ww));
-    }
-};
-// One patch of the tile's output (i0, j0; bh x bw pixels, at most kViewB / s square), the source block it comes from (ys, xs; nu rows of
-// nv pixels, s times the patch) and the affine map from output to LDS pixel: the s x s box of output pixel (il, jl) of the patch has its
-// first pixel (lowest row and column) at LDS pixel a0 + il ai + jl aj -- at s = 1 the pixel itself.
-struct ViewPatch {
-    int i0, j0, bh, bw, nu, nv, ys, xs, a0, ai, aj;
-    ViewPatch() = default;                                                        // (filled in by resize_patch, view_resize_kernels.hpp)
-    __device__ __forceinline__ ViewPatch(const ViewTile& t, int patch, int npx, int oh, int ow, int s) {
-        constexpr int PITCH = kViewPitch;
-        const int B = kViewB >> (s >> 1);                                         // kViewB / s for s = 1, 2, 4, without a division
-        const bool tr = t.tr, ry = t.ry, rx = t.rx;
-        i0 = (patch / npx) * B; j0 = (patch % npx) * B;                           // the patch, in output pixels
-        bh = min(B, oh - i0); bw = min(B, ow - j0);
-        const int u0 = tr ? j0 : i0;                                              // its rows and columns in the (flipped, turned) window
-        const int nub = tr ? bw : bh;                                             // (in boxes)
-        const int v0 = tr ? i0 : j0;
-        const int nvb = tr ? bh : bw;
-        nu = s * nub; nv = s * nvb;
-        ys = t.y0 + s * (ry ? t.wh - u0 - nub : u0); xs = t.x0 + s * (rx ? t.ww - v0 - nvb : v0);   // the source block: nu rows of nv pixels
-        const int su = ry ? -s * PITCH : s * PITCH, sv = rx ? -s : s;
-        a0 = (ry ? (nu - s) * PITCH : 0) + (rx ? nv - s : 0);
-        ai = tr ? sv : su; aj = tr ? su : sv;
-    }
-};
+// (the geometry -- Dihedral, ViewTile, ViewPatch -- is in view_geometry.hpp)
 
 // ---- read side: the four chunks of this lane (lr = tid >> 4, lc = tid & 15), requested before any arithmetic
 __device__ __forceinline__ void view_read(const ViewPatch& g, const uint8_t* src, size_t nbytes, int w, int lr, int lc, Chunk (&in)[4]) {

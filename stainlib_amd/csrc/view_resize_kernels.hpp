@@ -41,67 +41,7 @@
 
 namespace sl {
 
-constexpr int kResizeMaxRatio = 16;              // wh <= 16 nu, ww <= 16 nv: at most 17 taps per axis
-constexpr int kResizeMaxArea = 1 << 22;          // wh ww: 2 S + D < 2^31
-constexpr long kResizeMaxProduct = 1L << 30;     // an output side times a window side: the scaled coordinates are 32-bit
-
-// outputs per patch along an axis of `no` outputs from `nw` window pixels (nw <= 16 no): min(64, 63 no / nw), at least 3; does not grow with nw
-__host__ __device__ inline int resize_patch_edge(int no, int nw) {
-    if (no > nw) return 63L * no >= 64L * nw ? 64 : 63;
-    return 63 * no / nw;
-}
-// the largest window side along an axis of `no` outputs under the call's bound
-__host__ __device__ inline int resize_side_max(int no, int bound) { return (int)(16L * no < (long)bound ? 16L * no : (long)bound); }
-
-// The view of one tile (block-uniform): the code (Dihedral, view_kernels.hpp), the clamped window and the patch edges along the window's two axes.
-struct ResizeTile : Dihedral {
-    int nu, nv, wh, ww, y0, x0, bu, bv;
-    __device__ __forceinline__ ResizeTile(const int32_t* windows, int tile, int d_mask, int h, int w, int oh, int ow, int max_wh, int max_ww)
-        : Dihedral(__builtin_amdgcn_readfirstlane(windows[5 * (size_t)tile + 2]) & d_mask) {
-        const int32_t* const wv = windows + 5 * (size_t)tile;
-        nu = tr ? ow : oh; nv = tr ? oh : ow;                                     // the outputs along the window's rows and columns
-        wh = max(1, min(__builtin_amdgcn_readfirstlane(wv[3]), resize_side_max(nu, max_wh)));
-        ww = max(1, min(__builtin_amdgcn_readfirstlane(wv[4]), resize_side_max(nv, max_ww)));
-        y0 = max(0, min(__builtin_amdgcn_readfirstlane(wv[0]), h - wh));
-        x0 = max(0, min(__builtin_amdgcn_readfirstlane(wv[1]), w - ww));
-        bu = resize_patch_edge(nu, wh); bv = resize_patch_edge(nv, ww);
-    }
-};
-
-// One OUTPUT axis of a patch (block-uniform): o0 + t, t = 0 .. nb - 1, are its outputs; the axis has `no` outputs from `nw` window pixels,
-// runs backwards through the window when rev, and its source pixels start at window pixel `lo` (= LDS pixel 0 of that axis), `stride`
-// dwords apart in LDS.
-struct ResizeAxis {
-    int o0, nb, no, nw, lo, stride;
-    bool rev;
-    // the output's index along the window axis
-    __device__ __forceinline__ int at(int t) const { return rev ? no - 1 - (o0 + t) : o0 + t; }
-};
-
-// Patch `patch` of the tile: false when the tile has fewer patches.  g: i0, j0, bh, bw and the source block ys, xs, nu x nv for view_read
-// and view_stage; ai, aj: the patch's row and column axis.
-__device__ __forceinline__ bool resize_patch(const ResizeTile& t, int patch, int oh, int ow, ViewPatch& g, ResizeAxis& ai, ResizeAxis& aj) {
-    const int bi = t.tr ? t.bv : t.bu, bj = t.tr ? t.bu : t.bv;                  // the patch edge along output rows and columns
-    const int npi = (oh + bi - 1) / bi, npj = (ow + bj - 1) / bj;
-    if (patch >= npi * npj) return false;
-    g.i0 = (patch / npj) * bi; g.j0 = (patch % npj) * bj;
-    g.bh = min(bi, oh - g.i0); g.bw = min(bj, ow - g.j0);
-    ai.o0 = g.i0; ai.nb = g.bh; ai.no = oh; ai.nw = t.tr ? t.ww : t.wh; ai.rev = t.tr ? t.rx : t.ry; ai.stride = t.tr ? 1 : kViewPitch;
-    aj.o0 = g.j0; aj.nb = g.bw; aj.no = ow; aj.nw = t.tr ? t.wh : t.ww; aj.rev = t.tr ? t.ry : t.rx; aj.stride = t.tr ? kViewPitch : 1;
-    int n[2];
-    ResizeAxis* const ax[2] = {&ai, &aj};
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-        ResizeAxis& a = *ax[e];
-        const uint32_t first = (uint32_t)(a.rev ? a.no - a.o0 - a.nb : a.o0);    // the patch's outputs along the window axis: first .. first + nb - 1
-        a.lo = (int)(first * (uint32_t)a.nw / (uint32_t)a.no);
-        n[e] = (int)(((first + (uint32_t)a.nb) * (uint32_t)a.nw + (uint32_t)a.no - 1u) / (uint32_t)a.no) - a.lo;   // <= 64 (resize_patch_edge)
-    }
-    g.ys = t.y0 + (t.tr ? aj.lo : ai.lo); g.nu = min(t.tr ? n[1] : n[0], kViewB);     // (the min: the LDS block, whatever the arithmetic above)
-    g.xs = t.x0 + (t.tr ? ai.lo : aj.lo); g.nv = min(t.tr ? n[0] : n[1], kViewB);
-    g.a0 = 0; g.ai = ai.stride; g.aj = aj.stride;
-    return true;
-}
+// (the geometry -- the limits, resize_patch_edge, resize_side_max, ResizeTile, ResizeAxis, resize_patch -- is in view_geometry.hpp)
 
 // ---- taps: for output t of each patch axis the first LDS pixel it overlaps | the number it overlaps << 8 (threads 0 .. 2 kViewB - 1)
 __device__ __forceinline__ void resize_taps(const ResizeAxis& ai, const ResizeAxis& aj, uint32_t* s_tap, int tid) {

@@ -538,6 +538,74 @@ def normalize_view(rgb, windows, size, d_mask=7, M_src=None, maxC_src=None, M_tg
     return out
 
 
+# ---- companion planes through the windows of a view (sl_view_planes; see include/stainlib_hip.h and TileView.apply) ---------------------
+
+PLANES_DTYPES = (torch.bool, torch.uint8, torch.int8, torch.int16, torch.float16, torch.bfloat16, torch.int32, torch.float32, torch.int64,
+                 torch.float64)
+_PLANES_MODES = {"nearest": _ffi.PLANES_NEAREST, "area": _ffi.PLANES_AREA}
+
+
+def planes_hw(planes):
+    """(H, W) of companion planes (N, H, W) or (N, C, H, W), or ValueError (no device needed)"""
+    if not (isinstance(planes, torch.Tensor) and planes.dim() in (3, 4)):
+        raise ValueError("planes must be a contiguous CUDA tensor of shape (N, H, W) or (N, C, H, W)"
+                         + (f", not one of rank {planes.dim()}" if isinstance(planes, torch.Tensor) else ""))
+    return int(planes.shape[-2]), int(planes.shape[-1])
+
+
+def view_planes(planes, windows, size, d_mask=7, mode="nearest", out=None, shrink=1, resize=None):
+    """Companion planes through the windows of a view pass (sl_view_planes): `planes` (N, H, W) or (N, C, H, W), contiguous, on the
+    device, of a 1-, 2-, 4- or 8-byte dtype (PLANES_DTYPES; complex is refused) -> (N, oh, ow) or (N, C, oh, ow) of the same dtype.
+    windows, size, d_mask, shrink, resize: those of the normalize_view call of the images -- (N, 3) rows (y0, x0, d), or with
+    resize = (max_wh, max_ww) the (N, 5) rows of a resizing view; host windows are range-checked by _view_windows (ValueError), device
+    windows are clamped by the kernel with the image kernels' rules.
+    mode: "nearest" -- per tile and plane the window is sampled in the TILE's orientation at the pixel under each output's centre,
+    ((2 i + 1) nw) // (2 no) along an axis (stainlib_amd.tile_view.nearest_index), a bit copy, THEN flipped along the width if d & 4
+    and turned d & 3 quarter turns; "area" -- uint8 only, the images' box mean / area average per plane.
+    out: a contiguous tensor of the result's shape, dtype and device to write into (not `planes` itself)."""
+    from .tile_view import check_resize_size, check_size
+    h, w = planes_hw(planes)
+    n = int(planes.shape[0])
+    c = int(planes.shape[1]) if planes.dim() == 4 else 1
+    if planes.dtype not in PLANES_DTYPES:
+        raise ValueError(f"planes of dtype {planes.dtype} are not supported: an element must have 1, 2, 4 or 8 bytes "
+                         "(bool, uint8, int8, int16, float16, bfloat16, int32, float32, int64, float64)")
+    if not isinstance(mode, str) or mode not in _PLANES_MODES:
+        raise ValueError(f"mode must be 'nearest' or 'area', not {mode!r}")
+    if mode == "area" and planes.dtype != torch.uint8:
+        raise ValueError(f"mode='area' averages and is defined on uint8 planes only, not {planes.dtype} (labels go with mode='nearest')")
+    if resize is not None:
+        resize = _check_resize(resize, h, w, shrink)
+        oh, ow = check_resize_size(size, h, w, d_mask)
+    else:
+        oh, ow = check_size(size, h, w, d_mask, shrink)
+    win = _view_windows(windows, n, h, w, oh, ow, d_mask, shrink, resize)
+    if not planes.is_cuda:
+        raise ValueError("planes must be a contiguous CUDA tensor of shape (N, H, W) or (N, C, H, W), not a CPU tensor")
+    if not planes.is_contiguous():
+        raise ValueError("planes must be a contiguous CUDA tensor of shape (N, H, W) or (N, C, H, W): this one is not contiguous "
+                         "(channels-last planes are not supported)")
+    if n < 1 or c < 1 or h < 1 or w < 1:
+        raise ValueError(f"planes of shape {tuple(planes.shape)} hold no element")
+    dev = planes.device
+    shape = (n, oh, ow) if planes.dim() == 3 else (n, c, oh, ow)
+    if out is None:
+        out = torch.empty(shape, dtype=planes.dtype, device=dev)
+    elif not (isinstance(out, torch.Tensor) and tuple(out.shape) == shape and out.dtype == planes.dtype and out.device == dev
+              and out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous {planes.dtype} tensor of shape {shape} on {dev}")
+    elif out.data_ptr() == planes.data_ptr():
+        raise ValueError("out must not be planes itself: the view is not done in place")
+    if not isinstance(win, torch.Tensor):
+        win = torch.from_numpy(win).to(dev)
+    if win.device != dev:
+        raise ValueError(f"windows must be on {dev}")
+    mh, mw = resize if resize is not None else (0, 0)
+    _call("sl_view_planes", _ptr(planes), _ptr(out), n, c, h, w, planes.element_size(), oh, ow, _ptr(win), int(d_mask), int(shrink), mh, mw,
+          _PLANES_MODES[mode])
+    return out
+
+
 # ---- stain separation in the view pass (sl_stain_separate_view; see include/stainlib_hip.h) ---------------------------------------------
 
 def _separate_view_args(want, conc_dtype, fmt, out, shrink, M_tgt, maxC_tgt):
@@ -832,10 +900,16 @@ def _view_resize(view, windows, tiles):
     """resize= of the normalize_view call behind a batch method's view= (no device needed): None unless the view resizes
     (TileView(scale=)); else the bound of the window sides -- of host windows their own largest sides, of device windows (never read
     back) or none yet the largest the view can draw (TileView.window_bound)."""
+    if view is None or not view.resizing:
+        return None
+    return _view_resize_hw(view, windows, *(int(v) for v in tiles.shape[1:3]))
+
+
+def _view_resize_hw(view, windows, h, w):
+    """_view_resize on the tile size itself (TileView.apply has planes, not tiles)"""
     import numpy as np
     if view is None or not view.resizing:
         return None
-    h, w = (int(v) for v in tiles.shape[1:3])
     if windows is None or (isinstance(windows, torch.Tensor) and windows.is_cuda):
         return view.window_bound(h, w)
     try:

@@ -116,6 +116,52 @@ def area_resample(window, nu, nv):
     return ((2 * S + D) // (2 * D)).astype(np.uint8)
 
 
+def nearest_index(nw, no):
+    """The centre sample of the companion planes (TileView.apply, sl_view_planes) along an axis of nw window pixels and no outputs:
+    (no,) int64, k[i] = ((2 i + 1) nw) // (2 no), the pixel under the centre of output i -- i itself when nw == no, s i + s // 2 when
+    nw == s no."""
+    nw, no = int(nw), int(no)
+    if nw < 1 or no < 1:
+        raise ValueError(f"nearest_index needs at least one window pixel and one output, not ({nw}, {no})")
+    i = np.arange(no, dtype=np.int64)
+    return ((2 * i + 1) * nw) // (2 * no)
+
+
+def nearest_resample(window, nu, nv):
+    """The definition of mode="nearest" in numpy: the (wh, ww, ...) `window` of any dtype resampled to (nu, nv, ...) by the centre
+    sample, a copy of elements -- window[nearest_index(wh, nu)][:, nearest_index(ww, nv)]."""
+    window = np.asarray(window)
+    wh, ww = window.shape[:2]
+    return window[nearest_index(wh, nu)][:, nearest_index(ww, nv)]
+
+
+def view_planes_reference(planes, windows, size, shrink=1, mode="nearest"):
+    """TileView.apply in numpy, on windows already in range (what engine._view_windows accepts): `planes` (N, H, W) or (N, C, H, W) of
+    any dtype, `windows` (N, 3) rows (y0, x0, d) under `shrink`, or (N, 5) rows (y0, x0, d, wh, ww) of a resizing view; size = (oh, ow).
+    Per tile and plane: the window resampled in the TILE's orientation -- nearest_resample, or for mode="area" (uint8) area_resample,
+    of which the shrink's box mean (S + s s / 2) >> (2 log2 s) is the case wh = s nu --, THEN flipped along the width if d & 4 and
+    turned d & 3 quarter turns counter-clockwise."""
+    planes = np.asarray(planes)
+    windows = np.asarray(windows)
+    if mode not in ("nearest", "area"):
+        raise ValueError(f"mode must be 'nearest' or 'area', not {mode!r}")
+    if mode == "area" and planes.dtype != np.uint8:
+        raise ValueError("mode='area' is defined on uint8 planes only")
+    oh, ow = _size2(size)
+    s = check_shrink(shrink)
+    x = planes[:, None] if planes.ndim == 3 else planes
+    out = np.empty(x.shape[:2] + (oh, ow), dtype=x.dtype)
+    for t in range(x.shape[0]):
+        y0, x0, d = (int(v) for v in windows[t, :3])
+        nu, nv = (ow, oh) if d & 1 else (oh, ow)
+        wh, ww = (int(windows[t, 3]), int(windows[t, 4])) if windows.shape[1] == 5 else (s * nu, s * nv)
+        for c in range(x.shape[1]):
+            win = x[t, c, y0:y0 + wh, x0:x0 + ww]
+            r = nearest_resample(win, nu, nv) if mode == "nearest" else area_resample(win[..., None], nu, nv)[..., 0]
+            out[t, c] = np.rot90(r[:, ::-1] if d & 4 else r, d & 3)
+    return out[:, 0] if planes.ndim == 3 else out
+
+
 class TileView(object):
     """size: None (the full tile), an int or (oh, ow) -- the size of the OUTPUT.  flip: draw flips.  rot90: draw quarter turns (the
     view must then fit transposed as well).  Half turns are drawn whenever flips are: a flip along the height is a flip along the
@@ -207,6 +253,24 @@ class TileView(object):
             ww = int(np.clip(np.floor(np.sqrt(a * h * w * r) + 0.5), 1, resize_side_max(nv, min(w, bw))))
             win[t] = (np.random.randint(0, h - wh + 1), np.random.randint(0, w - ww + 1), d, wh, ww)
         return win
+
+    def apply(self, planes, windows=None, mode="nearest", out=None):
+        """The per-pixel companions of a batch -- class map, instance map, loss mask, tissue mask, distance map -- through the windows
+        their images went through (sl_view_planes): `planes` is a contiguous device tensor (N, H, W) or (N, C, H, W) of any 1-, 2-, 4-
+        or 8-byte dtype, `windows` what the image call with this view returned for (H, W) tiles (or self.draw(N, H, W)); returns
+        (N, oh, ow) / (N, C, oh, ow) of the same dtype.  Nothing is drawn here.
+        mode="nearest": every output element is a bit copy of the element under its centre (labels are never averaged), sampled in the
+        TILE's orientation and then flipped and turned (see nearest_index); mode="area" (uint8 only: 0 / 255 masks, soft maps): the
+        images' own box mean / area average per plane.  Without shrink or scale both are the same permutation.
+        Host windows are range-checked as for the image calls (ValueError); device windows are clamped by the kernel with the image
+        kernels' rules.  out: a tensor to write into."""
+        from . import engine
+        if windows is None:
+            raise ValueError("windows is required: pass what the image call with this view returned, or view.draw(N, H, W) "
+                             "-- apply draws nothing itself")
+        h, w = engine.planes_hw(planes)
+        return engine.view_planes(planes, windows, self.size, self.d_mask, mode=mode, out=out, shrink=self.shrink,
+                                  resize=engine._view_resize_hw(self, windows, h, w))
 
     def __repr__(self):
         tail = f", shrink={self.shrink}" if self.shrink != 1 else ""
