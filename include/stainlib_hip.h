@@ -812,6 +812,42 @@ SL_API int sl_stain_separate_view(const uint8_t* rgb, int n, int h, int w, int o
 SL_API int sl_view_planes(const void* planes, void* out, int n, int c, int h, int w, int elem_bytes, int oh, int ow,
                           const int32_t* windows, int d_mask, int shrink, int max_wh, int max_ww, int mode, void* stream);
 
+/* ---- arbitrary rotation, zoom, shear and translation in the one-pass loader: an affine view, bilinear for the images and nearest for
+ * their companion planes (stainlib_amd/csrc/view_affine.hip; an extension: segmentation and nuclei-detection recipes rotate every tile by
+ * any angle, zoom 0.8 - 1.2, shear and translate, image and label maps alike -- behind the call that is affine_grid / grid_sample on
+ * the widest data type, once per image and once per label plane, on pixels the rotation then pushes out of the frame) ----------------
+ * The definition is in integers, so "bit for bit" applies.  windows: n x 6 int32 on the device, windows[t] = (cy, cx, a00, a01, a10, a11),
+ * all in units of 2^-16 source pixel (Q = 65536); pixel k of an axis covers [k, k + 1).  (cy, cx) is the source position of the CENTRE of
+ * the output, a.. the source displacement per output pixel.  (oh, ow) is the size of the OUTPUT, one for the call.  For output pixel
+ * (i, j), with u = 2 i + 1 - oh and v = 2 j + 1 - ow:
+ *     Y = cy + ((a00 u + a01 v) >> 1)        X = cx + ((a10 u + a11 v) >> 1)                 (arithmetic shift = floor)
+ * Images (sl_normalize_view_affine; bilinear, 8-bit weights): ty = Y - Q/2, ky = ty >> 16, fy = (ty >> 8) & 255, the same for x; with
+ * p00, p01, p10, p11 the bytes of full[t] at (ky, kx), (ky, kx + 1), (ky + 1, kx), (ky + 1, kx + 1), per channel
+ *     b = ((256 - fy) ((256 - fx) p00 + fx p01) + fy ((256 - fx) p10 + fx p11) + 32768) >> 16
+ * full[t] is, as for every other view, the h x w x 3 uint8 image the statistics pattern names (sl_normalize_view's rule: the tile's
+ * own bytes, sl_normalize_apply's image or sl_normalize_jitter's): normalised / jittered per SOURCE pixel, every statistic the whole
+ * tile's, a tile whose fit failed gives its own bytes.  A tap outside [0, h) x [0, w) is the fill byte of its channel, fill_rgb =
+ * r | g << 8 | b << 16 in OUTPUT space (it is not normalised).  fmt != NULL: the tensor sl_to_tensor makes of b, as everywhere else.
+ * Planes (sl_view_planes_affine; nearest): out[t, ch][i, j] = planes[t, ch][Y >> 16, X >> 16], a bit copy of an elem_bytes element;
+ * outside the plane the low elem_bytes bytes of fill_bits.  planes / out: n x c x h x w and n x c x oh x ow, as for sl_view_planes.
+ * What follows from the definition: A = Q I with c = (h Q / 2, w Q / 2) and (oh, ow) = (h, w) is the identity; the eight signed
+ * permutation matrices (entries 0, +-Q) with the centre on a window's centre are sl_normalize_view's rot90(flip(window)), bit for bit;
+ * A = 2 Q I is (S + 2) >> 2 of every 2 x 2 box, the shrink = 2 rule.  A = 4 Q I is NOT the 4 x 4 box: bilinear takes four taps, the
+ * middle 2 x 2 of each box -- beyond two source pixels per output it aliases, and downsampling further is shrink / the resizing view.
+ * Limits, so that every quantity above is 32-bit: h, w, oh, ow <= 8192; the row sums Ry = |a00| + |a01| and Rx = |a10| + |a11| each
+ * <= 2 Q; cy in [-2^28, h Q + 2^28], cx in [-2^28, w Q + 2^28].  Zero and singular matrices are legal (a constant, a line).
+ * max_r (Q16, 1 <= max_r <= 2 Q): an upper bound of max(Ry, Rx) over the windows of this call; the launch is sized from it (the windows
+ * are never read back).  On the device cy and cx are clamped to their range; a tile with max(Ry, Rx) > max_r is written as fill
+ * EVERYWHERE -- there is no sensible clamp of a matrix.
+ * SL_ERR_BADARG before anything is launched: what sl_normalize_view / sl_view_planes refuse of rgb / planes, out, n, c, h, w,
+ * elem_bytes, alignment, the statistics pattern, params and fmt; a NULL windows; oh < 1 or ow < 1; h, w, oh or ow > 8192; max_r outside
+ * [1, 2 Q]; fill_rgb >= 2^24; more (tile, patch) or (plane, patch) pairs than 2^31 - 1 (a patch is min(64, 1 + 62 Q / max_r) outputs
+ * square).  No workspace; capture-safe like the rest (no allocation, no synchronisation, no memset).  out == rgb / out == planes is
+ * not supported.  Bicubic and antialiased filters, perspective and elastic warps, reflect / replicate borders and bilinear planes are
+ * other definitions and not offered. */
+SL_API int sl_normalize_view_affine(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int max_r, uint32_t fill_rgb, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, const double* alpha_beta, int augment_background, const SlParams* params, const SlTensorFormat* fmt, void* stream);
+SL_API int sl_view_planes_affine(const void* planes, void* out, int n, int c, int h, int w, int elem_bytes, int oh, int ow, const int32_t* windows, int max_r, uint64_t fill_bits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

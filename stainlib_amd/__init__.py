@@ -5,6 +5,7 @@ The export list mirrors stainlib/__init__.py:19-30.  ReinhardStainNormalizer and
 TensorFormat (an extension) turns the batched operators' uint8 results into model-ready float tensors.
 StainJitter (an extension) draws the per-tile (alpha, beta) of the augment_batch methods: stain jitter inside the apply pass.
 TileView (an extension) draws the per-tile crop / flip / quarter turn that view= applies inside the same pass.
+TileAffine (an extension) draws a per-tile rotation by any angle, zoom, shear and translation for view=: bilinear, in integers.
 Separated (an extension) is what the normalizers' separate / separate_batch return: per-stain images and concentration maps.
 Importing the package does not need a GPU; calling anything numeric does, and fails loudly without the
 HIP library -- there is no CPU fallback.
@@ -18,7 +19,7 @@ from .normalization.normalizer import (ExtractiveStainNormalizer, MacenkoNormali
                                        ReinhardStainNormalizer, VahadaneNormalizer)
 from .tensor_format import TensorFormat  # noqa: F401
 from .separated import Separated  # noqa: F401
-from .tile_view import TileView  # noqa: F401
+from .tile_view import TileAffine, TileView  # noqa: F401
 from .utils.stain_utils import LuminosityStandardizer  # noqa: F401
 from .utils.excepts import InvalidRangeError, TissueMaskException  # noqa: F401
 

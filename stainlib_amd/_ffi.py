@@ -204,6 +204,12 @@ _SIGNATURES["sl_stain_separate_view"] = (C.c_int, [_P, C.c_int, C.c_int, C.c_int
 # companion planes through the windows of a view (planes, out, n, c, h, w, elem_bytes, oh, ow, windows, d_mask, shrink, max_wh, max_ww, mode, stream)
 _SIGNATURES["sl_view_planes"] = (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int,
                                            C.c_int, C.c_int, _P])
+# the affine views (windows: n x 6 int32 on the device): rgb, out, n, h, w, oh, ow, windows, max_r, fill_rgb, <sl_normalize_view's statistics,
+# params, fmt>, stream -- and planes, out, n, c, h, w, elem_bytes, oh, ow, windows, max_r, fill_bits, stream
+_SIGNATURES["sl_normalize_view_affine"] = (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_uint32, _P, _P, _P, _P,
+                                                     _P, C.c_int, C.POINTER(SlParams), C.POINTER(SlTensorFormat), _P])
+_SIGNATURES["sl_view_planes_affine"] = (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_uint64,
+                                                  _P])
 PLANES_NEAREST, PLANES_AREA = range(2)
 POOL_STATE_DOUBLES, POOL_M, POOL_MAXC, POOL_STATUS, POOL_MISS = 64, 0, 6, 8, 9
 POOL2_STATE_DOUBLES, POOL2_HIST_WORDS, POOL2_WHY = 256, 2 * 8192 + 8 * 32, 33

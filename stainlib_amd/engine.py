@@ -606,6 +606,138 @@ def view_planes(planes, windows, size, d_mask=7, mode="nearest", out=None, shrin
     return out
 
 
+# ---- the affine views: rotation by any angle, zoom, shear, translation (sl_normalize_view_affine, sl_view_planes_affine; TileAffine) ------
+
+def _is_affine(view):
+    from .tile_view import TileAffine
+    return isinstance(view, TileAffine)
+
+
+def _no_affine(view, what, instead):
+    """ValueError for an affine view in a call that has no bilinear write side"""
+    if _is_affine(view):
+        raise ValueError(f"an affine view ({view!r}) is not supported by {what}: {instead}")
+
+
+def _affine_windows(windows, n, h, w, size, max_r):
+    """The (n, 6) int32 windows of an affine call (no device needed).  numpy / CPU windows are range-checked (tile_view.
+    affine_check_windows: ValueError) and come back as numpy; device windows are taken as they are -- the kernel clamps the centres and
+    writes a tile whose row sums pass max_r as fill; nothing is read back."""
+    from .tile_view import affine_check_windows
+    if isinstance(windows, torch.Tensor) and windows.is_cuda:
+        if not (windows.dtype == torch.int32 and tuple(windows.shape) == (n, 6) and windows.is_contiguous()):
+            raise ValueError(f"device windows of an affine view must be a contiguous int32 tensor of shape ({n}, 6)")
+        affine_check_windows(torch.zeros((n, 6), dtype=torch.int32), n, h, w, size, max_r)      # (the size and the bound alone)
+        return windows
+    return affine_check_windows(windows, n, h, w, size, max_r)
+
+
+def _affine_bound(view, windows):
+    """max_r of the call behind an affine view (no device needed): of host windows their own largest row sum (at least 1; beyond the
+    limit: the limit, and affine_check_windows says so), of device windows (never read back) or none yet the largest the view can
+    draw (TileAffine.bound)."""
+    import numpy as np
+    from .tile_view import AFFINE_MAX_R, affine_row_sums
+    if windows is None or (isinstance(windows, torch.Tensor) and windows.is_cuda):
+        return view.bound
+    try:
+        win = windows.numpy() if isinstance(windows, torch.Tensor) else np.asarray(windows)
+        if win.dtype.kind not in "iu" or win.ndim != 2 or win.shape[1] != 6 or win.shape[0] == 0:
+            raise TypeError
+    except (TypeError, ValueError, RuntimeError):
+        return view.bound                                    # (affine_check_windows says what is wrong with them)
+    return max(1, min(AFFINE_MAX_R, int(affine_row_sums(win).max())))
+
+
+def normalize_view_affine(rgb, windows, size, max_r, fill=255, M_src=None, maxC_src=None, M_tgt=None, maxC_tgt=None, alpha_beta=None,
+                          augment_background=False, params=None, fmt=None, out=None):
+    """A rotation by any angle, zoom, shear and translation per tile INSIDE the apply pass (sl_normalize_view_affine): per tile the image
+    that normalize_jitter (alpha_beta given), normalize_apply (M_src given) or nothing (M_src=None: the tiles' own bytes) writes, sampled
+    bilinearly with 8-bit weights at the positions windows[t] = (cy, cx, a00, a01, a10, a11) names (2^-16 source pixels; stainlib_amd.
+    tile_view.affine_resample is the definition, bit for bit).  The image is normalised / jittered per SOURCE pixel and the statistics
+    are the WHOLE tile's.
+    size: (oh, ow) of the OUTPUT, an int, or None (the tile's own size); it need not fit in the tile.  h, w, oh, ow <= 8192.
+    max_r: an int, 1 .. 2 Q = 131072 -- an upper bound of the row sums |a00| + |a01|, |a10| + |a11| of the call's windows (TileAffine.bound);
+    the launch is sized from it.
+    fill: an int or three ints 0 .. 255, the OUTPUT bytes of what lies outside the tile (not normalised).
+    windows: (N, 6) int32 (TileAffine.draw).  numpy or CPU tensor: range-checked, ValueError.  Device tensor: taken as it is -- the kernel
+    clamps the centres into their range and writes a tile whose row sums pass max_r as fill everywhere; nothing is synchronised.
+    fmt: a stainlib_amd.TensorFormat -> the (N,3,oh,ow) tensor, else (N,oh,ow,3) uint8."""
+    from .tensor_format import TensorFormat
+    from .tile_view import _fill3, affine_check_size
+    if not (isinstance(rgb, torch.Tensor) and rgb.dim() == 4 and rgb.shape[-1] == 3):
+        raise ValueError("expected a contiguous CUDA uint8 tensor of shape (N, H, W, 3)")
+    n, h, w = (int(v) for v in rgb.shape[:3])
+    oh, ow = affine_check_size(size, h, w)
+    f3 = _fill3(fill)
+    win = _affine_windows(windows, n, h, w, size, max_r)
+    _route_check(M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, params, n)
+    if fmt is not None and not isinstance(fmt, TensorFormat):
+        raise ValueError("fmt must be a stainlib_amd.TensorFormat or None (the uint8 image)")
+    _check_tiles(rgb)
+    dev = rgb.device
+    if not isinstance(win, torch.Tensor):
+        win = torch.from_numpy(win).to(dev)
+    if win.device != dev:
+        raise ValueError(f"windows must be on {dev}")
+    M_src, maxC_src, M_tgt, maxC_tgt, ab = _route_upload(n, dev, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta)
+    f, out = _image_out(out, rgb, n, oh, ow, fmt, "view")
+    _call("sl_normalize_view_affine", _ptr(rgb), _ptr(out), n, h, w, oh, ow, _ptr(win), int(max_r), f3[0] | (f3[1] << 8) | (f3[2] << 16),
+          _ptr(M_src), _ptr(maxC_src), _ptr(M_tgt), _ptr(maxC_tgt), _ptr(ab), 1 if augment_background else 0, _byref(params), _byref(f))
+    return out
+
+
+def _fill_bits(fill, dtype):
+    """the bit pattern of `fill` as one element of a planes dtype, as an unsigned int (ValueError if it is no number of that dtype)"""
+    try:
+        t = torch.tensor([fill], dtype=dtype)
+    except (TypeError, ValueError, RuntimeError, OverflowError):
+        raise ValueError(f"fill must be a number that a {dtype} element can hold, not {fill!r}") from None
+    es = t.element_size()
+    bits = int(t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[es])[0])
+    return bits & ((1 << (8 * es)) - 1)
+
+
+def view_planes_affine(planes, windows, size, max_r, fill=0, out=None):
+    """Companion planes through the windows of an affine view (sl_view_planes_affine): `planes` (N, H, W) or (N, C, H, W), contiguous, on
+    the device, of a 1-, 2-, 4- or 8-byte dtype (PLANES_DTYPES) -> (N, oh, ow) or (N, C, oh, ow) of the same dtype: per element the
+    NEAREST source element (Y >> 16, X >> 16) of the image view's coordinates, a bit copy (stainlib_amd.tile_view.affine_nearest is
+    the definition), outside the plane `fill` cast to the planes' dtype.  windows, size, max_r: those of the normalize_view_affine call of
+    the images.  out: a contiguous tensor of the result's shape, dtype and device to write into (not `planes` itself)."""
+    from .tile_view import affine_check_size
+    h, w = planes_hw(planes)
+    n = int(planes.shape[0])
+    c = int(planes.shape[1]) if planes.dim() == 4 else 1
+    if planes.dtype not in PLANES_DTYPES:
+        raise ValueError(f"planes of dtype {planes.dtype} are not supported: an element must have 1, 2, 4 or 8 bytes "
+                         "(bool, uint8, int8, int16, float16, bfloat16, int32, float32, int64, float64)")
+    oh, ow = affine_check_size(size, h, w)
+    bits = _fill_bits(fill, planes.dtype)
+    win = _affine_windows(windows, n, h, w, size, max_r)
+    if not planes.is_cuda:
+        raise ValueError("planes must be a contiguous CUDA tensor of shape (N, H, W) or (N, C, H, W), not a CPU tensor")
+    if not planes.is_contiguous():
+        raise ValueError("planes must be a contiguous CUDA tensor of shape (N, H, W) or (N, C, H, W): this one is not contiguous "
+                         "(channels-last planes are not supported)")
+    if n < 1 or c < 1:
+        raise ValueError(f"planes of shape {tuple(planes.shape)} hold no element")
+    dev = planes.device
+    shape = (n, oh, ow) if planes.dim() == 3 else (n, c, oh, ow)
+    if out is None:
+        out = torch.empty(shape, dtype=planes.dtype, device=dev)
+    elif not (isinstance(out, torch.Tensor) and tuple(out.shape) == shape and out.dtype == planes.dtype and out.device == dev
+              and out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous {planes.dtype} tensor of shape {shape} on {dev}")
+    elif out.data_ptr() == planes.data_ptr():
+        raise ValueError("out must not be planes itself: the view is not done in place")
+    if not isinstance(win, torch.Tensor):
+        win = torch.from_numpy(win).to(dev)
+    if win.device != dev:
+        raise ValueError(f"windows must be on {dev}")
+    _call("sl_view_planes_affine", _ptr(planes), _ptr(out), n, c, h, w, planes.element_size(), oh, ow, _ptr(win), int(max_r), bits)
+    return out
+
+
 # ---- stain separation in the view pass (sl_stain_separate_view; see include/stainlib_hip.h) ---------------------------------------------
 
 def _separate_view_args(want, conc_dtype, fmt, out, shrink, M_tgt, maxC_tgt):
@@ -686,6 +818,8 @@ def separate_view_check(view, windows, tensor_format, want, conc_dtype, tiles):
         if tensor_format is not None:
             raise ValueError("tensor_format= goes with view=: the fused full-tile tensor is view=TileView(None, flip=False, rot90=False)")
         return False
+    _no_affine(view, "separate_batch", "take the full-tile images through TensorFormat.convert(view=), which samples bilinearly "
+               "(bilinear concentration planes are another definition)")
     if getattr(view, "resizing", False):
         raise ValueError(f"a resizing view ({view!r}) is not supported by separate_batch: take the full-tile images through "
                          "TensorFormat.convert(view=), which resamples")
@@ -809,6 +943,8 @@ def _hed_call(hed, hed_sigmas, hed_biases, tiles, view=None):
         if hed_sigmas is not None or hed_biases is not None:
             raise ValueError("hed_sigmas= and hed_biases= go with hed= (a HedColorAugmenter)")
         return False
+    _no_affine(view, "the HED stage (hed=, HedColorAugmenter.transform_batch(view=))",
+               "take the HED result as a uint8 image through TensorFormat.convert(view=), which samples bilinearly")
     if not isinstance(hed, HedColorAugmenter):
         raise ValueError("hed must be a stainlib_amd HedColorAugmenter (its ranges, cutoff and skimage_mode are used)")
     if (hed_sigmas is None) != (hed_biases is None):
@@ -883,12 +1019,18 @@ def _view_call(view, windows, tiles, draw=True):
     """(size, d_mask, windows, shrink) of the view= / windows= pair of a batch method, checked without a device (ValueError): the windows
     as given, or drawn (TileView.draw; draw=False: left None for a later call)."""
     from .tile_view import TileView
-    if not isinstance(view, TileView):
+    if not isinstance(view, TileView) and not _is_affine(view):
         raise ValueError("view must be a stainlib_amd.TileView" + (" (windows= goes with view=)" if view is None else ""))
     if not (isinstance(tiles, torch.Tensor) and tiles.dim() == 4 and tiles.shape[-1] == 3):
         raise ValueError("expected a contiguous CUDA uint8 tensor of shape (N, H, W, 3)")
     n, h, w = (int(v) for v in tiles.shape[:3])
     oh, ow = view.out_size(h, w)
+    if _is_affine(view):                                     # (cy, cx, a00, a01, a10, a11) per tile; _view_pass makes the call
+        if windows is not None:
+            _affine_windows(windows, n, h, w, view.size, _affine_bound(view, windows))
+        elif draw:
+            windows = view.draw(n, h, w)
+        return view.size, 0, windows, 1
     if windows is not None:
         _view_windows(windows, n, h, w, oh, ow, view.d_mask, view.shrink, _view_resize(view, windows, tiles))
     elif draw:
@@ -933,10 +1075,20 @@ def route_stage(tiles, fit, route, fmt=None, out=None, view=None, windows=None, 
         x, windows, draw = hed_stage(tiles, *hed, view, windows, route, fmt=fmt, out=out)
         return (x, M, maxC, status) + ((windows,) if view is not None else ()) + (draw,)
     if view is not None:
-        size, d_mask, windows, shrink = _view_call(view, windows, tiles)
-        return normalize_view(tiles, windows, size, d_mask, fmt=fmt, out=out, shrink=shrink, resize=_view_resize(view, windows, tiles),
-                              **route), M, maxC, status, windows
+        x, windows = view_pass(tiles, view, windows, fmt=fmt, out=out, **route)
+        return x, M, maxC, status, windows
     return normalize_jitter(tiles, fmt=fmt, out=out, **route), M, maxC, status
+
+
+def view_pass(tiles, view, windows, fmt=None, out=None, **route):
+    """The ONE pass behind a view= argument, dispatched on the view's type -> (out, windows): the windows as given or drawn here
+    (_view_call), then normalize_view_affine for a TileAffine, normalize_view (its shrink, its resizing bound) for a TileView.  route:
+    the keyword arguments that name `full` ({}: the tiles themselves)."""
+    size, d_mask, windows, shrink = _view_call(view, windows, tiles)
+    if _is_affine(view):
+        return normalize_view_affine(tiles, windows, size, _affine_bound(view, windows), view.fill, fmt=fmt, out=out, **route), windows
+    return normalize_view(tiles, windows, size, d_mask, fmt=fmt, out=out, shrink=shrink, resize=_view_resize(view, windows, tiles),
+                          **route), windows
 
 
 def _fit(fn_name, op, rgb, params, ws, with_sweeps=False):
@@ -1263,6 +1415,8 @@ def slab_view(rgb, windows, size, state, mode, d_mask=7, mask_background=False, 
 
 def _lab_no_resize(view):
     """ValueError for a resizing view (TileView(scale=)) in a Lab-family call: their fused pass has no resampling write side."""
+    _no_affine(view, "the Lab-family calls (Reinhard, luminosity, pooled or per tile)",
+               "take their full-tile result through TensorFormat.convert(view=), which samples bilinearly")
     if getattr(view, "resizing", False):
         raise ValueError(f"a resizing view ({view!r}) is not supported by the Lab-family calls (Reinhard, luminosity, pooled or per "
                          "tile): take their full-tile result through TensorFormat.convert(view=), which resamples")

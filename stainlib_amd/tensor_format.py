@@ -63,9 +63,7 @@ class TensorFormat(object):
         luminosity ...).  Returns (the (N, 3, oh, ow) tensor, windows)."""
         from . import engine
         if view is not None or windows is not None:
-            size, d_mask, windows, shrink = engine._view_call(view, windows, tiles_u8)
-            return engine.normalize_view(tiles_u8, windows, size, d_mask, fmt=self, out=out, shrink=shrink,
-                                         resize=engine._view_resize(view, windows, tiles_u8)), windows
+            return engine.view_pass(tiles_u8, view, windows, fmt=self, out=out)
         return engine.to_tensor(tiles_u8, self, out=out)
 
     def __repr__(self):

@@ -16,6 +16,10 @@ pixel-area averaging in integers -- OpenCV's INTER_AREA for shrinking.  Along an
 scaled by no, source pixel k covers [k no, (k + 1) no), output i covers [i nw, (i + 1) nw) and c(i, k) is the length of their overlap;
 per channel b = (2 S + D) // (2 D) with S = sum cy(i, k) cx(j, l) window[k, l] and D = wh ww.  A window smaller than the output comes
 out piecewise constant with blended edges (the same formula), not bilinear.  area_resample below is that definition in numpy.
+
+TileAffine (at the end of the module) is the affine view: rotation by ANY angle, zoom, shear and translation, a view of one tile six
+int32 in 2^-16 source pixels, the image sampled bilinearly with 8-bit weights and its label maps by the nearest element, both in
+integers (sl_normalize_view_affine, sl_view_planes_affine); affine_coords / affine_resample / affine_nearest are that definition in numpy.
 """
 from __future__ import annotations
 
@@ -268,6 +272,9 @@ class TileView(object):
         if windows is None:
             raise ValueError("windows is required: pass what the image call with this view returned, or view.draw(N, H, W) "
                              "-- apply draws nothing itself")
+        if len(getattr(windows, "shape", ())) == 2 and windows.shape[1] == 6:
+            raise ValueError("six-column windows are those of an affine view (TileAffine.draw): take the planes through that "
+                             "TileAffine's apply -- a TileView's windows are (y0, x0, d) or (y0, x0, d, wh, ww)")
         h, w = engine.planes_hw(planes)
         return engine.view_planes(planes, windows, self.size, self.d_mask, mode=mode, out=out, shrink=self.shrink,
                                   resize=engine._view_resize_hw(self, windows, h, w))
@@ -285,3 +292,257 @@ def _reduce_area(wh, ww):
         f = np.sqrt(RESIZE_MAX_AREA / float(wh * ww))
         wh, ww = max(1, int(wh * f)), max(1, int(ww * f))           # (f < 1: a side above 1 gets smaller, so this ends)
     return int(wh), int(ww)
+
+
+# ---- the affine view: rotation by any angle, zoom, shear and translation (sl_normalize_view_affine, sl_view_planes_affine) ------------------
+# A view of one tile is a row of six int32, (cy, cx, a00, a01, a10, a11), all in units of 2^-16 source pixel; pixel k of an axis covers
+# [k, k + 1).  (cy, cx): the source position of the centre of the output; a..: the source displacement per output pixel.  The functions
+# below ARE the definition; the kernels are tested against them bit for bit.
+AFFINE_Q = 65536                 # one source pixel
+AFFINE_MAX_SIDE = 8192           # h, w, oh, ow
+AFFINE_MAX_R = 2 * AFFINE_Q      # a row sum |a00| + |a01|, |a10| + |a11|: at most two source pixels per output pixel
+AFFINE_CENTRE_SLACK = 1 << 28    # a centre lies within this of the tile
+
+
+def affine_coords(row, size):
+    """(Y, X), two (oh, ow) int64 arrays: the source position (2^-16 pixels) of every output pixel of a view `row` = (cy, cx, a00, a01,
+    a10, a11) with size = (oh, ow).  With u = 2 i + 1 - oh, v = 2 j + 1 - ow: Y = cy + ((a00 u + a01 v) >> 1), X = cx + ((a10 u + a11 v)
+    >> 1), the shift arithmetic (a floor)."""
+    oh, ow = _size2(size)
+    cy, cx, a00, a01, a10, a11 = (int(v) for v in np.asarray(row).reshape(6))
+    u = (2 * np.arange(oh, dtype=np.int64) + 1 - oh)[:, None]
+    v = (2 * np.arange(ow, dtype=np.int64) + 1 - ow)[None, :]
+    return cy + ((a00 * u + a01 * v) >> 1), cx + ((a10 * u + a11 * v) >> 1)
+
+
+def _fill3(fill):
+    """fill= of the images as three ints 0 .. 255 (an int: that byte in every channel), or ValueError"""
+    try:
+        f = (fill,) * 3 if isinstance(fill, (int, np.integer)) and not isinstance(fill, bool) else tuple(fill)
+        if len(f) != 3 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= 255 for v in f):
+            raise TypeError
+    except TypeError:
+        raise ValueError(f"fill of an affine view must be an int or three ints in 0 .. 255 (output bytes, r g b), not {fill!r}") from None
+    return tuple(int(v) for v in f)
+
+
+def affine_resample(full, row, size, fill=255):
+    """The definition of the affine view of an image in numpy: the (h, w, C) uint8 `full` sampled bilinearly with 8-bit weights at
+    affine_coords(row, size) -> (oh, ow, C) uint8.  ty = Y - Q/2, ky = ty >> 16, fy = (ty >> 8) & 255 (x likewise); p00 .. p11 the bytes
+    at (ky, kx), (ky, kx + 1), (ky + 1, kx), (ky + 1, kx + 1), a tap outside the image the fill byte of its channel (fill: an int or one
+    int per channel); b = ((256 - fy) ((256 - fx) p00 + fx p01) + fy ((256 - fx) p10 + fx p11) + 32768) >> 16."""
+    full = np.asarray(full)
+    if full.dtype != np.uint8 or full.ndim != 3:
+        raise ValueError("affine_resample is defined on an (h, w, C) uint8 image")
+    h, w, ch = full.shape
+    f = np.asarray(_fill3(fill) if ch == 3 else (int(fill),) * ch, dtype=np.int64)
+    Y, X = affine_coords(row, size)
+    ty, tx = Y - AFFINE_Q // 2, X - AFFINE_Q // 2
+    ky, kx, fy, fx = ty >> 16, tx >> 16, ((ty >> 8) & 255)[..., None], ((tx >> 8) & 255)[..., None]
+
+    def tap(y, x):
+        inside = (y >= 0) & (y < h) & (x >= 0) & (x < w)
+        v = full[np.clip(y, 0, h - 1), np.clip(x, 0, w - 1)].astype(np.int64)
+        return np.where(inside[..., None], v, f)
+    top = (256 - fx) * tap(ky, kx) + fx * tap(ky, kx + 1)
+    bot = (256 - fx) * tap(ky + 1, kx) + fx * tap(ky + 1, kx + 1)
+    return (((256 - fy) * top + fy * bot + 32768) >> 16).astype(np.uint8)
+
+
+def affine_nearest(plane, row, size, fill=0):
+    """The definition of the affine view of a companion plane in numpy: the (h, w) `plane` of any dtype -> (oh, ow) of that dtype, the
+    element at (Y >> 16, X >> 16) copied bit for bit, outside the plane `fill` (as an element of the plane's dtype)."""
+    plane = np.asarray(plane)
+    if plane.ndim != 2:
+        raise ValueError("affine_nearest is defined on an (h, w) plane")
+    h, w = plane.shape
+    Y, X = affine_coords(row, size)
+    ky, kx = Y >> 16, X >> 16
+    inside = (ky >= 0) & (ky < h) & (kx >= 0) & (kx < w)
+    out = np.full(ky.shape, np.asarray(fill).astype(plane.dtype), dtype=plane.dtype)
+    out[inside] = plane[ky[inside], kx[inside]]
+    return out
+
+
+def affine_row_sums(windows):
+    """(n,) int64: max(|a00| + |a01|, |a10| + |a11|) per row of (n, 6) windows"""
+    a = np.abs(np.asarray(windows).astype(np.int64)[:, 2:6])
+    return np.maximum(a[:, 0] + a[:, 1], a[:, 2] + a[:, 3])
+
+
+def affine_check_size(size, h, w):
+    """(oh, ow) of an affine view of size `size` (None: the tile's own (h, w)) out of (h, w) tiles: any size, or ValueError beyond the
+    limit that keeps the coordinates 32-bit (h, w, oh, ow <= 8192)."""
+    oh, ow = (int(h), int(w)) if size is None else _size2(size)
+    if min(int(h), int(w)) < 1 or max(oh, ow, int(h), int(w)) > AFFINE_MAX_SIDE:
+        raise ValueError(f"an affine view takes tiles and outputs of 1 .. {AFFINE_MAX_SIDE} pixels a side (32-bit coordinates), "
+                         f"not a {oh} x {ow} view of a {h} x {w} tile")
+    return oh, ow
+
+
+def affine_check_windows(windows, n, h, w, size=None, bound=AFFINE_MAX_R):
+    """The (n, 6) int32 windows of an affine view of (h, w) tiles, in range, as a contiguous int32 array -- or ValueError: a wrong shape
+    or a dtype that is not an integer one; a side above 8192; a row sum |a00| + |a01| or |a10| + |a11| above 2 Q (more than two source
+    pixels per output pixel: shrink= / scale= downsample further) or above `bound`, the max_r of the call; a centre outside
+    [-2^28, side Q + 2^28].  Zero and singular matrices are legal."""
+    what = "windows of an affine view must hold (cy, cx, a00, a01, a10, a11) per tile"
+    if windows is None:
+        raise ValueError(f"{what}: an (N, 6) int32 array (TileAffine.draw)")
+    affine_check_size(size, h, w)
+    if isinstance(bound, bool) or not isinstance(bound, (int, np.integer)) or not 1 <= int(bound) <= AFFINE_MAX_R:
+        raise ValueError(f"the bound max_r of an affine view must be an int in 1 .. 2 Q = {AFFINE_MAX_R} (2^-16 pixels), not {bound!r}")
+    try:
+        win = windows.numpy() if hasattr(windows, "numpy") and not isinstance(windows, np.ndarray) else np.asarray(windows)
+        if win.dtype.kind not in "iu":
+            raise TypeError
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(f"{what}: an (N, 6) integer array") from None
+    if win.shape != (int(n), 6):
+        raise ValueError(f"{what}: an ({int(n)}, 6) array, not one of shape {win.shape}")
+    win = win.astype(np.int64)
+    r = affine_row_sums(win)
+    bad = r > min(int(bound), AFFINE_MAX_R)
+    if bad.any():
+        t = int(np.argmax(bad))
+        raise ValueError(f"windows: tile {t} of the affine view has the row sum {int(r[t])} (2^-16 pixels), above "
+                         + (f"2 Q = {AFFINE_MAX_R}: more than two source pixels per output pixel (shrink= / scale= downsample further)"
+                            if r[t] > AFFINE_MAX_R else f"the call's bound max_r = {int(bound)}"))
+    for k, side, name in ((0, int(h), "cy"), (1, int(w), "cx")):
+        bad = (win[:, k] < -AFFINE_CENTRE_SLACK) | (win[:, k] > side * AFFINE_Q + AFFINE_CENTRE_SLACK)
+        if bad.any():
+            t = int(np.argmax(bad))
+            raise ValueError(f"windows: tile {t} of the affine view has the centre {name} = {int(win[t, k])}, outside "
+                             f"[-2^28, {side} Q + 2^28]")
+    return np.ascontiguousarray(win.astype(np.int32))
+
+
+def _pair(x, what, positive=False):
+    try:
+        lo, hi = (float(v) for v in x)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be a pair (lo, hi), not {x!r}") from None
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo <= hi) or (positive and lo <= 0.0):
+        raise ValueError(f"{what} must be a pair (lo, hi) of finite numbers with " + ("0 < " if positive else "") + f"lo <= hi, not {x!r}")
+    return lo, hi
+
+
+def _max_mix(a, b, lo, hi):
+    """max over theta in [lo, hi] degrees of a |cos theta| + b |sin theta| (a, b >= 0): the end points and the maxima
+    theta = k 180 +- atan(b / a) that lie inside"""
+    if hi - lo >= 180.0:
+        return float(np.hypot(a, b))
+    f = lambda d: a * abs(np.cos(np.radians(d))) + b * abs(np.sin(np.radians(d)))
+    best = max(f(lo), f(hi))
+    peak = np.degrees(np.arctan2(b, a))
+    for k in range(int(np.floor(lo / 180.0)) - 1, int(np.ceil(hi / 180.0)) + 2):
+        for d in (180.0 * k + peak, 180.0 * k - peak):
+            if lo <= d <= hi:
+                best = max(best, f(d))
+    return float(best)
+
+
+class TileAffine(object):
+    """The affine half of a segmentation loader's augmentation -- a rotation by ANY angle, a zoom, a shear, a translation and a flip,
+    different for every tile -- drawn on the host and applied INSIDE the view pass (engine.normalize_view_affine): the image bilinearly
+    with 8-bit weights in integers (affine_resample is the definition), its label maps by the nearest element (apply, affine_nearest).
+    size: None (the tile's own size), an int or (oh, ow) -- the size of the OUTPUT; it need not fit in the tile.
+    rotate: (lo, hi) degrees; zoom: (lo, hi), log-uniform, z > 1 magnifies; shear: (lo, hi) degrees, |shear| < 90; translate: (ty, tx)
+    or one number, the largest shift of the centre as a share of the tile's side, 0 .. 1; flip: draw mirror images;
+    fill: what lies outside the tile, an int or three ints 0 .. 255 -- OUTPUT bytes, not normalised.
+    A view of one tile is (cy, cx, a00, a01, a10, a11) in 2^-16 source pixels (see draw).  The kernels take at most two source pixels
+    per output pixel: both row sums |a00| + |a01|, |a10| + |a11| <= 2 Q.  Nothing is redrawn or clamped, so the CONSTRUCTOR refuses
+    ranges from which a draw could pass that limit, by this sufficient bound: with T = max |tan shear|, the real row sums are
+    (|c| + |c t - s|) / z <= ((1 + T) |c| + |s|) / z and (|s| + |s t + c|) / z <= ((1 + T) |s| + |c|) / z; R = the larger of the two
+    maxima over the rotate range (sqrt((1 + T)^2 + 1) once it spans 180 degrees) divided by zoom[0]; every entry is rounded to
+    the nearest 2^-16, at most 1/2 each, so an integer row sum is at most 65536 R + 1, and the constructor wants
+    ceil(65536 R (1 + 10^-12)) + 1 <= 2 Q = 131072.  That number is `bound`, the max_r of a call with windows on the device.
+    (zoom = 0.5 at no rotation meets the limit exactly and is refused by the + 1; zoom[0] = 0.50001 passes.)"""
+
+    def __init__(self, size=None, rotate=(-180, 180), zoom=(1, 1), shear=(0, 0), translate=(0, 0), flip=True, fill=255):
+        self.size = None if size is None else _size2(size)
+        self.rotate = _pair(rotate, "rotate")
+        self.zoom = _pair(zoom, "zoom", positive=True)
+        self.shear = _pair(shear, "shear")
+        if not (-90.0 < self.shear[0] and self.shear[1] < 90.0):
+            raise ValueError(f"shear must lie within (-90, 90) degrees, not {shear!r}")
+        if isinstance(translate, (int, float, np.integer, np.floating)) and not isinstance(translate, bool):
+            translate = (translate, translate)
+        try:
+            ty, tx = (float(v) for v in translate)
+            if not (0.0 <= ty <= 1.0 and 0.0 <= tx <= 1.0):
+                raise ValueError
+        except (TypeError, ValueError):
+            raise ValueError(f"translate must be a number or (ty, tx), shares of the tile's side in 0 .. 1, not {translate!r}") from None
+        self.translate = (ty, tx)
+        self.flip = bool(flip)
+        self.fill = _fill3(fill)
+        T = max(abs(np.tan(np.radians(self.shear[0]))), abs(np.tan(np.radians(self.shear[1]))))
+        lo, hi = self.rotate
+        R = max(_max_mix(1.0 + T, 1.0, lo, hi), _max_mix(1.0, 1.0 + T, lo, hi)) / self.zoom[0]
+        bound = int(np.ceil(AFFINE_Q * R * (1.0 + 1e-12))) + 1
+        if bound > AFFINE_MAX_R:
+            raise ValueError(f"TileAffine(rotate={rotate!r}, zoom={zoom!r}, shear={shear!r}) could draw a matrix with a row sum of "
+                             f"{bound / AFFINE_Q:.5f} source pixels per output pixel; the affine view takes at most 2 (bilinear aliases "
+                             "beyond): raise zoom[0] or narrow shear / rotate -- TileView(shrink=) / TileView(scale=) downsample further")
+        self._bound = bound
+
+    # what the view= plumbing of the batch methods asks of a view
+    resizing = False
+    shrink = 1
+    d_mask = 0
+
+    @property
+    def bound(self):
+        """max_r: an upper bound (2^-16 pixels) of the row sums of every matrix this view can draw -- what a call with windows on the
+        device sizes its launch from"""
+        return self._bound
+
+    @property
+    def fill_rgb(self):
+        """the fill as sl_normalize_view_affine takes it: r | g << 8 | b << 16"""
+        return self.fill[0] | (self.fill[1] << 8) | (self.fill[2] << 16)
+
+    def out_size(self, h, w):
+        return affine_check_size(self.size, h, w)
+
+    def draw(self, n, h, w):
+        """(n, 6) int32: cy, cx, a00, a01, a10, a11 per tile, from the GLOBAL numpy stream.  Six draws per tile, always, in this order:
+        theta = np.random.uniform(*rotate) degrees; z = exp(np.random.uniform(log zoom[0], log zoom[1])); phi = np.random.uniform(*shear)
+        degrees; e = -1 if np.random.randint(2) and flip else 1 (drawn also with flip=False); ty = np.random.uniform(-translate[0],
+        translate[0]); tx = np.random.uniform(-translate[1], translate[1]).  With c = cos theta, s = sin theta, t = tan phi:
+        A = (1 / z) [[c, e (c t - s)], [s, e (s t + c)]], the centre ((0.5 + ty) h, (0.5 + tx) w); every entry int(np.rint(65536 x)).
+        Nothing is redrawn or clamped (the constructor has refused ranges that could leave the limits)."""
+        n = int(n)
+        if n < 0:
+            raise ValueError("n must be >= 0")
+        self.out_size(h, w)
+        lz0, lz1 = np.log(self.zoom[0]), np.log(self.zoom[1])
+        win = np.empty((n, 6), dtype=np.int32)
+        for k in range(n):
+            theta = np.radians(np.random.uniform(self.rotate[0], self.rotate[1]))
+            z = np.exp(np.random.uniform(lz0, lz1))
+            t = np.tan(np.radians(np.random.uniform(self.shear[0], self.shear[1])))
+            e = -1.0 if np.random.randint(2) and self.flip else 1.0
+            ty = np.random.uniform(-self.translate[0], self.translate[0])
+            tx = np.random.uniform(-self.translate[1], self.translate[1])
+            c, s = np.cos(theta), np.sin(theta)
+            row = ((0.5 + ty) * h, (0.5 + tx) * w, c / z, e * (c * t - s) / z, s / z, e * (s * t + c) / z)
+            win[k] = [int(np.rint(AFFINE_Q * x)) for x in row]
+        return win
+
+    def apply(self, planes, windows=None, fill=0, out=None):
+        """The per-pixel companions of a batch through the windows their images went through (sl_view_planes_affine): `planes` is a
+        contiguous device tensor (N, H, W) or (N, C, H, W) of any 1-, 2-, 4- or 8-byte dtype, `windows` what the image call with this
+        view returned for (H, W) tiles (or self.draw(N, H, W)); returns (N, oh, ow) / (N, C, oh, ow) of the same dtype: per element
+        the NEAREST source element, (Y >> 16, X >> 16), a bit copy -- labels are never blended --, outside the plane `fill` (a
+        number, cast to the planes' dtype; e.g. an ignore index).  Nothing is drawn here.  Host windows are range-checked
+        (ValueError); device windows are taken as they are under this view's bound.  out: a tensor to write into."""
+        from . import engine
+        if windows is None:
+            raise ValueError("windows is required: pass what the image call with this view returned, or view.draw(N, H, W) "
+                             "-- apply draws nothing itself")
+        return engine.view_planes_affine(planes, windows, self.size, engine._affine_bound(self, windows), fill=fill, out=out)
+
+    def __repr__(self):
+        return (f"TileAffine(size={self.size}, rotate={self.rotate}, zoom={self.zoom}, shear={self.shear}, translate={self.translate}, "
+                f"flip={self.flip}, fill={self.fill})")
