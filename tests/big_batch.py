@@ -132,3 +132,50 @@ def period8_windows(n, h, w, oh, ow):
         y0, x0 = [(0, 0), (0, xmax), (ymax, 0), (ymax, xmax), (ymax, xmax // 2 | 1), (ymax // 2, xmax), (1, 2), (ymax - 1, xmax - 1)][t]
         win[t] = (y0, x0, t)
     return win[np.arange(n) % 8]
+
+
+def period8_resize_windows(n, h, w):
+    """(n, 5) int32 windows (y0, x0, d, wh, ww) of a resizing view with period 8 over the tiles: the eight codes; 64 x 64 windows
+    (tiles 0 .. 3 of a period) and 128 x 96 ones (4 .. 7) at period8_windows' corners, the tile's last row and last column among them.
+    The call's bound of the window sides is (128, 96)."""
+    win = np.empty((8, 5), dtype=np.int32)
+    for t in range(8):
+        wh, ww = (64, 64) if t < 4 else (128, 96)
+        ymax, xmax = h - wh, w - ww                          # (the sides are the TILE's, whatever the code)
+        y0, x0 = [(0, 0), (0, xmax), (ymax, 0), (ymax, xmax), (ymax, xmax // 2 | 1), (ymax // 2, xmax), (1, 2), (ymax - 1, xmax - 1)][t]
+        win[t] = (y0, x0, t, wh, ww)
+    assert (win[:, 0] + win[:, 3] <= h).all() and (win[:, 1] + win[:, 4] <= w).all() and (win[:, 0] + win[:, 3] == h).any() \
+        and (win[:, 1] + win[:, 4] == w).any()
+    return win[np.arange(n) % 8]
+
+
+# the dihedral code d as the matrix (a00, a01, a10, a11) / Q of an affine view: rot90(flip_w(window) if d & 4 else window, d & 3)
+AFFINE_DIHEDRAL = {0: (1, 0, 0, 1), 1: (0, 1, -1, 0), 2: (-1, 0, 0, -1), 3: (0, -1, 1, 0), 4: (1, 0, 0, -1), 5: (0, 1, 1, 0), 6: (-1, 0, 0, 1),
+                   7: (0, -1, -1, 0)}
+
+
+def period8_affine_windows(n, h, w, oh, ow, kind):
+    """(n, 6) int32 rows (cy, cx, a00, a01, a10, a11; 2^-16 source pixels) of an affine view with period 8 over the tiles.
+    kind "dihedral": the eight dihedral matrices about period8_windows' corner windows -- the plain view's bits.
+    kind "rotated": 30 and 45 degrees centred so that the patch reaches past the tile's last row and last column, a centre half
+    outside the tile (rotated, fractional), 30 degrees at the first row and column, a shear, a negative determinant, the row-sum limit
+    (45 degrees at sqrt 2) and the identity about a fractional centre."""
+    Q = 65536
+    if kind == "dihedral":
+        rows = []
+        for y0, x0, d in period8_windows(8, h, w, oh, ow).tolist():
+            wh, ww = (ow, oh) if d & 1 else (oh, ow)
+            rows.append([(2 * y0 + wh) * Q // 2, (2 * x0 + ww) * Q // 2] + [Q * v for v in AFFINE_DIHEDRAL[d]])
+    else:
+        def rot(deg, z=1.0):
+            c, s = np.cos(np.radians(deg)) / z, np.sin(np.radians(deg)) / z
+            return (c, -s, s, c)
+        r = max(oh, ow) / 2.0
+        reach30, reach45 = r * (np.cos(np.radians(30)) + np.sin(np.radians(30))), r * np.sqrt(2.0)
+        rows = [(h - reach30 + 4, w - reach30 + 4) + rot(30), (h - reach45 + 3, w - reach45 + 3) + rot(45),
+                (0.25, w / 2 + 0.3701) + rot(-17, 1.1), (reach30 - 4, reach30 - 4) + rot(30), (h / 2, w / 2, 1, 0.4, 0.1, 0.9),
+                (h - 50, 50, 0.8, 0.3, 0.2, -1.1), (h / 2, w / 2, 1, -1, 1, 1), (h / 2 + 0.5, w / 2 + 0.25, 1, 0, 0, 1)]
+        rows = [[int(np.rint(Q * v)) for v in row] for row in rows]
+    win = np.array(rows, dtype=np.int64)
+    assert win.shape == (8, 6) and int(np.abs(win[:, 2:]).reshape(8, 2, 2).sum(axis=2).max()) <= 2 * Q
+    return win.astype(np.int32)[np.arange(n) % 8]

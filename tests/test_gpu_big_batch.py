@@ -1,15 +1,24 @@
 """-m gpu: every per-tile entry point on batches whose byte offsets pass 2^31 and 2^32 (tests/big_batch.py: K = 4 distinct tiles
 repeated, 5464 tiles of 512 x 512 and 5444 tiles of 509 x 517).
 
+What it covers: the readers (tissue_mask, tile_moments, macenko_fit, vahadane_fit, reinhard_stats, normalize_sums); the full-tile
+writers (normalize_apply and its tensor form, to_tensor, macenko_transform, vahadane_transform, normalize_jitter, stain_augment,
+grayscale_augment, stain_separate, hed_augment, the Lab family); and the views -- normalize_view plain, under shrink=2 and 4, under
+resize= and through normalize_view_affine, normalize_hed_view, stain_separate_view, reinhard_view and luminosity_view -- with small
+windows of period 8 and, for the plain, the HED, the Lab and the affine view, once at full size in float32.  The companion planes
+(view_planes, view_planes_affine) have their big batches in tests/test_gpu_planes_view.py, the pooled slide chains in
+tests/test_gpu_big_shard.py.
+
 Each test makes one call on the whole batch and checks it three ways, on the device:
   periodic   tile i + K holds the bytes (and the side results) of tile i, over the whole batch, by one torch.equal (assert_periodic)
   anchor     the first K tiles against the oracle, under the bar the project already states for that entry point (u8_parity,
-             M_ATOL / MAXC_RTOL, V_ATOL, bit identity for the Lab family and for the tensor conversion of an anchored uint8 image)
+             M_ATOL / MAXC_RTOL, V_ATOL, bit identity for the Lab family and for the tensor conversion of an anchored uint8 image);
+             the resampling views against their numpy definitions on the K-tile base's full-tile result, bit for bit
   guard      where the entry point takes out=, the output sits between sentinel margins that must survive the call
 The only host-to-device copy is the K-tile base; only K (8 for the views) tiles and the per-tile scalars come back.  The K-periodic
 input of a shape (4.3 GB) is made once and shared by the tests of this file; each test states what it allocates beyond it, the
 gate (need_memory) counts that and every shared batch resident beside it against the 40 GB a test may hold -- the full-tile float32
-views drop the other shape's batch first and their own before the comparison -- and every test ends with release().  Order: the entry points that only read the batch first, then the writers."""
+views drop the other shape's batch first and their own before the comparison -- and every test ends with release().  Order: the entry points that only read the batch first, then the writers, then the views."""
 import types
 
 import numpy as np
@@ -18,8 +27,8 @@ import torch
 
 import stainlib_amd
 from oracle import stain_oracle as so
-from tests.big_batch import (K, SHAPES, assert_periodic, base_tiles, bits, guarded, need_memory, period8_windows, periodic_batch, periodic_rows,
-                             release)
+from tests.big_batch import (K, SHAPES, assert_periodic, base_tiles, bits, guarded, need_memory, period8_affine_windows,
+                             period8_resize_windows, period8_windows, periodic_batch, periodic_rows, release)
 from tests.gpu_util import oracle_fit_tile, u8_parity
 from tests.test_gpu_jitter import M_TGT, MAXC_TGT, MEAN, STD
 from tests.test_gpu_macenko import M_ATOL, MAXC_RTOL
@@ -688,5 +697,122 @@ def test_lab_view_full_tile_float32_is_convert_of_the_transform(name, kind, kw):
     dwin = torch.zeros((S.n, 3), dtype=torch.int32, device="cuda")
     out, _ = _guard_image(S, fmt, lambda o: view(S.dev, dwin, None, 0, fmt=fmt, out=o), label=f"{kind} view f32")
     _same_bits_alone(S, out, want, f"{kind}_view {name}: not the bits of the transform's tensor")
+    del out, want
+    release()
+
+
+# =============================================== the views added since: shrink, resize, affine, separation ===================================
+# (64 x 64 outputs under windows of period 8; the resampling views against their numpy definitions on the K-tile base's full-tile result)
+AFFINE_FILL = (10, 30, 200)
+
+
+def _first8(t):
+    """tiles 0 .. 7 of the batch from a K-tile tensor or array: tile i is tile i % K of the base"""
+    return t[np.arange(8) % K] if isinstance(t, np.ndarray) else t.index_select(0, torch.arange(8, device=t.device) % K)
+
+
+def _small_check(out, want8, label):
+    """periodic with period 8 over the whole batch, and the first 8 tiles are want8 (a CPU tensor) bit for bit"""
+    assert_periodic(out, period=8, label=label)
+    assert torch.equal(bits(out[:8].cpu().contiguous()), bits(want8.contiguous())), label
+
+
+@pytest.mark.parametrize("shrink", [2, 4])
+@pytest.mark.parametrize("route", ["apply", "raw"])
+@pytest.mark.parametrize("name", BOTH)
+def test_normalize_view_shrink_small_windows(name, route, shrink):
+    from stainlib_amd import engine
+    S = _state(name, 1 << 28)
+    kw, _ = _route(S, route)
+    win = period8_windows(S.n, S.h, S.w, 64 * shrink, 64 * shrink)
+    dwin = torch.from_numpy(win).cuda()
+    out, _ = _guard_image(S, None, lambda o: engine.normalize_view(S.dev, dwin, (64, 64), 7, out=o, shrink=shrink, **kw), 64, 64,
+                          label=f"view shrink={shrink} {route}")
+    kw8 = dict(kw, M_src=_first8(S.M4), maxC_src=_first8(S.mc4)) if kw else kw
+    want = engine.normalize_view(_first8(S.base), win[:8], (64, 64), 7, shrink=shrink, **kw8)       # the call on the K-tile base
+    _small_check(out, want.cpu(), f"normalize_view shrink={shrink} {route} {name}")
+    del out
+    release()
+
+
+@pytest.mark.parametrize("route", ["apply", "raw"])
+@pytest.mark.parametrize("name", BOTH)
+def test_normalize_view_resize_small_windows(name, route):
+    from stainlib_amd import engine
+    from tests.test_view_resize_host import want_view
+    S = _state(name, 1 << 28)
+    kw, full4 = _route(S, route)
+    win = period8_resize_windows(S.n, S.h, S.w)
+    dwin = torch.from_numpy(win).cuda()
+    out, _ = _guard_image(S, None, lambda o: engine.normalize_view(S.dev, dwin, (64, 64), 7, out=o, resize=(128, 96), **kw), 64, 64,
+                          label=f"view resize {route}")
+    want = want_view(_first8(full4.cpu().numpy()), win[:8], (64, 64), 7, (128, 96))                  # the definition, in numpy
+    _small_check(out, torch.from_numpy(want), f"normalize_view resize {route} {name}")
+    del out
+    release()
+
+
+@pytest.mark.parametrize("kind", ["dihedral", "rotated"])
+@pytest.mark.parametrize("route", ["apply", "raw"])
+@pytest.mark.parametrize("name", BOTH)
+def test_normalize_view_affine_small_windows(name, route, kind):
+    from stainlib_amd import engine
+    from stainlib_amd.tile_view import AFFINE_MAX_R, affine_resample
+    from tests.test_gpu_view import _ref
+    S = _state(name, 1 << 28)
+    kw, full4 = _route(S, route)
+    win = period8_affine_windows(S.n, S.h, S.w, 64, 64, kind)
+    dwin = torch.from_numpy(win).cuda()
+    out, _ = _guard_image(S, None, lambda o: engine.normalize_view_affine(S.dev, dwin, (64, 64), AFFINE_MAX_R, AFFINE_FILL, out=o, **kw), 64, 64,
+                          label=f"affine view {kind} {route}")
+    full8 = _first8(full4.cpu().numpy())
+    want = torch.from_numpy(np.stack([affine_resample(full8[t], win[t], (64, 64), AFFINE_FILL) for t in range(8)]))    # the definition
+    is_fill = (want == torch.tensor(AFFINE_FILL, dtype=torch.uint8)).all(dim=-1)
+    if kind == "dihedral":                                                       # (the plain view's bits, nothing outside the tile)
+        assert not bool(is_fill.any()) and torch.equal(want, _ref(_first8(full4.cpu()), period8_windows(8, S.h, S.w, 64, 64), 64, 64, 7))
+    else:                                                                        # (past the last row and column, and half outside)
+        assert all(bool(is_fill[t].any()) and not bool(is_fill[t].all()) for t in range(4))
+    _small_check(out, want, f"normalize_view_affine {kind} {route} {name}")
+    del out
+    release()
+
+
+@pytest.mark.parametrize("name", BOTH)
+def test_stain_separate_view_small_windows(name):
+    from stainlib_amd import engine
+    from stainlib_amd.engine import Separated
+    S = _state(name, 1 << 29)
+    win = period8_windows(S.n, S.h, S.w, 64, 64)
+    dwin = torch.from_numpy(win).cuda()
+    gs = {"norm": guarded(S.n * 64 * 64 * 3, torch.uint8, margin=MARGIN), "conc": guarded(S.n * 2 * 64 * 64, torch.float32, margin=MARGIN)}
+    bufs = Separated(*[(gs[k].body.view(S.n, 2, 64, 64) if k == "conc" else gs[k].body.view(S.n, 64, 64, 3)) if k in gs else None
+                       for k in Separated._fields])
+    got = engine.stain_separate_view(S.dev, dwin, (64, 64), S.M, S.mc, M_TGT, MAXC_TGT, want=("norm", "conc"), out=bufs)
+    for k in gs:
+        gs[k].check(f"stain_separate_view {k} {name}")
+    small = engine.stain_separate_view(_first8(S.base), win[:8], (64, 64), _first8(S.M4), _first8(S.mc4), M_TGT, MAXC_TGT,
+                                       want=("norm", "conc"))                   # the call on the K-tile base
+    assert got.h is None and got.e is None and got.conc.dtype == torch.float32 and int((small.conc != 0).sum()) > 0
+    for k in gs:
+        _small_check(getattr(got, k), getattr(small, k).cpu(), f"stain_separate_view {k} {name}")
+    _small_view_check(S, got.norm, _route(S, "apply")[1], win, f"stain_separate_view norm {name}")        # k_apply's bytes, windowed
+    del got, bufs, gs
+    release()
+
+
+@pytest.mark.parametrize("name", BOTH)
+def test_normalize_view_affine_full_tile_float32_is_the_tensor_entry_point(name):
+    """the identity about the tile's centre at the tile's own size (size=None): the output's byte offsets pass 2^32 as well"""
+    from stainlib_amd import engine
+    from stainlib_amd.tile_view import AFFINE_Q as Q
+    fmt = _fmt(torch.float32, False)
+    S = _full_tile_state(name)
+    kw, _ = _route(S, "apply")
+    want = engine.normalize_apply_tensor(S.dev, S.M, S.mc, M_TGT, MAXC_TGT, fmt)
+    assert (S.h * Q) % 2 == 0 and (S.w * Q) % 2 == 0
+    dwin = torch.tensor([S.h * Q // 2, S.w * Q // 2, Q, 0, 0, Q], dtype=torch.int32, device="cuda").repeat(S.n, 1).contiguous()
+    out, _ = _guard_image(S, fmt, lambda o: engine.normalize_view_affine(S.dev, dwin, None, Q, AFFINE_FILL, fmt=fmt, out=o, **kw),
+                          label="affine view f32")
+    _same_bits_alone(S, out, want, f"normalize_view_affine {name}: not the tensor entry point's bits")
     del out, want
     release()

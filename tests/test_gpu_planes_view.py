@@ -7,7 +7,9 @@ All comparisons are on bit patterns (integer views of the element's width); ther
 
 Every call writes into a buffer with sentinel elements before and after the output, which starts one element past an aligned address
 in half of the cases; the margins are checked after the call.  Element values differ from position to position (per plane distinct
-where the element is wide enough), and both dwords of an 8-byte element are distinct."""
+where the element is wide enough), and both dwords of an 8-byte element are distinct.
+
+The batches past 2^32 bytes of both planes kernels are here too (6): sl_view_planes on uint8, sl_view_planes_affine on int64."""
 import numpy as np
 import pytest
 import torch
@@ -287,6 +289,44 @@ def test_big_batch_of_uint8_planes_past_4_gib():
     assert_periodic(body, period=8, label="view_planes big batch")
     want = _ref(base[torch.arange(8) % 4], win[:8], 64, 64)
     assert torch.equal(body[:8], want)
+    del x, body
+    release()
+
+
+def test_big_batch_of_int64_planes_through_an_affine_view_past_4_gib():
+    """sl_view_planes_affine on int64 planes (n, 509, 517) of period 8, n the smallest whose bytes pass 2^32; 2^31 and 2^32 bytes fall
+    mid-plane.  The identity about the centre at full size is a bit copy of the input (output offsets pass 2^32 too); a rotated
+    64 x 64 view is periodic and its first period the definition (stainlib_amd.tile_view.affine_nearest)."""
+    from stainlib_amd import engine
+    from stainlib_amd.tile_view import AFFINE_MAX_R, AFFINE_Q as Q, affine_nearest
+    from tests.big_batch import period8_affine_windows
+    h, w, _ = SHAPES["odd"]
+    pb = h * w * 8
+    n = (1 << 32) // pb + 1
+    nbytes = n * pb
+    assert nbytes > 1 << 32 >= nbytes - pb and (1 << 31) % pb != 0 and (1 << 32) % pb != 0 and n > 16
+    need_memory(2 * nbytes + nbytes // 8 + (1 << 28))                             # the planes, the full-size output, one comparison's mask
+    base = _planes(torch.int64, (8, h, w))
+    assert len({base[t].numpy().tobytes() for t in range(8)}) == 8
+    x = periodic_batch(base.cuda(), n)
+    numel = n * h * w
+    buf = torch.full((16 + numel + 16,), 0x4d, dtype=torch.int64, device="cuda")
+    out = buf[16:16 + numel].view(n, h, w)
+    ident = torch.tensor([h * Q // 2, w * Q // 2, Q, 0, 0, Q], dtype=torch.int32, device="cuda").repeat(n, 1).contiguous()
+    assert engine.view_planes_affine(x, ident, None, Q, fill=-1, out=out) is out
+    torch.cuda.synchronize()
+    assert bool((buf[:16] == 0x4d).all()) and bool((buf[16 + numel:] == 0x4d).all()), "identity: written outside the output"
+    assert torch.equal(out, x), "the identity at full size is not a bit copy"
+    del out, buf, ident
+    release()
+    fill = -(2 ** 40) - 3
+    win = period8_affine_windows(n, h, w, 64, 64, "rotated")
+    dwin = torch.from_numpy(win).cuda()
+    body = _run(lambda o: engine.view_planes_affine(x, dwin, (64, 64), AFFINE_MAX_R, fill=fill, out=o), x, (n, 64, 64), "big affine planes")
+    assert_periodic(body, period=8, label="view_planes_affine big batch")
+    want = np.stack([affine_nearest(base[t].numpy(), win[t], (64, 64), fill) for t in range(8)])
+    assert all((want[t] == fill).any() and (want[t] != fill).any() for t in range(4))
+    assert np.array_equal(body[:8].numpy(), want)
     del x, body
     release()
 
