@@ -848,6 +848,34 @@ SL_API int sl_view_planes(const void* planes, void* out, int n, int c, int h, in
 SL_API int sl_normalize_view_affine(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int max_r, uint32_t fill_rgb, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, const double* alpha_beta, int augment_background, const SlParams* params, const SlTensorFormat* fmt, void* stream);
 SL_API int sl_view_planes_affine(const void* planes, void* out, int n, int c, int h, int w, int elem_bytes, int oh, int ow, const int32_t* windows, int max_r, uint64_t fill_bits, void* stream);
 
+/* ---- hue / saturation / brightness augmentation (stainlib_amd/csrc/hsb.hip; an extension: the HSV half of the Tellez et al. colour
+ * augmenters, the sibling of sl_hed_augment).  Defined in INTEGERS on bytes, so every route below computes the same bits.
+ * Q = 32768; rdiv(a, c) = (2 a + c) / (2 c), rnd(x) = (x + Q / 2) >> 15, integer division.  codes: n x 3 int32 on the device,
+ * (dhq, dsq, dvq) per tile -- from float shifts dh (turns, any real) and ds, dv in [-1, 1]: dhq = floor((dh mod 1) 6 Q + 1/2) mod 6 Q,
+ * dsq = floor(ds Q + 1/2), dvq = floor(dv Q + 1/2).  Codes outside their ranges are reduced by the kernel: dhq mod 6 Q (non-negative),
+ * dsq and dvq clamped to +-Q.  Per pixel (r, g, b): M = max, m = min, C = M - m;
+ *     hq = 0 when C == 0, else (base Q + rdiv((num + C) Q, C) - Q) mod 6 Q with (base, num) = (4, r - g) if M == b, else (2, b - r) if
+ *          M == g, else (0, g - b)              (blue wins ties over green, green over red, as in scikit-image's rgb2hsv)
+ *     s = 0 when M == 0, else rdiv(C Q, M);   v = rdiv(M Q, 255)
+ *     scale(x, d) = x if d == 0;  rnd(x (Q + d)) if d < 0;  rnd(x (Q + rnd((Q - x) d))) if d > 0       (towards Q, never past it)
+ *     hq' = (hq + dhq) mod 6 Q,  s' = scale(s, dsq),  v' = scale(v, dvq),  hi = hq' / Q,  fq = hq' - hi Q
+ *     p = rnd(v' (Q - s')),  q = rnd(v' (Q - rnd(fq s'))),  t = rnd(v' (Q - rnd((Q - fq) s')))
+ *     (R, G, B) by hi: 0 (v', t, p), 1 (q, v', p), 2 (p, v', t), 3 (p, q, v'), 4 (t, p, v'), 5 (v', p, q);  byte = (X 255 + Q / 2) >> 15
+ * Zero codes are the identity.  (stainlib_amd/augmentation/hsb.py holds the same in numpy; csrc/hsb_math.hpp in 32 bits.)
+ *
+ * sl_hsb_augment: out = HSB(rgb) per tile, one sweep, 3 B/px read.  fmt == NULL: out is the n x h x w x 3 uint8 image; else the tensor
+ * SlTensorFormat describes, bit for bit sl_to_tensor of that image, written directly.  SL_ERR_BADARG: what sl_to_tensor refuses of rgb,
+ * out, n, h, w and a non-NULL fmt; a NULL or misaligned codes.  out == rgb is not supported.
+ *
+ * sl_normalize_hsb_view: the view of HSB(full[t]) in ONE pass, full[t] the image the statistics pattern names as in sl_normalize_view
+ * (the tiles' own bytes, sl_normalize_apply's image, the jitter of tissue pixels or of all pixels).  max_wh == 0 (then max_ww == 0): the
+ * fixed-size view of sl_normalize_view_shrink -- windows n x 3, shrink 1, 2 or 4, the box mean taken of the HSB-mapped pixels.
+ * Otherwise the resizing view of sl_normalize_view_resize -- windows n x 5, shrink == 1, the area resample of the mapped pixels.  A tile
+ * whose fit failed: the view of HSB(its own bytes).  SL_ERR_BADARG before anything is launched: what those two calls refuse; max_wh == 0
+ * with max_ww != 0; a resizing view with shrink != 1; a NULL or misaligned codes.  Capture-safe like them. */
+SL_API int sl_hsb_augment(const uint8_t* rgb, void* out, int n, int h, int w, const int32_t* codes, const SlTensorFormat* fmt, void* stream);
+SL_API int sl_normalize_hsb_view(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, int shrink, int max_wh, int max_ww, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, const double* alpha_beta, int augment_background, const SlParams* params, const SlTensorFormat* fmt, const int32_t* codes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

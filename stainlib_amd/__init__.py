@@ -6,6 +6,7 @@ TensorFormat (an extension) turns the batched operators' uint8 results into mode
 StainJitter (an extension) draws the per-tile (alpha, beta) of the augment_batch methods: stain jitter inside the apply pass.
 TileView (an extension) draws the per-tile crop / flip / quarter turn that view= applies inside the same pass.
 TileAffine (an extension) draws a per-tile rotation by any angle, zoom, shear and translation for view=: bilinear, in integers.
+HsbColorAugmenter (an extension; HsbLight / HsbStrong presets) is the hue / saturation / brightness sibling of the HED augmenters, in integers.
 Separated (an extension) is what the normalizers' separate / separate_batch return: per-stain images and concentration maps.
 Importing the package does not need a GPU; calling anything numeric does, and fails loudly without the
 HIP library -- there is no CPU fallback.
@@ -13,6 +14,7 @@ HIP library -- there is no CPU fallback.
 from . import _ffi  # noqa: F401
 from .augmentation.augmenter import (HedLightColorAugmenter, HedLighterColorAugmenter,  # noqa: F401
                                      HedStrongColorAugmenter, StainAugmentor, GrayscaleAugmentor, StainJitter)
+from .augmentation.hsb import HsbColorAugmenter, HsbLightColorAugmenter, HsbStrongColorAugmenter  # noqa: F401
 from .extraction.macenko_stain_extractor import MacenkoStainExtractor  # noqa: F401
 from .extraction.vahadane_stain_extractor import VahadaneStainExtractor  # noqa: F401
 from .normalization.normalizer import (ExtractiveStainNormalizer, MacenkoNormalizer,  # noqa: F401

@@ -248,7 +248,8 @@ class StainAugmentor(object):
         out = engine.stain_augment(self._dev, self.stain_matrix[None], [alpha_beta], self.augment_background)
         return out[0].cpu().numpy()
 
-    def augment_batch(self, tiles, alpha_beta=None, tensor_format=None, view=None, windows=None, hed=None, hed_sigmas=None, hed_biases=None):
+    def augment_batch(self, tiles, alpha_beta=None, tensor_format=None, view=None, windows=None, hed=None, hed_sigmas=None, hed_biases=None,
+                      hsb=None, hsb_sigmas=None):
         """Batched extension: (N,H,W,3) uint8 device tensor -> (out, M, maxC, status) device tensors: every tile perturbed under its OWN
         stain matrix (this augmentor's extractor, fitted per tile) -- n fit() / pop() pairs in one fit and ONE pass, nothing through the
         host.  alpha_beta: (N, 4) = alpha0, beta0, alpha1, beta1 per tile; by default drawn from the global numpy stream exactly as N
@@ -262,6 +263,10 @@ class StainAugmentor(object):
         ``hed.transform_batch`` of the result above, then the view.  ``hed_sigmas``, ``hed_biases``: (N, 3) each; by default
         ``hed.randomize_batch(N)``, drawn after alpha_beta and BEFORE the windows.  The call then returns one more element at the end,
         ``engine.HedDraw(sigmas, biases, applied)``.
+        ``hsb``: an ``HsbColorAugmenter`` -- its hue / saturation / brightness map on every perturbed tile in the SAME pass
+        (engine.normalize_hsb_view): bit for bit ``hsb.transform_batch`` of the result above, then the view.  ``hsb_sigmas``: (N, 3); by
+        default ``hsb.randomize_batch(N)``, drawn after alpha_beta and BEFORE the windows.  One more element at the end,
+        ``engine.HsbDraw(sigmas, codes)``.  Not together with ``hed`` or a TileAffine.
         fit() / pop() are untouched by it."""
         from .. import engine
         jitter = StainJitter(self.sigma1, self.sigma2, self.augment_background)
@@ -269,12 +274,14 @@ class StainAugmentor(object):
         if view is not None or windows is not None:
             engine._view_call(view, windows, tiles, draw=False)
         with_hed = engine._hed_call(hed, hed_sigmas, hed_biases, tiles, view)
+        with_hsb = engine._hsb_call(hsb, hsb_sigmas, tiles, view, hed)
         n, h, w = engine._check_tiles(tiles)
         fit = (engine.macenko_fit if self._method == "macenko" else engine.vahadane_fit)(tiles)[:3]
         if alpha_beta is None:
             alpha_beta = jitter.draw(n)
         route = dict(M_tgt=None, maxC_tgt=None, alpha_beta=alpha_beta, augment_background=self.augment_background)
-        return engine.route_stage(tiles, fit, route, tensor_format, None, view, windows, (hed, hed_sigmas, hed_biases) if with_hed else None)
+        return engine.route_stage(tiles, fit, route, tensor_format, None, view, windows, (hed, hed_sigmas, hed_biases) if with_hed else None,
+                                  (hsb, hsb_sigmas) if with_hsb else None)
 
 
 class StainJitter(object):

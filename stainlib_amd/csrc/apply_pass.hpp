@@ -99,6 +99,12 @@ struct GroupPipe {
 #pragma unroll
         for (int k = 0; k < U * G; ++k) nxt[k / G][k % G] = fetch(T.g0 + tid + (k / G) * kWG, k % G);
     }
+    // the same for a sweep without statistics (k_hsb): the tile's bytes and the part's span [g0, g1) as they are
+    __device__ __forceinline__ GroupPipe(const uint8_t* tile, size_t tile_bytes, int tile_chunks, int g0, int g1_, int tid)
+        : src(tile), nbytes(tile_bytes), nch(tile_chunks), g1(g1_) {
+#pragma unroll
+        for (int k = 0; k < U * G; ++k) nxt[k / G][k % G] = fetch(g0 + tid + (k / G) * kWG, k % G);
+    }
     __device__ __forceinline__ void advance(int g) {           // in := the trip at g, nxt := the trip after it
 #pragma unroll
         for (int k = 0; k < U * G; ++k) {

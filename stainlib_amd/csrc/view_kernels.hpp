@@ -251,6 +251,11 @@ struct HedStage {
     __device__ __forceinline__ void init(int, int, const HedViewArgs*) {}
     __device__ __forceinline__ void apply(uint32_t (&)[4]) const {}
 };
+// HED = 2: the HSB map of sl_normalize_hsb_view (hsb_kernels.hpp specialises the stage; its arguments arrive in a struct of their own).
+// StageArgs<HED>: what view_body and view_resize_body hand to the stage's init.
+struct HsbViewArgs;
+template <int HED> struct StageArgs { typedef HedViewArgs type; };
+template <> struct StageArgs<2> { typedef HsbViewArgs type; };
 
 // DT: kDtU8 or a tensor type; LAYOUT: tensor only; MODE: kView*; HED: the stage above.  npx: patches per output row, npatch: per tile.
 template <int DT, int LAYOUT, int MODE, int HED>
@@ -258,7 +263,7 @@ __device__ __forceinline__ void view_body(const uint8_t* rgb, void* out, int h, 
                                           int npx, int npatch, const int32_t* windows, int d_mask, int shrink,
                                           const double* M_src, const double* maxC_src,
                                           const double* M_tgt, const double* maxC_tgt, const double* alpha_beta,
-                                          double lam, float ylimf, TensorK fmt, const HedViewArgs* hv) {
+                                          double lam, float ylimf, TensorK fmt, const typename StageArgs<HED>::type* hv) {
     constexpr int B = kViewB, PITCH = kViewPitch;
     static_assert(kWG == 256 && B == 64, "16 lanes x 4 pixels per row, 16 rows per pass, 4 passes");
     __shared__ float2 s_tab[256];
@@ -289,7 +294,7 @@ __device__ __forceinline__ void view_body(const uint8_t* rgb, void* out, int h, 
     auto raw = [&](const Chunk& c, uint32_t (&px)[4]) { unpack(c, px); };
 
     if (MODE == kViewRaw) {
-        if (HED != 0) __syncthreads();                              // the stage's table
+        if (HED == 1) __syncthreads();                              // the HED stage's table
         stage(raw);
     } else {
         const ApplyTile<1> A(blockIdx.x, npatch, P, rgb, M_src, maxC_src, M_tgt, maxC_tgt, lam);

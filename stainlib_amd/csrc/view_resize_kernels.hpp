@@ -139,7 +139,7 @@ __device__ __forceinline__ void view_resize_body(const uint8_t* rgb, void* out, 
                                                  const int32_t* windows, int d_mask, int max_wh, int max_ww,
                                                  const double* M_src, const double* maxC_src,
                                                  const double* M_tgt, const double* maxC_tgt, const double* alpha_beta,
-                                                 double lam, float ylimf, TensorK fmt, const HedViewArgs* hv) {
+                                                 double lam, float ylimf, TensorK fmt, const typename StageArgs<HED>::type* hv) {
     constexpr int B = kViewB, PITCH = kViewPitch;
     static_assert(kWG == 256 && B == 64, "16 lanes x 4 pixels per row, 16 rows per pass, 4 passes");
     __shared__ float2 s_tab[256];
@@ -173,7 +173,7 @@ __device__ __forceinline__ void view_resize_body(const uint8_t* rgb, void* out, 
     auto raw = [&](const Chunk& c, uint32_t (&px)[4]) { unpack(c, px); };
 
     if (MODE == kViewRaw) {
-        if (HED != 0) __syncthreads();                              // the stage's table
+        if (HED == 1) __syncthreads();                              // the HED stage's table
         stage(raw);
     } else {
         const ApplyTile<1> A(blockIdx.x, npatch, P, rgb, M_src, maxC_src, M_tgt, maxC_tgt, lam);

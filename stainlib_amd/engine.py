@@ -1015,6 +1015,123 @@ def hed_stage(tiles, hed, hed_sigmas, hed_biases, view, windows, route, fmt=None
     return x, windows, HedDraw(hed_sigmas, hed_biases, applied)
 
 
+# ---- hue / saturation / brightness augmentation (sl_hsb_augment, sl_normalize_hsb_view; see include/stainlib_hip.h, augmentation/hsb.py) ----
+
+HsbDraw = collections.namedtuple("HsbDraw", ["sigmas", "codes"])
+HsbDraw.__doc__ = """What the hsb= stage of a batch method did: the (N, 3) float64 sigmas it used (given or drawn: hue, saturation,
+brightness) and the (N, 3) int32 codes they gave (augmentation.hsb.hsb_codes), both numpy."""
+
+
+def _hsb_codes_rows(codes):
+    """The rows of an (N, 3) codes argument (no device needed): a device int32 tensor, or host integers that fit int32."""
+    import numpy as np
+    what = "codes must hold (dhq, dsq, dvq) per tile: an (N, 3) int32 array (augmentation.hsb.hsb_codes)"
+    if isinstance(codes, torch.Tensor):
+        if codes.dtype != torch.int32 or codes.dim() != 2 or codes.shape[1] != 3:
+            raise ValueError(what)
+        return int(codes.shape[0])
+    try:
+        arr = np.asarray(codes)
+        if arr.dtype.kind not in "iu":
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError(what) from None
+    if arr.ndim != 2 or arr.shape[1] != 3:
+        raise ValueError(f"{what}, not one of shape {arr.shape}")
+    if arr.size and (arr.min() < -2 ** 31 or arr.max() >= 2 ** 31):
+        raise ValueError("codes must fit int32")
+    return int(arr.shape[0])
+
+
+def _hsb_codes_device(codes, n, device):
+    import numpy as np
+    if _hsb_codes_rows(codes) != n:
+        raise ValueError(f"codes must have one row per tile ({n})")
+    if isinstance(codes, torch.Tensor):
+        return codes.to(device).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(codes).astype(np.int32))).to(device)
+
+
+def hsb_augment(rgb, codes, fmt=None, out=None):
+    """The HSB map of every tile in one sweep (sl_hsb_augment): codes (N, 3) int32 = (dhq, dsq, dvq) per tile (augmentation.hsb.hsb_codes;
+    a device tensor is taken as it is, out-of-range values are reduced by the kernel) -> (N,H,W,3) uint8, bit for bit
+    augmentation.hsb.hsb_reference; or with fmt (a stainlib_amd.TensorFormat) the (N,3,H,W) tensor, bit for bit fmt.convert of that image,
+    written directly."""
+    from .tensor_format import TensorFormat
+    if fmt is not None and not isinstance(fmt, TensorFormat):
+        raise ValueError("fmt must be a stainlib_amd.TensorFormat or None (the uint8 image)")
+    _hsb_codes_rows(codes)
+    n, h, w = _check_tiles(rgb)
+    c = _hsb_codes_device(codes, n, rgb.device)
+    f, out = _image_out(out, rgb, n, h, w, fmt, "HSB augmentation")
+    _call("sl_hsb_augment", _ptr(rgb), _ptr(out), n, h, w, _ptr(c), _byref(f))
+    return out
+
+
+def normalize_hsb_view(rgb, windows, size, d_mask, codes, M_src=None, maxC_src=None, M_tgt=None, maxC_tgt=None, alpha_beta=None,
+                       augment_background=False, params=None, fmt=None, out=None, shrink=1, resize=None):
+    """normalize_view of HSB(full[t]) in ONE pass (sl_normalize_hsb_view): `full` is normalize_view's (the route arguments are the same),
+    HSB(.) is hsb_augment with the tile's codes -- bit for bit hsb_augment of `full`, then normalize_view of the result, without a pixel
+    outside the window being touched.  shrink, resize: normalize_view's, acting on the HSB-mapped pixels.  A tile whose fit failed: the
+    view of HSB(its own bytes)."""
+    def codes_ok(n):
+        if _hsb_codes_rows(codes) != n:
+            raise ValueError(f"codes must have one row per tile ({n})")
+    n, h, w, oh, ow, win, M_src, maxC_src, M_tgt, maxC_tgt, ab, f, out = _view_prepare(
+        rgb, windows, size, d_mask, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, params, fmt, out, before_device=codes_ok, shrink=shrink,
+        resize=resize)
+    c = _hsb_codes_device(codes, n, rgb.device)
+    mh, mw = (int(resize[0]), int(resize[1])) if resize is not None else (0, 0)
+    _call("sl_normalize_hsb_view", _ptr(rgb), _ptr(out), n, h, w, oh, ow, _ptr(win), int(d_mask), int(shrink), mh, mw, _ptr(M_src),
+          _ptr(maxC_src), _ptr(M_tgt), _ptr(maxC_tgt), _ptr(ab), 1 if augment_background else 0, _byref(params), _byref(f), _ptr(c))
+    return out
+
+
+def _hsb_call(hsb, hsb_sigmas, tiles, view=None, hed=None):
+    """The hsb= / hsb_sigmas= arguments of a batch method, checked without a device and before any draw (ValueError).  True when the call
+    has an HSB stage.  view, hed: the call's view= and hed= -- an affine view and a HED stage do not go with it."""
+    from .augmentation.hsb import HsbColorAugmenter, hsb_codes
+    if hsb is None:
+        if hsb_sigmas is not None:
+            raise ValueError("hsb_sigmas= goes with hsb= (an HsbColorAugmenter)")
+        return False
+    if hed is not None:
+        raise ValueError("hsb= and hed= do not go together: a pass has one colour-augmentation stage (chain hed.transform_batch or "
+                         "hsb.transform_batch behind the call for the second)")
+    _no_affine(view, "the HSB stage (hsb=, HsbColorAugmenter.transform_batch(view=))",
+               "take the HSB result as a uint8 image through TensorFormat.convert(view=), which samples bilinearly")
+    if not isinstance(hsb, HsbColorAugmenter):
+        raise ValueError("hsb must be a stainlib_amd HsbColorAugmenter (its ranges are used)")
+    if not (isinstance(tiles, torch.Tensor) and tiles.dim() == 4 and tiles.shape[-1] == 3):
+        raise ValueError("expected a contiguous CUDA uint8 tensor of shape (N, H, W, 3)")
+    if hsb_sigmas is not None:
+        codes = hsb_codes(hsb_sigmas)
+        if codes.ndim != 2 or codes.shape[0] != int(tiles.shape[0]):
+            raise ValueError(f"hsb_sigmas must have one (hue, saturation, brightness) row per tile ({int(tiles.shape[0])})")
+    return True
+
+
+def hsb_stage(tiles, hsb, hsb_sigmas, view, windows, route, fmt=None, out=None):
+    """The hsb= stage of the batch methods, behind their fit and their own draws, on arguments _hsb_call / _view_call(draw=False) have
+    accepted: the draws the caller left open -- hsb.randomize_batch(N), THEN view.draw -- and ONE fused pass (normalize_hsb_view).  route:
+    normalize_view's keyword arguments that name `full` ({}: the tiles themselves).  Without a view the result is the full tile, code 0.
+    -> (out, windows or None, HsbDraw)."""
+    import numpy as np
+    from .augmentation.hsb import hsb_codes
+    n = int(tiles.shape[0])
+    if hsb_sigmas is None:
+        hsb_sigmas = hsb.randomize_batch(n)
+    sigmas = np.array(hsb_sigmas, dtype=np.float64)
+    codes = hsb_codes(sigmas)
+    if view is not None:
+        size, d_mask, windows, shrink = _view_call(view, windows, tiles)
+        win = windows
+    else:
+        size, d_mask, windows, win, shrink = None, 0, None, np.zeros((n, 3), dtype=np.int32), 1
+    x = normalize_hsb_view(tiles, win, size, d_mask, codes, fmt=fmt, out=out, shrink=shrink, resize=_view_resize(view, win, tiles), **route)
+    return x, windows, HsbDraw(sigmas, codes)
+
+
 def _view_call(view, windows, tiles, draw=True):
     """(size, d_mask, windows, shrink) of the view= / windows= pair of a batch method, checked without a device (ValueError): the windows
     as given, or drawn (TileView.draw; draw=False: left None for a later call)."""
@@ -1063,14 +1180,18 @@ def _view_resize_hw(view, windows, h, w):
     return max(1, min(h, int(win[:, 3].max()))), max(1, min(w, int(win[:, 4].max())))
 
 
-def route_stage(tiles, fit, route, fmt=None, out=None, view=None, windows=None, hed=None):
+def route_stage(tiles, fit, route, fmt=None, out=None, view=None, windows=None, hed=None, hsb=None):
     """The tail of the batch methods, behind their fit and their own draws, on arguments _jitter_args / _view_call(draw=False) / _hed_call
     have accepted: ONE pass over the tiles and the tuple the method returns, (out, M_src, maxC_src, status[, windows][, HedDraw]).
     fit: the fit's (M_src, maxC_src, status); route: the other arguments that name `full` (M_tgt, maxC_tgt and, for a jitter, alpha_beta
     and augment_background).  hed = (HedColorAugmenter, hed_sigmas, hed_biases): hed_stage; else with a view: normalize_view, the
-    windows drawn here if not given; else normalize_jitter."""
+    windows drawn here if not given; else normalize_jitter.  hsb = (HsbColorAugmenter, hsb_sigmas) that _hsb_call has accepted (never
+    with hed): hsb_stage, and HsbDraw at the end of the tuple."""
     M, maxC, status = fit
     route = dict(M_src=M, maxC_src=maxC, **route)
+    if hsb is not None:
+        x, windows, draw = hsb_stage(tiles, *hsb, view, windows, route, fmt=fmt, out=out)
+        return (x, M, maxC, status) + ((windows,) if view is not None else ()) + (draw,)
     if hed is not None:
         x, windows, draw = hed_stage(tiles, *hed, view, windows, route, fmt=fmt, out=out)
         return (x, M, maxC, status) + ((windows,) if view is not None else ()) + (draw,)

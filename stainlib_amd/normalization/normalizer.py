@@ -146,21 +146,22 @@ class ExtractiveStainNormalizer(object):
         """Per-tile (M, maxC, status) device tensors for a batch of candidate targets."""
         return self._fit_tiles(tiles, ws=ws)
 
-    def _route_batch(self, tiles, target, jitter, out, ws, tensor_format, view, windows, hed):
+    def _route_batch(self, tiles, target, jitter, out, ws, tensor_format, view, windows, hed, hsb=None):
         """The view= / hed= routes of transform_batch and all of augment_batch: the checks that are left (every one before the fit and
         before any draw), the fit of the whole tiles, then engine.route_stage -- ONE pass under the target (target=True) or every tile's
         own matrix, with the jitter's alpha_beta / augment_background ({}: none).  hed: None, or (hed, hed_sigmas, hed_biases) that
-        engine._hed_call has accepted.  -> (out, M_src, maxC_src, status[, windows][, HedDraw])."""
+        engine._hed_call has accepted; hsb: None, or (hsb, hsb_sigmas) that engine._hsb_call has accepted.
+        -> (out, M_src, maxC_src, status[, windows][, HedDraw or HsbDraw])."""
         from .. import engine
         if view is not None or windows is not None:
             engine._view_call(view, windows, tiles, draw=False)
         engine._check_tiles(tiles)
         fit = self._fit_tiles(tiles, ws=ws)
         M_t, c_t = self._target_on(tiles.device) if target else (None, None)
-        return engine.route_stage(tiles, fit, dict(M_tgt=M_t, maxC_tgt=c_t, **jitter), tensor_format, out, view, windows, hed)
+        return engine.route_stage(tiles, fit, dict(M_tgt=M_t, maxC_tgt=c_t, **jitter), tensor_format, out, view, windows, hed, hsb)
 
     def transform_batch(self, tiles, out=None, ws=None, tensor_format=None, _tensor_route=None, view=None, windows=None, hed=None,
-                        hed_sigmas=None, hed_biases=None):
+                        hed_sigmas=None, hed_biases=None, hsb=None, hsb_sigmas=None):
         """(N,H,W,3) uint8 device tensor -> (out, M_src, maxC_src, status) device tensors.  A tile whose
         status is non-zero (1 = empty tissue mask, 2 = degenerate, 3 = a zero 99th-percentile concentration) is passed through unchanged.
         ``ws``: an ``engine.Workspace`` to reuse (ONE stream at a time); by default every call takes its scratch from
@@ -174,11 +175,17 @@ class ExtractiveStainNormalizer(object):
         (engine.normalize_sums for its cutoff test on the image nobody writes, then engine.normalize_hed_view): bit for bit
         ``hed.transform_batch`` of the uint8 result, then the view and the conversion.  ``hed_sigmas``, ``hed_biases``: (N, 3) each; by
         default ``hed.randomize_batch(N)``, drawn BEFORE the windows.  Works with or without ``view`` / ``tensor_format``; the call then
-        returns one more element at the end, ``engine.HedDraw(sigmas, biases, applied)``."""
+        returns one more element at the end, ``engine.HedDraw(sigmas, biases, applied)``.
+        ``hsb``: an ``HsbColorAugmenter`` -- its hue / saturation / brightness map on every normalised tile in that same pass
+        (engine.normalize_hsb_view; no cutoff test, so nothing is read twice): bit for bit ``hsb.transform_batch`` of the uint8 result,
+        then the view and the conversion.  ``hsb_sigmas``: (N, 3); by default ``hsb.randomize_batch(N)``, drawn BEFORE the windows.  The
+        call then returns one more element at the end, ``engine.HsbDraw(sigmas, codes)``.  Not together with ``hed`` or a TileAffine."""
         from .. import engine
         with_hed = engine._hed_call(hed, hed_sigmas, hed_biases, tiles, view)
-        if with_hed or view is not None or windows is not None:
-            return self._route_batch(tiles, True, {}, out, ws, tensor_format, view, windows, (hed, hed_sigmas, hed_biases) if with_hed else None)
+        with_hsb = engine._hsb_call(hsb, hsb_sigmas, tiles, view, hed)
+        if with_hed or with_hsb or view is not None or windows is not None:
+            return self._route_batch(tiles, True, {}, out, ws, tensor_format, view, windows, (hed, hed_sigmas, hed_biases) if with_hed else None,
+                                     (hsb, hsb_sigmas) if with_hsb else None)
         if tensor_format is None:
             return self._transform_tiles(tiles, out=out, ws=ws)
         route = _tensor_route or TENSOR_ROUTE
@@ -229,7 +236,7 @@ class ExtractiveStainNormalizer(object):
 
     # -- stain jitter in the apply pass (an extension: RandStainNA / StainAugmentor-style augmentation of the normalised tiles) ----
     def augment_batch(self, tiles, alpha_beta, augment_background=False, normalize=True, out=None, ws=None, tensor_format=None, view=None,
-                      windows=None, hed=None, hed_sigmas=None, hed_biases=None):
+                      windows=None, hed=None, hed_sigmas=None, hed_biases=None, hsb=None, hsb_sigmas=None):
         """(N,H,W,3) uint8 device tensor -> (out, M_src, maxC_src, status): the per-tile fit, then ONE pass that normalises every tile
         and perturbs its stains: C_i * alpha_i + beta_i on the normalised concentrations of tissue pixels (every pixel with
         ``augment_background``), under the target's stain matrix, clipped.  ``alpha_beta``: (N, 4) = alpha0, beta0, alpha1, beta1 per
@@ -240,14 +247,18 @@ class ExtractiveStainNormalizer(object):
         ``view``, ``windows``: as in transform_batch -- the crop / flip / quarter turn of every tile in the same pass; the call then
         returns (out, M_src, maxC_src, status, windows).
         ``hed``, ``hed_sigmas``, ``hed_biases``: as in transform_batch -- the HedColorAugmenter's transform of the perturbed tile in the
-        same pass; one more element at the end of the returned tuple, ``engine.HedDraw``."""
+        same pass; one more element at the end of the returned tuple, ``engine.HedDraw``.
+        ``hsb``, ``hsb_sigmas``: as in transform_batch -- the HsbColorAugmenter's map of the perturbed tile in the same pass; one more
+        element at the end of the returned tuple, ``engine.HsbDraw``."""
         from .. import engine
         engine._jitter_args(None, None, alpha_beta, None, tensor_format, out)
         if normalize and not hasattr(self, "stain_matrix_target"):
             raise ValueError("augment_batch(normalize=True) needs a fitted target: call fit() first, or pass normalize=False")
         with_hed = engine._hed_call(hed, hed_sigmas, hed_biases, tiles, view)
+        with_hsb = engine._hsb_call(hsb, hsb_sigmas, tiles, view, hed)
         return self._route_batch(tiles, normalize, dict(alpha_beta=alpha_beta, augment_background=augment_background), out, ws,
-                                 tensor_format, view, windows, (hed, hed_sigmas, hed_biases) if with_hed else None)
+                                 tensor_format, view, windows, (hed, hed_sigmas, hed_biases) if with_hed else None,
+                                 (hsb, hsb_sigmas) if with_hsb else None)
 
     def separate(self, I, normalize=True):
         """An image (RGB uint8) -> Separated of numpy arrays: norm (= transform(I)), h, e ((H,W,3) uint8) and conc ((2,H,W) float32)."""
