@@ -37,7 +37,7 @@ static __global__ __launch_bounds__(kWG) void k_view_planes_affine(const uint8_t
     bool none;
     if (!affine_patch(vt, patch, h, w, oh, ow, g, none)) return;
 
-    const AffineLanes ln = affine_lanes(g.bw, tid, kWG);
+    const PatchLanes ln = patch_lanes(g.bw, tid, kWG);
     const int jl = ln.jl, bh = g.bh, bw = g.bw;
     if (jl >= bw) return;
     const int nvalid = min(4, bw - jl);

@@ -93,18 +93,7 @@ SL_GEOM_FN bool affine_patch(const AffineTile& t, int patch, int h, int w, int o
     return true;
 }
 
-// ---- write side: lanes walk OUTPUT rows, 4 adjacent outputs per lane; lanes per row = the power of two that covers the patch's width
-// (1 .. 16), so a narrow patch spreads its rows over all the lanes (resize_write's and k_view_planes' assignment).  Lane tid of `wg`
-// takes the outputs jl .. jl + 3 of rows il0, il0 + rows, ...
-struct AffineLanes { int il0, jl, rows; };
-SL_GEOM_FN AffineLanes affine_lanes(int bw, int tid, int wg) {
-    const int n4 = (bw + 3) >> 2;                                                // chunks of 4 outputs per output row, 1 .. 16
-    const int lg = n4 <= 1 ? 0 : 32 - __builtin_clz((unsigned)(n4 - 1));         // log2 of the lanes per row: 0 .. 4
-    AffineLanes l;
-    l.il0 = tid >> lg; l.jl = 4 * (tid & ((1 << lg) - 1)); l.rows = wg >> lg;
-    return l;
-}
-
+// ---- write side: the lanes of a patch are view_geometry.hpp's patch_lanes.
 // The four taps and the two 8-bit weights of one output pixel of the images: rows ky, ky + 1, columns kx, kx + 1 of the tile (any of
 // them may lie outside it), weights fy, fx of the second row / column out of 256.
 struct AffineTaps { int ky, kx, fy, fx; };

@@ -11,9 +11,10 @@
 //     b = ((256 - fy) ((256 - fx) p00 + fx p01) + fy ((256 - fx) p10 + fx p11) + 32768) >> 16.
 //
 // What is shared with k_view / k_view_resize: load12 / view_read (the read side), view_stage / view_unpack (the LDS stage, one packed dword
-// per SOURCE pixel, pitch 65), the apply / jitter arithmetic per source pixel (view_body's, statement for statement), cvt_chunk and
-// store_view4.  What is new: the geometry (view_affine_geometry.hpp: AffineTile, affine_patch, affine_at, affine_taps, affine_blend) and
-// the write side (affine_write).
+// per SOURCE pixel, pitch 65), the apply / jitter arithmetic per source pixel (view_route, view_kernels.hpp: the one copy this kernel
+// and view_resize_body run), the store tail from four packed pixels on (view_store_px4) and the lanes of a patch (patch_lanes,
+// view_geometry.hpp).  What is new: the geometry (view_affine_geometry.hpp: AffineTile, affine_patch, affine_at, affine_taps,
+// affine_blend) and the sampling of the write side (affine_write).
 //
 // Shape: ONE workgroup = one tile and one patch of b x b OUTPUT pixels, b = affine_patch_edge(max(Ry, Rx)) = min(64, 1 + 62 Q / R) per
 // tile and block-uniform, so that the taps of the patch fit the 64 x 64 LDS block along both axes.  The source block is the bounding
@@ -23,10 +24,10 @@
 // bound max_r of the row sums (affine_grid_patches); a workgroup past its tile's own patch count returns before it loads a pixel, a
 // patch whose box misses the tile -- and every patch of a tile whose row sums pass max_r -- reads nothing and writes the fill.
 //   write side  output rows, 4 adjacent output pixels per lane; 16, 8, 4, 2 or 1 lanes per row -- the power of two that covers the
-//               patch's width -- and 256 / that many rows per pass (resize_write's assignment).  Per output pixel Y, X from the block's
+//               patch's width -- and 256 / that many rows per pass (patch_lanes, as in resize_write).  Per output pixel Y, X from the block's
 //               scalars (two v_mad each), the four LDS slots (clamped into the block; inside a tile a tap IS in the block), four selects
 //               against the fill decided from the ABSOLUTE coordinates (unsigned compares with h, w), the blend (affine_blend: r and b as
-//               two 16-bit lanes of one dword in the row step), then cvt_chunk / store_view4 as everywhere.
+//               two 16-bit lanes of one dword in the row step), then view_store_px4.
 // LDS banking of the tap reads (pitch 65: bank (r + x) % 32 within each 32-lane half; the two taps of a row are adjacent dwords): lanes of
 // one output row are 4 outputs apart, i.e. 4 a01 / Q rows and 4 a11 / Q columns of LDS, so their bank stride is 4 (a01 + a11) / Q; the
 // next output row is (a00 + a10) / Q banks on.
@@ -52,13 +53,10 @@ namespace sl {
 template <int DT, int LAYOUT>
 __device__ __forceinline__ void affine_write(const AffineTile& t, const ViewPatch& g, bool none, const uint32_t* s_px, void* out, int tile,
                                              int h, int w, int oh, int ow, uint32_t fill, TensorK fmt, int tid) {
-    constexpr bool TENSOR = DT != kDtU8;
-    constexpr int SDT = TENSOR ? DT : kDtF32;
-    typedef typename Elem<SDT>::type T;
     const int i0 = g.i0, j0 = g.j0, bh = g.bh, bw = g.bw;
     const TensorK F = tensor_consts(fmt);
     const size_t PO = (size_t)oh * ow;
-    const AffineLanes ln = affine_lanes(bw, tid, kWG);       // 1 .. 16 lanes per row, 256 .. 16 rows per pass
+    const PatchLanes ln = patch_lanes(bw, tid, kWG);         // 1 .. 16 lanes per row, 256 .. 16 rows per pass
     const int jl = ln.jl;
     if (jl >= bw) return;                                    // (nothing below has a barrier)
     for (int il = ln.il0; il < bh; il += ln.rows) {
@@ -75,31 +73,14 @@ __device__ __forceinline__ void affine_write(const AffineTile& t, const ViewPatc
             const uint32_t p10 = y1in && x0in ? s_px[r1 + c0] : fill, p11 = y1in && x1in ? s_px[r1 + c1] : fill;
             px[p] = affine_blend(p00, p01, p10, p11, a.fy, a.fx);
         }
-        Chunk o;
-        o.w0 = px[0] | (px[1] << 24);
-        o.w1 = (px[1] >> 8) | (px[2] << 16);
-        o.w2 = (px[2] >> 16) | (px[3] << 8);
         const int nvalid = min(4, bw - jl);
         const size_t pix = (size_t)(i0 + il) * ow + (j0 + jl);
-        if (TENSOR) {
-            float v[12];
-            cvt_chunk(o, F, v);
-            T* const base = (T*)out + (size_t)tile * 3 * PO;
-            store_view4<SDT, LAYOUT>(base, PO, pix, nvalid, v);
-        } else {
-            uint8_t* const p = (uint8_t*)out + ((size_t)tile * PO + pix) * 3;
-            if (nvalid == 4) {
-                sl_u32x3u u; u.x = o.w0; u.y = o.w1; u.z = o.w2;
-                *(SL_GLOBAL sl_u32x3u*)as_global(p) = u;
-            } else {
-                for (int i = 0; i < 3 * nvalid; ++i) as_global(p)[i] = (uint8_t)chunk_byte(o, i);
-            }
-        }
+        view_store_px4<DT, LAYOUT>(px, out, tile, PO, pix, nvalid, F);
     }
 }
 
-// view_resize_body with the geometry and the write side above; everything between view_read and the barrier is view_body's, statement
-// for statement.  npatch: the host's upper bound of the patches of a tile.
+// view_resize_body with the geometry and the write side above and no stage (HED = 0); the arithmetic between view_read and the barrier
+// is view_route (view_kernels.hpp).  npatch: the host's upper bound of the patches of a tile.
 template <int DT, int LAYOUT, int MODE>
 static __global__ __launch_bounds__(kWG) void k_view_affine(const uint8_t* __restrict__ rgb, void* __restrict__ out, int h, int w, int oh,
                                                             int ow, int npatch, const int32_t* __restrict__ windows, int max_r,
@@ -133,74 +114,7 @@ static __global__ __launch_bounds__(kWG) void k_view_affine(const uint8_t* __res
     auto stage = [&](auto compute) {
         view_stage(g, s_px, lr, lc, in, [&](const Chunk& c, uint32_t (&px)[4]) { compute(c, px); });
     };
-    auto unpack = [](const Chunk& o, uint32_t (&px)[4]) { view_unpack(o, px); };
-    auto raw = [&](const Chunk& c, uint32_t (&px)[4]) { unpack(c, px); };
-
-    if (MODE == kViewRaw) {
-        stage(raw);
-    } else {
-        const ApplyTile<1> A(blockIdx.x, npatch, P, rgb, M_src, maxC_src, M_tgt, maxC_tgt, lam);
-        const ApplyK& K = A.K;
-        JitterK J;
-        if (MODE != kViewApply) {                                   // k_apply_jitter's constants
-            const double sc = 1.0 / A.unit;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                J.al[i] = in_vgpr(uni((float)alpha_beta[4 * (size_t)A.tile + 2 * i]));
-                J.be[i] = in_vgpr(uni((float)(alpha_beta[4 * (size_t)A.tile + 2 * i + 1] / (A.mct[i] / A.mcs[i]) * sc)));
-            }
-            J.ylimf = in_vgpr(ylimf);
-        }
-        __syncthreads();                                            // the table
-        if (SL_FIT_FAILED(A)) {                                     // the view of the source bytes
-            stage(raw);
-        } else if (MODE == kViewApply) {                            // k_apply: K.fast picks the lasso form and the cast
-            auto sweep = [&](auto fast_tag) {
-                constexpr bool FAST = decltype(fast_tag)::value;
-                stage([&](const Chunk& c, uint32_t (&px)[4]) {
-                    float t[12];
-#pragma unroll
-                    for (int p = 0; p < 4; ++p) {
-                        const float x = s_tab[chunk_byte(c, 3 * p + 0)].y, y = s_tab[chunk_byte(c, 3 * p + 1)].y,
-                                    z = s_tab[chunk_byte(c, 3 * p + 2)].y;
-                        float v[3];
-                        apply_px<FAST>(K, x, y, z, v);
-                        t[3 * p] = v[0]; t[3 * p + 1] = v[1]; t[3 * p + 2] = v[2];
-                    }
-                    unpack(FAST ? pack_trunc_fast(t) : pack_trunc_general(t), px);
-                });
-            };
-            if (K.fast) sweep(std::true_type{}); else sweep(std::false_type{});
-        } else {                                                    // k_apply_jitter: g12 picks the lasso form, the cast saturates
-            auto sweep = [&](auto fast_tag) {
-                constexpr bool FAST = decltype(fast_tag)::value;
-                stage([&](const Chunk& c, uint32_t (&px)[4]) {
-                    float t[12];
-#pragma unroll
-                    for (int p = 0; p < 4; ++p) {
-                        const float2 er = s_tab[chunk_byte(c, 3 * p + 0)];      // x = gamma, y = od32
-                        const float2 eg = s_tab[chunk_byte(c, 3 * p + 1)];
-                        const float2 eb = s_tab[chunk_byte(c, 3 * p + 2)];
-                        float c1, c2;
-                        apply_conc<FAST>(K, er.y, eg.y, eb.y, c1, c2);
-                        if (MODE == kViewJitAll) {
-                            c1 = fmaf(c1, J.al[0], J.be[0]);
-                            c2 = fmaf(c2, J.al[1], J.be[1]);
-                        } else {
-                            const bool tissue = is_tissue_f(er.x, eg.x, eb.x, J.ylimf);
-                            c1 = tissue ? fmaf(c1, J.al[0], J.be[0]) : c1;
-                            c2 = tissue ? fmaf(c2, J.al[1], J.be[1]) : c2;
-                        }
-#pragma unroll
-                        for (int ch = 0; ch < 3; ++ch)
-                            t[3 * p + ch] = 255.0f * __builtin_amdgcn_exp2f(fmaf(c1, K.q[0][ch], c2 * K.q[1][ch]));
-                    }
-                    unpack(pack_trunc_fast(t), px);
-                });
-            };
-            if (K.L.g12 >= 0.0f) sweep(std::true_type{}); else sweep(std::false_type{});
-        }
-    }
+    view_route<MODE, 0>(s_tab, stage, npatch, P, rgb, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, lam, ylimf);
     __syncthreads();
 
     affine_write<DT, LAYOUT>(vt, g, false, s_px, out, tile, h, w, oh, ow, fill, fmt, tid);

@@ -1,9 +1,10 @@
 // view_geometry.hpp -- the geometry of the view passes: the ONE decode of a window and the ONE clamp rule of the tree (Dihedral, ViewTile,
 // ViewPatch for the crop / shrink views; ResizeTile, ResizeAxis, resize_patch for the resizing view), moved out of view_kernels.hpp and
 // view_resize_kernels.hpp word for word so that k_view_planes (planes_view_kernels.hpp) and the CPU check of its lane arithmetic
-// (tests/planes_view_geometry.cpp) take them from here.  Integers only, no builtin outside __HIP_DEVICE_COMPILE__, nothing of HIP
+// (tests/planes_view_geometry.cpp) take them from here.  Integers only, no AMDGPU builtin outside __HIP_DEVICE_COMPILE__, nothing of HIP
 // included: a host compiler can include this header alone.  The kernels that used these pieces are unchanged instruction for
-// instruction (tools/isa_diff.py).
+// instruction (tools/isa_diff.py).  Also here: patch_lanes, the lanes-per-row assignment of the affine write sides
+// (tests/view_affine_geometry.cpp walks it; resize_write has the same lines written out: DESIGN 4.19.1).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -69,6 +70,18 @@ struct ViewPatch {
         ai = tr ? sv : su; aj = tr ? su : sv;
     }
 };
+
+// ---- the write side of the affine views (and, written out, of the resizing view): lanes walk OUTPUT rows, 4 adjacent outputs per lane; lanes per row = the power
+// of two that covers the patch's width bw (1 .. 16), so a narrow patch spreads its rows over all the lanes (affine_write,
+// k_view_planes_affine; resize_write and k_view_planes have the same assignment written out).  Lane tid of `wg` takes the outputs jl .. jl + 3 of rows il0, il0 + rows, ...
+struct PatchLanes { int il0, jl, rows; };
+SL_GEOM_FN PatchLanes patch_lanes(int bw, int tid, int wg) {
+    const int n4 = (bw + 3) >> 2;                                                // chunks of 4 outputs per output row, 1 .. 16
+    const int lg = n4 <= 1 ? 0 : 32 - __builtin_clz((unsigned)(n4 - 1));         // log2 of the lanes per row: 0 .. 4
+    PatchLanes l;
+    l.il0 = tid >> lg; l.jl = 4 * (tid & ((1 << lg) - 1)); l.rows = wg >> lg;
+    return l;
+}
 
 // ---- the resizing view (view_resize_kernels.hpp) -----------------------------------------------------------------------------------------
 constexpr int kResizeMaxRatio = 16;              // wh <= 16 nu, ww <= 16 nv: at most 17 taps per axis

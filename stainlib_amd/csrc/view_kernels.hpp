@@ -10,6 +10,13 @@
 // The kernel's body is view_body: k_view instantiates it as it stands, k_hed_view (hed_view_kernels.hpp) with the HED stage.  Its
 // geometry, read side, LDS stage and write side are callable pieces (ViewTile, ViewPatch, view_read, view_stage, view_write), which
 // k_lab_view (lab_view_kernels.hpp) puts around the Lab map.
+// What the resizing and the affine views (view_resize_kernels.hpp, view_affine_kernels.hpp) take from here besides those pieces:
+//   view_route      the route arithmetic per source pixel -- raw / failed fit / k_apply's sweep / k_apply_jitter's sweep with its
+//                   constants and barriers --, ONE copy for view_resize_body and k_view_affine.  view_body holds the same text written
+//                   out (its twin: folding it costs the tissue-only k_hed_view an occupancy step).
+//   view_store_px4  the store tail of a write side from four packed pixels on: affine_write's.  view_write_s and resize_write hold
+//                   the same text written out (twins: both measured slower on the shared function).
+// Two copies of the route arithmetic where there were three; which kernel changed by how much and the timings: DESIGN 4.19.1.
 //
 // Shape: ONE workgroup = one tile and one patch of kViewB x kViewB OUTPUT pixels.  The dihedral code (block-uniform, read once, a
 // run-time value) decides which kViewB x kViewB block of the source window that is; the two sides meet in LDS:
@@ -121,6 +128,36 @@ __device__ __forceinline__ void store_view4(typename Elem<DT>::type* base, size_
     }
 }
 
+// The store tail of a write side: four packed pixels r | g << 8 | b << 16 of one output row at pixel `pix` of tile `tile`, nvalid of them
+// existing (1 .. 4), as the uint8 image (one dwordx3, the ragged last lane byte by byte) or through cvt_chunk / store_view4.  PO: the
+// pixels of a tile's output, F: tensor_consts of the call's format.  affine_write ends in it; view_write_s below and resize_write keep
+// their own copies of these lines -- its twins: a change to one is a change to the others (DESIGN 4.19.1 for why they are not folded).
+template <int DT, int LAYOUT>
+__device__ __forceinline__ void view_store_px4(const uint32_t (&px)[4], void* out, int tile, size_t PO, size_t pix, int nvalid,
+                                               const TensorK& F) {
+    constexpr bool TENSOR = DT != kDtU8;
+    constexpr int SDT = TENSOR ? DT : kDtF32;
+    typedef typename Elem<SDT>::type T;
+    Chunk o;
+    o.w0 = px[0] | (px[1] << 24);
+    o.w1 = (px[1] >> 8) | (px[2] << 16);
+    o.w2 = (px[2] >> 16) | (px[3] << 8);
+    if (TENSOR) {
+        float v[12];
+        cvt_chunk(o, F, v);
+        T* const base = (T*)out + (size_t)tile * 3 * PO;
+        store_view4<SDT, LAYOUT>(base, PO, pix, nvalid, v);
+    } else {
+        uint8_t* const p = (uint8_t*)out + ((size_t)tile * PO + pix) * 3;
+        if (nvalid == 4) {
+            sl_u32x3u u; u.x = o.w0; u.y = o.w1; u.z = o.w2;
+            *(SL_GLOBAL sl_u32x3u*)as_global(p) = u;
+        } else {
+            for (int i = 0; i < 3 * nvalid; ++i) as_global(p)[i] = (uint8_t)chunk_byte(o, i);
+        }
+    }
+}
+
 // ---- the pieces of a view pass: geometry, read side, LDS stage, write side.  view_body below is their sequence for one patch per
 // ---- workgroup; k_lab_view (lab_view_kernels.hpp) loops them over a run of patches behind one table fill ------------------------------
 // (the geometry -- Dihedral, ViewTile, ViewPatch -- is in view_geometry.hpp)
@@ -179,6 +216,7 @@ __device__ __forceinline__ uint32_t view_box(const uint32_t* s_px, int at) {
 // ---- only (view_write below picks it by the block-uniform run-time one); S = 1 is the write side as it was, statement for statement.
 // Lanes: 16 / S per output row (the patch is 64 / S pixels wide), so 16 S rows per pass -- 4 passes at S = 1, ONE at S = 2 (32 rows, every
 // lane busy) and at S = 4 (16 rows: the first wave only; accepted, the pass is bound by the arithmetic in front of the stage).
+// From `Chunk o` on this is view_store_px4's text written out, its TWIN (the S = 1 float16 view was 1 - 2 % slower on it).
 template <int DT, int LAYOUT, int S>
 __device__ __forceinline__ void view_write_s(const ViewPatch& g, const uint32_t* s_px, void* out, int tile, int oh, int ow, TensorK fmt,
                                              int lr16, int lc16) {
@@ -257,7 +295,89 @@ struct HsbViewArgs;
 template <int HED> struct StageArgs { typedef HedViewArgs type; };
 template <> struct StageArgs<2> { typedef HsbViewArgs type; };
 
+// ---- the route arithmetic per source pixel of the staged view kernels: between the read side (the loads are in flight, the table fill is
+// ---- issued) and the barrier in front of the write side.  stage(compute) runs compute(chunk, px[4]) on the lane's four chunks and puts the
+// ---- pixels into LDS (the caller's view_stage, with its HedStage behind compute); s_tab: the {gamma, od32} table (MODE != kViewRaw).
+// view_resize_body and k_view_affine call it; view_body below holds the same text written out -- its twin: a change to one is a change
+// to the other (DESIGN 4.19.1 for why view_body is not folded).  HED == 1: the raw stage waits for the HED stage's table.
+template <int MODE, int HED, class Stage>
+__device__ __forceinline__ void view_route(const float2* s_tab, Stage&& stage, int npatch, int P, const uint8_t* rgb,
+                                           const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt,
+                                           const double* alpha_beta, double lam, float ylimf) {
+    auto unpack = [](const Chunk& o, uint32_t (&px)[4]) { view_unpack(o, px); };
+    auto raw = [&](const Chunk& c, uint32_t (&px)[4]) { unpack(c, px); };
+
+    if (MODE == kViewRaw) {
+        if (HED == 1) __syncthreads();                              // the HED stage's table
+        stage(raw);
+    } else {
+        const ApplyTile<1> A(blockIdx.x, npatch, P, rgb, M_src, maxC_src, M_tgt, maxC_tgt, lam);
+        const ApplyK& K = A.K;
+        JitterK J;
+        if (MODE != kViewApply) {                                   // k_apply_jitter's constants
+            const double sc = 1.0 / A.unit;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                J.al[i] = in_vgpr(uni((float)alpha_beta[4 * (size_t)A.tile + 2 * i]));
+                J.be[i] = in_vgpr(uni((float)(alpha_beta[4 * (size_t)A.tile + 2 * i + 1] / (A.mct[i] / A.mcs[i]) * sc)));
+            }
+            J.ylimf = in_vgpr(ylimf);
+        }
+        __syncthreads();                                            // the table
+        if (SL_FIT_FAILED(A)) {                                     // the view of the source bytes
+            stage(raw);
+        } else if (MODE == kViewApply) {                            // k_apply: K.fast picks the lasso form and the cast
+            auto sweep = [&](auto fast_tag) {
+                constexpr bool FAST = decltype(fast_tag)::value;
+                stage([&](const Chunk& c, uint32_t (&px)[4]) {
+                    float t[12];
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) {
+                        const float x = s_tab[chunk_byte(c, 3 * p + 0)].y, y = s_tab[chunk_byte(c, 3 * p + 1)].y,
+                                    z = s_tab[chunk_byte(c, 3 * p + 2)].y;
+                        float v[3];
+                        apply_px<FAST>(K, x, y, z, v);
+                        t[3 * p] = v[0]; t[3 * p + 1] = v[1]; t[3 * p + 2] = v[2];
+                    }
+                    unpack(FAST ? pack_trunc_fast(t) : pack_trunc_general(t), px);
+                });
+            };
+            if (K.fast) sweep(std::true_type{}); else sweep(std::false_type{});
+        } else {                                                    // k_apply_jitter: g12 picks the lasso form, the cast saturates
+            auto sweep = [&](auto fast_tag) {
+                constexpr bool FAST = decltype(fast_tag)::value;
+                stage([&](const Chunk& c, uint32_t (&px)[4]) {
+                    float t[12];
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) {
+                        const float2 er = s_tab[chunk_byte(c, 3 * p + 0)];      // x = gamma, y = od32
+                        const float2 eg = s_tab[chunk_byte(c, 3 * p + 1)];
+                        const float2 eb = s_tab[chunk_byte(c, 3 * p + 2)];
+                        float c1, c2;
+                        apply_conc<FAST>(K, er.y, eg.y, eb.y, c1, c2);
+                        if (MODE == kViewJitAll) {
+                            c1 = fmaf(c1, J.al[0], J.be[0]);
+                            c2 = fmaf(c2, J.al[1], J.be[1]);
+                        } else {
+                            const bool tissue = is_tissue_f(er.x, eg.x, eb.x, J.ylimf);
+                            c1 = tissue ? fmaf(c1, J.al[0], J.be[0]) : c1;
+                            c2 = tissue ? fmaf(c2, J.al[1], J.be[1]) : c2;
+                        }
+#pragma unroll
+                        for (int ch = 0; ch < 3; ++ch)
+                            t[3 * p + ch] = 255.0f * __builtin_amdgcn_exp2f(fmaf(c1, K.q[0][ch], c2 * K.q[1][ch]));
+                    }
+                    unpack(pack_trunc_fast(t), px);
+                });
+            };
+            if (K.L.g12 >= 0.0f) sweep(std::true_type{}); else sweep(std::false_type{});
+        }
+    }
+}
+
 // DT: kDtU8 or a tensor type; LAYOUT: tensor only; MODE: kView*; HED: the stage above.  npx: patches per output row, npatch: per tile.
+// From `unpack` to the last barrier this is view_route's text written out, its TWIN: a change to one is a change to the other.  Calling
+// view_route here costs the tissue-only k_hed_view an occupancy step (79 -> 81 VGPRs, 6 -> 5).
 template <int DT, int LAYOUT, int MODE, int HED>
 __device__ __forceinline__ void view_body(const uint8_t* rgb, void* out, int h, int w, int oh, int ow,
                                           int npx, int npatch, const int32_t* windows, int d_mask, int shrink,

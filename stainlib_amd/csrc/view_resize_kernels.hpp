@@ -12,8 +12,10 @@
 // kernel resamples in OUTPUT orientation: each output axis is one window axis, forwards or backwards.
 //
 // What is shared with k_view: load12 / view_read (the read side), view_stage / view_unpack (the LDS stage, one packed dword per SOURCE
-// pixel, pitch 65), the apply / jitter / HED arithmetic per source pixel (view_body's, statement for statement), cvt_chunk and
-// store_view4.  What is new: the geometry (ResizeTile, resize_patch) and the write side (resize_write).
+// pixel, pitch 65), the apply / jitter / HED arithmetic per source pixel (view_route: the one copy this body and k_view_affine run;
+// view_body holds its twin), cvt_chunk and store_view4.  What is new: the geometry (ResizeTile, resize_patch) and the write side
+// (resize_write).  Its lanes-per-row assignment is patch_lanes' (view_geometry.hpp) and its store tail view_store_px4's, both WRITTEN
+// OUT here: on the shared functions the uint8 views of 224^2 windows measured 0.2 - 0.4 % slower than the parent.
 //
 // Shape: ONE workgroup = one tile and one patch of at most 64 x 64 OUTPUT pixels whose source pixels fit the 64 x 64 LDS block.  Along an
 // axis the patch edge is resize_patch_edge(no, nw) = min(64, 63 no / nw) outputs: b outputs starting anywhere touch at most
@@ -64,7 +66,8 @@ __device__ __forceinline__ uint32_t resize_round(uint32_t S, uint32_t D, float r
 }
 
 // ---- write side: output rows, 4 adjacent pixels per lane (behind a barrier after the stage and resize_taps).  Lanes per output row: the
-// ---- power of two that covers the patch's width, 1 .. 16 (block-uniform), so that a narrow patch spreads its rows over all the lanes.
+// ---- power of two that covers the patch's width, 1 .. 16 (block-uniform), so that a narrow patch spreads its rows over all the lanes
+// ---- (patch_lanes' assignment, view_geometry.hpp; from `Chunk o` on: view_store_px4's text.  TWINS, see the head of this file).
 template <int DT, int LAYOUT>
 __device__ __forceinline__ void resize_write(const ViewPatch& g, const ResizeAxis& ai, const ResizeAxis& aj, const uint32_t* s_px,
                                              const uint32_t* s_tap, void* out, int tile, int oh, int ow, TensorK fmt, int tid) {
@@ -132,8 +135,8 @@ __device__ __forceinline__ void resize_write(const ViewPatch& g, const ResizeAxi
     }
 }
 
-// view_body with the geometry and the write side above; everything between view_read and the barrier is view_body's, statement for
-// statement.  npatch: the host's upper bound of the patches of a tile.
+// view_body with the geometry and the write side above; the arithmetic between view_read and the barrier is view_route
+// (view_kernels.hpp).  npatch: the host's upper bound of the patches of a tile.
 template <int DT, int LAYOUT, int MODE, int HED>
 __device__ __forceinline__ void view_resize_body(const uint8_t* rgb, void* out, int h, int w, int oh, int ow, int npatch,
                                                  const int32_t* windows, int d_mask, int max_wh, int max_ww,
@@ -169,75 +172,7 @@ __device__ __forceinline__ void view_resize_body(const uint8_t* rgb, void* out, 
             hed.apply(px);
         });
     };
-    auto unpack = [](const Chunk& o, uint32_t (&px)[4]) { view_unpack(o, px); };
-    auto raw = [&](const Chunk& c, uint32_t (&px)[4]) { unpack(c, px); };
-
-    if (MODE == kViewRaw) {
-        if (HED == 1) __syncthreads();                              // the HED stage's table
-        stage(raw);
-    } else {
-        const ApplyTile<1> A(blockIdx.x, npatch, P, rgb, M_src, maxC_src, M_tgt, maxC_tgt, lam);
-        const ApplyK& K = A.K;
-        JitterK J;
-        if (MODE != kViewApply) {                                   // k_apply_jitter's constants
-            const double sc = 1.0 / A.unit;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                J.al[i] = in_vgpr(uni((float)alpha_beta[4 * (size_t)A.tile + 2 * i]));
-                J.be[i] = in_vgpr(uni((float)(alpha_beta[4 * (size_t)A.tile + 2 * i + 1] / (A.mct[i] / A.mcs[i]) * sc)));
-            }
-            J.ylimf = in_vgpr(ylimf);
-        }
-        __syncthreads();                                            // the table
-        if (SL_FIT_FAILED(A)) {                                     // the view of the source bytes
-            stage(raw);
-        } else if (MODE == kViewApply) {                            // k_apply: K.fast picks the lasso form and the cast
-            auto sweep = [&](auto fast_tag) {
-                constexpr bool FAST = decltype(fast_tag)::value;
-                stage([&](const Chunk& c, uint32_t (&px)[4]) {
-                    float t[12];
-#pragma unroll
-                    for (int p = 0; p < 4; ++p) {
-                        const float x = s_tab[chunk_byte(c, 3 * p + 0)].y, y = s_tab[chunk_byte(c, 3 * p + 1)].y,
-                                    z = s_tab[chunk_byte(c, 3 * p + 2)].y;
-                        float v[3];
-                        apply_px<FAST>(K, x, y, z, v);
-                        t[3 * p] = v[0]; t[3 * p + 1] = v[1]; t[3 * p + 2] = v[2];
-                    }
-                    unpack(FAST ? pack_trunc_fast(t) : pack_trunc_general(t), px);
-                });
-            };
-            if (K.fast) sweep(std::true_type{}); else sweep(std::false_type{});
-        } else {                                                    // k_apply_jitter: g12 picks the lasso form, the cast saturates
-            auto sweep = [&](auto fast_tag) {
-                constexpr bool FAST = decltype(fast_tag)::value;
-                stage([&](const Chunk& c, uint32_t (&px)[4]) {
-                    float t[12];
-#pragma unroll
-                    for (int p = 0; p < 4; ++p) {
-                        const float2 er = s_tab[chunk_byte(c, 3 * p + 0)];      // x = gamma, y = od32
-                        const float2 eg = s_tab[chunk_byte(c, 3 * p + 1)];
-                        const float2 eb = s_tab[chunk_byte(c, 3 * p + 2)];
-                        float c1, c2;
-                        apply_conc<FAST>(K, er.y, eg.y, eb.y, c1, c2);
-                        if (MODE == kViewJitAll) {
-                            c1 = fmaf(c1, J.al[0], J.be[0]);
-                            c2 = fmaf(c2, J.al[1], J.be[1]);
-                        } else {
-                            const bool tissue = is_tissue_f(er.x, eg.x, eb.x, J.ylimf);
-                            c1 = tissue ? fmaf(c1, J.al[0], J.be[0]) : c1;
-                            c2 = tissue ? fmaf(c2, J.al[1], J.be[1]) : c2;
-                        }
-#pragma unroll
-                        for (int ch = 0; ch < 3; ++ch)
-                            t[3 * p + ch] = 255.0f * __builtin_amdgcn_exp2f(fmaf(c1, K.q[0][ch], c2 * K.q[1][ch]));
-                    }
-                    unpack(pack_trunc_fast(t), px);
-                });
-            };
-            if (K.L.g12 >= 0.0f) sweep(std::true_type{}); else sweep(std::false_type{});
-        }
-    }
+    view_route<MODE, HED>(s_tab, stage, npatch, P, rgb, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, lam, ylimf);
     __syncthreads();
 
     resize_write<DT, LAYOUT>(g, ai, aj, s_px, s_tap, out, tile, oh, ow, fmt, tid);

@@ -90,7 +90,7 @@ static void run(const Case& cs) {
             CHECK(g.nu == 0 && g.nv == 0, "an empty block of %d x %d", g.nu, g.nv);
         }
         for (int tid = 0; tid < 256; ++tid) {
-            const AffineLanes ln = affine_lanes(g.bw, tid, 256);
+            const PatchLanes ln = patch_lanes(g.bw, tid, 256);
             if (ln.jl >= g.bw) continue;
             for (int il = ln.il0; il < g.bh; il += ln.rows) {
                 for (int p = 0; p < 4; ++p) {
