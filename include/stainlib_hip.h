@@ -876,6 +876,27 @@ SL_API int sl_view_planes_affine(const void* planes, void* out, int n, int c, in
 SL_API int sl_hsb_augment(const uint8_t* rgb, void* out, int n, int h, int w, const int32_t* codes, const SlTensorFormat* fmt, void* stream);
 SL_API int sl_normalize_hsb_view(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, int shrink, int max_wh, int max_ww, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, const double* alpha_beta, int augment_background, const SlParams* params, const SlTensorFormat* fmt, const int32_t* codes, void* stream);
 
+/* ---- Gaussian blur in the view pass (stainlib_amd/csrc/view_blur.hip; an extension: the blur of the usual histopathology augmentation
+ * set, a per-tile separable filter in INTEGERS, so every route computes the same bits).  R = 8 is the largest radius, Q = 256 the weight
+ * sum per axis.  codes: n x 9 int32 on the device, (w_0 .. w_8) per tile: every w_k >= 0, w_0 + 2 (w_1 + .. + w_8) == 256; the tile's
+ * radius r is the largest k with w_k != 0; (256, 0, .., 0) is the identity.  Let full[t] be the h x w x 3 uint8 image the statistics
+ * pattern names as in sl_normalize_view (the tile's own bytes, sl_normalize_apply's image, the jitter of tissue pixels or of all pixels;
+ * a tile whose fit failed: its own bytes), normalised and jittered per source pixel with the WHOLE tile's statistics.  Per channel
+ *     Hs[y, x] = sum_{k=-8..8} w_|k| full[y, clamp(x + k, 0, w - 1)]                         (<= 65280, exact)
+ *     B[y, x]  = (sum_{k=-8..8} w_|k| Hs[clamp(y + k, 0, h - 1), x] + 32768) >> 16            (rounded once)
+ * The border replicates the TILE's edge, not the window's: the blur is of the whole image, and the view then cuts it.  The output is
+ * sl_normalize_view_shrink's view of B: windows[t] = (y0, x0, d), d_mask, (oh, ow), the clamp of the window into the tile, the flip and
+ * the quarter turns; with shrink = 2, 4 the box rule (S + s s / 2) >> (2 log2 s) on the bytes of B; fmt as there (the tensor is
+ * sl_to_tensor of those bytes).  Identity codes give sl_normalize_view_shrink's bits; a constant image stays constant.
+ * max_r (0 .. 8): the call's bound of the radii -- the launch is sized from it (patches of (64 - 2 max_r) / shrink outputs square), the
+ * codes themselves are not read on the host.  A tile whose codes fail the rule -- a negative weight, a sum other than 256, a non-zero w_k
+ * with k > max_r -- gets the identity; nothing is read out of bounds.  (stainlib_amd/augmentation/blur.py holds the same in numpy, and the
+ * rule from sigma to codes: r = min(8, ceil(3 sigma)), g_k = exp(-k k / (2 sigma sigma)) normalised over |k| <= r in binary64,
+ * w_k = floor(256 g_k + 1/2) for k >= 1, w_0 = 256 - 2 sum_{k >= 1} w_k; sigma <= 0: the identity.)
+ * SL_ERR_BADARG before anything is launched: what sl_normalize_view_shrink refuses; a NULL or misaligned codes; max_r outside 0 .. 8.
+ * out == rgb is not supported.  Capture-safe like sl_normalize_view. */
+SL_API int sl_normalize_blur_view(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, int shrink, int max_r, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, const double* alpha_beta, int augment_background, const SlParams* params, const SlTensorFormat* fmt, const int32_t* codes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

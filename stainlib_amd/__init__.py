@@ -7,6 +7,7 @@ StainJitter (an extension) draws the per-tile (alpha, beta) of the augment_batch
 TileView (an extension) draws the per-tile crop / flip / quarter turn that view= applies inside the same pass.
 TileAffine (an extension) draws a per-tile rotation by any angle, zoom, shear and translation for view=: bilinear, in integers.
 HsbColorAugmenter (an extension; HsbLight / HsbStrong presets) is the hue / saturation / brightness sibling of the HED augmenters, in integers.
+GaussianBlurAugmenter (an extension) is the Gaussian blur of that set: a per-tile integer separable filter, fused into the view pass (blur=).
 Separated (an extension) is what the normalizers' separate / separate_batch return: per-stain images and concentration maps.
 Importing the package does not need a GPU; calling anything numeric does, and fails loudly without the
 HIP library -- there is no CPU fallback.
@@ -15,6 +16,7 @@ from . import _ffi  # noqa: F401
 from .augmentation.augmenter import (HedLightColorAugmenter, HedLighterColorAugmenter,  # noqa: F401
                                      HedStrongColorAugmenter, StainAugmentor, GrayscaleAugmentor, StainJitter)
 from .augmentation.hsb import HsbColorAugmenter, HsbLightColorAugmenter, HsbStrongColorAugmenter  # noqa: F401
+from .augmentation.blur import GaussianBlurAugmenter  # noqa: F401
 from .extraction.macenko_stain_extractor import MacenkoStainExtractor  # noqa: F401
 from .extraction.vahadane_stain_extractor import VahadaneStainExtractor  # noqa: F401
 from .normalization.normalizer import (ExtractiveStainNormalizer, MacenkoNormalizer,  # noqa: F401

@@ -215,6 +215,10 @@ _SIGNATURES["sl_view_planes_affine"] = (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_
 _SIGNATURES["sl_hsb_augment"] = (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(SlTensorFormat), _P])
 _SIGNATURES["sl_normalize_hsb_view"] = (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P,
                                                   _P, _P, _P, C.c_int, C.POINTER(SlParams), C.POINTER(SlTensorFormat), _P, _P])
+# the blurred view (codes: n x 9 int32 on the device): rgb, out, n, h, w, oh, ow, windows, d_mask, shrink, max_r, <sl_normalize_view's statistics,
+# params, fmt>, codes, stream
+_SIGNATURES["sl_normalize_blur_view"] = (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P,
+                                                   _P, _P, C.c_int, C.POINTER(SlParams), C.POINTER(SlTensorFormat), _P, _P])
 PLANES_NEAREST, PLANES_AREA = range(2)
 POOL_STATE_DOUBLES, POOL_M, POOL_MAXC, POOL_STATUS, POOL_MISS = 64, 0, 6, 8, 9
 POOL2_STATE_DOUBLES, POOL2_HIST_WORDS, POOL2_WHY = 256, 2 * 8192 + 8 * 32, 33

@@ -1132,6 +1132,163 @@ def hsb_stage(tiles, hsb, hsb_sigmas, view, windows, route, fmt=None, out=None):
     return x, windows, HsbDraw(sigmas, codes)
 
 
+# ---- Gaussian blur in the view pass (sl_normalize_blur_view; see include/stainlib_hip.h, augmentation/blur.py) ---------------------------
+
+BlurDraw = collections.namedtuple("BlurDraw", ["sigmas", "codes"])
+BlurDraw.__doc__ = """What the blur= stage of a batch method did: the (N,) float64 sigmas it used (given or drawn; None when the call was
+given codes) and the (N, 9) int32 codes (w_0 .. w_8 per tile: augmentation.blur.blur_codes), both numpy.  The codes reproduce the call:
+pass them back as blur_sigmas=."""
+
+
+def _blur_codes_rows(codes, max_r=None):
+    """The rows of an (N, 9) codes argument (no device needed): a device int32 tensor (taken as it is: the kernel gives a tile whose codes
+    fail the rule the identity), or host integers, which are rule-checked here (ValueError) -- under max_r when that is given."""
+    import numpy as np
+    from .augmentation.blur import R, codes_ok
+    what = "codes must hold (w_0 .. w_8) per tile: an (N, 9) int32 array (augmentation.blur.blur_codes)"
+    if isinstance(codes, torch.Tensor) and codes.is_cuda:
+        if codes.dtype != torch.int32 or codes.dim() != 2 or codes.shape[1] != R + 1 or not codes.is_contiguous():
+            raise ValueError(what + ", contiguous")
+        return int(codes.shape[0])
+    try:
+        arr = codes.numpy() if isinstance(codes, torch.Tensor) else np.asarray(codes)
+        if arr.dtype.kind not in "iu":
+            raise TypeError
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(what) from None
+    if arr.ndim != 2 or arr.shape[1] != R + 1:
+        raise ValueError(f"{what}, not one of shape {arr.shape}")
+    bad = ~codes_ok(arr, R if max_r is None else max_r)
+    if bad.any():
+        t = int(np.argmax(bad))
+        raise ValueError(f"codes: tile {t} has {arr[t].tolist()}, which fails the rule: every w_k >= 0, w_0 + 2 (w_1 + .. + w_8) == 256"
+                         + (f", no weight beyond max_r = {max_r}" if max_r is not None else ""))
+    return int(arr.shape[0])
+
+
+def _blur_max_r(max_r, codes):
+    """max_r of a normalize_blur_view call (no device needed): 0 .. 8 as given; by default the largest radius of host codes (device codes
+    are never read back: they need it)."""
+    import numpy as np
+    from .augmentation.blur import R, codes_radius
+    if max_r is None:
+        if isinstance(codes, torch.Tensor) and codes.is_cuda:
+            raise ValueError("codes on the device need max_r=, the largest radius among them (0 .. 8): the launch is sized from it")
+        arr = codes.numpy() if isinstance(codes, torch.Tensor) else np.asarray(codes)
+        return int(codes_radius(arr).max()) if arr.size else 0
+    if isinstance(max_r, bool) or not isinstance(max_r, (int, np.integer)) or not 0 <= max_r <= R:
+        raise ValueError(f"max_r must be an int in 0 .. {R}, not {max_r!r}")
+    return int(max_r)
+
+
+def normalize_blur_view(rgb, windows, size, d_mask, codes, max_r=None, M_src=None, maxC_src=None, M_tgt=None, maxC_tgt=None, alpha_beta=None,
+                        augment_background=False, params=None, shrink=1, fmt=None, out=None):
+    """normalize_view of the BLURRED `full` in ONE pass (sl_normalize_blur_view): `full` is normalize_view's (the route arguments are the
+    same), the blur is augmentation.blur.blur_reference with the tile's codes -- of the whole tile, its border replicated, and the view
+    then cuts it: bit for bit blur_reference of `full`, then normalize_view of the result, without the pixels farther than max_r from the
+    window being touched.  codes: (N, 9) int32 = (w_0 .. w_8) per tile (blur_codes).  Host codes are rule-checked (ValueError) and max_r
+    defaults to their largest radius; a device tensor is taken as it is and needs max_r -- a tile whose codes fail the rule (a negative
+    weight, a sum other than 256, a weight beyond max_r) gets the identity; nothing is synchronised.  shrink: normalize_view's, the box
+    mean taken of the blurred bytes.  A tile whose fit failed: the view of its own blurred bytes."""
+    import numpy as np
+    _blur_codes_rows(codes)
+    mr = _blur_max_r(max_r, codes)
+
+    def codes_ok(n):
+        if _blur_codes_rows(codes, mr) != n:
+            raise ValueError(f"codes must have one row per tile ({n})")
+    n, h, w, oh, ow, win, M_src, maxC_src, M_tgt, maxC_tgt, ab, f, out = _view_prepare(
+        rgb, windows, size, d_mask, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, params, fmt, out, before_device=codes_ok, shrink=shrink)
+    if isinstance(codes, torch.Tensor) and codes.is_cuda:
+        if codes.device != rgb.device:
+            raise ValueError(f"codes must be on {rgb.device}")
+        c = codes
+    else:
+        arr = codes.numpy() if isinstance(codes, torch.Tensor) else np.asarray(codes)
+        c = torch.from_numpy(np.ascontiguousarray(arr.astype(np.int32))).to(rgb.device)
+    _call("sl_normalize_blur_view", _ptr(rgb), _ptr(out), n, h, w, oh, ow, _ptr(win), int(d_mask), int(shrink), mr, _ptr(M_src),
+          _ptr(maxC_src), _ptr(M_tgt), _ptr(maxC_tgt), _ptr(ab), 1 if augment_background else 0, _byref(params), _byref(f), _ptr(c))
+    return out
+
+
+def _blur_sigmas_or_codes(blur_sigmas, n=None):
+    """blur_sigmas= of a batch method (no device needed) -> (sigmas or None, codes): (N,) float sigmas -- or, to reproduce a call, the
+    (N, 9) integer codes it returned (BlurDraw.codes), rule-checked.  ValueError."""
+    import numpy as np
+    from .augmentation.blur import R, blur_codes
+    arr = None
+    if not isinstance(blur_sigmas, torch.Tensor):
+        try:
+            arr = np.asarray(blur_sigmas)
+        except (TypeError, ValueError):
+            arr = None
+    elif not blur_sigmas.is_cuda:
+        arr = blur_sigmas.numpy()
+    if arr is not None and arr.ndim == 2 and arr.dtype.kind in "iu" and arr.shape[1] == R + 1:
+        _blur_codes_rows(arr)
+        sigmas, codes = None, np.ascontiguousarray(arr.astype(np.int32))
+    else:
+        if arr is None:
+            raise ValueError("blur_sigmas must hold one blur sigma per tile: an (N,) array (or the (N, 9) codes a call returned)")
+        codes = blur_codes(arr)
+        if codes.ndim != 2:
+            raise ValueError("blur_sigmas must hold one blur sigma per tile: an (N,) array (or the (N, 9) codes a call returned)")
+        sigmas = np.array(arr, dtype=np.float64)
+    if n is not None and codes.shape[0] != n:
+        raise ValueError(f"blur_sigmas must have one entry per tile ({n})")
+    return sigmas, codes
+
+
+def _blur_call(blur, blur_sigmas, tiles, view=None, hed=None, hsb=None):
+    """The blur= / blur_sigmas= arguments of a batch method, checked without a device and before any draw (ValueError).  True when the call
+    has a blur stage.  view, hed, hsb: the call's view=, hed= and hsb= -- a resizing or affine view and a colour stage do not go with it."""
+    from .augmentation.blur import GaussianBlurAugmenter
+    if blur is None:
+        if blur_sigmas is not None:
+            raise ValueError("blur_sigmas= goes with blur= (a GaussianBlurAugmenter)")
+        return False
+    if hed is not None or hsb is not None:
+        raise ValueError("blur= does not go together with hed= or hsb=: a pass has one augmentation stage behind the route.  Chain them "
+                         "instead: augment_batch(hsb=), then blur.transform_batch(view=, tensor_format=)")
+    _no_affine(view, "the blur stage (blur=, GaussianBlurAugmenter.transform_batch(view=))",
+               "blur first (blur.transform_batch), then take the uint8 result through TensorFormat.convert(view=)")
+    if view is not None and getattr(view, "resizing", False):
+        raise ValueError("blur= does not go with a resizing view (TileView(scale=)): the blurred view has fixed-size windows.  Blur first "
+                         "(blur.transform_batch), then take the uint8 result through TensorFormat.convert(view=)")
+    if not isinstance(blur, GaussianBlurAugmenter):
+        raise ValueError("blur must be a stainlib_amd GaussianBlurAugmenter (its range is used)")
+    if not (isinstance(tiles, torch.Tensor) and tiles.dim() == 4 and tiles.shape[-1] == 3):
+        raise ValueError("expected a contiguous CUDA uint8 tensor of shape (N, H, W, 3)")
+    if blur_sigmas is not None:
+        _blur_sigmas_or_codes(blur_sigmas, int(tiles.shape[0]))
+    return True
+
+
+def _no_blur(blur, blur_sigmas, what):
+    """ValueError for blur= in a call that has no blurred pass"""
+    if blur is not None or blur_sigmas is not None:
+        raise ValueError(f"blur= is not supported by {what}: take its uint8 result through blur.transform_batch(view=, tensor_format=)")
+
+
+def blur_stage(tiles, blur, blur_sigmas, view, windows, route, fmt=None, out=None):
+    """The blur= stage of the batch methods, behind their fit and their own draws, on arguments _blur_call / _view_call(draw=False) have
+    accepted: the draws the caller left open -- blur.randomize_batch(N), THEN view.draw -- and ONE fused pass (normalize_blur_view).
+    route: normalize_view's keyword arguments that name `full` ({}: the tiles themselves).  Without a view the result is the full tile,
+    code 0.  -> (out, windows or None, BlurDraw)."""
+    import numpy as np
+    n = int(tiles.shape[0])
+    if blur_sigmas is None:
+        blur_sigmas = blur.randomize_batch(n)
+    sigmas, codes = _blur_sigmas_or_codes(blur_sigmas, n)
+    if view is not None:
+        size, d_mask, windows, shrink = _view_call(view, windows, tiles)
+        win = windows
+    else:
+        size, d_mask, windows, win, shrink = None, 0, None, np.zeros((n, 3), dtype=np.int32), 1
+    x = normalize_blur_view(tiles, win, size, d_mask, codes, fmt=fmt, out=out, shrink=shrink, **route)
+    return x, windows, BlurDraw(sigmas, codes)
+
+
 def _view_call(view, windows, tiles, draw=True):
     """(size, d_mask, windows, shrink) of the view= / windows= pair of a batch method, checked without a device (ValueError): the windows
     as given, or drawn (TileView.draw; draw=False: left None for a later call)."""
@@ -1180,15 +1337,19 @@ def _view_resize_hw(view, windows, h, w):
     return max(1, min(h, int(win[:, 3].max()))), max(1, min(w, int(win[:, 4].max())))
 
 
-def route_stage(tiles, fit, route, fmt=None, out=None, view=None, windows=None, hed=None, hsb=None):
+def route_stage(tiles, fit, route, fmt=None, out=None, view=None, windows=None, hed=None, hsb=None, blur=None):
     """The tail of the batch methods, behind their fit and their own draws, on arguments _jitter_args / _view_call(draw=False) / _hed_call
     have accepted: ONE pass over the tiles and the tuple the method returns, (out, M_src, maxC_src, status[, windows][, HedDraw]).
     fit: the fit's (M_src, maxC_src, status); route: the other arguments that name `full` (M_tgt, maxC_tgt and, for a jitter, alpha_beta
     and augment_background).  hed = (HedColorAugmenter, hed_sigmas, hed_biases): hed_stage; else with a view: normalize_view, the
     windows drawn here if not given; else normalize_jitter.  hsb = (HsbColorAugmenter, hsb_sigmas) that _hsb_call has accepted (never
-    with hed): hsb_stage, and HsbDraw at the end of the tuple."""
+    with hed): hsb_stage, and HsbDraw at the end of the tuple.  blur = (GaussianBlurAugmenter, blur_sigmas) that _blur_call has accepted
+    (never with hed or hsb): blur_stage, and BlurDraw at the end of the tuple."""
     M, maxC, status = fit
     route = dict(M_src=M, maxC_src=maxC, **route)
+    if blur is not None:
+        x, windows, draw = blur_stage(tiles, *blur, view, windows, route, fmt=fmt, out=out)
+        return (x, M, maxC, status) + ((windows,) if view is not None else ()) + (draw,)
     if hsb is not None:
         x, windows, draw = hsb_stage(tiles, *hsb, view, windows, route, fmt=fmt, out=out)
         return (x, M, maxC, status) + ((windows,) if view is not None else ()) + (draw,)

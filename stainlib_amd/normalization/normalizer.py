@@ -146,22 +146,22 @@ class ExtractiveStainNormalizer(object):
         """Per-tile (M, maxC, status) device tensors for a batch of candidate targets."""
         return self._fit_tiles(tiles, ws=ws)
 
-    def _route_batch(self, tiles, target, jitter, out, ws, tensor_format, view, windows, hed, hsb=None):
+    def _route_batch(self, tiles, target, jitter, out, ws, tensor_format, view, windows, hed, hsb=None, blur=None):
         """The view= / hed= routes of transform_batch and all of augment_batch: the checks that are left (every one before the fit and
         before any draw), the fit of the whole tiles, then engine.route_stage -- ONE pass under the target (target=True) or every tile's
         own matrix, with the jitter's alpha_beta / augment_background ({}: none).  hed: None, or (hed, hed_sigmas, hed_biases) that
-        engine._hed_call has accepted; hsb: None, or (hsb, hsb_sigmas) that engine._hsb_call has accepted.
-        -> (out, M_src, maxC_src, status[, windows][, HedDraw or HsbDraw])."""
+        engine._hed_call has accepted; hsb: None, or (hsb, hsb_sigmas) that engine._hsb_call has accepted; blur: None, or (blur, blur_sigmas)
+        that engine._blur_call has accepted.  -> (out, M_src, maxC_src, status[, windows][, HedDraw or HsbDraw or BlurDraw])."""
         from .. import engine
         if view is not None or windows is not None:
             engine._view_call(view, windows, tiles, draw=False)
         engine._check_tiles(tiles)
         fit = self._fit_tiles(tiles, ws=ws)
         M_t, c_t = self._target_on(tiles.device) if target else (None, None)
-        return engine.route_stage(tiles, fit, dict(M_tgt=M_t, maxC_tgt=c_t, **jitter), tensor_format, out, view, windows, hed, hsb)
+        return engine.route_stage(tiles, fit, dict(M_tgt=M_t, maxC_tgt=c_t, **jitter), tensor_format, out, view, windows, hed, hsb, blur)
 
     def transform_batch(self, tiles, out=None, ws=None, tensor_format=None, _tensor_route=None, view=None, windows=None, hed=None,
-                        hed_sigmas=None, hed_biases=None, hsb=None, hsb_sigmas=None):
+                        hed_sigmas=None, hed_biases=None, hsb=None, hsb_sigmas=None, blur=None, blur_sigmas=None):
         """(N,H,W,3) uint8 device tensor -> (out, M_src, maxC_src, status) device tensors.  A tile whose
         status is non-zero (1 = empty tissue mask, 2 = degenerate, 3 = a zero 99th-percentile concentration) is passed through unchanged.
         ``ws``: an ``engine.Workspace`` to reuse (ONE stream at a time); by default every call takes its scratch from
@@ -179,13 +179,20 @@ class ExtractiveStainNormalizer(object):
         ``hsb``: an ``HsbColorAugmenter`` -- its hue / saturation / brightness map on every normalised tile in that same pass
         (engine.normalize_hsb_view; no cutoff test, so nothing is read twice): bit for bit ``hsb.transform_batch`` of the uint8 result,
         then the view and the conversion.  ``hsb_sigmas``: (N, 3); by default ``hsb.randomize_batch(N)``, drawn BEFORE the windows.  The
-        call then returns one more element at the end, ``engine.HsbDraw(sigmas, codes)``.  Not together with ``hed`` or a TileAffine."""
+        call then returns one more element at the end, ``engine.HsbDraw(sigmas, codes)``.  Not together with ``hed`` or a TileAffine.
+        ``blur``: a ``GaussianBlurAugmenter`` -- its integer Gaussian blur of every normalised tile in that same pass
+        (engine.normalize_blur_view): bit for bit ``blur.transform_batch`` of the uint8 result -- the blur of the WHOLE tile, so a window's
+        edge sees the tile's real neighbours --, then the view and the conversion.  ``blur_sigmas``: (N,); by default
+        ``blur.randomize_batch(N)``, drawn BEFORE the windows (or the (N, 9) codes a call returned, to reproduce it).  The call then returns
+        one more element at the end, ``engine.BlurDraw(sigmas, codes)``.  Not together with ``hed`` or ``hsb`` (chain them), a
+        ``TileView(scale=)`` or a TileAffine."""
         from .. import engine
         with_hed = engine._hed_call(hed, hed_sigmas, hed_biases, tiles, view)
         with_hsb = engine._hsb_call(hsb, hsb_sigmas, tiles, view, hed)
-        if with_hed or with_hsb or view is not None or windows is not None:
+        with_blur = engine._blur_call(blur, blur_sigmas, tiles, view, hed, hsb)
+        if with_hed or with_hsb or with_blur or view is not None or windows is not None:
             return self._route_batch(tiles, True, {}, out, ws, tensor_format, view, windows, (hed, hed_sigmas, hed_biases) if with_hed else None,
-                                     (hsb, hsb_sigmas) if with_hsb else None)
+                                     (hsb, hsb_sigmas) if with_hsb else None, (blur, blur_sigmas) if with_blur else None)
         if tensor_format is None:
             return self._transform_tiles(tiles, out=out, ws=ws)
         route = _tensor_route or TENSOR_ROUTE
@@ -202,7 +209,7 @@ class ExtractiveStainNormalizer(object):
 
     # -- stain separation (an extension: torchstain's normalize(..., stains=True), the concentration maps of staintools) ----
     def separate_batch(self, tiles, want=("norm", "h", "e", "conc"), conc_dtype=None, normalize=True, ws=None, tensor_format=None, view=None,
-                       windows=None):
+                       windows=None, blur=None, blur_sigmas=None):
         """(N,H,W,3) uint8 device tensor -> (Separated, M_src, maxC_src, status): the per-tile fit, then ONE pass that writes what
         ``want`` names -- norm (transform_batch's image), h / e (the haematoxylin-only / eosin-only image, (N,H,W,3) uint8) and conc
         (the normalised concentrations, (N,2,H,W) planes of ``conc_dtype``: float32 by default, float16 or bfloat16).
@@ -214,9 +221,11 @@ class ExtractiveStainNormalizer(object):
         conc (N,2,oh,ow); the call then returns (Separated, M_src, maxC_src, status, windows).  ``TileView(shrink=2 or 4)`` box-shrinks
         the images as in transform_batch and does not go with 'conc' in ``want``; a resizing view (``TileView(scale=)``) is refused.
         ``tensor_format``: a ``stainlib_amd.TensorFormat`` (with ``view`` only; ``TileView(None, flip=False, rot90=False)`` is the
-        fused full-tile tensor) -- norm, h and e are then (N,3,oh,ow) tensors, bit for bit ``tensor_format.convert`` of the uint8 views."""
+        fused full-tile tensor) -- norm, h and e are then (N,3,oh,ow) tensors, bit for bit ``tensor_format.convert`` of the uint8 views.
+        ``blur``, ``blur_sigmas``: refused (ValueError) -- the separation pass has no blur stage."""
         import torch
         from .. import engine
+        engine._no_blur(blur, blur_sigmas, "separate_batch")
         conc_dtype = torch.float32 if conc_dtype is None else conc_dtype
         want = engine._separate_want(want, conc_dtype)
         with_view = engine.separate_view_check(view, windows, tensor_format, want, conc_dtype, tiles)
@@ -236,7 +245,7 @@ class ExtractiveStainNormalizer(object):
 
     # -- stain jitter in the apply pass (an extension: RandStainNA / StainAugmentor-style augmentation of the normalised tiles) ----
     def augment_batch(self, tiles, alpha_beta, augment_background=False, normalize=True, out=None, ws=None, tensor_format=None, view=None,
-                      windows=None, hed=None, hed_sigmas=None, hed_biases=None, hsb=None, hsb_sigmas=None):
+                      windows=None, hed=None, hed_sigmas=None, hed_biases=None, hsb=None, hsb_sigmas=None, blur=None, blur_sigmas=None):
         """(N,H,W,3) uint8 device tensor -> (out, M_src, maxC_src, status): the per-tile fit, then ONE pass that normalises every tile
         and perturbs its stains: C_i * alpha_i + beta_i on the normalised concentrations of tissue pixels (every pixel with
         ``augment_background``), under the target's stain matrix, clipped.  ``alpha_beta``: (N, 4) = alpha0, beta0, alpha1, beta1 per
@@ -249,16 +258,19 @@ class ExtractiveStainNormalizer(object):
         ``hed``, ``hed_sigmas``, ``hed_biases``: as in transform_batch -- the HedColorAugmenter's transform of the perturbed tile in the
         same pass; one more element at the end of the returned tuple, ``engine.HedDraw``.
         ``hsb``, ``hsb_sigmas``: as in transform_batch -- the HsbColorAugmenter's map of the perturbed tile in the same pass; one more
-        element at the end of the returned tuple, ``engine.HsbDraw``."""
+        element at the end of the returned tuple, ``engine.HsbDraw``.
+        ``blur``, ``blur_sigmas``: as in transform_batch -- the GaussianBlurAugmenter's blur of the perturbed tile in the same pass; one
+        more element at the end of the returned tuple, ``engine.BlurDraw``."""
         from .. import engine
         engine._jitter_args(None, None, alpha_beta, None, tensor_format, out)
         if normalize and not hasattr(self, "stain_matrix_target"):
             raise ValueError("augment_batch(normalize=True) needs a fitted target: call fit() first, or pass normalize=False")
         with_hed = engine._hed_call(hed, hed_sigmas, hed_biases, tiles, view)
         with_hsb = engine._hsb_call(hsb, hsb_sigmas, tiles, view, hed)
+        with_blur = engine._blur_call(blur, blur_sigmas, tiles, view, hed, hsb)
         return self._route_batch(tiles, normalize, dict(alpha_beta=alpha_beta, augment_background=augment_background), out, ws,
                                  tensor_format, view, windows, (hed, hed_sigmas, hed_biases) if with_hed else None,
-                                 (hsb, hsb_sigmas) if with_hsb else None)
+                                 (hsb, hsb_sigmas) if with_hsb else None, (blur, blur_sigmas) if with_blur else None)
 
     def separate(self, I, normalize=True):
         """An image (RGB uint8) -> Separated of numpy arrays: norm (= transform(I)), h, e ((H,W,3) uint8) and conc ((2,H,W) float32)."""
@@ -339,15 +351,18 @@ class ReinhardStainNormalizer(object):
         return out[0].cpu().numpy()
 
     def transform_batch(self, tiles, mask_background=False, luminosity_threshold=0.8, out=None, ws=None, tensor_format=None, view=None,
-                        windows=None):
+                        windows=None, blur=None, blur_sigmas=None):
         """Batched extension: (N,H,W,3) uint8 device tensor -> (out, stats (N,8): p90, means, stds, tissue pixels).
         ``tensor_format``: a ``stainlib_amd.TensorFormat``; `out` is then the (N,3,H,W) tensor in that format (the map writes a uint8
         scratch, ``tensor_format.convert`` reads it).
         ``view``: a ``stainlib_amd.TileView`` -- the unchanged statistics of the WHOLE tiles, then ONE map sweep that writes per tile only
         the window ``windows[t]`` (default: ``view.draw(N, H, W)``) of that result, flipped and turned, as (N,oh,ow,3) uint8 or, with a
         ``tensor_format``, the (N,3,oh,ow) tensor -- no uint8 scratch (engine.reinhard_view); the call returns (out, stats, windows).
-        ``TileView(None, flip=False, rot90=False)`` is the fused full-tile tensor.  ``windows`` without ``view`` is a ValueError."""
+        ``TileView(None, flip=False, rot90=False)`` is the fused full-tile tensor.  ``windows`` without ``view`` is a ValueError.
+        ``blur``, ``blur_sigmas``: refused (ValueError) -- the Lab family's fused pass has no blur stage; blur its uint8 result
+        (``blur.transform_batch(view=, tensor_format=)``)."""
         from .. import engine
+        engine._no_blur(blur, blur_sigmas, "the Lab family's fused calls (ReinhardStainNormalizer.transform_batch)")
         tm, ts = self._targets()
         if engine.lab_view_check(view, windows, tiles):
             return engine.reinhard_view(tiles, windows, None, tm, ts, mask_background=mask_background,

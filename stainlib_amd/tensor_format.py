@@ -55,13 +55,23 @@ class TensorFormat(object):
             raise ValueError(f"{what} must be three finite numbers, not {x!r}")
         return v
 
-    def convert(self, tiles_u8, out=None, view=None, windows=None):
+    def convert(self, tiles_u8, out=None, view=None, windows=None, blur=None, blur_sigmas=None):
         """(N, H, W, 3) uint8 device tensor -> (N, 3, H, W) tensor in this format (one streaming sweep, engine.to_tensor).
         ``out``: a tensor of that shape, dtype and memory format to write into.
         ``view``: a ``stainlib_amd.TileView`` -- per tile only the window ``windows[t]`` (default: ``view.draw(N, H, W)``), flipped and
         turned, converted in the same sweep (engine.normalize_view): the crop / flip / rot90 behind ANY uint8 result (Reinhard, HED,
-        luminosity ...).  Returns (the (N, 3, oh, ow) tensor, windows)."""
+        luminosity ...).  Returns (the (N, 3, oh, ow) tensor, windows).
+        ``blur``: a ``stainlib_amd.GaussianBlurAugmenter`` -- its integer Gaussian blur of every WHOLE tile in the same sweep
+        (engine.normalize_blur_view), then the view (if any) and the conversion.  ``blur_sigmas``: (N,); by default
+        ``blur.randomize_batch(N)``, drawn BEFORE the windows.  One more element at the end, ``engine.BlurDraw(sigmas, codes)``: the call
+        returns (tensor, BlurDraw) or (tensor, windows, BlurDraw).  Not with a ``TileView(scale=)`` or a TileAffine."""
         from . import engine
+        if engine._blur_call(blur, blur_sigmas, tiles_u8, view):
+            if view is not None or windows is not None:
+                engine._view_call(view, windows, tiles_u8, draw=False)
+            engine._check_tiles(tiles_u8)
+            x, windows, draw = engine.blur_stage(tiles_u8, blur, blur_sigmas, view, windows, {}, fmt=self, out=out)
+            return (x,) + ((windows,) if view is not None else ()) + (draw,)
         if view is not None or windows is not None:
             return engine.view_pass(tiles_u8, view, windows, fmt=self, out=out)
         return engine.to_tensor(tiles_u8, self, out=out)

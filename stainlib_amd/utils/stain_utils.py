@@ -97,15 +97,17 @@ class LuminosityStandardizer(object):
         return out[0].cpu().numpy()
 
     @staticmethod
-    def standardize_batch(tiles, percentile=95, out=None, ws=None, tensor_format=None, view=None, windows=None):
+    def standardize_batch(tiles, percentile=95, out=None, ws=None, tensor_format=None, view=None, windows=None, blur=None, blur_sigmas=None):
         """Batched extension: (N,H,W,3) uint8 device tensor -> (out, p (N,) float64: every tile's `percentile` of L8).
         ``tensor_format``: a ``stainlib_amd.TensorFormat``; `out` is then the (N,3,H,W) tensor in that format (the map writes a uint8
         scratch, ``tensor_format.convert`` reads it).
         ``view``: a ``stainlib_amd.TileView`` -- the unchanged statistics of the WHOLE tiles, then ONE map sweep that writes per tile only
         the window ``windows[t]`` (default: ``view.draw(N, H, W)``) of that result, flipped and turned, as (N,oh,ow,3) uint8 or the
         (N,3,oh,ow) tensor -- no uint8 scratch (engine.luminosity_view); the call returns (out, p, windows).  ``windows`` without
-        ``view`` is a ValueError."""
+        ``view`` is a ValueError.  ``blur``, ``blur_sigmas``: refused (ValueError) -- the Lab family's fused pass has no blur stage;
+        blur its uint8 result (``blur.transform_batch(view=, tensor_format=)``)."""
         from .. import engine
+        engine._no_blur(blur, blur_sigmas, "the Lab family's fused calls (LuminosityStandardizer.standardize_batch)")
         if engine.lab_view_check(view, windows, tiles):
             return engine.luminosity_view(tiles, windows, None, percentile, fmt=tensor_format, out=out, ws=ws, view=view)
         if tensor_format is None:
