@@ -843,10 +843,42 @@ SL_API int sl_view_planes(const void* planes, void* out, int n, int c, int h, in
  * elem_bytes, alignment, the statistics pattern, params and fmt; a NULL windows; oh < 1 or ow < 1; h, w, oh or ow > 8192; max_r outside
  * [1, 2 Q]; fill_rgb >= 2^24; more (tile, patch) or (plane, patch) pairs than 2^31 - 1 (a patch is min(64, 1 + 62 Q / max_r) outputs
  * square).  No workspace; capture-safe like the rest (no allocation, no synchronisation, no memset).  out == rgb / out == planes is
- * not supported.  Bicubic and antialiased filters, perspective and elastic warps, reflect / replicate borders and bilinear planes are
+ * not supported.  Bicubic and antialiased filters, perspective warps (elastic ones: sl_normalize_view_elastic below), reflect / replicate borders and bilinear planes are
  * other definitions and not offered. */
 SL_API int sl_normalize_view_affine(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int max_r, uint32_t fill_rgb, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, const double* alpha_beta, int augment_background, const SlParams* params, const SlTensorFormat* fmt, void* stream);
 SL_API int sl_view_planes_affine(const void* planes, void* out, int n, int c, int h, int w, int elem_bytes, int oh, int ow, const int32_t* windows, int max_r, uint64_t fill_bits, void* stream);
+
+/* ---- elastic deformation in the one-pass loader: the affine view plus a smooth per-pixel displacement, for the images and their
+ * companion planes alike (stainlib_amd/csrc/view_elastic.hip; an extension: the U-Net recipe of segmentation and nuclei-detection
+ * loaders -- random displacements on a coarse grid, interpolated smoothly -- behind the call that is a per-pixel float field of
+ * N x H x W x 2 and grid_sample once for the image and once more per label plane) ------------------------------------------------------
+ * The definition is in integers, so "bit for bit" applies.  windows: sl_normalize_view_affine's n x 6 rows.  field: n x gh x gw x 2 int32
+ * on the device, a control lattice per tile of displacements (dy, dx) in units of 1/256 SOURCE pixel (the resolution of the 8-bit
+ * bilinear weights) on cells of 2^k OUTPUT pixels, k = cell_log2 in 4 .. 8, one for the call:
+ *     gh = ((oh + 2^k - 1) >> k) + 2        gw = ((ow + 2^k - 1) >> k) + 2
+ * max_d in 0 .. 8 (source pixels), one for the call, bounds the field: every control value is CLAMPED to +-256 max_d by the kernel (any
+ * int32 is safe).  The displacement of output pixel (i, j) is the uniform quadratic B-spline of the lattice -- C1-smooth, weights exact
+ * integers:
+ *     along i:  t = ((2 i + 1) << 8) >> (k + 1);   a = t >> 8;   f = t & 255
+ *               wy = ((256 - f)^2,  131072 - (256 - f)^2 - f^2,  f^2)                          (>= 0, sum 2^17)
+ *     along j:  b, wx likewise from j
+ *     r[q]  = (sum_{p=0..2} wx[p] field[a + q][b + p][m] + 65536) >> 17                        (q = 0, 1, 2; arithmetic shift)
+ *     d[m]  = (sum_{q=0..2} wy[q] r[q] + 65536) >> 17                                          (m = 0: y, 1: x)
+ *     Y = cy + ((a00 u + a01 v) >> 1) + (d[0] << 8)        X = cx + ((a10 u + a11 v) >> 1) + (d[1] << 8)
+ * with the affine view's u = 2 i + 1 - oh, v = 2 j + 1 - ow.  From (Y, X) on everything is the affine view's: the taps, the fill outside
+ * the tile and the blend of the images (sl_normalize_view_elastic), the element at (Y >> 16, X >> 16) or the fill of the planes
+ * (sl_view_planes_elastic) -- a label plane and its image go through the same (Y, X).  What follows: |d| <= max |field| (a convex
+ * combination, rounded to nearest); a zero field is the affine view bit for bit; a constant field (c_y, c_x) is the affine view with
+ * the centre moved by (c_y << 8, c_x << 8).  Every intermediate is 32-bit.
+ * max_r: sl_normalize_view_affine's bound of the row sums; a tile beyond it is written as fill.  The grid is sized on the host from max_r
+ * and max_d: a workgroup takes min(64, 1 + (62 - 2 max_d) Q / R) outputs a side and stages the box of its four affine corners grown by
+ * max_d pixels, cut to the tile.
+ * Returns SL_ERR_BADARG before anything is launched for whatever the affine entry point refuses, a NULL or misaligned field, cell_log2
+ * outside 4 .. 8 and max_d outside 0 .. 8; n == 0 is SL_OK and launches nothing.  No workspace; capture-safe like the rest.  out == rgb
+ * / out == planes is not supported.  Displacements above 8 pixels, cells below 16, cubic or Gaussian-smoothed fields, perspective warps
+ * and bilinear planes are other definitions and not offered. */
+SL_API int sl_normalize_view_elastic(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int max_r, const int32_t* field, int cell_log2, int max_d, uint32_t fill_rgb, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, const double* alpha_beta, int augment_background, const SlParams* params, const SlTensorFormat* fmt, void* stream);
+SL_API int sl_view_planes_elastic(const void* planes, void* out, int n, int c, int h, int w, int elem_bytes, int oh, int ow, const int32_t* windows, int max_r, const int32_t* field, int cell_log2, int max_d, uint64_t fill_bits, void* stream);
 
 /* ---- hue / saturation / brightness augmentation (stainlib_amd/csrc/hsb.hip; an extension: the HSV half of the Tellez et al. colour
  * augmenters, the sibling of sl_hed_augment).  Defined in INTEGERS on bytes, so every route below computes the same bits.

@@ -6,6 +6,8 @@ TensorFormat (an extension) turns the batched operators' uint8 results into mode
 StainJitter (an extension) draws the per-tile (alpha, beta) of the augment_batch methods: stain jitter inside the apply pass.
 TileView (an extension) draws the per-tile crop / flip / quarter turn that view= applies inside the same pass.
 TileAffine (an extension) draws a per-tile rotation by any angle, zoom, shear and translation for view=: bilinear, in integers.
+TileElastic (an extension) adds an elastic deformation to it -- a quadratic B-spline of a coarse lattice of random displacements, in
+integers, for images and label planes alike; its windows are an ElasticWindows(affine, field).
 HsbColorAugmenter (an extension; HsbLight / HsbStrong presets) is the hue / saturation / brightness sibling of the HED augmenters, in integers.
 GaussianBlurAugmenter (an extension) is the Gaussian blur of that set: a per-tile integer separable filter, fused into the view pass (blur=).
 Separated (an extension) is what the normalizers' separate / separate_batch return: per-stain images and concentration maps.
@@ -23,7 +25,7 @@ from .normalization.normalizer import (ExtractiveStainNormalizer, MacenkoNormali
                                        ReinhardStainNormalizer, VahadaneNormalizer)
 from .tensor_format import TensorFormat  # noqa: F401
 from .separated import Separated  # noqa: F401
-from .tile_view import TileAffine, TileView  # noqa: F401
+from .tile_view import ElasticWindows, TileAffine, TileElastic, TileView  # noqa: F401
 from .utils.stain_utils import LuminosityStandardizer  # noqa: F401
 from .utils.excepts import InvalidRangeError, TissueMaskException  # noqa: F401
 

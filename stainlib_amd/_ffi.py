@@ -210,6 +210,13 @@ _SIGNATURES["sl_normalize_view_affine"] = (C.c_int, [_P, _P, C.c_int, C.c_int, C
                                                      _P, C.c_int, C.POINTER(SlParams), C.POINTER(SlTensorFormat), _P])
 _SIGNATURES["sl_view_planes_affine"] = (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_uint64,
                                                   _P])
+# the elastic views (field: n x gh x gw x 2 int32 on the device): the affine views' parameters with `const int32_t* field, int cell_log2,
+# int max_d` behind max_r
+for _name in ("sl_normalize_view", "sl_view_planes"):
+    _res, _args = _SIGNATURES[_name + "_affine"]
+    _i = 9 if _name == "sl_normalize_view" else 11
+    _SIGNATURES[_name + "_elastic"] = (_res, _args[:_i] + [_P, C.c_int, C.c_int] + _args[_i:])
+del _name, _res, _args, _i
 # hue / saturation / brightness augmentation (codes: n x 3 int32 on the device): rgb, out, n, h, w, codes, fmt, stream -- and the view pass
 # with the HSB stage: rgb, out, n, h, w, oh, ow, windows, d_mask, shrink, max_wh, max_ww, <sl_normalize_view's statistics, params, fmt>, codes, stream
 _SIGNATURES["sl_hsb_augment"] = (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(SlTensorFormat), _P])

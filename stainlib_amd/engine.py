@@ -623,7 +623,10 @@ def _affine_windows(windows, n, h, w, size, max_r):
     """The (n, 6) int32 windows of an affine call (no device needed).  numpy / CPU windows are range-checked (tile_view.
     affine_check_windows: ValueError) and come back as numpy; device windows are taken as they are -- the kernel clamps the centres and
     writes a tile whose row sums pass max_r as fill; nothing is read back."""
-    from .tile_view import affine_check_windows
+    from .tile_view import ElasticWindows, affine_check_windows
+    if isinstance(windows, ElasticWindows):
+        raise ValueError("these windows are the ElasticWindows of an elastic view: pass them with the TileElastic that drew them, or "
+                         "windows.affine for the affine part alone")
     if isinstance(windows, torch.Tensor) and windows.is_cuda:
         if not (windows.dtype == torch.int32 and tuple(windows.shape) == (n, 6) and windows.is_contiguous()):
             raise ValueError(f"device windows of an affine view must be a contiguous int32 tensor of shape ({n}, 6)")
@@ -735,6 +738,148 @@ def view_planes_affine(planes, windows, size, max_r, fill=0, out=None):
     if win.device != dev:
         raise ValueError(f"windows must be on {dev}")
     _call("sl_view_planes_affine", _ptr(planes), _ptr(out), n, c, h, w, planes.element_size(), oh, ow, _ptr(win), int(max_r), bits)
+    return out
+
+
+# ---- the elastic views: the affine view plus a smooth displacement field (sl_normalize_view_elastic, sl_view_planes_elastic; TileElastic) ---
+
+def _is_elastic(view):
+    from .tile_view import TileElastic
+    return isinstance(view, TileElastic)
+
+
+def _on_device(x):
+    return isinstance(x, torch.Tensor) and x.is_cuda
+
+
+def _elastic_parts(windows):
+    """(affine, field) of the windows= of an elastic view (no device needed), or ValueError: anything but an ElasticWindows, or one
+    with a part on each side"""
+    from .tile_view import ElasticWindows
+    if not isinstance(windows, ElasticWindows):
+        raise ValueError("windows of an elastic view must be the stainlib_amd.ElasticWindows(affine, field) a call with this TileElastic "
+                         "returned (or view.draw(N, H, W)), not " + ("a plain array of affine rows: wrap it as ElasticWindows(rows, field) "
+                                                                     "with a field of elastic_grid_shape" if hasattr(windows, "shape")
+                                                                     else type(windows).__name__))
+    if _on_device(windows.affine) != _on_device(windows.field):
+        raise ValueError("the two parts of an ElasticWindows must live on the same side: both on the host (range-checked) or both on the "
+                         "device (clamped by the kernel) -- move one of them")
+    return windows.affine, windows.field
+
+
+def _elastic_field(field, n, size, cell, max_d):
+    """The (n, gh, gw, 2) int32 field of an elastic call (no device needed).  A numpy / CPU field is range-checked (tile_view.
+    elastic_check_field: ValueError) and comes back as numpy; a device field is taken as it is -- the kernel clamps every control value
+    to +-256 max_d; nothing is read back."""
+    from .tile_view import elastic_check_field, elastic_grid_shape
+    if _on_device(field):
+        shape = (n,) + elastic_grid_shape(size, cell) + (2,)
+        if not (field.dtype == torch.int32 and tuple(field.shape) == shape and field.is_contiguous()):
+            raise ValueError(f"the device field of an elastic view must be a contiguous int32 tensor of shape {shape}")
+        elastic_check_field(torch.zeros(shape, dtype=torch.int32), n, size, cell, max_d)        # (the cell and the bound alone)
+        return field
+    return elastic_check_field(field, n, size, cell, max_d)
+
+
+def _elastic_bound(view, windows):
+    """(max_r, max_d) of the call behind an elastic view (no device needed): max_r as _affine_bound; max_d of a host field its own
+    largest control displacement in whole pixels, rounded up (beyond the limit: the limit, and elastic_check_field says so), of a
+    device field (never read back) or none yet the largest the view can draw (TileElastic.max_d)."""
+    import numpy as np
+    from .tile_view import ELASTIC_MAX_D, ELASTIC_UNIT, ElasticWindows
+    if not isinstance(windows, ElasticWindows):
+        return view.bound, view.max_d
+    max_r = _affine_bound(view, windows.affine)
+    field = windows.field
+    if _on_device(field):
+        return max_r, view.max_d
+    try:
+        f = field.numpy() if isinstance(field, torch.Tensor) else np.asarray(field)
+        if f.dtype.kind not in "iu" or f.size == 0:
+            raise TypeError
+    except (TypeError, ValueError, RuntimeError):
+        return max_r, view.max_d                             # (elastic_check_field says what is wrong with it)
+    return max_r, min(ELASTIC_MAX_D, (int(np.abs(f.astype(np.int64)).max()) + ELASTIC_UNIT - 1) // ELASTIC_UNIT)
+
+
+def normalize_view_elastic(rgb, windows, field, size, cell, max_r, max_d, fill=255, M_src=None, maxC_src=None, M_tgt=None, maxC_tgt=None,
+                           alpha_beta=None, augment_background=False, params=None, fmt=None, out=None):
+    """normalize_view_affine with a smooth per-pixel displacement on top (sl_normalize_view_elastic): per tile the image the statistics
+    pattern names, sampled bilinearly at the affine positions of windows[t] moved by the quadratic B-spline of the control lattice
+    field[t] (stainlib_amd.tile_view.elastic_resample is the definition, bit for bit).
+    windows, size, max_r, fill, the statistics, fmt, out: normalize_view_affine's.
+    field: (N, gh, gw, 2) int32, (dy, dx) per lattice node in 1/256 source pixel, (gh, gw) = tile_view.elastic_grid_shape(size, cell).
+    numpy or CPU tensor: range-checked against max_d, ValueError.  Device tensor: taken as it is -- the kernel clamps every control
+    value to +-256 max_d.  Both windows and field on the host, or both on the device.
+    cell: the lattice spacing in OUTPUT pixels, a power of two 16 .. 256.  max_d: an int 0 .. 8, an upper bound in source pixels of
+    the control displacements of the call (TileElastic.max_d); the launch is sized from max_r and max_d."""
+    from .tensor_format import TensorFormat
+    from .tile_view import _cell_log2, _fill3, affine_check_size
+    if not (isinstance(rgb, torch.Tensor) and rgb.dim() == 4 and rgb.shape[-1] == 3):
+        raise ValueError("expected a contiguous CUDA uint8 tensor of shape (N, H, W, 3)")
+    n, h, w = (int(v) for v in rgb.shape[:3])
+    oh, ow = affine_check_size(size, h, w)
+    f3 = _fill3(fill)
+    if _on_device(windows) != _on_device(field):
+        raise ValueError("windows and field of an elastic view must live on the same side: both on the host or both on the device")
+    win = _affine_windows(windows, n, h, w, size, max_r)
+    fld = _elastic_field(field, n, (oh, ow), cell, max_d)
+    _route_check(M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, params, n)
+    if fmt is not None and not isinstance(fmt, TensorFormat):
+        raise ValueError("fmt must be a stainlib_amd.TensorFormat or None (the uint8 image)")
+    _check_tiles(rgb)
+    dev = rgb.device
+    if not isinstance(win, torch.Tensor):
+        win, fld = torch.from_numpy(win).to(dev), torch.from_numpy(fld).to(dev)
+    if win.device != dev or fld.device != dev:
+        raise ValueError(f"windows and field must be on {dev}")
+    M_src, maxC_src, M_tgt, maxC_tgt, ab = _route_upload(n, dev, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta)
+    f, out = _image_out(out, rgb, n, oh, ow, fmt, "view")
+    _call("sl_normalize_view_elastic", _ptr(rgb), _ptr(out), n, h, w, oh, ow, _ptr(win), int(max_r), _ptr(fld), _cell_log2(cell), int(max_d),
+          f3[0] | (f3[1] << 8) | (f3[2] << 16), _ptr(M_src), _ptr(maxC_src), _ptr(M_tgt), _ptr(maxC_tgt), _ptr(ab),
+          1 if augment_background else 0, _byref(params), _byref(f))
+    return out
+
+
+def view_planes_elastic(planes, windows, field, size, cell, max_r, max_d, fill=0, out=None):
+    """view_planes_affine through an elastic view (sl_view_planes_elastic): per element the NEAREST source element (Y >> 16, X >> 16) of
+    the image view's coordinates (stainlib_amd.tile_view.elastic_nearest is the definition), outside the plane `fill`.  windows, field,
+    size, cell, max_r, max_d: those of the normalize_view_elastic call of the images; planes, fill, out: view_planes_affine's."""
+    from .tile_view import _cell_log2, affine_check_size
+    h, w = planes_hw(planes)
+    n = int(planes.shape[0])
+    c = int(planes.shape[1]) if planes.dim() == 4 else 1
+    if planes.dtype not in PLANES_DTYPES:
+        raise ValueError(f"planes of dtype {planes.dtype} are not supported: an element must have 1, 2, 4 or 8 bytes "
+                         "(bool, uint8, int8, int16, float16, bfloat16, int32, float32, int64, float64)")
+    oh, ow = affine_check_size(size, h, w)
+    bits = _fill_bits(fill, planes.dtype)
+    if _on_device(windows) != _on_device(field):
+        raise ValueError("windows and field of an elastic view must live on the same side: both on the host or both on the device")
+    win = _affine_windows(windows, n, h, w, size, max_r)
+    fld = _elastic_field(field, n, (oh, ow), cell, max_d)
+    if not planes.is_cuda:
+        raise ValueError("planes must be a contiguous CUDA tensor of shape (N, H, W) or (N, C, H, W), not a CPU tensor")
+    if not planes.is_contiguous():
+        raise ValueError("planes must be a contiguous CUDA tensor of shape (N, H, W) or (N, C, H, W): this one is not contiguous "
+                         "(channels-last planes are not supported)")
+    if n < 1 or c < 1:
+        raise ValueError(f"planes of shape {tuple(planes.shape)} hold no element")
+    dev = planes.device
+    shape = (n, oh, ow) if planes.dim() == 3 else (n, c, oh, ow)
+    if out is None:
+        out = torch.empty(shape, dtype=planes.dtype, device=dev)
+    elif not (isinstance(out, torch.Tensor) and tuple(out.shape) == shape and out.dtype == planes.dtype and out.device == dev
+              and out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous {planes.dtype} tensor of shape {shape} on {dev}")
+    elif out.data_ptr() == planes.data_ptr():
+        raise ValueError("out must not be planes itself: the view is not done in place")
+    if not isinstance(win, torch.Tensor):
+        win, fld = torch.from_numpy(win).to(dev), torch.from_numpy(fld).to(dev)
+    if win.device != dev or fld.device != dev:
+        raise ValueError(f"windows and field must be on {dev}")
+    _call("sl_view_planes_elastic", _ptr(planes), _ptr(out), n, c, h, w, planes.element_size(), oh, ow, _ptr(win), int(max_r), _ptr(fld),
+          _cell_log2(cell), int(max_d), bits)
     return out
 
 
@@ -1292,13 +1437,25 @@ def blur_stage(tiles, blur, blur_sigmas, view, windows, route, fmt=None, out=Non
 def _view_call(view, windows, tiles, draw=True):
     """(size, d_mask, windows, shrink) of the view= / windows= pair of a batch method, checked without a device (ValueError): the windows
     as given, or drawn (TileView.draw; draw=False: left None for a later call)."""
-    from .tile_view import TileView
+    from .tile_view import ElasticWindows, TileView
     if not isinstance(view, TileView) and not _is_affine(view):
         raise ValueError("view must be a stainlib_amd.TileView" + (" (windows= goes with view=)" if view is None else ""))
+    if isinstance(windows, ElasticWindows) and not _is_elastic(view):
+        raise ValueError(f"these windows are the ElasticWindows of an elastic view and do not go with {view!r}: pass them with the "
+                         "TileElastic that drew them, or windows.affine for the affine part alone")
     if not (isinstance(tiles, torch.Tensor) and tiles.dim() == 4 and tiles.shape[-1] == 3):
         raise ValueError("expected a contiguous CUDA uint8 tensor of shape (N, H, W, 3)")
     n, h, w = (int(v) for v in tiles.shape[:3])
     oh, ow = view.out_size(h, w)
+    if _is_elastic(view):                                    # ElasticWindows(affine, field); view_pass makes the call
+        if windows is not None:
+            affine, field = _elastic_parts(windows)
+            max_r, max_d = _elastic_bound(view, windows)
+            _affine_windows(affine, n, h, w, view.size, max_r)
+            _elastic_field(field, n, (oh, ow), view.cell, max_d)
+        elif draw:
+            windows = view.draw(n, h, w)
+        return view.size, 0, windows, 1
     if _is_affine(view):                                     # (cy, cx, a00, a01, a10, a11) per tile; _view_pass makes the call
         if windows is not None:
             _affine_windows(windows, n, h, w, view.size, _affine_bound(view, windows))
@@ -1364,9 +1521,13 @@ def route_stage(tiles, fit, route, fmt=None, out=None, view=None, windows=None, 
 
 def view_pass(tiles, view, windows, fmt=None, out=None, **route):
     """The ONE pass behind a view= argument, dispatched on the view's type -> (out, windows): the windows as given or drawn here
-    (_view_call), then normalize_view_affine for a TileAffine, normalize_view (its shrink, its resizing bound) for a TileView.  route:
+    (_view_call), then normalize_view_elastic for a TileElastic, normalize_view_affine for a TileAffine, normalize_view (its shrink, its resizing bound) for a TileView.  route:
     the keyword arguments that name `full` ({}: the tiles themselves)."""
     size, d_mask, windows, shrink = _view_call(view, windows, tiles)
+    if _is_elastic(view):
+        max_r, max_d = _elastic_bound(view, windows)
+        return normalize_view_elastic(tiles, windows.affine, windows.field, size, view.cell, max_r, max_d, view.fill, fmt=fmt, out=out,
+                                      **route), windows
     if _is_affine(view):
         return normalize_view_affine(tiles, windows, size, _affine_bound(view, windows), view.fill, fmt=fmt, out=out, **route), windows
     return normalize_view(tiles, windows, size, d_mask, fmt=fmt, out=out, shrink=shrink, resize=_view_resize(view, windows, tiles),

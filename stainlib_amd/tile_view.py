@@ -17,11 +17,18 @@ scaled by no, source pixel k covers [k no, (k + 1) no), output i covers [i nw, (
 per channel b = (2 S + D) // (2 D) with S = sum cy(i, k) cx(j, l) window[k, l] and D = wh ww.  A window smaller than the output comes
 out piecewise constant with blended edges (the same formula), not bilinear.  area_resample below is that definition in numpy.
 
-TileAffine (at the end of the module) is the affine view: rotation by ANY angle, zoom, shear and translation, a view of one tile six
+TileAffine (behind the views above) is the affine view: rotation by ANY angle, zoom, shear and translation, a view of one tile six
 int32 in 2^-16 source pixels, the image sampled bilinearly with 8-bit weights and its label maps by the nearest element, both in
 integers (sl_normalize_view_affine, sl_view_planes_affine); affine_coords / affine_resample / affine_nearest are that definition in numpy.
+
+TileElastic (at the end of the module) is the elastic view: a TileAffine plus a smooth per-pixel displacement, the quadratic B-spline of
+a coarse lattice of random control displacements in 1/256 source pixel, in integers (sl_normalize_view_elastic, sl_view_planes_elastic);
+its windows are an ElasticWindows(affine, field); elastic_displacement / elastic_coords / elastic_resample / elastic_nearest are that
+definition in numpy.
 """
 from __future__ import annotations
+
+from collections import namedtuple
 
 import numpy as np
 
@@ -275,6 +282,9 @@ class TileView(object):
         if len(getattr(windows, "shape", ())) == 2 and windows.shape[1] == 6:
             raise ValueError("six-column windows are those of an affine view (TileAffine.draw): take the planes through that "
                              "TileAffine's apply -- a TileView's windows are (y0, x0, d) or (y0, x0, d, wh, ww)")
+        if isinstance(windows, ElasticWindows):
+            raise ValueError("these windows are the ElasticWindows of an elastic view: take the planes through the apply of the "
+                             "TileElastic that drew them")
         h, w = engine.planes_hw(planes)
         return engine.view_planes(planes, windows, self.size, self.d_mask, mode=mode, out=out, shrink=self.shrink,
                                   resize=engine._view_resize_hw(self, windows, h, w))
@@ -334,19 +344,7 @@ def affine_resample(full, row, size, fill=255):
     full = np.asarray(full)
     if full.dtype != np.uint8 or full.ndim != 3:
         raise ValueError("affine_resample is defined on an (h, w, C) uint8 image")
-    h, w, ch = full.shape
-    f = np.asarray(_fill3(fill) if ch == 3 else (int(fill),) * ch, dtype=np.int64)
-    Y, X = affine_coords(row, size)
-    ty, tx = Y - AFFINE_Q // 2, X - AFFINE_Q // 2
-    ky, kx, fy, fx = ty >> 16, tx >> 16, ((ty >> 8) & 255)[..., None], ((tx >> 8) & 255)[..., None]
-
-    def tap(y, x):
-        inside = (y >= 0) & (y < h) & (x >= 0) & (x < w)
-        v = full[np.clip(y, 0, h - 1), np.clip(x, 0, w - 1)].astype(np.int64)
-        return np.where(inside[..., None], v, f)
-    top = (256 - fx) * tap(ky, kx) + fx * tap(ky, kx + 1)
-    bot = (256 - fx) * tap(ky + 1, kx) + fx * tap(ky + 1, kx + 1)
-    return (((256 - fy) * top + fy * bot + 32768) >> 16).astype(np.uint8)
+    return _bilinear_at(full, *affine_coords(row, size), fill)
 
 
 def affine_nearest(plane, row, size, fill=0):
@@ -546,3 +544,202 @@ class TileAffine(object):
     def __repr__(self):
         return (f"TileAffine(size={self.size}, rotate={self.rotate}, zoom={self.zoom}, shear={self.shear}, translate={self.translate}, "
                 f"flip={self.flip}, fill={self.fill})")
+
+
+# ---- the elastic view: the affine view plus a smooth displacement field (sl_normalize_view_elastic, sl_view_planes_elastic) ------------------
+# A view of one tile is an affine row AND a control lattice field[t] of shape (gh, gw, 2): displacements (dy, dx) in units of 1/256 source
+# pixel -- the resolution of the 8-bit bilinear weights -- on a grid of cells of `cell` OUTPUT pixels, interpolated by a uniform quadratic
+# B-spline whose weights are exact integers.  The functions below ARE the definition; the kernels are tested against them bit for bit.
+ELASTIC_UNIT = 256               # field units per source pixel
+ELASTIC_MAX_D = 8                # the largest displacement, in source pixels
+ELASTIC_CELLS = (16, 32, 64, 128, 256)
+
+ElasticWindows = namedtuple("ElasticWindows", ["affine", "field"])
+ElasticWindows.__doc__ = """The windows of an elastic view: affine, (N, 6) int32 -- TileAffine's rows --, and field, (N, gh, gw, 2) int32 --
+the control displacements (dy, dx) in 1/256 source pixel (elastic_grid_shape).  Both on the host or both on the device."""
+
+
+def _cell_log2(cell):
+    if isinstance(cell, bool) or not isinstance(cell, (int, np.integer)) or int(cell) not in ELASTIC_CELLS:
+        raise ValueError(f"cell of an elastic view must be a power of two from 16 to 256 (output pixels per lattice cell), not {cell!r}")
+    return int(cell).bit_length() - 1
+
+
+def elastic_grid_shape(size, cell):
+    """(gh, gw): the control lattice of an elastic view of size = (oh, ow) with cells of `cell` output pixels; with k = log2 cell,
+    gh = ((oh + 2^k - 1) >> k) + 2, gw likewise -- every output pixel has its 3 x 3 nodes"""
+    oh, ow = _size2(size)
+    k = _cell_log2(cell)
+    return ((oh + (1 << k) - 1) >> k) + 2, ((ow + (1 << k) - 1) >> k) + 2
+
+
+def _elastic_weights(no, k):
+    """(a, w): per output 0 .. no - 1 of an axis the first of its three nodes and their (no, 3) int64 weights out of 2^17:
+    t = ((2 o + 1) << 8) >> (k + 1), a = t >> 8, f = t & 255, w = ((256 - f)^2, 131072 - (256 - f)^2 - f^2, f^2)"""
+    t = ((2 * np.arange(no, dtype=np.int64) + 1) << 8) >> (k + 1)
+    a, f = t >> 8, t & 255
+    w0, w2 = (256 - f) ** 2, f ** 2
+    return a, np.stack([w0, 131072 - w0 - w2, w2], axis=1)
+
+
+def elastic_displacement(field, size, cell):
+    """(oh, ow, 2) int64: the displacement (dy, dx), in 1/256 source pixel, of every output pixel under the (gh, gw, 2) control lattice
+    `field`: the uniform quadratic B-spline r[q] = (sum_p wx[p] field[a + q][b + p] + 65536) >> 17, d = (sum_q wy[q] r[q] + 65536) >> 17
+    (arithmetic shifts; the weights of _elastic_weights).  |d| <= max |field|; 32-bit for |field| <= 2048."""
+    oh, ow = _size2(size)
+    k = _cell_log2(cell)
+    field = np.asarray(field)
+    if field.dtype.kind not in "iu" or field.shape != elastic_grid_shape(size, cell) + (2,):
+        raise ValueError(f"the field of one tile must be an integer array of shape {elastic_grid_shape(size, cell) + (2,)}, not "
+                         f"{field.dtype} {field.shape}")
+    f = field.astype(np.int64)
+    a, wy = _elastic_weights(oh, k)
+    b, wx = _elastic_weights(ow, k)
+    # r[g, j, m]: every lattice row g at every output column j
+    r = (sum(wx[None, :, p, None] * f[:, b + p, :] for p in range(3)) + 65536) >> 17
+    return (sum(wy[:, None, q, None] * r[a + q] for q in range(3)) + 65536) >> 17
+
+
+def elastic_coords(row, field, size, cell):
+    """(Y, X), two (oh, ow) int64 arrays: affine_coords(row, size) plus the displacement, Y += d[0] << 8, X += d[1] << 8"""
+    Y, X = affine_coords(row, size)
+    d = elastic_displacement(field, size, cell)
+    return Y + (d[..., 0] << 8), X + (d[..., 1] << 8)
+
+
+def _bilinear_at(full, Y, X, fill):
+    """affine_resample from (Y, X) on: affine_taps, the four taps with the fill outside the image, affine_blend"""
+    h, w, ch = full.shape
+    f = np.asarray(_fill3(fill) if ch == 3 else (int(fill),) * ch, dtype=np.int64)
+    ty, tx = Y - AFFINE_Q // 2, X - AFFINE_Q // 2
+    ky, kx, fy, fx = ty >> 16, tx >> 16, ((ty >> 8) & 255)[..., None], ((tx >> 8) & 255)[..., None]
+
+    def tap(y, x):
+        inside = (y >= 0) & (y < h) & (x >= 0) & (x < w)
+        v = full[np.clip(y, 0, h - 1), np.clip(x, 0, w - 1)].astype(np.int64)
+        return np.where(inside[..., None], v, f)
+    top = (256 - fx) * tap(ky, kx) + fx * tap(ky, kx + 1)
+    bot = (256 - fx) * tap(ky + 1, kx) + fx * tap(ky + 1, kx + 1)
+    return (((256 - fy) * top + fy * bot + 32768) >> 16).astype(np.uint8)
+
+
+def elastic_resample(full, row, field, size, cell, fill=255):
+    """The definition of the elastic view of an image in numpy: the (h, w, C) uint8 `full` sampled at elastic_coords(row, field, size,
+    cell) exactly as affine_resample samples at affine_coords -> (oh, ow, C) uint8."""
+    full = np.asarray(full)
+    if full.dtype != np.uint8 or full.ndim != 3:
+        raise ValueError("elastic_resample is defined on an (h, w, C) uint8 image")
+    return _bilinear_at(full, *elastic_coords(row, field, size, cell), fill)
+
+
+def elastic_nearest(plane, row, field, size, cell, fill=0):
+    """The definition of the elastic view of a companion plane in numpy: the element at (Y >> 16, X >> 16) of the (h, w) `plane`, (Y, X)
+    = elastic_coords(row, field, size, cell), copied bit for bit; outside the plane `fill`."""
+    plane = np.asarray(plane)
+    if plane.ndim != 2:
+        raise ValueError("elastic_nearest is defined on an (h, w) plane")
+    h, w = plane.shape
+    Y, X = elastic_coords(row, field, size, cell)
+    ky, kx = Y >> 16, X >> 16
+    inside = (ky >= 0) & (ky < h) & (kx >= 0) & (kx < w)
+    out = np.full(ky.shape, np.asarray(fill).astype(plane.dtype), dtype=plane.dtype)
+    out[inside] = plane[ky[inside], kx[inside]]
+    return out
+
+
+def elastic_check_max_d(max_d):
+    if isinstance(max_d, bool) or not isinstance(max_d, (int, np.integer)) or not 0 <= int(max_d) <= ELASTIC_MAX_D:
+        raise ValueError(f"the bound max_d of an elastic view must be an int in 0 .. {ELASTIC_MAX_D} (source pixels), not {max_d!r}")
+    return int(max_d)
+
+
+def elastic_check_field(field, n, size, cell, max_d):
+    """The (n, gh, gw, 2) int32 field of an elastic view of size = (oh, ow), in range, as a contiguous int32 array -- or ValueError: a
+    wrong shape (elastic_grid_shape) or a dtype that is not an integer one; a cell that is no power of two in 16 .. 256; max_d outside
+    0 .. 8; a control value beyond +-256 max_d, the call's bound (the message names the tile)."""
+    what = "the field of an elastic view must hold (dy, dx) per lattice node and tile, in 1/256 source pixel"
+    gh, gw = elastic_grid_shape(size, cell)
+    max_d = elastic_check_max_d(max_d)
+    if field is None:
+        raise ValueError(f"{what}: an (N, {gh}, {gw}, 2) int32 array (TileElastic.draw)")
+    try:
+        f = field.numpy() if hasattr(field, "numpy") and not isinstance(field, np.ndarray) else np.asarray(field)
+        if f.dtype.kind not in "iu":
+            raise TypeError
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(f"{what}: an (N, {gh}, {gw}, 2) integer array") from None
+    if f.shape != (int(n), gh, gw, 2):
+        raise ValueError(f"{what}: an ({int(n)}, {gh}, {gw}, 2) array (cell = {int(cell)}), not one of shape {f.shape}")
+    f = f.astype(np.int64)
+    bad = (np.abs(f) > ELASTIC_UNIT * max_d).reshape(int(n), -1).any(axis=1)
+    if bad.any():
+        t = int(np.argmax(bad))
+        raise ValueError(f"field: tile {t} of the elastic view has a control displacement of {int(np.abs(f[t]).max())} (1/256 pixel), above "
+                         f"the call's bound 256 max_d = {ELASTIC_UNIT * max_d}")
+    return np.ascontiguousarray(f.astype(np.int32))
+
+
+class TileElastic(TileAffine):
+    """Elastic deformation -- the U-Net recipe: random displacements on a coarse grid, interpolated smoothly -- on top of TileAffine's
+    rotation / zoom / shear / translation / flip, drawn on the host and applied INSIDE the view pass (engine.normalize_view_elastic): the
+    image bilinearly (elastic_resample is the definition), its label maps by the nearest element (apply, elastic_nearest), both through
+    the same (Y, X).  TileAffine's arguments and defaults, plus
+    magnitude: (lo, hi) source pixels, 0 <= lo <= hi <= 8 -- per tile the largest control displacement m is uniform in [lo, hi] and every
+    control value uniform in [-m, m]; cell: the lattice spacing in OUTPUT pixels, a power of two from 16 to 256.
+    The displacement of an output pixel is a quadratic B-spline of the lattice (C1-smooth; |d| <= m).  Its slope is at most 2 m / cell
+    source pixels per output pixel (adjacent control values differ by at most 2 m, and the spline's derivative is a convex combination
+    of adjacent differences over a cell), so the CONSTRUCTOR refuses magnitude[1] > cell / 4: below that the slope is at most 1/2 and
+    the map cannot fold at the identity.  This is a sufficient bound, not a necessary one; under a zoom that magnifies it is looser still.
+    max_d = ceil(magnitude[1]) is the displacement bound of a call whose field lives on the device; `bound` stays TileAffine's."""
+
+    def __init__(self, size=None, rotate=(-180, 180), zoom=(1, 1), shear=(0, 0), translate=(0, 0), flip=True, fill=255, magnitude=(0, 4),
+                 cell=32):
+        super().__init__(size, rotate, zoom, shear, translate, flip, fill)
+        self.cell_log2 = _cell_log2(cell)
+        self.cell = int(cell)
+        try:
+            lo, hi = (float(v) for v in magnitude)
+            if not (0.0 <= lo <= hi <= float(ELASTIC_MAX_D)):
+                raise ValueError
+        except (TypeError, ValueError):
+            raise ValueError(f"magnitude must be a pair (lo, hi) of source pixels with 0 <= lo <= hi <= {ELASTIC_MAX_D}, not "
+                             f"{magnitude!r}") from None
+        if hi > self.cell / 4.0:
+            raise ValueError(f"TileElastic(magnitude={magnitude!r}, cell={cell}) could fold the tile: the spline's slope is at most "
+                             f"2 magnitude / cell source pixels per output pixel, and magnitude[1] <= cell / 4 = {self.cell / 4.0:g} keeps it "
+                             "at most 1/2 -- lower magnitude[1] or raise cell")
+        self.magnitude = (lo, hi)
+
+    @property
+    def max_d(self):
+        """max_d: an upper bound (source pixels, an int 0 .. 8) of every control displacement this view can draw -- what a call with the
+        field on the device sizes its launch from"""
+        return int(np.ceil(self.magnitude[1]))
+
+    def draw(self, n, h, w):
+        """ElasticWindows(affine, field) from the GLOBAL numpy stream, in this order: TileAffine.draw(n, h, w), unchanged -- six draws
+        per tile --; m = np.random.uniform(lo, hi, n); z = np.random.uniform(-1, 1, (n, gh, gw, 2)), (gh, gw) = elastic_grid_shape(
+        out_size(h, w), cell).  field = np.rint(256 m z) as int32: |field| <= 256 m <= 256 max_d.  Uniform draws are bounded: nothing is
+        clipped or redrawn."""
+        affine = super().draw(n, h, w)
+        gh, gw = elastic_grid_shape(self.out_size(h, w), self.cell)
+        m = np.random.uniform(self.magnitude[0], self.magnitude[1], int(n))
+        z = np.random.uniform(-1.0, 1.0, (int(n), gh, gw, 2))
+        return ElasticWindows(affine, np.rint(ELASTIC_UNIT * m[:, None, None, None] * z).astype(np.int32))
+
+    def apply(self, planes, windows=None, fill=0, out=None):
+        """TileAffine.apply through an elastic view (sl_view_planes_elastic): `windows` is the ElasticWindows the image call with this
+        view returned for (H, W) tiles (or self.draw(N, H, W)); per element the NEAREST source element at the image's own (Y, X)
+        (elastic_nearest), a bit copy, outside the plane `fill`.  Nothing is drawn here.  Host windows are range-checked (ValueError);
+        device windows are taken as they are under this view's bound and max_d."""
+        from . import engine
+        if windows is None:
+            raise ValueError("windows is required: pass the ElasticWindows the image call with this view returned, or view.draw(N, H, W) "
+                             "-- apply draws nothing itself")
+        affine, field = engine._elastic_parts(windows)
+        max_r, max_d = engine._elastic_bound(self, windows)
+        return engine.view_planes_elastic(planes, affine, field, self.size, self.cell, max_r, max_d, fill=fill, out=out)
+
+    def __repr__(self):
+        return (f"TileElastic(size={self.size}, rotate={self.rotate}, zoom={self.zoom}, shear={self.shear}, translate={self.translate}, "
+                f"flip={self.flip}, fill={self.fill}, magnitude={self.magnitude}, cell={self.cell})")
