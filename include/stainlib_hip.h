@@ -929,6 +929,34 @@ SL_API int sl_normalize_hsb_view(const uint8_t* rgb, void* out, int n, int h, in
  * out == rgb is not supported.  Capture-safe like sl_normalize_view. */
 SL_API int sl_normalize_blur_view(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, int shrink, int max_r, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, const double* alpha_beta, int augment_background, const SlParams* params, const SlTensorFormat* fmt, const int32_t* codes, void* stream);
 
+/* ---- the post stage: a tone curve and additive noise on the bytes a call WRITES (stainlib_amd/csrc/post.hip; an extension: brightness /
+ * contrast / gamma and the Gaussian-noise item of the Tellez et al. / HoVer-Net augmentation set).  Defined in INTEGERS on bytes, so every
+ * route below computes the same bits.  The stage acts on a uint8 image n x oh x ow x 3 -- the OUTPUT: behind the view, the box shrink or the
+ * area resample, in front of the tensor conversion.  Per tile, pixel p = i ow + j, channel c, byte b:
+ *     tone   b1 = tables[256 t + b]: 256 bytes per tile, the same for the three channels; any 256 bytes are a table, 0 .. 255 the identity
+ *     noise  codes[4 t ..] = (sq, k0, k1, mono), int32; k0, k1 the bit patterns of two uint32.  W = Philox4x32-10 of the counter
+ *            (p, 0, 0, 0) under the key (k0, k1) (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85; ten rounds, the
+ *            key bumped between rounds).  Channel c takes W[c], or W[3] for all three when mono != 0.  G = (the sum of the word's four
+ *            bytes) - 510 (mean 0, variance 21845: a four-fold Irwin-Hall sum, tails cut at 3.45 sigma).  n = (G sq + 32768) >> 16
+ *            (arithmetic), b2 = clamp(b1 + n, 0, 255).  sq = floor(sigma 65536 / sqrt(21845) + 1/2) for a sigma of 0 .. 64 bytes, so
+ *            0 <= sq <= 28378; values outside are clamped by the kernel; sq == 0 is the identity.
+ * tables, codes: device pointers; each may be NULL (that half is absent), not both; codes 4-byte aligned.  A tile's noise depends on its
+ * key and on p, never on its position in the batch.  (stainlib_amd/augmentation/noise.py holds the same in numpy; csrc/post_math.hpp in
+ * 32 bits.)
+ *
+ * sl_post_augment: out = post(rgb) per tile, the full tile (oh x ow = h x w), one sweep, 3 B/px read.  fmt == NULL: out is the n x h x w x 3
+ * uint8 image; else the tensor SlTensorFormat describes, bit for bit sl_to_tensor of that image, written directly.  SL_ERR_BADARG: what
+ * sl_to_tensor refuses of rgb, out, n, h, w and a non-NULL fmt; tables and codes both NULL; misaligned codes.  out == rgb is not supported.
+ *
+ * sl_normalize_post_view: post(view of full[t]) in ONE pass, full[t] the image the statistics pattern names as in sl_normalize_view (the
+ * tiles' own bytes, sl_normalize_apply's image, the jitter of tissue pixels or of all pixels); p counts in the view's OUTPUT.  max_wh == 0
+ * (then max_ww == 0): the fixed-size view of sl_normalize_view_shrink -- windows n x 3, shrink 1, 2 or 4, the stage behind the box mean.
+ * Otherwise the resizing view of sl_normalize_view_resize -- windows n x 5, shrink == 1, the stage behind the area resample.  A tile whose
+ * fit failed: post(the view of its own bytes).  SL_ERR_BADARG before anything is launched: what those two calls refuse; max_wh == 0 with
+ * max_ww != 0; a resizing view with shrink != 1; tables and codes both NULL; misaligned codes.  Capture-safe like them. */
+SL_API int sl_post_augment(const uint8_t* rgb, void* out, int n, int h, int w, const uint8_t* tables, const int32_t* codes, const SlTensorFormat* fmt, void* stream);
+SL_API int sl_normalize_post_view(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, int shrink, int max_wh, int max_ww, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, const double* alpha_beta, int augment_background, const SlParams* params, const SlTensorFormat* fmt, const uint8_t* tables, const int32_t* codes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,8 @@ TileElastic (an extension) adds an elastic deformation to it -- a quadratic B-sp
 integers, for images and label planes alike; its windows are an ElasticWindows(affine, field).
 HsbColorAugmenter (an extension; HsbLight / HsbStrong presets) is the hue / saturation / brightness sibling of the HED augmenters, in integers.
 GaussianBlurAugmenter (an extension) is the Gaussian blur of that set: a per-tile integer separable filter, fused into the view pass (blur=).
+GaussianNoiseAugmenter and ToneCurveAugmenter (extensions) are its noise and brightness / contrast / gamma items: integer maps on the
+WRITTEN pixels of the view pass (noise=, tone=); the per-pixel noise is a counter-based generator (Philox4x32-10) on the device.
 Separated (an extension) is what the normalizers' separate / separate_batch return: per-stain images and concentration maps.
 Importing the package does not need a GPU; calling anything numeric does, and fails loudly without the
 HIP library -- there is no CPU fallback.
@@ -19,6 +21,7 @@ from .augmentation.augmenter import (HedLightColorAugmenter, HedLighterColorAugm
                                      HedStrongColorAugmenter, StainAugmentor, GrayscaleAugmentor, StainJitter)
 from .augmentation.hsb import HsbColorAugmenter, HsbLightColorAugmenter, HsbStrongColorAugmenter  # noqa: F401
 from .augmentation.blur import GaussianBlurAugmenter  # noqa: F401
+from .augmentation.noise import GaussianNoiseAugmenter, ToneCurveAugmenter  # noqa: F401
 from .extraction.macenko_stain_extractor import MacenkoStainExtractor  # noqa: F401
 from .extraction.vahadane_stain_extractor import VahadaneStainExtractor  # noqa: F401
 from .normalization.normalizer import (ExtractiveStainNormalizer, MacenkoNormalizer,  # noqa: F401

@@ -226,6 +226,11 @@ _SIGNATURES["sl_normalize_hsb_view"] = (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_
 # params, fmt>, codes, stream
 _SIGNATURES["sl_normalize_blur_view"] = (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P,
                                                    _P, _P, C.c_int, C.POINTER(SlParams), C.POINTER(SlTensorFormat), _P, _P])
+# the post stage (tables: n x 256 bytes, codes: n x 4 int32, on the device; each may be null, not both): rgb, out, n, h, w, tables, codes, fmt,
+# stream -- and the view pass with the stage on its write side: sl_normalize_hsb_view's arguments with tables, codes in place of its codes
+_SIGNATURES["sl_post_augment"] = (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.POINTER(SlTensorFormat), _P])
+_SIGNATURES["sl_normalize_post_view"] = (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P,
+                                                   _P, _P, _P, C.c_int, C.POINTER(SlParams), C.POINTER(SlTensorFormat), _P, _P, _P])
 PLANES_NEAREST, PLANES_AREA = range(2)
 POOL_STATE_DOUBLES, POOL_M, POOL_MAXC, POOL_STATUS, POOL_MISS = 64, 0, 6, 8, 9
 POOL2_STATE_DOUBLES, POOL2_HIST_WORDS, POOL2_WHY = 256, 2 * 8192 + 8 * 32, 33

@@ -249,7 +249,7 @@ class StainAugmentor(object):
         return out[0].cpu().numpy()
 
     def augment_batch(self, tiles, alpha_beta=None, tensor_format=None, view=None, windows=None, hed=None, hed_sigmas=None, hed_biases=None,
-                      hsb=None, hsb_sigmas=None, blur=None, blur_sigmas=None):
+                      hsb=None, hsb_sigmas=None, blur=None, blur_sigmas=None, noise=None, tone=None, noise_sigmas=None, tone_params=None):
         """Batched extension: (N,H,W,3) uint8 device tensor -> (out, M, maxC, status) device tensors: every tile perturbed under its OWN
         stain matrix (this augmentor's extractor, fitted per tile) -- n fit() / pop() pairs in one fit and ONE pass, nothing through the
         host.  alpha_beta: (N, 4) = alpha0, beta0, alpha1, beta1 per tile; by default drawn from the global numpy stream exactly as N
@@ -271,6 +271,12 @@ class StainAugmentor(object):
         (engine.normalize_blur_view): bit for bit ``blur.transform_batch`` of the result above, then the view.  ``blur_sigmas``: (N,); by
         default ``blur.randomize_batch(N)``, drawn after alpha_beta and BEFORE the windows.  One more element at the end,
         ``engine.BlurDraw(sigmas, codes)``.  Not together with ``hed``, ``hsb``, a ``TileView(scale=)`` or a TileAffine.
+        ``noise``, ``tone``: a ``GaussianNoiseAugmenter`` / a ``ToneCurveAugmenter`` -- the post stage in the SAME pass
+        (engine.normalize_post_view): the tone curve, then the additive noise, per WRITTEN pixel, behind the view and in front of the
+        conversion: bit for bit ``augmentation.noise.post_reference`` of the uint8 image the call writes without them.  ``tone_params``:
+        (N, 3), ``noise_sigmas``: (N,) -- or the tables / codes a call returned; by default ``tone.randomize_batch(N)``, then
+        ``noise.randomize_batch(N)``, drawn after alpha_beta and BEFORE the windows.  One more element at the end, ``engine.PostDraw``.
+        Not together with ``hed``, ``hsb``, ``blur``, a TileAffine or a TileElastic.
         fit() / pop() are untouched by it."""
         from .. import engine
         jitter = StainJitter(self.sigma1, self.sigma2, self.augment_background)
@@ -280,13 +286,15 @@ class StainAugmentor(object):
         with_hed = engine._hed_call(hed, hed_sigmas, hed_biases, tiles, view)
         with_hsb = engine._hsb_call(hsb, hsb_sigmas, tiles, view, hed)
         with_blur = engine._blur_call(blur, blur_sigmas, tiles, view, hed, hsb)
+        with_post = engine._post_call(noise, tone, noise_sigmas, tone_params, tiles, view, hed, hsb, blur)
         n, h, w = engine._check_tiles(tiles)
         fit = (engine.macenko_fit if self._method == "macenko" else engine.vahadane_fit)(tiles)[:3]
         if alpha_beta is None:
             alpha_beta = jitter.draw(n)
         route = dict(M_tgt=None, maxC_tgt=None, alpha_beta=alpha_beta, augment_background=self.augment_background)
         return engine.route_stage(tiles, fit, route, tensor_format, None, view, windows, (hed, hed_sigmas, hed_biases) if with_hed else None,
-                                  (hsb, hsb_sigmas) if with_hsb else None, (blur, blur_sigmas) if with_blur else None)
+                                  (hsb, hsb_sigmas) if with_hsb else None, (blur, blur_sigmas) if with_blur else None,
+                                  (noise, tone, noise_sigmas, tone_params) if with_post else None)
 
 
 class StainJitter(object):

@@ -212,14 +212,23 @@ __device__ __forceinline__ uint32_t view_box(const uint32_t* s_px, int at) {
     return ((rb >> SH) & 0x00ff00ffu) | ((gg >> SH) << 8);
 }
 
+// A stage on the WRITE side, between the four packed pixels of an output row and their packing into a Chunk: the post stage of
+// sl_normalize_post_view (post_kernels.hpp: PostStage), which acts on OUTPUT pixels and needs their index in the tile's output.  The
+// default is empty -- kOn = false: the hook's statement is discarded and every other kernel's code is what it was (tools/isa_diff.py).
+// apply(px, g, il, jl, ow): the lane holds the outputs (il, jl .. jl + 3) of patch g, some of which may not exist.
+struct ViewNoPost {
+    static constexpr bool kOn = false;
+    __device__ __forceinline__ void apply(uint32_t (&)[4], const ViewPatch&, int, int, int) const {}
+};
+
 // ---- write side: output rows, 4 adjacent pixels per lane (behind a barrier after the stage).  S: the shrink, a compile-time value HERE
 // ---- only (view_write below picks it by the block-uniform run-time one); S = 1 is the write side as it was, statement for statement.
 // Lanes: 16 / S per output row (the patch is 64 / S pixels wide), so 16 S rows per pass -- 4 passes at S = 1, ONE at S = 2 (32 rows, every
 // lane busy) and at S = 4 (16 rows: the first wave only; accepted, the pass is bound by the arithmetic in front of the stage).
 // From `Chunk o` on this is view_store_px4's text written out, its TWIN (the S = 1 float16 view was 1 - 2 % slower on it).
-template <int DT, int LAYOUT, int S>
+template <int DT, int LAYOUT, int S, class Post = ViewNoPost>
 __device__ __forceinline__ void view_write_s(const ViewPatch& g, const uint32_t* s_px, void* out, int tile, int oh, int ow, TensorK fmt,
-                                             int lr16, int lc16) {
+                                             int lr16, int lc16, const Post& post = Post()) {
     constexpr bool TENSOR = DT != kDtU8;
     constexpr int SDT = TENSOR ? DT : kDtF32;
     constexpr int LPR = 16 / S, NPASS = S == 1 ? 4 : 1;      // lanes per output row, passes
@@ -242,6 +251,7 @@ __device__ __forceinline__ void view_write_s(const ViewPatch& g, const uint32_t*
 #pragma unroll
             for (int p = 0; p < 4; ++p) px[p] = view_box<S>(s_px, row + min(jl + p, bw - 1) * aj);
         }
+        if constexpr (Post::kOn) post.apply(px, g, il, jl, ow);
         Chunk o;
         o.w0 = px[0] | (px[1] << 24);
         o.w1 = (px[1] >> 8) | (px[2] << 16);
@@ -268,12 +278,12 @@ __device__ __forceinline__ void view_write_s(const ViewPatch& g, const uint32_t*
 }
 
 // the write side of a patch under the run-time shrink s (block-uniform: one scalar branch)
-template <int DT, int LAYOUT>
+template <int DT, int LAYOUT, class Post = ViewNoPost>
 __device__ __forceinline__ void view_write(const ViewPatch& g, const uint32_t* s_px, void* out, int tile, int oh, int ow, TensorK fmt,
-                                           int lr, int lc, int s) {
-    if (s == 1) view_write_s<DT, LAYOUT, 1>(g, s_px, out, tile, oh, ow, fmt, lr, lc);
-    else if (s == 2) view_write_s<DT, LAYOUT, 2>(g, s_px, out, tile, oh, ow, fmt, lr, lc);
-    else view_write_s<DT, LAYOUT, 4>(g, s_px, out, tile, oh, ow, fmt, lr, lc);
+                                           int lr, int lc, int s, const Post& post = Post()) {
+    if (s == 1) view_write_s<DT, LAYOUT, 1>(g, s_px, out, tile, oh, ow, fmt, lr, lc, post);
+    else if (s == 2) view_write_s<DT, LAYOUT, 2>(g, s_px, out, tile, oh, ow, fmt, lr, lc, post);
+    else view_write_s<DT, LAYOUT, 4>(g, s_px, out, tile, oh, ow, fmt, lr, lc, post);
 }
 
 // A further stage between the truncation to bytes and the LDS write, on the four packed pixels `stage` holds.  HED = 0: none -- the
@@ -378,12 +388,14 @@ __device__ __forceinline__ void view_route(const float2* s_tab, Stage&& stage, i
 // DT: kDtU8 or a tensor type; LAYOUT: tensor only; MODE: kView*; HED: the stage above.  npx: patches per output row, npatch: per tile.
 // From `unpack` to the last barrier this is view_route's text written out, its TWIN: a change to one is a change to the other.  Calling
 // view_route here costs the tissue-only k_hed_view an occupancy step (79 -> 81 VGPRs, 6 -> 5).
-template <int DT, int LAYOUT, int MODE, int HED>
+// Post: the write-side stage (ViewNoPost: none); a PostStage has filled its table before the call, behind the barrier below.
+template <int DT, int LAYOUT, int MODE, int HED, class Post = ViewNoPost>
 __device__ __forceinline__ void view_body(const uint8_t* rgb, void* out, int h, int w, int oh, int ow,
                                           int npx, int npatch, const int32_t* windows, int d_mask, int shrink,
                                           const double* M_src, const double* maxC_src,
                                           const double* M_tgt, const double* maxC_tgt, const double* alpha_beta,
-                                          double lam, float ylimf, TensorK fmt, const typename StageArgs<HED>::type* hv) {
+                                          double lam, float ylimf, TensorK fmt, const typename StageArgs<HED>::type* hv,
+                                          const Post& post = Post()) {
     constexpr int B = kViewB, PITCH = kViewPitch;
     static_assert(kWG == 256 && B == 64, "16 lanes x 4 pixels per row, 16 rows per pass, 4 passes");
     __shared__ float2 s_tab[256];
@@ -481,7 +493,7 @@ __device__ __forceinline__ void view_body(const uint8_t* rgb, void* out, int h, 
     }
     __syncthreads();
 
-    view_write<DT, LAYOUT>(g, s_px, out, tile, oh, ow, fmt, lr, lc, s);
+    view_write<DT, LAYOUT>(g, s_px, out, tile, oh, ow, fmt, lr, lc, s, post);
 }
 
 template <int DT, int LAYOUT, int MODE>

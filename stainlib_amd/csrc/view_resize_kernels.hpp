@@ -68,9 +68,10 @@ __device__ __forceinline__ uint32_t resize_round(uint32_t S, uint32_t D, float r
 // ---- write side: output rows, 4 adjacent pixels per lane (behind a barrier after the stage and resize_taps).  Lanes per output row: the
 // ---- power of two that covers the patch's width, 1 .. 16 (block-uniform), so that a narrow patch spreads its rows over all the lanes
 // ---- (patch_lanes' assignment, view_geometry.hpp; from `Chunk o` on: view_store_px4's text.  TWINS, see the head of this file).
-template <int DT, int LAYOUT>
+template <int DT, int LAYOUT, class Post = ViewNoPost>
 __device__ __forceinline__ void resize_write(const ViewPatch& g, const ResizeAxis& ai, const ResizeAxis& aj, const uint32_t* s_px,
-                                             const uint32_t* s_tap, void* out, int tile, int oh, int ow, TensorK fmt, int tid) {
+                                             const uint32_t* s_tap, void* out, int tile, int oh, int ow, TensorK fmt, int tid,
+                                             const Post& post = Post()) {
     constexpr bool TENSOR = DT != kDtU8;
     constexpr int SDT = TENSOR ? DT : kDtF32;
     typedef typename Elem<SDT>::type T;
@@ -112,6 +113,7 @@ __device__ __forceinline__ void resize_write(const ViewPatch& g, const ResizeAxi
             }
             px[p] = resize_round(S0, D, rden) | (resize_round(S1, D, rden) << 8) | (resize_round(S2, D, rden) << 16);
         }
+        if constexpr (Post::kOn) post.apply(px, g, il, jl, ow);
         Chunk o;
         o.w0 = px[0] | (px[1] << 24);
         o.w1 = (px[1] >> 8) | (px[2] << 16);
@@ -137,12 +139,13 @@ __device__ __forceinline__ void resize_write(const ViewPatch& g, const ResizeAxi
 
 // view_body with the geometry and the write side above; the arithmetic between view_read and the barrier is view_route
 // (view_kernels.hpp).  npatch: the host's upper bound of the patches of a tile.
-template <int DT, int LAYOUT, int MODE, int HED>
+template <int DT, int LAYOUT, int MODE, int HED, class Post = ViewNoPost>
 __device__ __forceinline__ void view_resize_body(const uint8_t* rgb, void* out, int h, int w, int oh, int ow, int npatch,
                                                  const int32_t* windows, int d_mask, int max_wh, int max_ww,
                                                  const double* M_src, const double* maxC_src,
                                                  const double* M_tgt, const double* maxC_tgt, const double* alpha_beta,
-                                                 double lam, float ylimf, TensorK fmt, const typename StageArgs<HED>::type* hv) {
+                                                 double lam, float ylimf, TensorK fmt, const typename StageArgs<HED>::type* hv,
+                                                 const Post& post = Post()) {
     constexpr int B = kViewB, PITCH = kViewPitch;
     static_assert(kWG == 256 && B == 64, "16 lanes x 4 pixels per row, 16 rows per pass, 4 passes");
     __shared__ float2 s_tab[256];
@@ -175,7 +178,7 @@ __device__ __forceinline__ void view_resize_body(const uint8_t* rgb, void* out, 
     view_route<MODE, HED>(s_tab, stage, npatch, P, rgb, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, lam, ylimf);
     __syncthreads();
 
-    resize_write<DT, LAYOUT>(g, ai, aj, s_px, s_tap, out, tile, oh, ow, fmt, tid);
+    resize_write<DT, LAYOUT>(g, ai, aj, s_px, s_tap, out, tile, oh, ow, fmt, tid, post);
 }
 
 template <int DT, int LAYOUT, int MODE>

@@ -1434,6 +1434,225 @@ def blur_stage(tiles, blur, blur_sigmas, view, windows, route, fmt=None, out=Non
     return x, windows, BlurDraw(sigmas, codes)
 
 
+# ---- the post stage: tone curve and additive noise on the bytes a call writes (sl_post_augment, sl_normalize_post_view; see
+# ---- include/stainlib_hip.h, augmentation/noise.py) ---------------------------------------------------------------------------------------
+
+PostDraw = collections.namedtuple("PostDraw", ["tone_params", "tone_tables", "noise_sigmas", "noise_codes"])
+PostDraw.__doc__ = """What the tone= / noise= stage of a batch method did: the (N, 3) float64 (brightness, contrast, gamma) it used (given
+or drawn; None when the call was given tables) and the (N, 256) uint8 tables they gave; the (N,) float64 noise sigmas (None when the call
+was given codes) and the (N, 4) int32 codes (sq, k0, k1, mono), all numpy.  The fields of an absent augmenter are None.  The tables and
+the codes reproduce the call: pass them back as tone_params= / noise_sigmas=."""
+
+
+def _post_host(x):
+    """a host array of an argument, or None for a device tensor (taken as it is, never read back)"""
+    import numpy as np
+    if isinstance(x, torch.Tensor):
+        return None if x.is_cuda else x.numpy()
+    return np.asarray(x)
+
+
+def _post_tables_rows(tables):
+    """The rows of an (N, 256) tables argument (no device needed): uint8, on the device (contiguous) or the host.  Any bytes are a table."""
+    what = "tables must hold one tone curve per tile: an (N, 256) uint8 array (augmentation.noise.tone_table)"
+    try:
+        arr = _post_host(tables)
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(what) from None
+    if arr is None:
+        if tables.dtype != torch.uint8 or tables.dim() != 2 or tables.shape[1] != 256 or not tables.is_contiguous():
+            raise ValueError(what + ", contiguous")
+        return int(tables.shape[0])
+    if arr.dtype.name != "uint8" or arr.ndim != 2 or arr.shape[1] != 256:
+        raise ValueError(f"{what}, not {arr.dtype} of shape {arr.shape}")
+    return int(arr.shape[0])
+
+
+def _post_codes_rows(codes):
+    """The rows of an (N, 4) codes argument (no device needed): a device int32 tensor (taken as it is: the kernel clamps sq), or host
+    integers that fit int32 and whose sq lies in [0, SQ_MAX] (ValueError)."""
+    from .augmentation.noise import SQ_MAX
+    what = "codes must hold (sq, k0, k1, mono) per tile: an (N, 4) int32 array (augmentation.noise.noise_codes)"
+    try:
+        arr = _post_host(codes)
+        if arr is not None and arr.dtype.kind not in "iu":
+            raise TypeError
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(what) from None
+    if arr is None:
+        if codes.dtype != torch.int32 or codes.dim() != 2 or codes.shape[1] != 4 or not codes.is_contiguous():
+            raise ValueError(what + ", contiguous")
+        return int(codes.shape[0])
+    if arr.ndim != 2 or arr.shape[1] != 4:
+        raise ValueError(f"{what}, not one of shape {arr.shape}")
+    if arr.size and (arr.min() < -2 ** 31 or arr.max() >= 2 ** 31):
+        raise ValueError("codes must fit int32 (the key words as their bit patterns)")
+    if arr.size and (arr[:, 0].min() < 0 or arr[:, 0].max() > SQ_MAX):
+        raise ValueError(f"codes: sq must lie in [0, {SQ_MAX}] (a sigma of 0 .. 64 bytes)")
+    return int(arr.shape[0])
+
+
+def _post_check(tables, codes, n=None):
+    if tables is None and codes is None:
+        raise ValueError("the post stage needs tables= (a tone curve per tile) or codes= (the noise codes per tile), or both")
+    for x, rows, name in ((tables, _post_tables_rows, "tables"), (codes, _post_codes_rows, "codes")):
+        if x is not None and rows(x) != n and n is not None:
+            raise ValueError(f"{name} must have one row per tile ({n})")
+
+
+def _post_device(x, dtype, device):
+    import numpy as np
+    if x is None:
+        return None
+    if isinstance(x, torch.Tensor) and x.is_cuda:
+        if x.device != device:
+            raise ValueError(f"tables and codes must be on {device}")
+        return x
+    return torch.from_numpy(np.ascontiguousarray(_post_host(x).astype(dtype))).to(device)
+
+
+def post_augment(u8, tables=None, codes=None, fmt=None, out=None):
+    """The post stage on every full tile in one sweep (sl_post_augment): tables (N, 256) uint8 and / or codes (N, 4) int32 = (sq, k0, k1,
+    mono) per tile (augmentation.noise: tone_table, noise_codes; host arrays are checked, a device tensor is taken as it is and sq is
+    clamped by the kernel) -> (N,H,W,3) uint8, bit for bit augmentation.noise.post_reference; or with fmt (a stainlib_amd.TensorFormat)
+    the (N,3,H,W) tensor, bit for bit fmt.convert of that image, written directly."""
+    import numpy as np
+    from .tensor_format import TensorFormat
+    if fmt is not None and not isinstance(fmt, TensorFormat):
+        raise ValueError("fmt must be a stainlib_amd.TensorFormat or None (the uint8 image)")
+    _post_check(tables, codes)
+    n, h, w = _check_tiles(u8)
+    _post_check(tables, codes, n)
+    t, c = _post_device(tables, np.uint8, u8.device), _post_device(codes, np.int32, u8.device)
+    f, out = _image_out(out, u8, n, h, w, fmt, "post stage")
+    _call("sl_post_augment", _ptr(u8), _ptr(out), n, h, w, _ptr(t), _ptr(c), _byref(f))
+    return out
+
+
+def normalize_post_view(rgb, windows, size, d_mask, tables=None, codes=None, M_src=None, maxC_src=None, M_tgt=None, maxC_tgt=None,
+                        alpha_beta=None, augment_background=False, params=None, shrink=1, resize=None, fmt=None, out=None):
+    """post(normalize_view of `full`) in ONE pass (sl_normalize_post_view): `full` is normalize_view's (the route arguments are the same),
+    post(.) is post_augment with the tile's table and codes on the view's OUTPUT -- bit for bit normalize_view to uint8, then
+    post_augment of the result, then the conversion.  shrink, resize: normalize_view's; the stage acts behind them, per written pixel.  A
+    tile whose fit failed: post(the view of its own bytes)."""
+    import numpy as np
+    _post_check(tables, codes)
+    n, h, w, oh, ow, win, M_src, maxC_src, M_tgt, maxC_tgt, ab, f, out = _view_prepare(
+        rgb, windows, size, d_mask, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, params, fmt, out,
+        before_device=lambda n: _post_check(tables, codes, n), shrink=shrink, resize=resize)
+    t, c = _post_device(tables, np.uint8, rgb.device), _post_device(codes, np.int32, rgb.device)
+    mh, mw = (int(resize[0]), int(resize[1])) if resize is not None else (0, 0)
+    _call("sl_normalize_post_view", _ptr(rgb), _ptr(out), n, h, w, oh, ow, _ptr(win), int(d_mask), int(shrink), mh, mw, _ptr(M_src),
+          _ptr(maxC_src), _ptr(M_tgt), _ptr(maxC_tgt), _ptr(ab), 1 if augment_background else 0, _byref(params), _byref(f), _ptr(t), _ptr(c))
+    return out
+
+
+_POST_CHAIN = "take the uint8 result (or view) first, then noise.transform_batch(u8, tensor_format=) / tone.transform_batch(u8, tensor_format=)"
+
+
+def _noise_arg(noise, noise_sigmas, n=None):
+    """noise_sigmas= of a batch method (no device needed) -> (sigmas or None, codes): (N,) float sigmas under the augmenter's current key
+    -- or, to reproduce a call, the (N, 4) integer codes it returned (PostDraw.noise_codes; a device tensor is taken as it is).  ValueError."""
+    import numpy as np
+    what = "noise_sigmas must hold one noise sigma per tile: an (N,) array (or the (N, 4) codes a call returned)"
+    try:
+        arr = _post_host(noise_sigmas)
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(what) from None
+    if arr is None or (arr.ndim == 2 and arr.dtype.kind in "iu"):
+        rows, sigmas = _post_codes_rows(noise_sigmas), None
+        codes = noise_sigmas if arr is None else np.ascontiguousarray(arr.astype(np.int32))
+    else:
+        if arr.ndim != 1:
+            raise ValueError(what)
+        codes = noise.codes(arr, None)
+        rows, sigmas = codes.shape[0], np.array(arr, dtype=np.float64)
+    if n is not None and rows != n:
+        raise ValueError(f"noise_sigmas must have one entry per tile ({n})")
+    return sigmas, codes
+
+
+def _tone_arg(tone_params, n=None):
+    """tone_params= of a batch method (no device needed) -> (params or None, tables): (N, 3) float (brightness, contrast, gamma) -- or,
+    to reproduce a call, the (N, 256) uint8 tables it returned (PostDraw.tone_tables; a device tensor is taken as it is).  ValueError."""
+    import numpy as np
+    from .augmentation.noise import tone_tables
+    what = "tone_params must hold (brightness, contrast, gamma) per tile: an (N, 3) array (or the (N, 256) uint8 tables a call returned)"
+    try:
+        arr = _post_host(tone_params)
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(what) from None
+    if arr is None or (arr.ndim == 2 and arr.shape[1] == 256):
+        rows, params, tables = _post_tables_rows(tone_params), None, tone_params if arr is None else np.ascontiguousarray(arr)
+    else:
+        if arr.ndim != 2 or arr.shape[1] != 3:
+            raise ValueError(what)
+        tables = tone_tables(arr)
+        rows, params = tables.shape[0], np.array(arr, dtype=np.float64)
+    if n is not None and rows != n:
+        raise ValueError(f"tone_params must have one row per tile ({n})")
+    return params, tables
+
+
+def _post_call(noise, tone, noise_sigmas, tone_params, tiles, view=None, hed=None, hsb=None, blur=None):
+    """The noise= / tone= / noise_sigmas= / tone_params= arguments of a batch method, checked without a device and before any draw
+    (ValueError).  True when the call has a post stage.  view, hed, hsb, blur: the call's other stages -- an affine or elastic view and
+    a stage on source pixels do not go with it."""
+    from .augmentation.noise import GaussianNoiseAugmenter, ToneCurveAugmenter
+    if noise is None and noise_sigmas is not None:
+        raise ValueError("noise_sigmas= goes with noise= (a GaussianNoiseAugmenter)")
+    if tone is None and tone_params is not None:
+        raise ValueError("tone_params= goes with tone= (a ToneCurveAugmenter)")
+    if noise is None and tone is None:
+        return False
+    if hed is not None or hsb is not None or blur is not None:
+        raise ValueError("noise= / tone= do not go together with hed=, hsb= or blur=: those act on source pixels, the post stage on the "
+                         "written ones, and a pass has one augmentation stage.  Chain them instead: " + _POST_CHAIN)
+    if _is_affine(view) or _is_elastic(view):
+        raise ValueError(f"an affine or elastic view ({view!r}) is not supported by the post stage (noise=, tone=): its write side is "
+                         "bilinear.  Chain them instead: " + _POST_CHAIN)
+    if noise is not None and not isinstance(noise, GaussianNoiseAugmenter):
+        raise ValueError("noise must be a stainlib_amd GaussianNoiseAugmenter (its range and channel mode are used)")
+    if tone is not None and not isinstance(tone, ToneCurveAugmenter):
+        raise ValueError("tone must be a stainlib_amd ToneCurveAugmenter (its ranges are used)")
+    if not (isinstance(tiles, torch.Tensor) and tiles.dim() == 4 and tiles.shape[-1] == 3):
+        raise ValueError("expected a contiguous CUDA uint8 tensor of shape (N, H, W, 3)")
+    n = int(tiles.shape[0])
+    if tone_params is not None:
+        _tone_arg(tone_params, n)
+    if noise_sigmas is not None:
+        _noise_arg(noise, noise_sigmas, n)
+    return True
+
+
+def _no_post(noise, tone, noise_sigmas, tone_params, what):
+    """ValueError for noise= / tone= in a call that has no post stage"""
+    if noise is not None or tone is not None or noise_sigmas is not None or tone_params is not None:
+        raise ValueError(f"noise= / tone= are not supported by {what}: " + _POST_CHAIN)
+
+
+def post_stage(tiles, noise, tone, noise_sigmas, tone_params, view, windows, route, fmt=None, out=None):
+    """The noise= / tone= stage of the batch methods, behind their fit and their own draws, on arguments _post_call /
+    _view_call(draw=False) have accepted: the draws the caller left open -- tone.randomize_batch(N), THEN noise.randomize_batch(N), THEN
+    view.draw -- and ONE fused pass (normalize_post_view).  route: normalize_view's keyword arguments that name `full` ({}: the tiles
+    themselves).  Without a view the result is the full tile, code 0.  -> (out, windows or None, PostDraw)."""
+    import numpy as np
+    n = int(tiles.shape[0])
+    params = tables = sigmas = codes = None
+    if tone is not None:
+        params, tables = tone.randomize_batch(n) if tone_params is None else _tone_arg(tone_params, n)
+    if noise is not None:
+        sigmas, codes = noise.randomize_batch(n) if noise_sigmas is None else _noise_arg(noise, noise_sigmas, n)
+    if view is not None:
+        size, d_mask, windows, shrink = _view_call(view, windows, tiles)
+        win = windows
+    else:
+        size, d_mask, windows, win, shrink = None, 0, None, np.zeros((n, 3), dtype=np.int32), 1
+    x = normalize_post_view(tiles, win, size, d_mask, tables, codes, fmt=fmt, out=out, shrink=shrink,
+                            resize=_view_resize(view, win, tiles), **route)
+    return x, windows, PostDraw(params, tables, sigmas, codes)
+
+
 def _view_call(view, windows, tiles, draw=True):
     """(size, d_mask, windows, shrink) of the view= / windows= pair of a batch method, checked without a device (ValueError): the windows
     as given, or drawn (TileView.draw; draw=False: left None for a later call)."""
@@ -1494,16 +1713,20 @@ def _view_resize_hw(view, windows, h, w):
     return max(1, min(h, int(win[:, 3].max()))), max(1, min(w, int(win[:, 4].max())))
 
 
-def route_stage(tiles, fit, route, fmt=None, out=None, view=None, windows=None, hed=None, hsb=None, blur=None):
+def route_stage(tiles, fit, route, fmt=None, out=None, view=None, windows=None, hed=None, hsb=None, blur=None, post=None):
     """The tail of the batch methods, behind their fit and their own draws, on arguments _jitter_args / _view_call(draw=False) / _hed_call
     have accepted: ONE pass over the tiles and the tuple the method returns, (out, M_src, maxC_src, status[, windows][, HedDraw]).
     fit: the fit's (M_src, maxC_src, status); route: the other arguments that name `full` (M_tgt, maxC_tgt and, for a jitter, alpha_beta
     and augment_background).  hed = (HedColorAugmenter, hed_sigmas, hed_biases): hed_stage; else with a view: normalize_view, the
     windows drawn here if not given; else normalize_jitter.  hsb = (HsbColorAugmenter, hsb_sigmas) that _hsb_call has accepted (never
     with hed): hsb_stage, and HsbDraw at the end of the tuple.  blur = (GaussianBlurAugmenter, blur_sigmas) that _blur_call has accepted
-    (never with hed or hsb): blur_stage, and BlurDraw at the end of the tuple."""
+    (never with hed or hsb): blur_stage, and BlurDraw at the end of the tuple.  post = (noise, tone, noise_sigmas, tone_params) that
+    _post_call has accepted (never with hed, hsb or blur): post_stage, and PostDraw at the end of the tuple."""
     M, maxC, status = fit
     route = dict(M_src=M, maxC_src=maxC, **route)
+    if post is not None:
+        x, windows, draw = post_stage(tiles, *post, view, windows, route, fmt=fmt, out=out)
+        return (x, M, maxC, status) + ((windows,) if view is not None else ()) + (draw,)
     if blur is not None:
         x, windows, draw = blur_stage(tiles, *blur, view, windows, route, fmt=fmt, out=out)
         return (x, M, maxC, status) + ((windows,) if view is not None else ()) + (draw,)

@@ -146,22 +146,23 @@ class ExtractiveStainNormalizer(object):
         """Per-tile (M, maxC, status) device tensors for a batch of candidate targets."""
         return self._fit_tiles(tiles, ws=ws)
 
-    def _route_batch(self, tiles, target, jitter, out, ws, tensor_format, view, windows, hed, hsb=None, blur=None):
+    def _route_batch(self, tiles, target, jitter, out, ws, tensor_format, view, windows, hed, hsb=None, blur=None, post=None):
         """The view= / hed= routes of transform_batch and all of augment_batch: the checks that are left (every one before the fit and
         before any draw), the fit of the whole tiles, then engine.route_stage -- ONE pass under the target (target=True) or every tile's
         own matrix, with the jitter's alpha_beta / augment_background ({}: none).  hed: None, or (hed, hed_sigmas, hed_biases) that
         engine._hed_call has accepted; hsb: None, or (hsb, hsb_sigmas) that engine._hsb_call has accepted; blur: None, or (blur, blur_sigmas)
-        that engine._blur_call has accepted.  -> (out, M_src, maxC_src, status[, windows][, HedDraw or HsbDraw or BlurDraw])."""
+        that engine._blur_call has accepted; post: None, or (noise, tone, noise_sigmas, tone_params) that engine._post_call has accepted.
+        -> (out, M_src, maxC_src, status[, windows][, HedDraw or HsbDraw or BlurDraw or PostDraw])."""
         from .. import engine
         if view is not None or windows is not None:
             engine._view_call(view, windows, tiles, draw=False)
         engine._check_tiles(tiles)
         fit = self._fit_tiles(tiles, ws=ws)
         M_t, c_t = self._target_on(tiles.device) if target else (None, None)
-        return engine.route_stage(tiles, fit, dict(M_tgt=M_t, maxC_tgt=c_t, **jitter), tensor_format, out, view, windows, hed, hsb, blur)
+        return engine.route_stage(tiles, fit, dict(M_tgt=M_t, maxC_tgt=c_t, **jitter), tensor_format, out, view, windows, hed, hsb, blur, post)
 
     def transform_batch(self, tiles, out=None, ws=None, tensor_format=None, _tensor_route=None, view=None, windows=None, hed=None,
-                        hed_sigmas=None, hed_biases=None, hsb=None, hsb_sigmas=None, blur=None, blur_sigmas=None):
+                        hed_sigmas=None, hed_biases=None, hsb=None, hsb_sigmas=None, blur=None, blur_sigmas=None, noise=None, tone=None, noise_sigmas=None, tone_params=None):
         """(N,H,W,3) uint8 device tensor -> (out, M_src, maxC_src, status) device tensors.  A tile whose
         status is non-zero (1 = empty tissue mask, 2 = degenerate, 3 = a zero 99th-percentile concentration) is passed through unchanged.
         ``ws``: an ``engine.Workspace`` to reuse (ONE stream at a time); by default every call takes its scratch from
@@ -185,14 +186,23 @@ class ExtractiveStainNormalizer(object):
         edge sees the tile's real neighbours --, then the view and the conversion.  ``blur_sigmas``: (N,); by default
         ``blur.randomize_batch(N)``, drawn BEFORE the windows (or the (N, 9) codes a call returned, to reproduce it).  The call then returns
         one more element at the end, ``engine.BlurDraw(sigmas, codes)``.  Not together with ``hed`` or ``hsb`` (chain them), a
-        ``TileView(scale=)`` or a TileAffine."""
+        ``TileView(scale=)`` or a TileAffine.
+        ``noise``, ``tone``: a ``GaussianNoiseAugmenter`` / a ``ToneCurveAugmenter`` -- the post stage, in that same pass
+        (engine.normalize_post_view): the tone curve, then the additive noise, per WRITTEN pixel -- behind the view, the box shrink or the
+        area resample, in front of the conversion: bit for bit ``augmentation.noise.post_reference`` of the uint8 image the call writes
+        without them.  ``tone_params``: (N, 3) (brightness, contrast, gamma), ``noise_sigmas``: (N,) in bytes -- or the tables / codes a
+        call returned, to reproduce it; by default ``tone.randomize_batch(N)``, then ``noise.randomize_batch(N)``, drawn BEFORE the
+        windows.  One more element at the end, ``engine.PostDraw(tone_params, tone_tables, noise_sigmas, noise_codes)``.  Not together
+        with ``hed``, ``hsb`` or ``blur`` (chain them), a TileAffine or a TileElastic."""
         from .. import engine
         with_hed = engine._hed_call(hed, hed_sigmas, hed_biases, tiles, view)
         with_hsb = engine._hsb_call(hsb, hsb_sigmas, tiles, view, hed)
         with_blur = engine._blur_call(blur, blur_sigmas, tiles, view, hed, hsb)
-        if with_hed or with_hsb or with_blur or view is not None or windows is not None:
+        with_post = engine._post_call(noise, tone, noise_sigmas, tone_params, tiles, view, hed, hsb, blur)
+        if with_hed or with_hsb or with_blur or with_post or view is not None or windows is not None:
             return self._route_batch(tiles, True, {}, out, ws, tensor_format, view, windows, (hed, hed_sigmas, hed_biases) if with_hed else None,
-                                     (hsb, hsb_sigmas) if with_hsb else None, (blur, blur_sigmas) if with_blur else None)
+                                     (hsb, hsb_sigmas) if with_hsb else None, (blur, blur_sigmas) if with_blur else None,
+                                     (noise, tone, noise_sigmas, tone_params) if with_post else None)
         if tensor_format is None:
             return self._transform_tiles(tiles, out=out, ws=ws)
         route = _tensor_route or TENSOR_ROUTE
@@ -209,7 +219,7 @@ class ExtractiveStainNormalizer(object):
 
     # -- stain separation (an extension: torchstain's normalize(..., stains=True), the concentration maps of staintools) ----
     def separate_batch(self, tiles, want=("norm", "h", "e", "conc"), conc_dtype=None, normalize=True, ws=None, tensor_format=None, view=None,
-                       windows=None, blur=None, blur_sigmas=None):
+                       windows=None, blur=None, blur_sigmas=None, noise=None, tone=None, noise_sigmas=None, tone_params=None):
         """(N,H,W,3) uint8 device tensor -> (Separated, M_src, maxC_src, status): the per-tile fit, then ONE pass that writes what
         ``want`` names -- norm (transform_batch's image), h / e (the haematoxylin-only / eosin-only image, (N,H,W,3) uint8) and conc
         (the normalised concentrations, (N,2,H,W) planes of ``conc_dtype``: float32 by default, float16 or bfloat16).
@@ -222,10 +232,12 @@ class ExtractiveStainNormalizer(object):
         the images as in transform_batch and does not go with 'conc' in ``want``; a resizing view (``TileView(scale=)``) is refused.
         ``tensor_format``: a ``stainlib_amd.TensorFormat`` (with ``view`` only; ``TileView(None, flip=False, rot90=False)`` is the
         fused full-tile tensor) -- norm, h and e are then (N,3,oh,ow) tensors, bit for bit ``tensor_format.convert`` of the uint8 views.
-        ``blur``, ``blur_sigmas``: refused (ValueError) -- the separation pass has no blur stage."""
+        ``blur``, ``blur_sigmas``: refused (ValueError) -- the separation pass has no blur stage.
+        ``noise``, ``tone``, ``noise_sigmas``, ``tone_params``: refused (ValueError) -- the separation pass has no post stage."""
         import torch
         from .. import engine
         engine._no_blur(blur, blur_sigmas, "separate_batch")
+        engine._no_post(noise, tone, noise_sigmas, tone_params, "separate_batch")
         conc_dtype = torch.float32 if conc_dtype is None else conc_dtype
         want = engine._separate_want(want, conc_dtype)
         with_view = engine.separate_view_check(view, windows, tensor_format, want, conc_dtype, tiles)
@@ -245,7 +257,7 @@ class ExtractiveStainNormalizer(object):
 
     # -- stain jitter in the apply pass (an extension: RandStainNA / StainAugmentor-style augmentation of the normalised tiles) ----
     def augment_batch(self, tiles, alpha_beta, augment_background=False, normalize=True, out=None, ws=None, tensor_format=None, view=None,
-                      windows=None, hed=None, hed_sigmas=None, hed_biases=None, hsb=None, hsb_sigmas=None, blur=None, blur_sigmas=None):
+                      windows=None, hed=None, hed_sigmas=None, hed_biases=None, hsb=None, hsb_sigmas=None, blur=None, blur_sigmas=None, noise=None, tone=None, noise_sigmas=None, tone_params=None):
         """(N,H,W,3) uint8 device tensor -> (out, M_src, maxC_src, status): the per-tile fit, then ONE pass that normalises every tile
         and perturbs its stains: C_i * alpha_i + beta_i on the normalised concentrations of tissue pixels (every pixel with
         ``augment_background``), under the target's stain matrix, clipped.  ``alpha_beta``: (N, 4) = alpha0, beta0, alpha1, beta1 per
@@ -260,7 +272,9 @@ class ExtractiveStainNormalizer(object):
         ``hsb``, ``hsb_sigmas``: as in transform_batch -- the HsbColorAugmenter's map of the perturbed tile in the same pass; one more
         element at the end of the returned tuple, ``engine.HsbDraw``.
         ``blur``, ``blur_sigmas``: as in transform_batch -- the GaussianBlurAugmenter's blur of the perturbed tile in the same pass; one
-        more element at the end of the returned tuple, ``engine.BlurDraw``."""
+        more element at the end of the returned tuple, ``engine.BlurDraw``.
+        ``noise``, ``tone``, ``noise_sigmas``, ``tone_params``: as in transform_batch -- the post stage on the written pixels of the
+        perturbed tile in the same pass; one more element at the end of the returned tuple, ``engine.PostDraw``."""
         from .. import engine
         engine._jitter_args(None, None, alpha_beta, None, tensor_format, out)
         if normalize and not hasattr(self, "stain_matrix_target"):
@@ -268,9 +282,11 @@ class ExtractiveStainNormalizer(object):
         with_hed = engine._hed_call(hed, hed_sigmas, hed_biases, tiles, view)
         with_hsb = engine._hsb_call(hsb, hsb_sigmas, tiles, view, hed)
         with_blur = engine._blur_call(blur, blur_sigmas, tiles, view, hed, hsb)
+        with_post = engine._post_call(noise, tone, noise_sigmas, tone_params, tiles, view, hed, hsb, blur)
         return self._route_batch(tiles, normalize, dict(alpha_beta=alpha_beta, augment_background=augment_background), out, ws,
                                  tensor_format, view, windows, (hed, hed_sigmas, hed_biases) if with_hed else None,
-                                 (hsb, hsb_sigmas) if with_hsb else None, (blur, blur_sigmas) if with_blur else None)
+                                 (hsb, hsb_sigmas) if with_hsb else None, (blur, blur_sigmas) if with_blur else None,
+                                 (noise, tone, noise_sigmas, tone_params) if with_post else None)
 
     def separate(self, I, normalize=True):
         """An image (RGB uint8) -> Separated of numpy arrays: norm (= transform(I)), h, e ((H,W,3) uint8) and conc ((2,H,W) float32)."""
@@ -351,7 +367,7 @@ class ReinhardStainNormalizer(object):
         return out[0].cpu().numpy()
 
     def transform_batch(self, tiles, mask_background=False, luminosity_threshold=0.8, out=None, ws=None, tensor_format=None, view=None,
-                        windows=None, blur=None, blur_sigmas=None):
+                        windows=None, blur=None, blur_sigmas=None, noise=None, tone=None, noise_sigmas=None, tone_params=None):
         """Batched extension: (N,H,W,3) uint8 device tensor -> (out, stats (N,8): p90, means, stds, tissue pixels).
         ``tensor_format``: a ``stainlib_amd.TensorFormat``; `out` is then the (N,3,H,W) tensor in that format (the map writes a uint8
         scratch, ``tensor_format.convert`` reads it).
@@ -363,6 +379,7 @@ class ReinhardStainNormalizer(object):
         (``blur.transform_batch(view=, tensor_format=)``)."""
         from .. import engine
         engine._no_blur(blur, blur_sigmas, "the Lab family's fused calls (ReinhardStainNormalizer.transform_batch)")
+        engine._no_post(noise, tone, noise_sigmas, tone_params, "the Lab family's fused calls (ReinhardStainNormalizer.transform_batch)")
         tm, ts = self._targets()
         if engine.lab_view_check(view, windows, tiles):
             return engine.reinhard_view(tiles, windows, None, tm, ts, mask_background=mask_background,

@@ -55,7 +55,8 @@ class TensorFormat(object):
             raise ValueError(f"{what} must be three finite numbers, not {x!r}")
         return v
 
-    def convert(self, tiles_u8, out=None, view=None, windows=None, blur=None, blur_sigmas=None):
+    def convert(self, tiles_u8, out=None, view=None, windows=None, blur=None, blur_sigmas=None, noise=None, tone=None, noise_sigmas=None,
+                tone_params=None):
         """(N, H, W, 3) uint8 device tensor -> (N, 3, H, W) tensor in this format (one streaming sweep, engine.to_tensor).
         ``out``: a tensor of that shape, dtype and memory format to write into.
         ``view``: a ``stainlib_amd.TileView`` -- per tile only the window ``windows[t]`` (default: ``view.draw(N, H, W)``), flipped and
@@ -64,8 +65,20 @@ class TensorFormat(object):
         ``blur``: a ``stainlib_amd.GaussianBlurAugmenter`` -- its integer Gaussian blur of every WHOLE tile in the same sweep
         (engine.normalize_blur_view), then the view (if any) and the conversion.  ``blur_sigmas``: (N,); by default
         ``blur.randomize_batch(N)``, drawn BEFORE the windows.  One more element at the end, ``engine.BlurDraw(sigmas, codes)``: the call
-        returns (tensor, BlurDraw) or (tensor, windows, BlurDraw).  Not with a ``TileView(scale=)`` or a TileAffine."""
+        returns (tensor, BlurDraw) or (tensor, windows, BlurDraw).  Not with a ``TileView(scale=)`` or a TileAffine.
+        ``noise``, ``tone``: a ``stainlib_amd.GaussianNoiseAugmenter`` / ``ToneCurveAugmenter`` -- the post stage in the same sweep
+        (engine.normalize_post_view): the tone curve, then the additive noise, per WRITTEN pixel -- behind the view (if any), in front of
+        the conversion: bit for bit this call on ``augmentation.noise.post_reference`` of the uint8 view.  ``tone_params``: (N, 3),
+        ``noise_sigmas``: (N,) -- or the tables / codes a call returned; by default ``tone.randomize_batch(N)``, then
+        ``noise.randomize_batch(N)``, drawn BEFORE the windows.  One more element at the end, ``engine.PostDraw``.  Not with ``blur``, a
+        TileAffine or a TileElastic."""
         from . import engine
+        if engine._post_call(noise, tone, noise_sigmas, tone_params, tiles_u8, view, blur=blur):
+            if view is not None or windows is not None:
+                engine._view_call(view, windows, tiles_u8, draw=False)
+            engine._check_tiles(tiles_u8)
+            x, windows, draw = engine.post_stage(tiles_u8, noise, tone, noise_sigmas, tone_params, view, windows, {}, fmt=self, out=out)
+            return (x,) + ((windows,) if view is not None else ()) + (draw,)
         if engine._blur_call(blur, blur_sigmas, tiles_u8, view):
             if view is not None or windows is not None:
                 engine._view_call(view, windows, tiles_u8, draw=False)

@@ -97,7 +97,7 @@ class LuminosityStandardizer(object):
         return out[0].cpu().numpy()
 
     @staticmethod
-    def standardize_batch(tiles, percentile=95, out=None, ws=None, tensor_format=None, view=None, windows=None, blur=None, blur_sigmas=None):
+    def standardize_batch(tiles, percentile=95, out=None, ws=None, tensor_format=None, view=None, windows=None, blur=None, blur_sigmas=None, noise=None, tone=None, noise_sigmas=None, tone_params=None):
         """Batched extension: (N,H,W,3) uint8 device tensor -> (out, p (N,) float64: every tile's `percentile` of L8).
         ``tensor_format``: a ``stainlib_amd.TensorFormat``; `out` is then the (N,3,H,W) tensor in that format (the map writes a uint8
         scratch, ``tensor_format.convert`` reads it).
@@ -108,6 +108,7 @@ class LuminosityStandardizer(object):
         blur its uint8 result (``blur.transform_batch(view=, tensor_format=)``)."""
         from .. import engine
         engine._no_blur(blur, blur_sigmas, "the Lab family's fused calls (LuminosityStandardizer.standardize_batch)")
+        engine._no_post(noise, tone, noise_sigmas, tone_params, "the Lab family's fused calls (LuminosityStandardizer.standardize_batch)")
         if engine.lab_view_check(view, windows, tiles):
             return engine.luminosity_view(tiles, windows, None, percentile, fmt=tensor_format, out=out, ws=ws, view=view)
         if tensor_format is None:
