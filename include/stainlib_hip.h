@@ -957,6 +957,40 @@ SL_API int sl_normalize_blur_view(const uint8_t* rgb, void* out, int n, int h, i
 SL_API int sl_post_augment(const uint8_t* rgb, void* out, int n, int h, int w, const uint8_t* tables, const int32_t* codes, const SlTensorFormat* fmt, void* stream);
 SL_API int sl_normalize_post_view(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, int shrink, int max_wh, int max_ww, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, const double* alpha_beta, int augment_background, const SlParams* params, const SlTensorFormat* fmt, const uint8_t* tables, const int32_t* codes, void* stream);
 
+/* ---- the one-pass recipe: a colour stage, a view and the post stage TOGETHER (stainlib_amd/csrc/recipe.hip; nothing new is defined,
+ * the stages above are composed).  With full[t] the uint8 image the statistics pattern names as in sl_normalize_view:
+ *     out[t] = convert( post( view( colour(full[t]) ) ) )
+ *   colour  on SOURCE pixels, at most one: sl_hed_augment under hed_applied[t] (sl_normalize_hed_view's stage: hed_sigma, hed_bias n x 3
+ *           binary64, hed_applied n int32, skimage_mode 0 only), or the HSB map of sl_normalize_hsb_view (hsb_codes n x 3 int32)
+ *   view    the definition of its entry point: the window, flip and turn and the box shrink of sl_normalize_view_shrink, the area resample
+ *           of sl_normalize_view_resize, the bilinear sample of sl_normalize_view_affine or sl_normalize_view_elastic
+ *   post    on WRITTEN pixels: sl_normalize_post_view's stage (tone_tables n x 256 or NULL, then noise_codes n x 4 int32 or NULL), with
+ *           p = i ow + j counted in the view's output
+ * All arrays are device pointers; an absent stage is NULL and is the identity, so a recipe with one stage is bit for bit that stage's own
+ * call.  Consequences of the order: the fill byte of an affine / elastic view is in output space -- it does NOT take the colour stage and
+ * it DOES take the post stage; so does a tile written entirely as fill (a row of windows beyond max_r) and a patch whose source box misses
+ * the tile.  A tile whose fit failed is the recipe applied to its own bytes.
+ * struct_size must be sizeof(SlViewStages).
+ *
+ * sl_normalize_stages_view: sl_normalize_post_view's geometry (max_wh == 0: fixed-size with shrink 1, 2, 4; else resizing).  A call whose
+ * stages one existing entry point covers -- a colour stage alone, or the post stage alone -- is forwarded to it.
+ * sl_normalize_stages_view_affine, sl_normalize_stages_view_elastic: the arguments of sl_normalize_view_affine / _view_elastic.
+ * SL_ERR_BADARG before anything is launched: what the parent entry point refuses; stages NULL or of another struct_size; no stage at all;
+ * HED and HSB both; an incomplete HED triple; skimage_mode != 0; hsb_codes or noise_codes not 4-byte aligned.  n == 0: SL_OK, nothing
+ * launched.  No workspace; capture-safe like the parents.  out == rgb is not supported. */
+typedef struct SlViewStages {
+    uint32_t struct_size;
+    const double *hed_sigma, *hed_bias;   /* n x 3 each */
+    const int32_t* hed_applied;           /* n */
+    int skimage_mode;                     /* 0 only */
+    const int32_t* hsb_codes;             /* n x 3; not together with HED */
+    const uint8_t* tone_tables;           /* n x 256 or NULL */
+    const int32_t* noise_codes;           /* n x 4 or NULL */
+} SlViewStages;
+SL_API int sl_normalize_stages_view(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int d_mask, int shrink, int max_wh, int max_ww, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, const double* alpha_beta, int augment_background, const SlParams* params, const SlTensorFormat* fmt, const SlViewStages* stages, void* stream);
+SL_API int sl_normalize_stages_view_affine(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int max_r, uint32_t fill_rgb, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, const double* alpha_beta, int augment_background, const SlParams* params, const SlTensorFormat* fmt, const SlViewStages* stages, void* stream);
+SL_API int sl_normalize_stages_view_elastic(const uint8_t* rgb, void* out, int n, int h, int w, int oh, int ow, const int32_t* windows, int max_r, const int32_t* field, int cell_log2, int max_d, uint32_t fill_rgb, const double* M_src, const double* maxC_src, const double* M_tgt, const double* maxC_tgt, const double* alpha_beta, int augment_background, const SlParams* params, const SlTensorFormat* fmt, const SlViewStages* stages, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@ HsbColorAugmenter (an extension; HsbLight / HsbStrong presets) is the hue / satu
 GaussianBlurAugmenter (an extension) is the Gaussian blur of that set: a per-tile integer separable filter, fused into the view pass (blur=).
 GaussianNoiseAugmenter and ToneCurveAugmenter (extensions) are its noise and brightness / contrast / gamma items: integer maps on the
 WRITTEN pixels of the view pass (noise=, tone=); the per-pixel noise is a counter-based generator (Philox4x32-10) on the device.
+Recipe (an extension) holds one colour stage, one view of any kind and the tone / noise stage for ONE pass (recipe=).
 Separated (an extension) is what the normalizers' separate / separate_batch return: per-stain images and concentration maps.
 Importing the package does not need a GPU; calling anything numeric does, and fails loudly without the
 HIP library -- there is no CPU fallback.
@@ -27,6 +28,7 @@ from .extraction.vahadane_stain_extractor import VahadaneStainExtractor  # noqa:
 from .normalization.normalizer import (ExtractiveStainNormalizer, MacenkoNormalizer,  # noqa: F401
                                        ReinhardStainNormalizer, VahadaneNormalizer)
 from .tensor_format import TensorFormat  # noqa: F401
+from .recipe import Recipe  # noqa: F401
 from .separated import Separated  # noqa: F401
 from .tile_view import ElasticWindows, TileAffine, TileElastic, TileView  # noqa: F401
 from .utils.stain_utils import LuminosityStandardizer  # noqa: F401

@@ -77,6 +77,20 @@ class SlSeparateOut(C.Structure):
     ]
 
 
+class SlViewStages(C.Structure):
+    """The stages of the one-pass recipe (sl_normalize_stages_view*; a HOST struct, the pointers in it are DEVICE pointers, NULL = absent)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("hed_sigma", C.c_void_p),
+        ("hed_bias", C.c_void_p),
+        ("hed_applied", C.c_void_p),
+        ("skimage_mode", C.c_int),
+        ("hsb_codes", C.c_void_p),
+        ("tone_tables", C.c_void_p),
+        ("noise_codes", C.c_void_p),
+    ]
+
+
 DTYPE_F32, DTYPE_F16, DTYPE_BF16 = range(3)
 LAYOUT_NCHW, LAYOUT_NHWC = range(2)
 
@@ -231,6 +245,12 @@ _SIGNATURES["sl_normalize_blur_view"] = (C.c_int, [_P, _P, C.c_int, C.c_int, C.c
 _SIGNATURES["sl_post_augment"] = (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.POINTER(SlTensorFormat), _P])
 _SIGNATURES["sl_normalize_post_view"] = (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P,
                                                    _P, _P, _P, C.c_int, C.POINTER(SlParams), C.POINTER(SlTensorFormat), _P, _P, _P])
+# the one-pass recipe: the parent's arguments (sl_normalize_post_view's without tables, codes; sl_normalize_view_affine's; _view_elastic's) with
+# `const SlViewStages* stages` in front of the stream
+_SIGNATURES["sl_normalize_stages_view"] = (C.c_int, _SIGNATURES["sl_normalize_post_view"][1][:-3] + [C.POINTER(SlViewStages), _P])
+for _name in ("affine", "elastic"):
+    _SIGNATURES["sl_normalize_stages_view_" + _name] = (C.c_int, _SIGNATURES["sl_normalize_view_" + _name][1][:-1] + [C.POINTER(SlViewStages), _P])
+del _name
 PLANES_NEAREST, PLANES_AREA = range(2)
 POOL_STATE_DOUBLES, POOL_M, POOL_MAXC, POOL_STATUS, POOL_MISS = 64, 0, 6, 8, 9
 POOL2_STATE_DOUBLES, POOL2_HIST_WORDS, POOL2_WHY = 256, 2 * 8192 + 8 * 32, 33

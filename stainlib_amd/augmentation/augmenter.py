@@ -249,7 +249,8 @@ class StainAugmentor(object):
         return out[0].cpu().numpy()
 
     def augment_batch(self, tiles, alpha_beta=None, tensor_format=None, view=None, windows=None, hed=None, hed_sigmas=None, hed_biases=None,
-                      hsb=None, hsb_sigmas=None, blur=None, blur_sigmas=None, noise=None, tone=None, noise_sigmas=None, tone_params=None):
+                      hsb=None, hsb_sigmas=None, blur=None, blur_sigmas=None, noise=None, tone=None, noise_sigmas=None, tone_params=None,
+                      recipe=None, recipe_draw=None):
         """Batched extension: (N,H,W,3) uint8 device tensor -> (out, M, maxC, status) device tensors: every tile perturbed under its OWN
         stain matrix (this augmentor's extractor, fitted per tile) -- n fit() / pop() pairs in one fit and ONE pass, nothing through the
         host.  alpha_beta: (N, 4) = alpha0, beta0, alpha1, beta1 per tile; by default drawn from the global numpy stream exactly as N
@@ -277,10 +278,17 @@ class StainAugmentor(object):
         (N, 3), ``noise_sigmas``: (N,) -- or the tables / codes a call returned; by default ``tone.randomize_batch(N)``, then
         ``noise.randomize_batch(N)``, drawn after alpha_beta and BEFORE the windows.  One more element at the end, ``engine.PostDraw``.
         Not together with ``hed``, ``hsb``, ``blur``, a TileAffine or a TileElastic.
+        ``recipe``: a ``stainlib_amd.Recipe(view=, color=, noise=, tone=)`` -- a colour stage (HED or HSB) on the perturbed SOURCE pixels, a
+        view of any kind and tone / noise on the WRITTEN pixels TOGETHER in that one pass (engine.recipe_stage), drawn after alpha_beta in
+        the order colour, tone, noise, view; the call returns (out, M, maxC, status, ``engine.RecipeDraw(windows, color, post)``), and
+        ``recipe_draw``, that RecipeDraw passed back, reproduces it.  Not together with any other keyword from ``view`` on.
         fit() / pop() are untouched by it."""
         from .. import engine
         jitter = StainJitter(self.sigma1, self.sigma2, self.augment_background)
         engine._jitter_args(None, None, alpha_beta if alpha_beta is not None else np.empty((0, 4)), None, tensor_format, None)
+        with_recipe = engine._recipe_call(recipe, recipe_draw, tiles, view=view, windows=windows, hed=hed, hed_sigmas=hed_sigmas,
+                                          hed_biases=hed_biases, hsb=hsb, hsb_sigmas=hsb_sigmas, blur=blur, blur_sigmas=blur_sigmas,
+                                          noise=noise, tone=tone, noise_sigmas=noise_sigmas, tone_params=tone_params)
         if view is not None or windows is not None:
             engine._view_call(view, windows, tiles, draw=False)
         with_hed = engine._hed_call(hed, hed_sigmas, hed_biases, tiles, view)
@@ -294,7 +302,8 @@ class StainAugmentor(object):
         route = dict(M_tgt=None, maxC_tgt=None, alpha_beta=alpha_beta, augment_background=self.augment_background)
         return engine.route_stage(tiles, fit, route, tensor_format, None, view, windows, (hed, hed_sigmas, hed_biases) if with_hed else None,
                                   (hsb, hsb_sigmas) if with_hsb else None, (blur, blur_sigmas) if with_blur else None,
-                                  (noise, tone, noise_sigmas, tone_params) if with_post else None)
+                                  (noise, tone, noise_sigmas, tone_params) if with_post else None,
+                                  (recipe, recipe_draw) if with_recipe else None)
 
 
 class StainJitter(object):

@@ -1,0 +1,5 @@
+// recipe_view_hsb.hip -- the one-pass recipe (recipe_kernels.hpp; launchers: recipe_launch.hpp): the fixed-size view behind the HSB stage, with the post stage.
+// One of the translation units the recipe's kernel families are spread over, so that a parallel build compiles them side by side.
+#include "recipe_launch.hpp"
+
+template int sl::recipe_launch_view<2>(const sl::RecipeCall&);

@@ -50,9 +50,10 @@ namespace sl {
 
 // ---- write side: output rows, 4 adjacent pixels per lane (behind a barrier after the stage, or with none: nothing staged).  fill: the
 // ---- packed fill pixel r | g << 8 | b << 16.
-template <int DT, int LAYOUT>
+// ---- Post: the stage on the written pixels (ViewNoPost: none), fill pixels included; its table is in LDS behind a barrier.
+template <int DT, int LAYOUT, class Post = ViewNoPost>
 __device__ __forceinline__ void affine_write(const AffineTile& t, const ViewPatch& g, bool none, const uint32_t* s_px, void* out, int tile,
-                                             int h, int w, int oh, int ow, uint32_t fill, TensorK fmt, int tid) {
+                                             int h, int w, int oh, int ow, uint32_t fill, TensorK fmt, int tid, const Post& post = Post()) {
     const int i0 = g.i0, j0 = g.j0, bh = g.bh, bw = g.bw;
     const TensorK F = tensor_consts(fmt);
     const size_t PO = (size_t)oh * ow;
@@ -73,14 +74,66 @@ __device__ __forceinline__ void affine_write(const AffineTile& t, const ViewPatc
             const uint32_t p10 = y1in && x0in ? s_px[r1 + c0] : fill, p11 = y1in && x1in ? s_px[r1 + c1] : fill;
             px[p] = affine_blend(p00, p01, p10, p11, a.fy, a.fx);
         }
+        if constexpr (Post::kOn) post.apply(px, g, il, jl, ow);  // (post_lane: the duplicates of a ragged last lane stay as they are)
         const int nvalid = min(4, bw - jl);
         const size_t pix = (size_t)(i0 + il) * ow + (j0 + jl);
         view_store_px4<DT, LAYOUT>(px, out, tile, PO, pix, nvalid, F);
     }
 }
 
-// view_resize_body with the geometry and the write side above and no stage (HED = 0); the arithmetic between view_read and the barrier
-// is view_route (view_kernels.hpp).  npatch: the host's upper bound of the patches of a tile.
+// view_resize_body with the geometry and the write side above; the arithmetic between view_read and the barrier is view_route
+// (view_kernels.hpp).  npatch: the host's upper bound of the patches of a tile.  HED: the stage on SOURCE pixels (0: none) -- the fill is
+// in output space and does not take it --; Post: the stage on written pixels, the fill included (ViewNoPost: none).  A PostStage has
+// filled its table before the call; the barrier in front of the write side stands between that fill and its first use, and the `none`
+// path, which has no barrier of its own, gets one (block-uniform).  The recipes (recipe_kernels.hpp) instantiate it with stages.
+// k_view_affine below holds the same text written out with no stage -- its TWIN: a change to one is a change to the other.  Calling the
+// body from it leaves registers, LDS and occupancy alone but re-orders the code of 28 of its 34 instantiations (tools/isa_diff.py; +-
+// some tens of bytes each), and the existing kernels stay function for function what they were (as 4.19.1 for view_body).
+template <int DT, int LAYOUT, int MODE, int HED = 0, class Post = ViewNoPost>
+__device__ __forceinline__ void affine_body(const uint8_t* rgb, void* out, int h, int w, int oh, int ow, int npatch, const int32_t* windows,
+                                            int max_r, uint32_t fill, const double* M_src, const double* maxC_src, const double* M_tgt,
+                                            const double* maxC_tgt, const double* alpha_beta, double lam, float ylimf, TensorK fmt,
+                                            const typename StageArgs<HED>::type* hv = nullptr, const Post& post = Post()) {
+    constexpr int B = kViewB, PITCH = kViewPitch;
+    static_assert(kWG == 256 && B == 64, "16 lanes x 4 pixels per row, 16 rows per pass, 4 passes");
+    __shared__ float2 s_tab[256];
+    __shared__ uint32_t s_px[B * PITCH];
+    const int tid = threadIdx.x;
+    const int lr = tid >> 4, lc = tid & 15;
+    const int tile = blockIdx.x / npatch, patch = blockIdx.x % npatch;
+    const int P = h * w;
+    const size_t nbytes = (size_t)P * 3;
+    const uint8_t* const src = rgb + (size_t)tile * nbytes;
+
+    // the view of this tile (block-uniform), the source block of this patch -- or no patch: the grid is sized for the call's bound --,
+    // or no block: the fill alone
+    const AffineTile vt(windows, tile, h, w, max_r);
+    ViewPatch g;
+    bool none;
+    if (!affine_patch(vt, patch, h, w, oh, ow, g, none)) return;
+    if (none) {
+        if constexpr (Post::kOn) __syncthreads();                // the post stage's table
+        affine_write<DT, LAYOUT>(vt, g, true, s_px, out, tile, h, w, oh, ow, fill, fmt, tid, post);
+        return;
+    }
+    if (MODE != kViewRaw) fill_gam_od_lut(s_tab);
+    HedStage<HED> hed;
+    hed.init(tid, tile, hv);
+    Chunk in[4];
+    view_read(g, src, nbytes, w, lr, lc, in);
+    auto stage = [&](auto compute) {
+        view_stage(g, s_px, lr, lc, in, [&](const Chunk& c, uint32_t (&px)[4]) {
+            compute(c, px);
+            hed.apply(px);
+        });
+    };
+    view_route<MODE, HED>(s_tab, stage, npatch, P, rgb, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, lam, ylimf);
+    __syncthreads();
+
+    affine_write<DT, LAYOUT>(vt, g, false, s_px, out, tile, h, w, oh, ow, fill, fmt, tid, post);
+}
+
+// affine_body<DT, LAYOUT, MODE, 0, ViewNoPost> written out (see there)
 template <int DT, int LAYOUT, int MODE>
 static __global__ __launch_bounds__(kWG) void k_view_affine(const uint8_t* __restrict__ rgb, void* __restrict__ out, int h, int w, int oh,
                                                             int ow, int npatch, const int32_t* __restrict__ windows, int max_r,

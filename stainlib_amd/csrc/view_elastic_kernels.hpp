@@ -8,7 +8,7 @@
 // view's plus (d[0] << 8, d[1] << 8), d the spline of field[t] at (i, j) in 1/256 source pixel; from (Y, X) on everything is the affine
 // view's: affine_taps, the four taps with the fill outside the tile, affine_blend.
 //
-// What is shared with k_view_affine: everything but the geometry -- view_read / view_stage / view_route<MODE, 0> on the block, ONE
+// What is shared with k_view_affine: everything but the geometry -- view_read / view_stage / view_route on the block, ONE
 // barrier, the slots, selects and blend of the write side, view_store_px4.  What is new: ElasticTile's patch edge min(64, 1 + (62 - 2
 // max_d) Q / R), elastic_patch's block -- the box of the four affine corners grown by max_d pixels, cut to the tile -- and the field.
 //
@@ -35,10 +35,11 @@ __device__ __forceinline__ void elastic_stage(const ElasticTile& t, const Elasti
 }
 
 // ---- write side: affine_write with elastic_at in place of affine_at; the spline's row weights once per output row of a lane
-template <int DT, int LAYOUT>
+// ---- (Post: affine_write's)
+template <int DT, int LAYOUT, class Post = ViewNoPost>
 __device__ __forceinline__ void elastic_write(const ElasticTile& t, const ViewPatch& g, const ElasticNodes& e, bool none, const uint32_t* s_px,
                                               const int32_t* s_nodes, void* out, int tile, int h, int w, int oh, int ow, uint32_t fill,
-                                              TensorK fmt, int tid) {
+                                              TensorK fmt, int tid, const Post& post = Post()) {
     const int i0 = g.i0, j0 = g.j0, bh = g.bh, bw = g.bw;
     const TensorK F = tensor_consts(fmt);
     const size_t PO = (size_t)oh * ow;
@@ -60,13 +61,65 @@ __device__ __forceinline__ void elastic_write(const ElasticTile& t, const ViewPa
             const uint32_t p10 = y1in && x0in ? s_px[r1 + c0] : fill, p11 = y1in && x1in ? s_px[r1 + c1] : fill;
             px[p] = affine_blend(p00, p01, p10, p11, a.fy, a.fx);
         }
+        if constexpr (Post::kOn) post.apply(px, g, il, jl, ow);
         const int nvalid = min(4, bw - jl);
         const size_t pix = (size_t)(i0 + il) * ow + (j0 + jl);
         view_store_px4<DT, LAYOUT>(px, out, tile, PO, pix, nvalid, F);
     }
 }
 
-// k_view_affine with the geometry and the write side above.  npatch: the host's upper bound of the patches of a tile.
+// affine_body with the geometry and the write side above (HED, Post: as there).  npatch: the host's upper bound of the patches of a tile.
+// The recipes (recipe_kernels.hpp) instantiate it; k_view_elastic below holds the same text written out with no stage, its TWIN, for
+// affine_body's reason.
+template <int DT, int LAYOUT, int MODE, int HED = 0, class Post = ViewNoPost>
+__device__ __forceinline__ void elastic_body(const uint8_t* rgb, void* out, int h, int w, int oh, int ow, int npatch, const int32_t* windows,
+                                             int max_r, const int32_t* field, int cell_log2, int max_d, uint32_t fill, const double* M_src,
+                                             const double* maxC_src, const double* M_tgt, const double* maxC_tgt, const double* alpha_beta,
+                                             double lam, float ylimf, TensorK fmt, const typename StageArgs<HED>::type* hv = nullptr,
+                                             const Post& post = Post()) {
+    constexpr int B = kViewB, PITCH = kViewPitch;
+    static_assert(kWG == 256 && B == 64, "16 lanes x 4 pixels per row, 16 rows per pass, 4 passes");
+    __shared__ float2 s_tab[256];
+    __shared__ uint32_t s_px[B * PITCH];
+    __shared__ __attribute__((aligned(8))) int32_t s_nodes[kElasticLds];
+    const int tid = threadIdx.x;
+    const int lr = tid >> 4, lc = tid & 15;
+    const int tile = blockIdx.x / npatch, patch = blockIdx.x % npatch;
+    const int P = h * w;
+    const size_t nbytes = (size_t)P * 3;
+    const uint8_t* const src = rgb + (size_t)tile * nbytes;
+
+    // the view of this tile (block-uniform), the source block and the nodes of this patch -- or no patch: the grid is sized for the
+    // call's bounds --, or no block: the fill alone
+    const ElasticTile vt(windows, tile, h, w, max_r, cell_log2, max_d);
+    ViewPatch g;
+    ElasticNodes e;
+    bool none;
+    if (!elastic_patch(vt, patch, h, w, oh, ow, g, e, none)) return;
+    if (none) {
+        if constexpr (Post::kOn) __syncthreads();                // the post stage's table
+        elastic_write<DT, LAYOUT>(vt, g, e, true, s_px, s_nodes, out, tile, h, w, oh, ow, fill, fmt, tid, post);
+        return;
+    }
+    if (MODE != kViewRaw) fill_gam_od_lut(s_tab);
+    HedStage<HED> hed;
+    hed.init(tid, tile, hv);
+    Chunk in[4];
+    view_read(g, src, nbytes, w, lr, lc, in);
+    elastic_stage(vt, e, field, tile, oh, ow, s_nodes, tid);
+    auto stage = [&](auto compute) {
+        view_stage(g, s_px, lr, lc, in, [&](const Chunk& c, uint32_t (&px)[4]) {
+            compute(c, px);
+            hed.apply(px);
+        });
+    };
+    view_route<MODE, HED>(s_tab, stage, npatch, P, rgb, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, lam, ylimf);
+    __syncthreads();
+
+    elastic_write<DT, LAYOUT>(vt, g, e, false, s_px, s_nodes, out, tile, h, w, oh, ow, fill, fmt, tid, post);
+}
+
+// elastic_body<DT, LAYOUT, MODE, 0, ViewNoPost> written out (see there)
 template <int DT, int LAYOUT, int MODE>
 static __global__ __launch_bounds__(kWG) void k_view_elastic(const uint8_t* __restrict__ rgb, void* __restrict__ out, int h, int w, int oh,
                                                              int ow, int npatch, const int32_t* __restrict__ windows, int max_r,

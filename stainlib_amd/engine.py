@@ -666,6 +666,14 @@ def normalize_view_affine(rgb, windows, size, max_r, fill=255, M_src=None, maxC_
     windows: (N, 6) int32 (TileAffine.draw).  numpy or CPU tensor: range-checked, ValueError.  Device tensor: taken as it is -- the kernel
     clamps the centres into their range and writes a tile whose row sums pass max_r as fill everywhere; nothing is synchronised.
     fmt: a stainlib_amd.TensorFormat -> the (N,3,oh,ow) tensor, else (N,oh,ow,3) uint8."""
+    return _view_affine_call(None, rgb, windows, size, max_r, fill, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, augment_background, params,
+                             fmt, out)
+
+
+def _view_affine_call(stages, rgb, windows, size, max_r, fill, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, augment_background, params, fmt,
+                      out):
+    """normalize_view_affine (stages=None) and normalize_stages_view_affine (stages: _stages_check's keyword arguments): the checks in
+    normalize_view_affine's order, the stages' behind them and before anything is on the device, then the one call."""
     from .tensor_format import TensorFormat
     from .tile_view import _fill3, affine_check_size
     if not (isinstance(rgb, torch.Tensor) and rgb.dim() == 4 and rgb.shape[-1] == 3):
@@ -677,6 +685,8 @@ def normalize_view_affine(rgb, windows, size, max_r, fill=255, M_src=None, maxC_
     _route_check(M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, params, n)
     if fmt is not None and not isinstance(fmt, TensorFormat):
         raise ValueError("fmt must be a stainlib_amd.TensorFormat or None (the uint8 image)")
+    if stages is not None:
+        _stages_check(n, **stages)
     _check_tiles(rgb)
     dev = rgb.device
     if not isinstance(win, torch.Tensor):
@@ -685,8 +695,10 @@ def normalize_view_affine(rgb, windows, size, max_r, fill=255, M_src=None, maxC_
         raise ValueError(f"windows must be on {dev}")
     M_src, maxC_src, M_tgt, maxC_tgt, ab = _route_upload(n, dev, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta)
     f, out = _image_out(out, rgb, n, oh, ow, fmt, "view")
-    _call("sl_normalize_view_affine", _ptr(rgb), _ptr(out), n, h, w, oh, ow, _ptr(win), int(max_r), f3[0] | (f3[1] << 8) | (f3[2] << 16),
-          _ptr(M_src), _ptr(maxC_src), _ptr(M_tgt), _ptr(maxC_tgt), _ptr(ab), 1 if augment_background else 0, _byref(params), _byref(f))
+    st, keep = _stages_upload(n, dev, **stages) if stages is not None else ((), None)
+    _call("sl_normalize_view_affine" if stages is None else "sl_normalize_stages_view_affine", _ptr(rgb), _ptr(out), n, h, w, oh, ow, _ptr(win),
+          int(max_r), f3[0] | (f3[1] << 8) | (f3[2] << 16), _ptr(M_src), _ptr(maxC_src), _ptr(M_tgt), _ptr(maxC_tgt), _ptr(ab),
+          1 if augment_background else 0, _byref(params), _byref(f), *st)
     return out
 
 
@@ -813,6 +825,14 @@ def normalize_view_elastic(rgb, windows, field, size, cell, max_r, max_d, fill=2
     value to +-256 max_d.  Both windows and field on the host, or both on the device.
     cell: the lattice spacing in OUTPUT pixels, a power of two 16 .. 256.  max_d: an int 0 .. 8, an upper bound in source pixels of
     the control displacements of the call (TileElastic.max_d); the launch is sized from max_r and max_d."""
+    return _view_elastic_call(None, rgb, windows, field, size, cell, max_r, max_d, fill, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta,
+                              augment_background, params, fmt, out)
+
+
+def _view_elastic_call(stages, rgb, windows, field, size, cell, max_r, max_d, fill, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta,
+                       augment_background, params, fmt, out):
+    """normalize_view_elastic (stages=None) and normalize_stages_view_elastic (stages: _stages_check's keyword arguments), as
+    _view_affine_call."""
     from .tensor_format import TensorFormat
     from .tile_view import _cell_log2, _fill3, affine_check_size
     if not (isinstance(rgb, torch.Tensor) and rgb.dim() == 4 and rgb.shape[-1] == 3):
@@ -827,6 +847,8 @@ def normalize_view_elastic(rgb, windows, field, size, cell, max_r, max_d, fill=2
     _route_check(M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, params, n)
     if fmt is not None and not isinstance(fmt, TensorFormat):
         raise ValueError("fmt must be a stainlib_amd.TensorFormat or None (the uint8 image)")
+    if stages is not None:
+        _stages_check(n, **stages)
     _check_tiles(rgb)
     dev = rgb.device
     if not isinstance(win, torch.Tensor):
@@ -835,9 +857,10 @@ def normalize_view_elastic(rgb, windows, field, size, cell, max_r, max_d, fill=2
         raise ValueError(f"windows and field must be on {dev}")
     M_src, maxC_src, M_tgt, maxC_tgt, ab = _route_upload(n, dev, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta)
     f, out = _image_out(out, rgb, n, oh, ow, fmt, "view")
-    _call("sl_normalize_view_elastic", _ptr(rgb), _ptr(out), n, h, w, oh, ow, _ptr(win), int(max_r), _ptr(fld), _cell_log2(cell), int(max_d),
-          f3[0] | (f3[1] << 8) | (f3[2] << 16), _ptr(M_src), _ptr(maxC_src), _ptr(M_tgt), _ptr(maxC_tgt), _ptr(ab),
-          1 if augment_background else 0, _byref(params), _byref(f))
+    st, keep = _stages_upload(n, dev, **stages) if stages is not None else ((), None)
+    _call("sl_normalize_view_elastic" if stages is None else "sl_normalize_stages_view_elastic", _ptr(rgb), _ptr(out), n, h, w, oh, ow,
+          _ptr(win), int(max_r), _ptr(fld), _cell_log2(cell), int(max_d), f3[0] | (f3[1] << 8) | (f3[2] << 16), _ptr(M_src), _ptr(maxC_src),
+          _ptr(M_tgt), _ptr(maxC_tgt), _ptr(ab), 1 if augment_background else 0, _byref(params), _byref(f), *st)
     return out
 
 
@@ -1713,7 +1736,7 @@ def _view_resize_hw(view, windows, h, w):
     return max(1, min(h, int(win[:, 3].max()))), max(1, min(w, int(win[:, 4].max())))
 
 
-def route_stage(tiles, fit, route, fmt=None, out=None, view=None, windows=None, hed=None, hsb=None, blur=None, post=None):
+def route_stage(tiles, fit, route, fmt=None, out=None, view=None, windows=None, hed=None, hsb=None, blur=None, post=None, recipe=None):
     """The tail of the batch methods, behind their fit and their own draws, on arguments _jitter_args / _view_call(draw=False) / _hed_call
     have accepted: ONE pass over the tiles and the tuple the method returns, (out, M_src, maxC_src, status[, windows][, HedDraw]).
     fit: the fit's (M_src, maxC_src, status); route: the other arguments that name `full` (M_tgt, maxC_tgt and, for a jitter, alpha_beta
@@ -1721,9 +1744,14 @@ def route_stage(tiles, fit, route, fmt=None, out=None, view=None, windows=None, 
     windows drawn here if not given; else normalize_jitter.  hsb = (HsbColorAugmenter, hsb_sigmas) that _hsb_call has accepted (never
     with hed): hsb_stage, and HsbDraw at the end of the tuple.  blur = (GaussianBlurAugmenter, blur_sigmas) that _blur_call has accepted
     (never with hed or hsb): blur_stage, and BlurDraw at the end of the tuple.  post = (noise, tone, noise_sigmas, tone_params) that
-    _post_call has accepted (never with hed, hsb or blur): post_stage, and PostDraw at the end of the tuple."""
+    _post_call has accepted (never with hed, hsb or blur): post_stage, and PostDraw at the end of the tuple.  recipe = (Recipe,
+    recipe_draw) that _recipe_call has accepted (never with any of the others or a view): recipe_stage, and (out, M_src, maxC_src,
+    status, RecipeDraw)."""
     M, maxC, status = fit
     route = dict(M_src=M, maxC_src=maxC, **route)
+    if recipe is not None:
+        x, draw = recipe_stage(tiles, *recipe, route, fmt=fmt, out=out)
+        return x, M, maxC, status, draw
     if post is not None:
         x, windows, draw = post_stage(tiles, *post, view, windows, route, fmt=fmt, out=out)
         return (x, M, maxC, status) + ((windows,) if view is not None else ()) + (draw,)
@@ -1755,6 +1783,228 @@ def view_pass(tiles, view, windows, fmt=None, out=None, **route):
         return normalize_view_affine(tiles, windows, size, _affine_bound(view, windows), view.fill, fmt=fmt, out=out, **route), windows
     return normalize_view(tiles, windows, size, d_mask, fmt=fmt, out=out, shrink=shrink, resize=_view_resize(view, windows, tiles),
                           **route), windows
+
+
+# ---- the one-pass recipe: a colour stage, any view and the post stage together (sl_normalize_stages_view*; see include/stainlib_hip.h) ------
+
+RecipeDraw = collections.namedtuple("RecipeDraw", ["windows", "color", "post"])
+RecipeDraw.__doc__ = """What a recipe= call did: `windows` as the view's own call returns them ((N, 3 | 5 | 6) int32 or ElasticWindows; None
+without a view), `color` the HedDraw or HsbDraw of its colour stage (or None) and `post` the PostDraw of its tone / noise stage (or None).
+Passed back as recipe_draw= with the same Recipe it reproduces the call."""
+
+_STAGE_KEYS = ("hed_sigma", "hed_bias", "hed_applied", "skimage_mode", "hsb_codes", "tables", "codes")
+
+
+def _stages_check(n, hed_sigma=None, hed_bias=None, hed_applied=None, skimage_mode=0, hsb_codes=None, tables=None, codes=None):
+    """The stage arguments of normalize_stages_view* (no device needed; ValueError): at most one colour stage -- the HED triple of
+    normalize_hed_view (skimage_mode 0 only) or the codes of normalize_hsb_view --, the tables / codes of normalize_post_view, at
+    least one stage, one row per tile each."""
+    hed = [x is not None for x in (hed_sigma, hed_bias, hed_applied)]
+    if any(hed) and not all(hed):
+        raise ValueError("hed_sigma, hed_bias and hed_applied go together: the (N, 3) sigmas and biases and the (N,) decision per tile")
+    if all(hed) and hsb_codes is not None:
+        raise ValueError("a recipe has one colour stage: the HED triple or hsb_codes, not both")
+    if skimage_mode != _ffi.HED_SKIMAGE_018:
+        raise ValueError(f"skimage_mode {skimage_mode!r}: the recipe's HED stage runs in the kernel, which knows skimage_mode '0.18' (0) only")
+    if not any(hed) and hsb_codes is None and tables is None and codes is None:
+        raise ValueError("a recipe call needs a stage: the HED triple, hsb_codes=, tables= or codes=")
+    if all(hed):
+        for x, what in ((hed_sigma, "hed_sigma"), (hed_bias, "hed_bias")):
+            if _hed_rows(x, what) != n:
+                raise ValueError(f"{what} must have one row per tile ({n})")
+    if hsb_codes is not None and _hsb_codes_rows(hsb_codes) != n:
+        raise ValueError(f"hsb_codes must have one row per tile ({n})")
+    if tables is not None or codes is not None:
+        _post_check(tables, codes, n)
+
+
+def _stages_upload(n, dev, hed_sigma=None, hed_bias=None, hed_applied=None, skimage_mode=0, hsb_codes=None, tables=None, codes=None):
+    """The stages _stages_check has accepted on the device -> ((reference to the SlViewStages,), what must outlive the call)."""
+    import numpy as np
+    keep = [
+        _f64(hed_sigma, (n, 3), dev) if hed_sigma is not None else None,
+        _f64(hed_bias, (n, 3), dev) if hed_bias is not None else None,
+        torch.as_tensor(hed_applied, device=dev).to(torch.int32).reshape(n).contiguous() if hed_applied is not None else None,
+        _hsb_codes_device(hsb_codes, n, dev) if hsb_codes is not None else None,
+        _post_device(tables, np.uint8, dev),
+        _post_device(codes, np.int32, dev),
+    ]
+    ptr = lambda t: t.data_ptr() if t is not None else None       # noqa: E731
+    st = _ffi.SlViewStages(C.sizeof(_ffi.SlViewStages), ptr(keep[0]), ptr(keep[1]), ptr(keep[2]), int(skimage_mode), ptr(keep[3]), ptr(keep[4]),
+                           ptr(keep[5]))
+    keep.append(st)
+    return (C.byref(st),), keep
+
+
+def normalize_stages_view(rgb, windows, size, d_mask, M_src=None, maxC_src=None, M_tgt=None, maxC_tgt=None, alpha_beta=None,
+                          augment_background=False, params=None, fmt=None, out=None, shrink=1, resize=None, **stages):
+    """convert(post(view(colour(full)))) in ONE pass on a fixed-size, box-shrinking or resizing view (sl_normalize_stages_view): `full`,
+    windows, size, d_mask, shrink, resize, fmt, out are normalize_view's.  stages (keywords): hed_sigma, hed_bias, hed_applied[,
+    skimage_mode=0] -- normalize_hed_view's stage on SOURCE pixels -- or hsb_codes -- normalize_hsb_view's --; tables, codes --
+    normalize_post_view's stage on WRITTEN pixels, p counted in the view's output.  At least one stage, at most one colour stage
+    (ValueError).  Bit for bit the chain of those calls; an absent stage is the identity."""
+    bad = sorted(set(stages) - set(_STAGE_KEYS))
+    if bad:
+        raise TypeError(f"normalize_stages_view got unexpected keyword arguments {bad}")
+    n, h, w, oh, ow, win, M_src, maxC_src, M_tgt, maxC_tgt, ab, f, out = _view_prepare(
+        rgb, windows, size, d_mask, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, params, fmt, out,
+        before_device=lambda n: _stages_check(n, **stages), shrink=shrink, resize=resize)
+    st, keep = _stages_upload(n, rgb.device, **stages)
+    mh, mw = (int(resize[0]), int(resize[1])) if resize is not None else (0, 0)
+    _call("sl_normalize_stages_view", _ptr(rgb), _ptr(out), n, h, w, oh, ow, _ptr(win), int(d_mask), int(shrink), mh, mw, _ptr(M_src),
+          _ptr(maxC_src), _ptr(M_tgt), _ptr(maxC_tgt), _ptr(ab), 1 if augment_background else 0, _byref(params), _byref(f), *st)
+    del keep
+    return out
+
+
+def normalize_stages_view_affine(rgb, windows, size, max_r, fill=255, M_src=None, maxC_src=None, M_tgt=None, maxC_tgt=None, alpha_beta=None,
+                                 augment_background=False, params=None, fmt=None, out=None, **stages):
+    """normalize_stages_view on an affine view (sl_normalize_stages_view_affine): windows, size, max_r, fill and the rest are
+    normalize_view_affine's, stages normalize_stages_view's.  The fill is in OUTPUT space: it does not take the colour stage and it does
+    take the post stage, and so does a tile written entirely as fill (device windows beyond max_r)."""
+    bad = sorted(set(stages) - set(_STAGE_KEYS))
+    if bad:
+        raise TypeError(f"normalize_stages_view_affine got unexpected keyword arguments {bad}")
+    return _view_affine_call(stages, rgb, windows, size, max_r, fill, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta, augment_background, params,
+                             fmt, out)
+
+
+def normalize_stages_view_elastic(rgb, windows, field, size, cell, max_r, max_d, fill=255, M_src=None, maxC_src=None, M_tgt=None,
+                                  maxC_tgt=None, alpha_beta=None, augment_background=False, params=None, fmt=None, out=None, **stages):
+    """normalize_stages_view on an elastic view (sl_normalize_stages_view_elastic): windows, field, size, cell, max_r, max_d, fill and the
+    rest are normalize_view_elastic's, stages and the fill's treatment normalize_stages_view_affine's."""
+    bad = sorted(set(stages) - set(_STAGE_KEYS))
+    if bad:
+        raise TypeError(f"normalize_stages_view_elastic got unexpected keyword arguments {bad}")
+    return _view_elastic_call(stages, rgb, windows, field, size, cell, max_r, max_d, fill, M_src, maxC_src, M_tgt, maxC_tgt, alpha_beta,
+                              augment_background, params, fmt, out)
+
+
+def _recipe_draw_check(recipe, draw, tiles):
+    """recipe_draw= against its recipe (no device needed; ValueError): a complete RecipeDraw whose parts match the recipe's stages, each
+    part through the checker of its own keyword (_view_call, _hed_rows, _hsb_codes_rows, _tone_arg, _noise_arg)."""
+    from .augmentation.augmenter import HedColorAugmenter
+    n = int(tiles.shape[0])
+    if not isinstance(draw, RecipeDraw):
+        raise ValueError("recipe_draw must be the engine.RecipeDraw(windows, color, post) a recipe= call returned")
+    if (recipe.view is None) != (draw.windows is None):
+        raise ValueError("recipe_draw.windows does not match the recipe: " + ("the recipe has no view" if recipe.view is None else
+                                                                               f"the recipe's view ({recipe.view!r}) needs its windows"))
+    if recipe.view is not None:
+        _view_call(recipe.view, draw.windows, tiles, draw=False)
+    if recipe.color is None:
+        if draw.color is not None:
+            raise ValueError("recipe_draw.color does not match the recipe: the recipe has no colour stage")
+    elif isinstance(recipe.color, HedColorAugmenter):
+        if not isinstance(draw.color, HedDraw):
+            raise ValueError("recipe_draw.color does not match the recipe: a HedColorAugmenter needs the engine.HedDraw the call returned")
+        for x, what in ((draw.color.sigmas, "recipe_draw.color.sigmas"), (draw.color.biases, "recipe_draw.color.biases")):
+            if _hed_rows(x, what) != n:
+                raise ValueError(f"{what} must have one row per tile ({n})")
+    else:
+        if not isinstance(draw.color, HsbDraw):
+            raise ValueError("recipe_draw.color does not match the recipe: an HsbColorAugmenter needs the engine.HsbDraw the call returned")
+        if _hsb_codes_rows(draw.color.codes) != n:
+            raise ValueError(f"recipe_draw.color.codes must have one row per tile ({n})")
+    if recipe.noise is None and recipe.tone is None:
+        if draw.post is not None:
+            raise ValueError("recipe_draw.post does not match the recipe: the recipe has no tone or noise stage")
+        return
+    if not isinstance(draw.post, PostDraw):
+        raise ValueError("recipe_draw.post does not match the recipe: tone= / noise= need the engine.PostDraw the call returned")
+    if (recipe.tone is None) != (draw.post.tone_tables is None):
+        raise ValueError("recipe_draw.post.tone_tables does not match the recipe's tone stage")
+    if (recipe.noise is None) != (draw.post.noise_codes is None):
+        raise ValueError("recipe_draw.post.noise_codes does not match the recipe's noise stage")
+    if recipe.tone is not None:
+        _tone_arg(draw.post.tone_tables, n)
+    if recipe.noise is not None:
+        _noise_arg(recipe.noise, draw.post.noise_codes, n)
+
+
+def _recipe_call(recipe, recipe_draw, tiles, **others):
+    """The recipe= / recipe_draw= arguments of a batch method, checked without a device and before any draw (ValueError).  True when the
+    call has a recipe.  others: the call's own view and stage keywords by name -- none of them goes with a recipe."""
+    from .recipe import Recipe
+    if recipe is None:
+        if recipe_draw is not None:
+            raise ValueError("recipe_draw= goes with recipe= (the stainlib_amd.Recipe that made it)")
+        return False
+    if not isinstance(recipe, Recipe):
+        raise ValueError("recipe must be a stainlib_amd.Recipe")
+    given = [k for k, v in others.items() if v is not None]
+    if given:
+        raise ValueError("recipe= does not go together with " + ", ".join(k + "=" for k in given) + ": the recipe holds the call's view and "
+                         "every stage (Recipe(view=, color=, noise=, tone=)); to reproduce a call pass the RecipeDraw it returned as recipe_draw=")
+    if not (isinstance(tiles, torch.Tensor) and tiles.dim() == 4 and tiles.shape[-1] == 3):
+        raise ValueError("expected a contiguous CUDA uint8 tensor of shape (N, H, W, 3)")
+    if recipe_draw is not None:
+        _recipe_draw_check(recipe, recipe_draw, tiles)
+    elif recipe.view is not None:
+        _view_call(recipe.view, None, tiles, draw=False)
+    return True
+
+
+def _no_recipe(recipe, recipe_draw, what, instead):
+    """ValueError for recipe= in a call that has no recipe"""
+    if recipe is not None or recipe_draw is not None:
+        raise ValueError(f"recipe= is not supported by {what}: {instead}")
+
+
+def recipe_stage(tiles, recipe, recipe_draw, route, fmt=None, out=None):
+    """The recipe= stage of the batch methods, behind their fit and their own draws, on arguments _recipe_call has accepted: the draws --
+    color.randomize_batch(N), THEN tone.randomize_batch(N), THEN noise.randomize_batch(N), THEN view.draw -- or the parts of recipe_draw
+    in their place, the HED cutoff decision (hed_decide, also on a replay) and ONE fused pass (normalize_stages_view*, by the view's
+    type).  route: normalize_view's keyword arguments that name `full` ({}: the tiles themselves).  Without a view the result is the
+    full tile, code 0.  -> (out, RecipeDraw)."""
+    import numpy as np
+    from .augmentation.augmenter import HedColorAugmenter
+    from .augmentation.hsb import hsb_codes
+    n = int(tiles.shape[0])
+    view, color, noise, tone = recipe.view, recipe.color, recipe.noise, recipe.tone
+    is_hed = isinstance(color, HedColorAugmenter)
+    stages, cdraw, pdraw = {}, None, None
+    if color is not None:
+        if is_hed:
+            sigmas, biases = color.randomize_batch(n) if recipe_draw is None else (recipe_draw.color.sigmas, recipe_draw.color.biases)
+        elif recipe_draw is None:
+            sigmas = np.array(color.randomize_batch(n), dtype=np.float64)
+            codes = hsb_codes(sigmas)
+        else:
+            sigmas, codes = recipe_draw.color.sigmas, recipe_draw.color.codes
+    if tone is not None or noise is not None:
+        params = tables = nsig = ncodes = None
+        if tone is not None:
+            params, tables = tone.randomize_batch(n) if recipe_draw is None else (recipe_draw.post.tone_params,
+                                                                                   _tone_arg(recipe_draw.post.tone_tables, n)[1])
+        if noise is not None:
+            nsig, ncodes = noise.randomize_batch(n) if recipe_draw is None else (recipe_draw.post.noise_sigmas,
+                                                                                 _noise_arg(noise, recipe_draw.post.noise_codes, n)[1])
+        pdraw = PostDraw(params, tables, nsig, ncodes)
+        stages.update(tables=tables, codes=ncodes)
+    windows = None
+    if view is not None:
+        size, d_mask, windows, shrink = _view_call(view, recipe_draw.windows if recipe_draw is not None else None, tiles)
+    if color is not None:
+        if is_hed:
+            applied = hed_decide(tiles, color._cutoff_range, **route)
+            cdraw = HedDraw(sigmas, biases, applied)
+            stages.update(hed_sigma=sigmas, hed_bias=biases, hed_applied=applied, skimage_mode=color._skimage_mode)
+        else:
+            cdraw = HsbDraw(sigmas, codes)
+            stages.update(hsb_codes=codes)
+    if view is None:
+        x = normalize_stages_view(tiles, np.zeros((n, 3), dtype=np.int32), None, 0, fmt=fmt, out=out, **route, **stages)
+    elif _is_elastic(view):
+        max_r, max_d = _elastic_bound(view, windows)
+        x = normalize_stages_view_elastic(tiles, windows.affine, windows.field, size, view.cell, max_r, max_d, view.fill, fmt=fmt, out=out,
+                                          **route, **stages)
+    elif _is_affine(view):
+        x = normalize_stages_view_affine(tiles, windows, size, _affine_bound(view, windows), view.fill, fmt=fmt, out=out, **route, **stages)
+    else:
+        x = normalize_stages_view(tiles, windows, size, d_mask, fmt=fmt, out=out, shrink=shrink, resize=_view_resize(view, windows, tiles),
+                                  **route, **stages)
+    return x, RecipeDraw(windows, cdraw, pdraw)
 
 
 def _fit(fn_name, op, rgb, params, ws, with_sweeps=False):

@@ -146,23 +146,26 @@ class ExtractiveStainNormalizer(object):
         """Per-tile (M, maxC, status) device tensors for a batch of candidate targets."""
         return self._fit_tiles(tiles, ws=ws)
 
-    def _route_batch(self, tiles, target, jitter, out, ws, tensor_format, view, windows, hed, hsb=None, blur=None, post=None):
+    def _route_batch(self, tiles, target, jitter, out, ws, tensor_format, view, windows, hed, hsb=None, blur=None, post=None, recipe=None):
         """The view= / hed= routes of transform_batch and all of augment_batch: the checks that are left (every one before the fit and
         before any draw), the fit of the whole tiles, then engine.route_stage -- ONE pass under the target (target=True) or every tile's
         own matrix, with the jitter's alpha_beta / augment_background ({}: none).  hed: None, or (hed, hed_sigmas, hed_biases) that
         engine._hed_call has accepted; hsb: None, or (hsb, hsb_sigmas) that engine._hsb_call has accepted; blur: None, or (blur, blur_sigmas)
-        that engine._blur_call has accepted; post: None, or (noise, tone, noise_sigmas, tone_params) that engine._post_call has accepted.
-        -> (out, M_src, maxC_src, status[, windows][, HedDraw or HsbDraw or BlurDraw or PostDraw])."""
+        that engine._blur_call has accepted; post: None, or (noise, tone, noise_sigmas, tone_params) that engine._post_call has accepted;
+        recipe: None, or (Recipe, recipe_draw) that engine._recipe_call has accepted.
+        -> (out, M_src, maxC_src, status[, windows][, HedDraw or HsbDraw or BlurDraw or PostDraw or RecipeDraw])."""
         from .. import engine
         if view is not None or windows is not None:
             engine._view_call(view, windows, tiles, draw=False)
         engine._check_tiles(tiles)
         fit = self._fit_tiles(tiles, ws=ws)
         M_t, c_t = self._target_on(tiles.device) if target else (None, None)
-        return engine.route_stage(tiles, fit, dict(M_tgt=M_t, maxC_tgt=c_t, **jitter), tensor_format, out, view, windows, hed, hsb, blur, post)
+        return engine.route_stage(tiles, fit, dict(M_tgt=M_t, maxC_tgt=c_t, **jitter), tensor_format, out, view, windows, hed, hsb, blur, post,
+                                  recipe)
 
     def transform_batch(self, tiles, out=None, ws=None, tensor_format=None, _tensor_route=None, view=None, windows=None, hed=None,
-                        hed_sigmas=None, hed_biases=None, hsb=None, hsb_sigmas=None, blur=None, blur_sigmas=None, noise=None, tone=None, noise_sigmas=None, tone_params=None):
+                        hed_sigmas=None, hed_biases=None, hsb=None, hsb_sigmas=None, blur=None, blur_sigmas=None, noise=None, tone=None, noise_sigmas=None, tone_params=None,
+                        recipe=None, recipe_draw=None):
         """(N,H,W,3) uint8 device tensor -> (out, M_src, maxC_src, status) device tensors.  A tile whose
         status is non-zero (1 = empty tissue mask, 2 = degenerate, 3 = a zero 99th-percentile concentration) is passed through unchanged.
         ``ws``: an ``engine.Workspace`` to reuse (ONE stream at a time); by default every call takes its scratch from
@@ -193,8 +196,18 @@ class ExtractiveStainNormalizer(object):
         without them.  ``tone_params``: (N, 3) (brightness, contrast, gamma), ``noise_sigmas``: (N,) in bytes -- or the tables / codes a
         call returned, to reproduce it; by default ``tone.randomize_batch(N)``, then ``noise.randomize_batch(N)``, drawn BEFORE the
         windows.  One more element at the end, ``engine.PostDraw(tone_params, tone_tables, noise_sigmas, noise_codes)``.  Not together
-        with ``hed``, ``hsb`` or ``blur`` (chain them), a TileAffine or a TileElastic."""
+        with ``hed``, ``hsb`` or ``blur`` (chain them), a TileAffine or a TileElastic.
+        ``recipe``: a ``stainlib_amd.Recipe(view=, color=, noise=, tone=)`` -- a colour stage (HED or HSB) on the normalised SOURCE pixels, a
+        view of any kind and tone / noise on the WRITTEN pixels TOGETHER in that one pass (engine.recipe_stage): bit for bit the chain
+        of the calls above.  The draws: ``color.randomize_batch(N)``, ``tone.randomize_batch(N)``, ``noise.randomize_batch(N)``,
+        ``view.draw(N, H, W)``, in this order.  The call returns (out, M_src, maxC_src, status, ``engine.RecipeDraw(windows, color,
+        post)``); ``recipe_draw``: that RecipeDraw passed back reproduces the call.  Not together with any other keyword above from
+        ``view`` on."""
         from .. import engine
+        if engine._recipe_call(recipe, recipe_draw, tiles, view=view, windows=windows, hed=hed, hed_sigmas=hed_sigmas, hed_biases=hed_biases,
+                               hsb=hsb, hsb_sigmas=hsb_sigmas, blur=blur, blur_sigmas=blur_sigmas, noise=noise, tone=tone,
+                               noise_sigmas=noise_sigmas, tone_params=tone_params):
+            return self._route_batch(tiles, True, {}, out, ws, tensor_format, None, None, None, recipe=(recipe, recipe_draw))
         with_hed = engine._hed_call(hed, hed_sigmas, hed_biases, tiles, view)
         with_hsb = engine._hsb_call(hsb, hsb_sigmas, tiles, view, hed)
         with_blur = engine._blur_call(blur, blur_sigmas, tiles, view, hed, hsb)
@@ -219,7 +232,8 @@ class ExtractiveStainNormalizer(object):
 
     # -- stain separation (an extension: torchstain's normalize(..., stains=True), the concentration maps of staintools) ----
     def separate_batch(self, tiles, want=("norm", "h", "e", "conc"), conc_dtype=None, normalize=True, ws=None, tensor_format=None, view=None,
-                       windows=None, blur=None, blur_sigmas=None, noise=None, tone=None, noise_sigmas=None, tone_params=None):
+                       windows=None, blur=None, blur_sigmas=None, noise=None, tone=None, noise_sigmas=None, tone_params=None, recipe=None,
+                       recipe_draw=None):
         """(N,H,W,3) uint8 device tensor -> (Separated, M_src, maxC_src, status): the per-tile fit, then ONE pass that writes what
         ``want`` names -- norm (transform_batch's image), h / e (the haematoxylin-only / eosin-only image, (N,H,W,3) uint8) and conc
         (the normalised concentrations, (N,2,H,W) planes of ``conc_dtype``: float32 by default, float16 or bfloat16).
@@ -233,9 +247,11 @@ class ExtractiveStainNormalizer(object):
         ``tensor_format``: a ``stainlib_amd.TensorFormat`` (with ``view`` only; ``TileView(None, flip=False, rot90=False)`` is the
         fused full-tile tensor) -- norm, h and e are then (N,3,oh,ow) tensors, bit for bit ``tensor_format.convert`` of the uint8 views.
         ``blur``, ``blur_sigmas``: refused (ValueError) -- the separation pass has no blur stage.
-        ``noise``, ``tone``, ``noise_sigmas``, ``tone_params``: refused (ValueError) -- the separation pass has no post stage."""
+        ``noise``, ``tone``, ``noise_sigmas``, ``tone_params``: refused (ValueError) -- the separation pass has no post stage.
+        ``recipe``, ``recipe_draw``: refused (ValueError) -- the separation pass has no stages."""
         import torch
         from .. import engine
+        engine._no_recipe(recipe, recipe_draw, "separate_batch", "its pass has no colour or post stage; take view= for the windows alone")
         engine._no_blur(blur, blur_sigmas, "separate_batch")
         engine._no_post(noise, tone, noise_sigmas, tone_params, "separate_batch")
         conc_dtype = torch.float32 if conc_dtype is None else conc_dtype
@@ -257,7 +273,8 @@ class ExtractiveStainNormalizer(object):
 
     # -- stain jitter in the apply pass (an extension: RandStainNA / StainAugmentor-style augmentation of the normalised tiles) ----
     def augment_batch(self, tiles, alpha_beta, augment_background=False, normalize=True, out=None, ws=None, tensor_format=None, view=None,
-                      windows=None, hed=None, hed_sigmas=None, hed_biases=None, hsb=None, hsb_sigmas=None, blur=None, blur_sigmas=None, noise=None, tone=None, noise_sigmas=None, tone_params=None):
+                      windows=None, hed=None, hed_sigmas=None, hed_biases=None, hsb=None, hsb_sigmas=None, blur=None, blur_sigmas=None, noise=None, tone=None, noise_sigmas=None, tone_params=None,
+                      recipe=None, recipe_draw=None):
         """(N,H,W,3) uint8 device tensor -> (out, M_src, maxC_src, status): the per-tile fit, then ONE pass that normalises every tile
         and perturbs its stains: C_i * alpha_i + beta_i on the normalised concentrations of tissue pixels (every pixel with
         ``augment_background``), under the target's stain matrix, clipped.  ``alpha_beta``: (N, 4) = alpha0, beta0, alpha1, beta1 per
@@ -274,11 +291,18 @@ class ExtractiveStainNormalizer(object):
         ``blur``, ``blur_sigmas``: as in transform_batch -- the GaussianBlurAugmenter's blur of the perturbed tile in the same pass; one
         more element at the end of the returned tuple, ``engine.BlurDraw``.
         ``noise``, ``tone``, ``noise_sigmas``, ``tone_params``: as in transform_batch -- the post stage on the written pixels of the
-        perturbed tile in the same pass; one more element at the end of the returned tuple, ``engine.PostDraw``."""
+        perturbed tile in the same pass; one more element at the end of the returned tuple, ``engine.PostDraw``.
+        ``recipe``, ``recipe_draw``: as in transform_batch -- the Recipe's colour stage on the perturbed tile, its view and its tone / noise
+        in the same pass; the call returns (out, M_src, maxC_src, status, ``engine.RecipeDraw``)."""
         from .. import engine
         engine._jitter_args(None, None, alpha_beta, None, tensor_format, out)
         if normalize and not hasattr(self, "stain_matrix_target"):
             raise ValueError("augment_batch(normalize=True) needs a fitted target: call fit() first, or pass normalize=False")
+        if engine._recipe_call(recipe, recipe_draw, tiles, view=view, windows=windows, hed=hed, hed_sigmas=hed_sigmas, hed_biases=hed_biases,
+                               hsb=hsb, hsb_sigmas=hsb_sigmas, blur=blur, blur_sigmas=blur_sigmas, noise=noise, tone=tone,
+                               noise_sigmas=noise_sigmas, tone_params=tone_params):
+            return self._route_batch(tiles, normalize, dict(alpha_beta=alpha_beta, augment_background=augment_background), out, ws,
+                                     tensor_format, None, None, None, recipe=(recipe, recipe_draw))
         with_hed = engine._hed_call(hed, hed_sigmas, hed_biases, tiles, view)
         with_hsb = engine._hsb_call(hsb, hsb_sigmas, tiles, view, hed)
         with_blur = engine._blur_call(blur, blur_sigmas, tiles, view, hed, hsb)
@@ -367,7 +391,8 @@ class ReinhardStainNormalizer(object):
         return out[0].cpu().numpy()
 
     def transform_batch(self, tiles, mask_background=False, luminosity_threshold=0.8, out=None, ws=None, tensor_format=None, view=None,
-                        windows=None, blur=None, blur_sigmas=None, noise=None, tone=None, noise_sigmas=None, tone_params=None):
+                        windows=None, blur=None, blur_sigmas=None, noise=None, tone=None, noise_sigmas=None, tone_params=None, recipe=None,
+                        recipe_draw=None):
         """Batched extension: (N,H,W,3) uint8 device tensor -> (out, stats (N,8): p90, means, stds, tissue pixels).
         ``tensor_format``: a ``stainlib_amd.TensorFormat``; `out` is then the (N,3,H,W) tensor in that format (the map writes a uint8
         scratch, ``tensor_format.convert`` reads it).
@@ -376,8 +401,11 @@ class ReinhardStainNormalizer(object):
         ``tensor_format``, the (N,3,oh,ow) tensor -- no uint8 scratch (engine.reinhard_view); the call returns (out, stats, windows).
         ``TileView(None, flip=False, rot90=False)`` is the fused full-tile tensor.  ``windows`` without ``view`` is a ValueError.
         ``blur``, ``blur_sigmas``: refused (ValueError) -- the Lab family's fused pass has no blur stage; blur its uint8 result
-        (``blur.transform_batch(view=, tensor_format=)``)."""
+        (``blur.transform_batch(view=, tensor_format=)``).  ``recipe``, ``recipe_draw``: refused (ValueError) likewise -- take the uint8
+        result through ``tensor_format.convert(u8, recipe=)``."""
         from .. import engine
+        engine._no_recipe(recipe, recipe_draw, "the Lab family's fused calls (ReinhardStainNormalizer.transform_batch)",
+                          "take its uint8 result through TensorFormat.convert(u8, recipe=)")
         engine._no_blur(blur, blur_sigmas, "the Lab family's fused calls (ReinhardStainNormalizer.transform_batch)")
         engine._no_post(noise, tone, noise_sigmas, tone_params, "the Lab family's fused calls (ReinhardStainNormalizer.transform_batch)")
         tm, ts = self._targets()

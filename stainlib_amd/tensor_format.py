@@ -56,7 +56,7 @@ class TensorFormat(object):
         return v
 
     def convert(self, tiles_u8, out=None, view=None, windows=None, blur=None, blur_sigmas=None, noise=None, tone=None, noise_sigmas=None,
-                tone_params=None):
+                tone_params=None, recipe=None, recipe_draw=None):
         """(N, H, W, 3) uint8 device tensor -> (N, 3, H, W) tensor in this format (one streaming sweep, engine.to_tensor).
         ``out``: a tensor of that shape, dtype and memory format to write into.
         ``view``: a ``stainlib_amd.TileView`` -- per tile only the window ``windows[t]`` (default: ``view.draw(N, H, W)``), flipped and
@@ -71,8 +71,16 @@ class TensorFormat(object):
         the conversion: bit for bit this call on ``augmentation.noise.post_reference`` of the uint8 view.  ``tone_params``: (N, 3),
         ``noise_sigmas``: (N,) -- or the tables / codes a call returned; by default ``tone.randomize_batch(N)``, then
         ``noise.randomize_batch(N)``, drawn BEFORE the windows.  One more element at the end, ``engine.PostDraw``.  Not with ``blur``, a
-        TileAffine or a TileElastic."""
+        TileAffine or a TileElastic.
+        ``recipe``: a ``stainlib_amd.Recipe(view=, color=, noise=, tone=)`` -- a colour stage (HED or HSB) on the SOURCE pixels, a view of
+        any kind and tone / noise on the WRITTEN pixels TOGETHER in the same sweep (engine.recipe_stage), drawn in the order colour,
+        tone, noise, view.  Returns (tensor, ``engine.RecipeDraw(windows, color, post)``); ``recipe_draw``, that RecipeDraw passed back,
+        reproduces the call.  Not together with any other keyword from ``view`` on."""
         from . import engine
+        if engine._recipe_call(recipe, recipe_draw, tiles_u8, view=view, windows=windows, blur=blur, blur_sigmas=blur_sigmas, noise=noise,
+                               tone=tone, noise_sigmas=noise_sigmas, tone_params=tone_params):
+            engine._check_tiles(tiles_u8)
+            return engine.recipe_stage(tiles_u8, recipe, recipe_draw, {}, fmt=self, out=out)
         if engine._post_call(noise, tone, noise_sigmas, tone_params, tiles_u8, view, blur=blur):
             if view is not None or windows is not None:
                 engine._view_call(view, windows, tiles_u8, draw=False)

@@ -97,7 +97,8 @@ class LuminosityStandardizer(object):
         return out[0].cpu().numpy()
 
     @staticmethod
-    def standardize_batch(tiles, percentile=95, out=None, ws=None, tensor_format=None, view=None, windows=None, blur=None, blur_sigmas=None, noise=None, tone=None, noise_sigmas=None, tone_params=None):
+    def standardize_batch(tiles, percentile=95, out=None, ws=None, tensor_format=None, view=None, windows=None, blur=None, blur_sigmas=None, noise=None, tone=None, noise_sigmas=None, tone_params=None,
+                          recipe=None, recipe_draw=None):
         """Batched extension: (N,H,W,3) uint8 device tensor -> (out, p (N,) float64: every tile's `percentile` of L8).
         ``tensor_format``: a ``stainlib_amd.TensorFormat``; `out` is then the (N,3,H,W) tensor in that format (the map writes a uint8
         scratch, ``tensor_format.convert`` reads it).
@@ -105,8 +106,11 @@ class LuminosityStandardizer(object):
         the window ``windows[t]`` (default: ``view.draw(N, H, W)``) of that result, flipped and turned, as (N,oh,ow,3) uint8 or the
         (N,3,oh,ow) tensor -- no uint8 scratch (engine.luminosity_view); the call returns (out, p, windows).  ``windows`` without
         ``view`` is a ValueError.  ``blur``, ``blur_sigmas``: refused (ValueError) -- the Lab family's fused pass has no blur stage;
-        blur its uint8 result (``blur.transform_batch(view=, tensor_format=)``)."""
+        blur its uint8 result (``blur.transform_batch(view=, tensor_format=)``).  ``recipe``, ``recipe_draw``: refused (ValueError)
+        likewise -- take the uint8 result through ``tensor_format.convert(u8, recipe=)``."""
         from .. import engine
+        engine._no_recipe(recipe, recipe_draw, "the Lab family's fused calls (LuminosityStandardizer.standardize_batch)",
+                          "take its uint8 result through TensorFormat.convert(u8, recipe=)")
         engine._no_blur(blur, blur_sigmas, "the Lab family's fused calls (LuminosityStandardizer.standardize_batch)")
         engine._no_post(noise, tone, noise_sigmas, tone_params, "the Lab family's fused calls (LuminosityStandardizer.standardize_batch)")
         if engine.lab_view_check(view, windows, tiles):
